@@ -13,6 +13,8 @@ layer on a side stream as each layer's gradients become final (dp.LayerwiseAllRe
 Inputs are resident in HBM before the timed region.  Rank 0 prints ONE JSON line (contract in the task statement),
 including `roofline` for the dominant kernel (HIP-event timing on the launch stream via fil_profile_begin/_end)
 and `cpu_baseline` (the oracle's op-for-op torch-CPU restatement of the reference TF2 graph, timed on this host).
+--dump-outputs DIR also writes what the last timed step returned (output and every gradient, float32) as DIR/<name>.npy;
+the inputs are seeded, so two builds run with the same arguments can be compared array for array.
 """
 import argparse
 import json
@@ -486,6 +488,20 @@ class stdout_to_stderr:
         os.close(self.saved)
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: write each array as <out_dir>/<name>.npy (float32), at most DUMP_LIMIT_BYTES in all."""
+    host = {k: v.detach().float().cpu().numpy() for k, v in arrays.items()}
+    total = sum(a.nbytes for a in host.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise RuntimeError("--dump-outputs: %d bytes of outputs exceed the %d-byte limit" % (total, DUMP_LIMIT_BYTES))
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in host.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a)
+
+
 def timed_steps(step, fence, steps):
     fence()
     t0 = time.perf_counter()
@@ -524,8 +540,13 @@ def main():
     ap.add_argument("--no-graph-replay", action="store_true", help="skip the HIP-graph replay timing of the headline step (profiling runs: "
                     "keeps the number of step iterations the PMC summarisers expect)")
     ap.add_argument("--no-candidate", action="store_true", help="skip the split-bf16 candidate (FIL_CIN_BF16X3) timed beside the headline")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="headline only: after the timed windows, write what the last timed step returned (out, dx, dW<l>, db<l>, "
+                         "d_dense_w, d_dense_b; rank 0) as DIR/<name>.npy in float32")
     ap.add_argument("--stub", default="", help=argparse.SUPPRESS)   # tests: module with install(namespace) -> CPU/gloo stand-ins
     args = ap.parse_args()
+    if args.dump_outputs and args.workload != "cin":
+        sys.exit("bench.py: --dump-outputs covers the headline workload (--workload cin) only")
     if args.workload in ("deepfm", "xdeepfm"):
         print(json.dumps(deepfm_benchmark(args)))
         return 0
@@ -596,8 +617,12 @@ def main():
                             ready_events=ready)
         return out
 
+    last = {}
+
     def step(mode=args.cin_mode, comm=True):
         out = compute(mode)
+        if args.dump_outputs:
+            last["out"] = out
         if use_dist and comm:
             if ready is None and device.type == "cuda":   # --no-overlap: the whole bucket after the backward, on the compute stream
                 dist.all_reduce(flat, op=dist.ReduceOp.SUM)
@@ -668,6 +693,13 @@ def main():
         window_dts.append(max_over_ranks(timed_steps(step, fence, args.steps)))
         if prof_on:
             _lib.profile_end()
+    # what the last timed step handed its caller, taken before the candidate below overwrites the gradient buffers
+    if args.dump_outputs and rank == 0:
+        arrays = dict(out=last["out"], dx=grads["dx"], d_dense_w=grads["ddw"], d_dense_b=grads["ddb"])
+        for l in range(L):
+            arrays["dW%d" % (l + 1)] = grads["dW"][l]
+            arrays["db%d" % (l + 1)] = grads["db"][l]
+        dump_outputs(args.dump_outputs, arrays)
 
     # The LABELLED reduced-operand mode of the same step (fil.h FIL_CIN_BF16X3: the three GEMM launches on split-bf16 operands, six
     # bf16 MFMAs per product, fp32 accumulate), timed under the headline's protocol AFTER its windows and reported BESIDE it:

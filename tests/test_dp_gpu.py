@@ -143,6 +143,41 @@ def test_bench_line_accounting():
     assert res["value"] == pytest.approx(4096 / (res["ms_per_step"] * 1e-3), rel=1e-9)
 
 
+def test_bench_dump_outputs_are_the_timed_step(tmp_path):
+    """`bench.py --dump-outputs DIR` writes what the last timed step returned: the output and every gradient, float32, one file each.
+    The output and dx rows are independent of the other rows: the first 64 are held against the fp64 oracle on the same inputs."""
+    import json
+    import subprocess
+    import sys
+    import numpy as np
+    import bench
+    from ml_function_amd import synth
+    from oracle import closed
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "2", "--warmup", "1", "--windows", "1", "--no-side",
+                        "--no-cpu-baseline", "--no-graph-replay", "--no-candidate", "--dump-outputs", str(tmp_path)],
+                       env=env, cwd=root, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    assert json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][0])["steps"] == 2
+    B, F, K, conv = bench.B_PER_GPU, bench.F, bench.K, bench.CONV
+    got = {n[:-4]: np.load(tmp_path / n) for n in os.listdir(tmp_path)}
+    shapes = dict(out=(B, 1), dx=(B, F, K), d_dense_w=(len(conv) * K, 1), d_dense_b=(1,))
+    hp = F
+    for l, h in enumerate(conv):
+        shapes["dW%d" % (l + 1)], shapes["db%d" % (l + 1)] = (hp * F, h), (h,)
+        hp = h
+    assert {k: v.shape for k, v in got.items()} == shapes
+    assert all(v.dtype == np.float32 and np.isfinite(v).all() for v in got.values())
+    par = synth.cin_case(B, F, K, conv, seed=synth.SEED)
+    d = synth.cin_case(B, F, K, conv, seed=synth.SEED + 1)
+    n = 64
+    want = closed.cin_fwd(d["x"][:n], par["Ws"], par["bs"], par["dense_w"], par["dense_b"])
+    dx = closed.cin_bwd(d["x"][:n], par["Ws"], par["bs"], par["dense_w"], d["g"][:n, :1])[0]
+    rel = lambda a, b: float(np.abs(a - b).max() / np.abs(b).max())
+    assert rel(got["out"][:n], want) < 1e-5 and rel(got["dx"][:n], dx) < 1e-5
+
+
 def _free_port():
     s = socket.socket()
     s.bind(("127.0.0.1", 0))

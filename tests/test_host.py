@@ -59,13 +59,15 @@ def test_every_entry_point_validates_its_arguments(lib):
 def test_host_shim_under_asan_ubsan():
     """The same calls against the AddressSanitizer + UBSan build of the host shim (hipcc instruments the host pass only: GPU
     sanitizers are not available on this pool).  A heap / stack overrun, use-after-free or undefined behaviour in argument
-    checking, workspace sizing, launch planning (dw_plan, bwd_grid ...) or error formatting aborts the child."""
+    checking, workspace sizing, launch planning (dw_plan, bwd_grid ...) or error formatting aborts the child.  The child sees no GPU
+    even on a machine that has one (ROCR_ / HIP_VISIBLE_DEVICES=-1): the HIP runtime bringing a real device up inside an
+    ASan process runs out of memory under the sanitizer's allocator, and these calls never launch anything anyway."""
     from ml_function_amd import build as _build
     asan_lib = _build.build_asan()
     rt = _build.asan_runtime()
     assert os.path.exists(rt), rt
     env = dict(os.environ, LD_PRELOAD=rt, ASAN_OPTIONS="detect_leaks=0:halt_on_error=1:abort_on_error=0",
-               UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1")
+               UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1", ROCR_VISIBLE_DEVICES="-1", HIP_VISIBLE_DEVICES="-1")
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     r = subprocess.run([sys.executable, os.path.join(root, "tests", "host_calls.py"), asan_lib], env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0 and "host calls ok" in r.stdout, (r.stdout[-500:], r.stderr[-3000:])
