@@ -52,6 +52,9 @@ def main():
     ap.add_argument("--dense", type=int, default=13)
     ap.add_argument("--embed-dim", type=int, default=16)
     ap.add_argument("--lr", type=float, default=1e-3)
+    ap.add_argument("--cin-precision", default="f32", choices=["f32", "bf16"],
+                    help="XDeepFM only: bf16 = the CIN's labelled bf16 training mode (one bf16 MFMA per product in its three GEMM "
+                         "launches, ~1e-3 relative error); f32 = the exact chain")
     ap.add_argument("--no-graph", action="store_true",
                     help="run every step eagerly (default on one GPU: the whole step -- forward, backward, Adam -- is captured once "
                          "into a HIP graph and replayed; the C ABI neither allocates nor synchronises, so it is capture-safe)")
@@ -82,7 +85,7 @@ def main():
     fi = models.FeatureInput(sparseInfo=info, useLinear=args.model != "DCN" and args.model != "AutoInt", useAddLinear=single,
                              useFlattenLinear=True)
     body = {"FM": models.FM, "DeepFM": models.DeepFM, "DCN": models.DCN, "AutoInt": models.AutoInt, "NFM": models.NFM,
-            "AFM": models.AFM, "XDeepFM": lambda: models.XDeepFM(conv_size=[128, 128, 128])}[args.model]()
+            "AFM": models.AFM, "XDeepFM": lambda: models.XDeepFM(conv_size=[128, 128, 128], precision=args.cin_precision)}[args.model]()
     torch.manual_seed(0)  # identical replicas
     model = models.CTRModel(fi, body).to(device)
     table = (dense_df.to_numpy(np.float32), ids_df.to_numpy(np.int64), labels)

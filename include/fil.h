@@ -39,7 +39,7 @@ typedef enum { FIL_F32 = 0, FIL_BF16 = 1 } fil_dtype;
 /* ABI version: bumped on EVERY change of an entry point's argument list or semantics.  fil_version() returns the value the
  * library was compiled with; the ctypes binding (ml_function_amd/_lib.py) refuses a library whose value differs from this
  * header's, so a stale prebuilt .so can never be called with shifted arguments. */
-#define FIL_ABI_VERSION 215
+#define FIL_ABI_VERSION 216
 int fil_version(void);                 /* == FIL_ABI_VERSION of the header the library was built from */
 const char* fil_last_error(void);      /* thread-local, never NULL */
 
@@ -151,6 +151,32 @@ int fil_cin_bwd(const float* x, const float* const* W, const float* const* bias,
                 float* const* dbias, float* ddense_w, float* ddense_b, int B, int F, int K, int L, const int* H,
                 int output_dim, int mode, void* const* grad_ready_events, void* workspace, size_t workspace_bytes,
                 void* stream);
+/* fil_cin_fwd_p / fil_cin_bwd_p (ABI 216): fil_cin_fwd / fil_cin_bwd with an operand precision beside `mode`.
+ *   precision FIL_CIN_PREC_DEFAULT (0): exactly what `mode` selects (the same call as fil_cin_fwd / fil_cin_bwd).
+ *   precision FIL_CIN_PREC_BF16 (1): the LABELLED bf16 training mode.  Wherever the merged quadratic tail runs (the places
+ *       FIL_CIN_BF16X3 can run: three layers, H_1 == 128 column chunk, F in the split kernels' menu, above 16,384 rows unless
+ *       FIL_CIN_TAIL_ALWAYS) its three GEMM launches round every operand ONCE to bf16 (nearest even) and take ONE
+ *       v_mfma_f32_32x32x16_bf16 per product with fp32 accumulation (csrc/cin_qsplit.h, NP = 1); everything else stays exact fp32.
+ *       Error ~1e-3 relative (one bf16 rounding per operand over an F(F+1)/2-long reduction): a mode of its own, never the default.
+ *       Elsewhere the call runs the exact kernels; fil_cin_precision_used says which.  (At the few F where no one-plane dZ kernel
+ *       exists -- those the two-pass BF16X3 dZ kernel refuses -- the data gradient runs exact.)
+ *       Combined with mode bit FIL_CIN_BF16X3: FIL_ERR_ARG.  Any other precision code: FIL_ERR_ARG.
+ *   saved / workspace sizes: fil_cin_saved_bytes / fil_cin_*_workspace_bytes cover every precision.  Allocates nothing, never
+ *   synchronises, graph-capturable, bit-identical for identical inputs, like the exact path.
+ *   grad_ready_events: recorded at the same points as FIL_CIN_BF16X3's (fil_cin_grad_ready_points(.., mode, ..) holds for either
+ *   precision: they do not depend on it).
+ * fil_cin_precision_used: the precision a call with these arguments actually runs (FIL_CIN_PREC_BF16 or FIL_CIN_PREC_DEFAULT; B = 0:
+ *   DEFAULT, nothing runs), or a (negative) error code for arguments the _p entry points refuse. */
+enum fil_cin_precision { FIL_CIN_PREC_DEFAULT = 0, FIL_CIN_PREC_BF16 = 1 };
+int fil_cin_precision_used(int B, int F, int K, int L, const int* H, int mode, int precision);
+int fil_cin_fwd_p(const float* x, const float* const* W, const float* const* bias, const float* dense_w,
+                  const float* dense_b, float* out, float* pooled, float* saved, int B, int F, int K, int L,
+                  const int* H, int output_dim, int mode, int precision, void* workspace, size_t workspace_bytes, void* stream);
+int fil_cin_bwd_p(const float* x, const float* const* W, const float* const* bias, const float* dense_w,
+                  const float* pooled, const float* saved, const float* g, float* dx, float* const* dW,
+                  float* const* dbias, float* ddense_w, float* ddense_b, int B, int F, int K, int L, const int* H,
+                  int output_dim, int mode, int precision, void* const* grad_ready_events, void* workspace, size_t workspace_bytes,
+                  void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * A4  AutoInt interacting layer -- replaces MultHeadAttentionLayer.call + ProductAttentionLayer.call

@@ -228,11 +228,16 @@ static bool qmerge_used(const CinShape& s, int mode, const CinTune& tune) {
   return qtail_used(s, mode, tune) && 3 * s.F + 3 <= s.HSmax() && (mode & FIL_CIN_NOQMERGE) == 0 && knobs().qmerge != 0;   // (xe | gxR | dxR share one gradient buffer)
 }
 // ... on split-bf16 operands (cin_qsplit.h, FIL_CIN_BF16X3): where the merged kernels run in their full form and a split kernel exists
+// ... or on one bf16 plane per operand (FIL_CIN_PREC_BF16 of the _p entry points): the same places, the same kernels with NP = 1.  The
+// precision travels inside the library as a mode bit that the public entry points never accept (their modes stop at 1023).
+constexpr int kCinPrecBf16 = 1 << 20;
+static int qsplit_planes(int mode) { return (mode & kCinPrecBf16) != 0 ? 1 : 3; }
 static bool qsplit_fwd_menu(int JT) { return JT >= 2 && JT <= 12 && JT % 2 == 0; }   // (F <= 41 on the merged tail: JT <= 12)
 static bool qsplit_used(const CinShape& s, int mode, const CinTune& tune) {
-  return (mode & FIL_CIN_BF16X3) != 0 && qmerge_used(s, mode, tune) && knobs().fwdq != 0 && knobs().dz2 != 0 && s.HS(0) == 128 &&
+  return (mode & (FIL_CIN_BF16X3 | kCinPrecBf16)) != 0 && qmerge_used(s, mode, tune) && knobs().fwdq != 0 && knobs().dz2 != 0 && s.HS(0) == 128 &&
          qsplit_fwd_menu(cin_jt_sym(s.F));
 }
+// (three planes; the one-plane mode uses the first third of the same buffers)
 static size_t qsplit_wb_bytes(const CinShape& s) { return (size_t)cin_qs_steps(s.F, cin_jt_sym(s.F)) * kQsStageBytes; }
 static size_t qsplit_wzb_bytes(const CinShape& s) {     // one layer's slot-ordered weights as split planes (tiles x 8 steps x 3 KiB)
   const int jts = cin_jt_sym(s.F);
@@ -407,25 +412,57 @@ extern "C" int fil_cin_grad_ready_points(int B, int F, int K, int L, const int* 
   return pt;
 }
 
-extern "C" int fil_cin_fwd(const float* x, const float* const* W, const float* const* bias, const float* dense_w,
-                           const float* dense_b, float* out, float* pooled, float* saved, int B, int F, int K, int L,
-                           const int* H, int output_dim, int mode, void* workspace, size_t workspace_bytes, void* stream) {
+// FIL_CHECK_ARG inside the shared bodies of the fwd / bwd entry points: the message names the entry point called (`who`)
+#define FIL_CIN_CHECK_ARG(cond)                                                        \
+  do {                                                                                 \
+    if (!(cond)) return ::fil::fail(FIL_ERR_ARG, "%s: bad argument: %s", who, #cond); \
+  } while (0)
+
+// precision code of the _p entry points -> the internal mode bit (FIL_OK), or FIL_ERR_ARG
+static int cin_precision_bits(const char* who, int mode, int precision, int* bits) {
+  if (precision != FIL_CIN_PREC_DEFAULT && precision != FIL_CIN_PREC_BF16)
+    return fail(FIL_ERR_ARG, "%s: precision %d (0 DEFAULT, 1 BF16)", who, precision);
+  if (precision == FIL_CIN_PREC_BF16 && (mode & FIL_CIN_BF16X3) != 0)
+    return fail(FIL_ERR_ARG, "%s: precision BF16 with mode bit BF16X3 (mode %d): two operand precisions", who, mode);
+  *bits = precision == FIL_CIN_PREC_BF16 ? kCinPrecBf16 : 0;
+  return FIL_OK;
+}
+
+extern "C" int fil_cin_precision_used(int B, int F, int K, int L, const int* H, int mode, int precision) {
   CinShape s;
-  int rc = check_shape("fil_cin_fwd", B, F, K, L, H, s);
+  if (int rc = check_shape("fil_cin_precision_used", B, F, K, L, H, s)) return rc;
+  if (mode < 0 || mode > 1023 || (mode & kCinRetiredBits) != 0) return fail(FIL_ERR_UNSUPPORTED, "fil_cin_precision_used: mode %d", mode);
+  int bits = 0;
+  if (int rc = cin_precision_bits("fil_cin_precision_used", mode, precision, &bits)) return rc;
+  if (bits == 0 || B == 0) return FIL_CIN_PREC_DEFAULT;
+  return qsplit_used(s, mode | bits, CinTune(mode)) ? FIL_CIN_PREC_BF16 : FIL_CIN_PREC_DEFAULT;
+}
+
+static int cin_fwd_impl(const char* who, const float* x, const float* const* W, const float* const* bias, const float* dense_w,
+                        const float* dense_b, float* out, float* pooled, float* saved, int B, int F, int K, int L,
+                        const int* H, int output_dim, int mode, int precision, void* workspace, size_t workspace_bytes, void* stream) {
+  CinShape s;
+  int rc = check_shape(who, B, F, K, L, H, s);
   if (rc != FIL_OK) return rc;
   if (mode < 0 || mode > 1023 || (mode & kCinRetiredBits) != 0)
-    return fail(FIL_ERR_UNSUPPORTED, "fil_cin_fwd: mode %d (bits: 1 general kernels, 2 BF16X3, 4 MB2, 8 NOSYM, 16 X_TRANSPOSED, 32 NOTAIL, 64 TAIL_ALWAYS, 128 NOKSPLIT, 256 NOQTAIL, 512 NOQMERGE)", mode);
+    return fail(FIL_ERR_UNSUPPORTED, "%s: mode %d (bits: 1 general kernels, 2 BF16X3, 4 MB2, 8 NOSYM, 16 X_TRANSPOSED, 32 NOTAIL, 64 TAIL_ALWAYS, 128 NOKSPLIT, 256 NOQTAIL, 512 NOQMERGE)", who, mode);
+  {
+    int bits = 0;
+    if ((rc = cin_precision_bits(who, mode, precision, &bits)) != FIL_OK) return rc;
+    mode |= bits;
+  }
   const bool xt_in = (mode & FIL_CIN_X_TRANSPOSED) != 0;   // x is already [B*K][F] (fil_embed_gather_xt): no input transpose
   const CinTune tune(mode);
   const bool tail = tail_used(s, mode);                    // last two layers as one implicit GEMM (cin_tail.h)
   const bool qtail = qtail_used(s, mode, tune);            // ... as a quadratic form over field pairs (cin_qtail.h)
   const bool qmerge = qmerge_used(s, mode, tune);          // ... with merged launches (cin_qmerge.h)
   const bool qsplit = qsplit_used(s, mode, tune);          // ... on split-bf16 operands (cin_qsplit.h)
+  const int qnp = qsplit_planes(mode);                     //     of three planes each (BF16X3) or one (PREC_BF16)
   const TailGeom tg = tail_geom(s);
   mode &= 1;
   if (B == 0) return FIL_OK;
-  FIL_CHECK_ARG(x && W && bias && pooled && saved);
-  FIL_CHECK_ARG(output_dim != 1 || (dense_w && dense_b && out));
+  FIL_CIN_CHECK_ARG(x && W && bias && pooled && saved);
+  FIL_CIN_CHECK_ARG(output_dim != 1 || (dense_w && dense_b && out));
   if (workspace == nullptr || workspace_bytes < fwd_ws_bytes(s))
     return fail(FIL_ERR_WORKSPACE, "fil_cin_fwd: workspace %zu < %zu bytes", workspace_bytes, fwd_ws_bytes(s));
   hipStream_t st = (hipStream_t)stream;
@@ -476,7 +513,7 @@ extern "C" int fil_cin_fwd(const float* x, const float* const* W, const float* c
   // launch instead of four
   const bool prep_fused = tail && tune.sym;
   if (qtail) {
-    FIL_CHECK_ARG(W[0] && W[L - 1] && W[L - 2]);
+    FIL_CIN_CHECK_ARG(W[0] && W[L - 1] && W[L - 2]);
     ProfScope ps("cin_fwd_prep", st, 2.0 * M * F * sizeof(float));
     const int JTs = cin_jt_sym(F), chunks0 = chunks_of(H[0]);
     const long npack = (long)chunks0 * F * 2 * JTs * 128;
@@ -490,7 +527,7 @@ extern "C" int fil_cin_fwd(const float* x, const float* const* W, const float* c
     hipLaunchKernelGGL(cin_qtail_prep_kernel, dim3(nt + npk + nwl + nwp), dim3(256), sh, st, x, xT_own, F, K, nt, W[0], Wf, H[0], 2 * JTs, chunks0, npk,
                        W[L - 1], qtWsumL, tg.Hq, tg.HL, nwl, W[L - 2], qtWsumP, qtWsnP, tg.Hpp, 2 * JT, chunks_of(tg.Hpp), x2T, XL, xt_in ? 1 : 0);
   } else if (prep_fused) {
-    FIL_CHECK_ARG(W[0] && W[L - 1]);
+    FIL_CIN_CHECK_ARG(W[0] && W[L - 1]);
     ProfScope ps("cin_fwd_prep", st, 2.0 * M * F * sizeof(float));
     const int JTs = cin_jt_sym(F), chunks0 = chunks_of(H[0]);
     const long npack = (long)chunks0 * F * 2 * JTs * 128;
@@ -510,12 +547,12 @@ extern "C" int fil_cin_fwd(const float* x, const float* const* W, const float* c
   bool fused_last = false;   // the last layer's sum-pool was produced by the epilogue of the layer below
   bool head_done = false;    // merged forward: pooled and out came out of cin_fwdq_kernel's epilogue
   for (int l = 0; l < L; ++l) {
-    FIL_CHECK_ARG(W[l] && bias[l]);
+    FIL_CIN_CHECK_ARG(W[l] && bias[l]);
     if (qtail && qmerge && l == 0 && knobs().fwdq != 0 && s.HS(0) == 128) {
       // ---- merged quadratic tail, forward (cin_qmerge.h): [x1 | R] = pairs(x) [W1s | Ts] in ONE launch of 256 columns, all three
       // sum-pools in its epilogue.  T (and its packed operand copies) depend on the weights alone: they come first.
       const int p = tg.p, lL = L - 1, Hpp = tg.Hpp, Hq = tg.Hq, HS0 = s.HS(0);
-      FIL_CHECK_ARG(W[p] && W[lL] && bias[p] && bias[lL]);
+      FIL_CIN_CHECK_ARG(W[p] && W[lL] && bias[p] && bias[lL]);
       const int JTs = cin_jt_sym(F), chunks = chunks_of(Hpp);
       float* x1T = sv.take<float>((size_t)M * HS0);   // (the first layer's map: same place in `saved` as on the other paths)
       {
@@ -541,8 +578,12 @@ extern "C" int fil_cin_fwd(const float* x, const float* const* W, const float* c
           const int nbf = (int)std::min<long>((npack + 255) / 256, 1024), nbz = (int)std::min<long>(((long)tiles * 32 * HS0 + 255) / 256, 1024);
           // (split-bf16 mode: + the forward's planes of [W1s | Ts], from W1 and T themselves)
           const int NTq = qsplit ? cin_qs_steps(F, JTs) : 0, nbq = qsplit ? std::min(cdiv(NTq * 512, 256), 512) : 0;
-          hipLaunchKernelGGL(cin_qtail_pack_kernel, dim3(nbf + nbz + nbq), dim3(256), 0, st, qtT, WfT, qtWzT, F, Hpp, JTs, chunks, nbf, HS0, tiles, nbz, W[0],
-                             H[0], Wb, NTq);
+          if (qnp == 1)
+            hipLaunchKernelGGL(cin_qtail_pack_kernel<1>, dim3(nbf + nbz + nbq), dim3(256), 0, st, qtT, WfT, qtWzT, F, Hpp, JTs, chunks, nbf, HS0, tiles, nbz,
+                               W[0], H[0], Wb, NTq);
+          else
+            hipLaunchKernelGGL(cin_qtail_pack_kernel<3>, dim3(nbf + nbz + nbq), dim3(256), 0, st, qtT, WfT, qtWzT, F, Hpp, JTs, chunks, nbf, HS0, tiles, nbz,
+                               W[0], H[0], Wb, NTq);
         }
       }
       FIL_CHECK_LAUNCH();
@@ -560,7 +601,7 @@ extern "C" int fil_cin_fwd(const float* x, const float* const* W, const float* c
         if (qsplit) {
           // split-bf16 operands (their planes came out of the pack launch above): the same GEMM on the bf16 pipe
           const int NT = cin_qs_steps(F, JTs);
-          if (!cin_launch_fwdq_b(st, JTs, x2T, XL, Wb, NT, bias[0], qtWsnP, JT, qtCvec, x1T, qtR, HS0, const_cast<float*>(pa.part[0]),
+          if (!cin_launch_fwdq_b(st, qnp, JTs, x2T, XL, Wb, NT, bias[0], qtWsnP, JT, qtCvec, x1T, qtR, HS0, const_cast<float*>(pa.part[0]),
                                  const_cast<float*>(pa.part[p]), const_cast<float*>(pa.part[lL]), (int)M, F, H[0], hf))
             return fail(FIL_ERR_UNSUPPORTED, "fil_cin_fwd: no split-bf16 forward kernel for JT=%d (F=%d)", JTs, F);
         } else if (!cin_launch_fwdq(st, JTs, x2T, XL, Wf, WfT, bias[0], qtWsnP, JT, qtCvec, x1T, qtR, HS0, const_cast<float*>(pa.part[0]),
@@ -575,7 +616,7 @@ extern "C" int fil_cin_fwd(const float* x, const float* const* W, const float* c
       // ---- quadratic tail (cin_qtail.h): R = (pairs of x) T through the first layer's pair-symmetric forward kernel,
       // pool_L = <x1, R> + <x, c> + const, pool_p through the pooled-weights shortcut
       const int lL = L - 1, Hpp = tg.Hpp, Hq = tg.Hq, HS0 = s.HS(0);
-      FIL_CHECK_ARG(W[lL] && bias[lL]);
+      FIL_CIN_CHECK_ARG(W[lL] && bias[lL]);
       const int JTs = cin_jt_sym(F), chunks = chunks_of(Hpp);
       {
         ProfScope ps("cin_tail_prep", st);
@@ -587,7 +628,7 @@ extern "C" int fil_cin_fwd(const float* x, const float* const* W, const float* c
         const long npack = (long)chunks * F * 2 * JTs * 128;
         const int tiles = cdiv(F, cin_dz_h_per_period(JTs)) * cin_dz_tiles_per_period(JTs) + 1;
         const int nbf = (int)std::min<long>((npack + 255) / 256, 1024), nbz = (int)std::min<long>(((long)tiles * 32 * HS0 + 255) / 256, 1024);
-        hipLaunchKernelGGL(cin_qtail_pack_kernel, dim3(nbf + nbz), dim3(256), 0, st, qtT, Wf, qtWzT, F, Hpp, JTs, chunks, nbf, HS0, tiles);
+        hipLaunchKernelGGL(cin_qtail_pack_kernel<3>, dim3(nbf + nbz), dim3(256), 0, st, qtT, Wf, qtWzT, F, Hpp, JTs, chunks, nbf, HS0, tiles);
       }
       FIL_CHECK_LAUNCH();
       {
@@ -617,7 +658,7 @@ extern "C" int fil_cin_fwd(const float* x, const float* const* W, const float* c
     if (tail && l == tg.p) {
       // ---- fused tail: layers p = L-2 and L-1 through Ueff = W_p [1 | wsum_L]: F+1 output columns instead of H_p
       const int lL = L - 1;
-      FIL_CHECK_ARG(W[lL] && bias[lL]);
+      FIL_CIN_CHECK_ARG(W[lL] && bias[lL]);
       float* Y = tailY;
       float* Uz = tailUz;
       float* bmT = tailBmT;
@@ -680,7 +721,7 @@ extern "C" int fil_cin_fwd(const float* x, const float* const* W, const float* c
         hipLaunchKernelGGL(cin_pack_wf_kernel, dim3((int)std::min<long>((npack + 255) / 256, 2048)), dim3(256), 0, st, W[l], Wf, Hp, F, Hl, 2 * JT, chunks);
         const float* wsn = nullptr;
         if (fuse_next) {
-          FIL_CHECK_ARG(W[l + 1] && bias[l + 1]);
+          FIL_CIN_CHECK_ARG(W[l + 1] && bias[l + 1]);
           float* wsn_buf = Wf + (size_t)npack;   // behind this layer's packed weights
           hipLaunchKernelGGL(cin_wsum_wsn_kernel, dim3(cdiv(Hl * F, 8)), dim3(256), 0, st, W[l + 1], wsum, Hl * F, H[l + 1], wsn_buf, Hl, F, 2 * JT,
                              chunks);
@@ -705,25 +746,45 @@ extern "C" int fil_cin_fwd(const float* x, const float* const* W, const float* c
   return FIL_OK;
 }
 
-extern "C" int fil_cin_bwd(const float* x, const float* const* W, const float* const* bias, const float* dense_w,
-                           const float* pooled, const float* saved, const float* g, float* dx, float* const* dW,
-                           float* const* dbias, float* ddense_w, float* ddense_b, int B, int F, int K, int L, const int* H,
-                           int output_dim, int mode, void* const* grad_ready_events, void* workspace, size_t workspace_bytes,
-                           void* stream) {
+extern "C" int fil_cin_fwd(const float* x, const float* const* W, const float* const* bias, const float* dense_w,
+                           const float* dense_b, float* out, float* pooled, float* saved, int B, int F, int K, int L,
+                           const int* H, int output_dim, int mode, void* workspace, size_t workspace_bytes, void* stream) {
+  return cin_fwd_impl("fil_cin_fwd", x, W, bias, dense_w, dense_b, out, pooled, saved, B, F, K, L, H, output_dim, mode, FIL_CIN_PREC_DEFAULT, workspace,
+                      workspace_bytes, stream);
+}
+
+extern "C" int fil_cin_fwd_p(const float* x, const float* const* W, const float* const* bias, const float* dense_w,
+                             const float* dense_b, float* out, float* pooled, float* saved, int B, int F, int K, int L,
+                             const int* H, int output_dim, int mode, int precision, void* workspace, size_t workspace_bytes, void* stream) {
+  return cin_fwd_impl("fil_cin_fwd_p", x, W, bias, dense_w, dense_b, out, pooled, saved, B, F, K, L, H, output_dim, mode, precision, workspace,
+                      workspace_bytes, stream);
+}
+
+static int cin_bwd_impl(const char* who, const float* x, const float* const* W, const float* const* bias, const float* dense_w,
+                        const float* pooled, const float* saved, const float* g, float* dx, float* const* dW,
+                        float* const* dbias, float* ddense_w, float* ddense_b, int B, int F, int K, int L, const int* H,
+                        int output_dim, int mode, int precision, void* const* grad_ready_events, void* workspace, size_t workspace_bytes,
+                        void* stream) {
   CinShape s;
-  int rc = check_shape("fil_cin_bwd", B, F, K, L, H, s);
+  int rc = check_shape(who, B, F, K, L, H, s);
   if (rc != FIL_OK) return rc;
   if (mode < 0 || mode > 1023 || (mode & kCinRetiredBits) != 0)
-    return fail(FIL_ERR_UNSUPPORTED, "fil_cin_bwd: mode %d (bits: 1 general kernels, 2 BF16X3, 4 MB2, 8 NOSYM, 16 X_TRANSPOSED, 32 NOTAIL, 64 TAIL_ALWAYS, 128 NOKSPLIT, 256 NOQTAIL, 512 NOQMERGE)", mode);
+    return fail(FIL_ERR_UNSUPPORTED, "%s: mode %d (bits: 1 general kernels, 2 BF16X3, 4 MB2, 8 NOSYM, 16 X_TRANSPOSED, 32 NOTAIL, 64 TAIL_ALWAYS, 128 NOKSPLIT, 256 NOQTAIL, 512 NOQMERGE)", who, mode);
+  {
+    int bits = 0;
+    if ((rc = cin_precision_bits(who, mode, precision, &bits)) != FIL_OK) return rc;
+    mode |= bits;
+  }
   const bool xt_in = (mode & FIL_CIN_X_TRANSPOSED) != 0;
   const CinTune tune(mode);
   const bool tail = tail_used(s, mode);
   const bool qtail = qtail_used(s, mode, tune);
   const bool qmerge = qmerge_used(s, mode, tune);
   const bool qsplit = qsplit_used(s, mode, tune);
+  const int qnp = qsplit_planes(mode);
   const TailGeom tg = tail_geom(s);
   mode &= 1;
-  FIL_CHECK_ARG(W && dW && dbias);
+  FIL_CIN_CHECK_ARG(W && dW && dbias);
   hipStream_t st = (hipStream_t)stream;
   const size_t LK = (size_t)L * K;
   // grad_ready_events[l] (l < L): recorded once dW[l] and dbias[l] are final; [L]: the dense head's gradients.  The
@@ -744,8 +805,8 @@ extern "C" int fil_cin_bwd(const float* x, const float* const* W, const float* c
     for (int l = 0; l <= L; ++l) ready(l);
     return FIL_OK;
   }
-  FIL_CHECK_ARG(g && dx && saved && (x || !xt_in));
-  FIL_CHECK_ARG(output_dim != 1 || (dense_w && pooled && ddense_w && ddense_b));
+  FIL_CIN_CHECK_ARG(g && dx && saved && (x || !xt_in));
+  FIL_CIN_CHECK_ARG(output_dim != 1 || (dense_w && pooled && ddense_w && ddense_b));
   if (workspace == nullptr || workspace_bytes < bwd_ws_bytes(s))
     return fail(FIL_ERR_WORKSPACE, "fil_cin_bwd: workspace %zu < %zu bytes", workspace_bytes, bwd_ws_bytes(s));
   const long M = s.M();
@@ -825,7 +886,7 @@ extern "C" int fil_cin_bwd(const float* x, const float* const* W, const float* c
     // gradients stay two launches of the pair-symmetric dZ kernel (G1 with W1, then the unscaled x1 with T, scaled by dP_L in the
     // final transpose).  G1 = dP_p S + dP_1 + dP_L R and the shortcut's dX part come out of cin_last_bwd2_kernel.
     const int p = tg.p, lL = L - 1, Hpp = tg.Hpp, Hq = tg.Hq, HS0 = s.HS(0);
-    FIL_CHECK_ARG(bias && W[0] && W[p] && W[lL] && bias[p] && dW[0] && dW[p] && dW[lL] && dbias[0] && dbias[p] && dbias[lL]);
+    FIL_CIN_CHECK_ARG(bias && W[0] && W[p] && W[lL] && bias[p] && dW[0] && dW[p] && dW[lL] && dbias[0] && dbias[p] && dbias[lL]);
     const float* xpT = maps[p - 1];
     const int xps = s.xps(p);
     const float* dPp = dPsrc + (size_t)p * K;
@@ -845,13 +906,19 @@ extern "C" int fil_cin_bwd(const float* x, const float* const* W, const float* c
     {
       ProfScope ps("cin_tail_a", st, (double)M * (2 * F + 3) * sizeof(float));
       const size_t sh = (size_t)256 * (F + 3 + (output_dim == 1 ? L : 0)) * sizeof(float);
-      allow_lds(cin_qtail_xe_kernel, sh);
+      allow_lds(cin_qtail_xe_kernel<3>, sh);
+      allow_lds(cin_qtail_xe_kernel<1>, sh);
       const int np = (int)std::min<long>(((long)tiles0 * 32 * HS0 + 255) / 256, 1024);   // + W1 in the dZ kernel's slot order
       const int nq2 = qsplit ? 2 * std::min(cdiv(tiles0 * 512, 256), 256) : 0;           // + (split-bf16 mode) W1s and Ts in slot order as planes
       // (output_dim == 1: + the dense head's backward -- dP and the block partials of ddense_w | ddense_b)
-      hipLaunchKernelGGL(cin_qtail_xe_kernel, dim3(qt_ndc + np + nq2), dim3(kXeThreads), sh, st, xT, dPL, dPp, (int)LK, K, xe, qt_dcpart, (int)M, F, qt_ndc,
-                         output_dim == 1 ? g : nullptr, dense_w, pooled, dP, qt_hpart, (int)LK, lL, p, W[0], Wz, H[0], JTs, HS0, tiles0, np, qtT, Hpp,
-                         Wzb1, Wzb2);
+      if (qnp == 1)
+        hipLaunchKernelGGL(cin_qtail_xe_kernel<1>, dim3(qt_ndc + np + nq2), dim3(kXeThreads), sh, st, xT, dPL, dPp, (int)LK, K, xe, qt_dcpart, (int)M, F,
+                           qt_ndc, output_dim == 1 ? g : nullptr, dense_w, pooled, dP, qt_hpart, (int)LK, lL, p, W[0], Wz, H[0], JTs, HS0, tiles0, np, qtT,
+                           Hpp, Wzb1, Wzb2);
+      else
+        hipLaunchKernelGGL(cin_qtail_xe_kernel<3>, dim3(qt_ndc + np + nq2), dim3(kXeThreads), sh, st, xT, dPL, dPp, (int)LK, K, xe, qt_dcpart, (int)M, F,
+                           qt_ndc, output_dim == 1 ? g : nullptr, dense_w, pooled, dP, qt_hpart, (int)LK, lL, p, W[0], Wz, H[0], JTs, HS0, tiles0, np, qtT,
+                           Hpp, Wzb1, Wzb2);
     }
     FIL_CHECK_LAUNCH();
     {
@@ -864,7 +931,7 @@ extern "C" int fil_cin_bwd(const float* x, const float* const* W, const float* c
       ProfScope ps("cin_bwd_dw_q", st, algo1 + algo_tail, gemm_flops(M, 1, Cl, H[0]) + gemm_flops(M, 1, Cl, Hpp));
       if (qsplit) {   // split-bf16 operands (cin_qsplit.h): one partial per row split
         const DwqbPlan bp = cin_dwqb_plan(M, Cl + F, cu_count());
-        cin_launch_dwq_b(st, bp, Gbuf[cur], xpT, HS0, xe, XE, part, (int)M, F, symD);
+        cin_launch_dwq_b(st, qnp, bp, Gbuf[cur], xpT, HS0, xe, XE, part, (int)M, F, symD);
         dw_parts = bp.splits;
       } else {
         const bool f4 = knobs().dwfold4 != 0;
@@ -910,7 +977,7 @@ extern "C" int fil_cin_bwd(const float* x, const float* const* W, const float* c
       // (the kernel also finishes dx: + the shortcut's part in dxT, + dP_L c, transposed to [B,F,K] on the way out)
       bool split_done = false;
       if (qsplit) {   // split-bf16 operands (the planes of both layers' slot-ordered weights came out of the operand-row launch)
-        split_done = cin_launch_dz2_b(st, JTs, Gbuf[cur], xpT, HS0, dPL, (int)LK, K, Wzb1, Wzb2, xT, dxT, /*accumulate=*/1, (int)M, F, H[0], Hpp, periods, dx, qtCvec);
+        split_done = cin_launch_dz2_b(st, qnp, JTs, Gbuf[cur], xpT, HS0, dPL, (int)LK, K, Wzb1, Wzb2, xT, dxT, /*accumulate=*/1, (int)M, F, H[0], Hpp, periods, dx, qtCvec);
       }
       if (!split_done &&
           !cin_launch_dz2(st, JTs, Gbuf[cur], xpT, HS0, dPL, (int)LK, K, Wz, qtWzT, xT, dxT, /*accumulate=*/1, (int)M, F, H[0], Hpp, periods, dx, qtCvec))
@@ -941,7 +1008,7 @@ extern "C" int fil_cin_bwd(const float* x, const float* const* W, const float* c
     // first layer's pair-symmetric dW / dZ kernels with x1 (unscaled) as their "gradient" operand: dT = (pairs of x, one factor scaled
     // by dP_L)^T x1, the two halves of d<x1,R>/dx come out per row and are scaled by dP_L afterwards; G^{p-1} += dP_L R is elementwise.
     const int p = tg.p, lL = L - 1, Hpp = tg.Hpp, Hq = tg.Hq, HS0 = s.HS(0);
-    FIL_CHECK_ARG(bias && W[p] && W[lL] && bias[p] && dW[p] && dW[lL] && dbias[p] && dbias[lL]);
+    FIL_CIN_CHECK_ARG(bias && W[p] && W[lL] && bias[p] && dW[p] && dW[lL] && dbias[p] && dbias[lL]);
     const float* xpT = maps[p - 1];
     const int xps = s.xps(p);
     const float* dPp = dPsrc + (size_t)p * K;
@@ -958,7 +1025,7 @@ extern "C" int fil_cin_bwd(const float* x, const float* const* W, const float* c
       allow_lds(cin_qtail_scale_kernel, sh);
       const int nh = output_dim == 1 ? cdiv((int)LK + 1, 64) : 0;   // + the head's partial sums (as in the fused tail's first launch)
       // ... and the first layer's dZ weights in slot order (the packed-W buffer is idle until that layer's dZ kernel)
-      FIL_CHECK_ARG(W[0]);
+      FIL_CIN_CHECK_ARG(W[0]);
       const int JTs0 = cin_jt_sym(F);
       const int tiles0 = cdiv(F, cin_dz_h_per_period(JTs0)) * cin_dz_tiles_per_period(JTs0) + 1;
       const int np = (int)std::min<long>(((long)tiles0 * 32 * HS0 + 255) / 256, 1024);
@@ -1017,7 +1084,7 @@ extern "C" int fil_cin_bwd(const float* x, const float* const* W, const float* c
   } else if (tail) {
     // ---- fused tail: both top layers' parameter gradients from Q = Z_p^T A (F+2 columns), data gradients from A Ueff^T
     const int p = tg.p, lL = L - 1;
-    FIL_CHECK_ARG(bias && W[p] && W[lL] && bias[p] && dW[p] && dW[lL] && dbias[p] && dbias[lL]);
+    FIL_CIN_CHECK_ARG(bias && W[p] && W[lL] && bias[p] && dW[p] && dW[lL] && dbias[p] && dbias[lL]);
     const float* xpT = maps[p - 1];
     const int xps = s.xps(p);
     const double algo = gemm_flops(M, tg.Hpp, F, tg.Hq) + gemm_flops(M, tg.Hq, F, tg.HL);   // the two layers of the reference graph
@@ -1031,7 +1098,7 @@ extern "C" int fil_cin_bwd(const float* x, const float* const* W, const float* c
       const int nh = output_dim == 1 ? cdiv((int)LK + 1, 64) : 0;
       int np = 0, JTs = 0, tiles0 = 0;
       if (wz_prepacked) {
-        FIL_CHECK_ARG(W[0]);
+        FIL_CIN_CHECK_ARG(W[0]);
         JTs = cin_jt_sym(F);
         tiles0 = cdiv(F, cin_dz_h_per_period(JTs)) * cin_dz_tiles_per_period(JTs) + 1;
         np = (int)std::min<long>(((long)tiles0 * 32 * s.HS(0) + 255) / 256, 1024);
@@ -1077,7 +1144,7 @@ extern "C" int fil_cin_bwd(const float* x, const float* const* W, const float* c
   } else if (mode == 0) {
     // ---- last layer through the pooled-weights shortcut (see cin_last_* kernels)
     const int l = L - 1;
-    FIL_CHECK_ARG(W[l] && dW[l] && dbias[l]);
+    FIL_CIN_CHECK_ARG(W[l] && dW[l] && dbias[l]);
     const int Hp = s.Hp(l), Hl = H[l], xps = s.xps(l);
     const float* xpT = l == 0 ? xT : maps[l - 1];
     const float* dPl = dPsrc + (size_t)l * K;
@@ -1130,7 +1197,7 @@ extern "C" int fil_cin_bwd(const float* x, const float* const* W, const float* c
     FIL_CHECK_LAUNCH();
   }
   for (int l = ltop; l >= 0; --l) {
-    FIL_CHECK_ARG(W[l] && dW[l] && dbias[l]);
+    FIL_CIN_CHECK_ARG(W[l] && dW[l] && dbias[l]);
     const int Hp = s.Hp(l), Hl = H[l], HSl = s.HS(l), xps = s.xps(l);
     const float* xpT = l == 0 ? xT : maps[l - 1];
     const float* G = Gbuf[cur];
@@ -1215,4 +1282,22 @@ extern "C" int fil_cin_bwd(const float* x, const float* const* W, const float* c
   }
   FIL_CHECK_LAUNCH();
   return FIL_OK;
+}
+
+extern "C" int fil_cin_bwd(const float* x, const float* const* W, const float* const* bias, const float* dense_w,
+                           const float* pooled, const float* saved, const float* g, float* dx, float* const* dW,
+                           float* const* dbias, float* ddense_w, float* ddense_b, int B, int F, int K, int L, const int* H,
+                           int output_dim, int mode, void* const* grad_ready_events, void* workspace, size_t workspace_bytes,
+                           void* stream) {
+  return cin_bwd_impl("fil_cin_bwd", x, W, bias, dense_w, pooled, saved, g, dx, dW, dbias, ddense_w, ddense_b, B, F, K, L, H, output_dim, mode,
+                      FIL_CIN_PREC_DEFAULT, grad_ready_events, workspace, workspace_bytes, stream);
+}
+
+extern "C" int fil_cin_bwd_p(const float* x, const float* const* W, const float* const* bias, const float* dense_w,
+                             const float* pooled, const float* saved, const float* g, float* dx, float* const* dW,
+                             float* const* dbias, float* ddense_w, float* ddense_b, int B, int F, int K, int L, const int* H,
+                             int output_dim, int mode, int precision, void* const* grad_ready_events, void* workspace, size_t workspace_bytes,
+                             void* stream) {
+  return cin_bwd_impl("fil_cin_bwd_p", x, W, bias, dense_w, pooled, saved, g, dx, dW, dbias, ddense_w, ddense_b, B, F, K, L, H, output_dim, mode,
+                      precision, grad_ready_events, workspace, workspace_bytes, stream);
 }

@@ -326,6 +326,7 @@ static __global__ __launch_bounds__(256) void cin_reduce_expand_q_kernel(const f
 // (cf. cin_qtail_scale_kernel).  Further workgroups: [nscale, +nhead) the dense head's partial sums -> ddense_w | ddense_b; the
 // rest: the first layer's pair weights in the dZ kernel's slot order.   LDS: [256][F + 3 + L].  kXeThreads threads.
 constexpr int kXeThreads = 1024;
+template <int NP = 3>   // planes of the split-bf16 modes' weights
 static __global__ __launch_bounds__(kXeThreads) void cin_qtail_xe_kernel(const float* __restrict__ xT, const float* __restrict__ dPL,
                                                                   const float* __restrict__ dPp, int ldp, int K, float* __restrict__ xe,
                                                                   float* __restrict__ dcpart, int M, int F, int nscale,
@@ -343,8 +344,8 @@ static __global__ __launch_bounds__(kXeThreads) void cin_qtail_xe_kernel(const f
     if (b < npz) cin_pack_wz_sym_body(W0, Wz, F, H0, JTs, HS0, tiles0, b, npz);
     else {   // split-bf16 mode: both layers' slot-ordered weights as planes (cin_qs_pack_wz_body), half of the extra workgroups each
       const int nq = ((int)gridDim.x - nscale - npz) >> 1, q = b - npz;
-      if (q < nq) cin_qs_pack_wz_body(W0, H0, Wzb1, tiles0, F, JTs, q, nq);
-      else if (q < 2 * nq) cin_qs_pack_wz_body(Tq, HT, Wzb2, tiles0, F, JTs, q - nq, nq);
+      if (q < nq) cin_qs_pack_wz_body<NP>(W0, H0, Wzb1, tiles0, F, JTs, q, nq);
+      else if (q < 2 * nq) cin_qs_pack_wz_body<NP>(Tq, HT, Wzb2, tiles0, F, JTs, q - nq, nq);
     }
     return;
   }

@@ -10,6 +10,11 @@
 // A bf16 piece keeps fp32's exponent range, so there is no scaling; what differs from the exact kernels: the accumulation order
 // (six partial products per term), and an infinite operand gives NaN (inf - inf in its second piece) where the exact chain gives inf.
 //
+// One-plane mode (FIL_CIN_PREC_BF16 of fil_cin_fwd_p / fil_cin_bwd_p; template argument NP = 1, the split is NP = 3): the same three
+// kernels with every operand rounded ONCE to bf16 (nearest even, v_cvt_pk_bf16_f32) and one MFMA per product -- a sixth of the matrix
+// work and a third of the plane bytes; the result carries one bf16 rounding per operand (~1e-3 relative), so it is a mode of its own.
+// The NP = 3 instantiations are the split kernels as they were (same ISA).
+//
 // MFMA 32x32x16 operand maps: lane (r = lane & 31, half = lane >> 5) supplies A[i = r][k = 8 half .. 8 half + 7] and
 // B[k = 8 half .. 8 half + 7][j = r], eight bf16 in four dwords; the accumulator layout is the 32x32x2 one (mfma32_row).
 #pragma once
@@ -26,15 +31,19 @@ namespace fil {
 //     registers instead is 24 KB per wave and step: 64 B/clk/CU at two waves per SIMD, the whole L1 bandwidth.
 //   A (generated): the lane keeps a sliding window of its row's wrapped positions (x2T, cin_transpose_in_body) over the period's HPS
 //     values of h -- product, cut, pack: ~60 vector instructions per step, issued in the shadow of the step's 48 MFMAs, one step ahead.
-template <int JT, int NW>   // NW waves per workgroup: 8 (one workgroup per CU, ring of 4) or 4 (two independent ones per CU, rings of 3)
+// One plane (NP = 1): 8 KB per step, so the ring of each 4-wave workgroup is kQbStages deep -- five steps of DMA ahead instead of two, for
+// steps that now hold 8 MFMAs per wave instead of 48 (48 KB of LDS per workgroup, two per CU).
+constexpr int kQbStages = 6;
+template <int JT, int NW, int NP = 3>   // NW waves per workgroup: 8 (one workgroup per CU, ring of 4) or 4 (two independent ones per CU, rings of 3)
 __global__ __launch_bounds__(64 * NW, 2) void cin_fwdq_b_kernel(const float* __restrict__ x2T, int XL, const u32x4* __restrict__ Wb, int NT,
                                                             const float* __restrict__ bias1, const float* __restrict__ wsn, int JTG,
                                                             const float* __restrict__ cvec, float* __restrict__ x1T, float* __restrict__ RT, int HS,
                                                             float* __restrict__ pool1, float* __restrict__ pool_p, float* __restrict__ pool_L, int M, int F,
                                                             int H, CinHeadFold hf) {
   using G = QsGeo<JT>;
-  constexpr int HPS = G::HPS, KP = G::KP, WS = G::WS, NS = NW == 8 ? kQsStages : 3, SB = kQsStageBytes;
-  constexpr int PW = 24 / NW;                                            // 1-KB DMA pieces of a step per wave
+  constexpr int HPS = G::HPS, KP = G::KP, WS = G::WS, NS = NP == 1 ? kQbStages : NW == 8 ? kQsStages : 3, SB = qs_stage_bytes(NP);
+  constexpr int PW = 8 * NP / NW;                                        // 1-KB DMA pieces of a step per wave
+  static_assert(PW * NW == 8 * NP, "a step is a whole number of pieces per wave");
   extern __shared__ __attribute__((aligned(16))) unsigned char ring[];   // [NS][SB]
   __shared__ float lin_s[NW][32];
   __shared__ float pv_s[NW][3][32];
@@ -77,25 +86,25 @@ __global__ __launch_bounds__(64 * NW, 2) void cin_fwdq_b_kernel(const float* __r
 #pragma unroll
   for (int s = 0; s < NS - 1; ++s) dma(s);
   // A operand of a step of the current period / of the first step of the next one
-  auto make_a = [&](int kk, u32x4 (&a)[3]) {
+  auto make_a = [&](int kk, u32x4 (&a)[NP]) {
     float p[8];
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
       const int st = 8 * kk + e;   // compile-time
       p[e] = xp[st / JT] * wl[st / JT + 2 * (st % JT)];
     }
-    split3(p, a);
+    split_planes<NP>(p, a);
   };
-  auto make_a_next = [&](const float (&xnm)[HPS], u32x4 (&a)[3]) {
+  auto make_a_next = [&](const float (&xnm)[HPS], u32x4 (&a)[NP]) {
     float p[8];
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
       const int t = HPS + e / JT + 2 * (e % JT);   // the next period's window is this one shifted by HPS, its tail = wn
       p[e] = xnm[e / JT] * (t < WS ? wl[t < WS ? t : 0] : wn[t >= WS ? t - WS : 0]);
     }
-    split3(p, a);
+    split_planes<NP>(p, a);
   };
-  u32x4 acur[3], anext[3];
+  u32x4 acur[NP], anext[NP];
   make_a(0, acur);
   const int nper = NT / KP;
   const int ldsb = lane * 16;
@@ -130,19 +139,19 @@ __global__ __launch_bounds__(64 * NW, 2) void cin_fwdq_b_kernel(const float* __r
         make_a_next(xn, anext);
       }
       const unsigned char* sb = ring + (t % NS) * SB + ldsb;
-      u32x4 b[2][3];
+      u32x4 b[2][NP];
 #pragma unroll
-      for (int pl = 0; pl < 3; ++pl) b[0][pl] = *reinterpret_cast<const u32x4*>(sb + (pl * 8) * 1024);
+      for (int pl = 0; pl < NP; ++pl) b[0][pl] = *reinterpret_cast<const u32x4*>(sb + (pl * 8) * 1024);
 #pragma unroll
       for (int nb = 0; nb < 8; ++nb) {
         if (nb + 1 < 8) {
 #pragma unroll
-          for (int pl = 0; pl < 3; ++pl) b[(nb + 1) & 1][pl] = *reinterpret_cast<const u32x4*>(sb + (pl * 8 + nb + 1) * 1024);
+          for (int pl = 0; pl < NP; ++pl) b[(nb + 1) & 1][pl] = *reinterpret_cast<const u32x4*>(sb + (pl * 8 + nb + 1) * 1024);
         }
-        acc[nb] = mfma_split(acur, b[nb & 1], acc[nb]);
+        acc[nb] = mfma_planes<NP>(acur, b[nb & 1], acc[nb]);
       }
 #pragma unroll
-      for (int pl = 0; pl < 3; ++pl) acur[pl] = anext[pl];
+      for (int pl = 0; pl < NP; ++pl) acur[pl] = anext[pl];
     }
     // slide the window
 #pragma unroll
@@ -167,8 +176,9 @@ __global__ __launch_bounds__(64 * NW, 2) void cin_fwdq_b_kernel(const float* __r
 // steps deep, 16-byte scalar-offset buffer loads): 24 KB per tile and wave -- the LDS holds the two workgroups' dX images, there is no
 // room for a shared ring, so this kernel is bound by the L1 (64 B/clk/CU = its MFMA time at two waves per SIMD).
 //
-// Wzb [tile][step t][plane][lane][8 bf16]: cin_qs_pack_wz_body (cin_split.h).
-template <int JT, int G>
+// Wzb [tile][step t][plane][lane][8 bf16]: cin_qs_pack_wz_body (cin_split.h).  One plane (NP = 1): 8 KB per tile and wave from the L1,
+// the MFMA time a sixth: the slot contraction (~140 instructions per 256 cycles of MFMA) is what the tile waits on.
+template <int JT, int G, int NP = 3>
 __global__ __launch_bounds__(256, 2) void cin_dz2_b_kernel(const float* __restrict__ g1T, const float* __restrict__ g2T, int HS,
                                                            const float* __restrict__ dsc, int ldp, int K, const u32x4* __restrict__ Wzb1,
                                                            const u32x4* __restrict__ Wzb2, const float* __restrict__ xT, float* __restrict__ dxT,
@@ -212,11 +222,11 @@ __global__ __launch_bounds__(256, 2) void cin_dz2_b_kernel(const float* __restri
     dpl = dsc[bb * ldp + (mq - bb * K)];
   }
   __builtin_amdgcn_wave_barrier();
-  const long wbytes = ((long)periods * P + 1) * NT * 3 * 1024;
+  const long wbytes = ((long)periods * P + 1) * NT * NP * 1024;
   const int wo = lane * 16;
   // B operand of the current pass: the lane's half row (columns past the layer's width and rows past M zeroed; pass 1: scaled by dP_L),
   // cut into the planes of the tile's eight steps
-  u32x4 gpl[NT][3];
+  u32x4 gpl[NT][NP];
   auto to_gpl = [&](const f32x4s (&gv4)[16], int Hk, float sc) {
 #pragma unroll
     for (int t = 0; t < NT; ++t) {
@@ -227,7 +237,7 @@ __global__ __launch_bounds__(256, 2) void cin_dz2_b_kernel(const float* __restri
         const float gv = gv4[2 * t + (e >> 2)][e & 3];   // (a copy: __builtin_bit_cast on the vector ELEMENT expression reads element 0 for every e)
         p[e] = __builtin_bit_cast(float, __builtin_bit_cast(int, gv) & keep) * sc;
       }
-      split3(p, gpl[t]);
+      split_planes<NP>(p, gpl[t]);
     }
   };
   to_gpl(gq, H1, 1.f);
@@ -239,14 +249,14 @@ __global__ __launch_bounds__(256, 2) void cin_dz2_b_kernel(const float* __restri
     const float sc = pass == 0 ? 1.f : dpl;
     const __amdgpu_buffer_rsrc_t rw = make_rsrc(reinterpret_cast<const float*>(pass == 0 ? Wzb1 : Wzb2), wbytes);
     auto ldw = [&](int t, int st, int pl) {   // step st of tile t
-      return __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rw, wo + pl * 1024, (t * NT + st) * 3072, 0));
+      return __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rw, wo + pl * 1024, (t * NT + st) * (NP * 1024), 0));
     };
     constexpr int QD = 4;   // queue depth in steps (half a tile)
-    u32x4 q[QD][3];
+    u32x4 q[QD][NP];
 #pragma unroll
     for (int st = 0; st < QD; ++st)
 #pragma unroll
-      for (int pl = 0; pl < 3; ++pl) q[st][pl] = ldw(0, st, pl);
+      for (int pl = 0; pl < NP; ++pl) q[st][pl] = ldw(0, st, pl);
     if (pass == 1) {
       const f32x4s* grow4 = reinterpret_cast<const f32x4s*>(gT + mq * HS + half * 64);
       f32x4s g2[16];
@@ -313,9 +323,9 @@ __global__ __launch_bounds__(256, 2) void cin_dz2_b_kernel(const float* __restri
         for (int i = 0; i < 16; ++i) d[i] = 0.f;
 #pragma unroll
         for (int st = 0; st < NT; ++st) {
-          d = mfma_split(q[st % QD], gpl[st], d);
+          d = mfma_planes<NP>(q[st % QD], gpl[st], d);
 #pragma unroll
-          for (int pl = 0; pl < 3; ++pl) q[st % QD][pl] = st + QD < NT ? ldw(t, st + QD, pl) : ldw(t + 1, st + QD - NT, pl);
+          for (int pl = 0; pl < NP; ++pl) q[st % QD][pl] = st + QD < NT ? ldw(t, st + QD, pl) : ldw(t + 1, st + QD - NT, pl);
           if (st % SPB == SPB - 1) {
             const int blk = st / SPB;   // block of G slots: blk*G .. blk*G + G-1
 #pragma unroll
@@ -355,7 +365,7 @@ __global__ __launch_bounds__(256, 2) void cin_dz2_b_kernel(const float* __restri
   cin_dz2_finish(smem, wave, lane, wrow0, M, F, K, dsc, ldp, dxT, accumulate, dx, cvec);
 }
 
-bool cin_launch_dz2_b(hipStream_t st, int JT, const float* g1T, const float* g2T, int HS, const float* dsc, int ldp, int K, const u32x4* Wzb1,
+bool cin_launch_dz2_b(hipStream_t st, int NP, int JT, const float* g1T, const float* g2T, int HS, const float* dsc, int ldp, int K, const u32x4* Wzb1,
                       const u32x4* Wzb2, const float* xT, float* dxT, int accumulate, int M, int F, int H1, int H2, int periods, float* dx,
                       const float* cvec);
 
@@ -375,9 +385,12 @@ bool cin_launch_dz2_b(hipStream_t st, int JT, const float* g1T, const float* g2T
 // the A planes: ~250 instructions between the barrier and the first MFMA -- runs under the other's MFMAs on the same SIMDs (as ONE
 // 8-wave workgroup sharing the barrier the two waves of a SIMD were in step and the matrix pipe idled through that phase: 178 us).
 // 26 tiles at F = 39 are 6 groups of four and one of two (2 of 28 wave slots idle).  No fold of split pairs (the LDS is the rings'):
-// one partial [C][256] per row split, summed by cin_reduce_expand_q_kernel as before.
+// one partial [C][256] per row split, summed by cin_reduce_expand_q_kernel as before.  One plane (NP = 1): the same plan with 8-KB
+// plane slots (28 KB of LDS per workgroup); the split pairs are not folded there either.
 constexpr int kDwqbPlaneSlot = 24 * 1024, kDwqbXeSlot = 4096;
 constexpr int kDwqbHalfBytes = 2 * kDwqbPlaneSlot + 3 * kDwqbXeSlot;   // planes ring (2) + xe ring (3) of one half workgroup
+constexpr int dwqb_plane_slot(int NP) { return NP * 8 * 1024; }
+constexpr int dwqb_lds_bytes(int NP) { return 2 * dwqb_plane_slot(NP) + 3 * kDwqbXeSlot; }
 struct DwqbPlan {
   int tiles, groups, splits, rows_per_split, items, wgs;
 };
@@ -395,11 +408,12 @@ inline DwqbPlan cin_dwqb_plan(long M, int C, int cus) {
   return p;
 }
 
-template <int XS = 3>   // xe ring slots (a template so that only the translation unit that launches it compiles it)
+template <int XS = 3, int NP = 3>   // xe ring slots (a template so that only the translation unit that launches it compiles it)
 __global__ __launch_bounds__(256, 2) void cin_dwq_b_kernel(const float* __restrict__ gT, const float* __restrict__ x1T, int HS, const float* __restrict__ xe,
                                                            int XE, float* __restrict__ part, int M, int F, int symD, int rows_per_split, int splits,
                                                            int groups, int items) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char lds[];   // planes 2 x 24 KB | xe 3 x 4 KB
+  extern __shared__ __attribute__((aligned(16))) unsigned char lds[];   // planes 2 x NP x 8 KB | xe 3 x 4 KB
+  constexpr int PS = dwqb_plane_slot(NP);
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int r = lane & 31, half = lane >> 5;
   const int w4 = wave;
@@ -419,7 +433,7 @@ __global__ __launch_bounds__(256, 2) void cin_dwq_b_kernel(const float* __restri
   const __amdgpu_buffer_rsrc_t r1 = make_rsrc_uniform(x1T + (live ? m_lo * HS : 0), mrem * HS * 4);
   const __amdgpu_buffer_rsrc_t rx = make_rsrc_uniform(xe + (live ? m_lo * XE : 0), mrem * XE * 4);
   unsigned char* hbase = lds;
-  unsigned char* xring = hbase + 2 * kDwqbPlaneSlot;
+  unsigned char* xring = hbase + 2 * PS;
   const int steps = rows_per_split >> 4;
   const int c = c0 + r;
   const int cc = c < C ? c : C - 1;
@@ -450,13 +464,13 @@ __global__ __launch_bounds__(256, 2) void cin_dwq_b_kernel(const float* __restri
     }
   };
   auto cut_raw = [&](int t) {   // -> the planes of step t, ring slot t % 2
-    unsigned char* dst = hbase + (t & 1) * kDwqbPlaneSlot + lane * 16;
+    unsigned char* dst = hbase + (t & 1) * PS + lane * 16;
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
-      u32x4 a[3];
-      split3(raw[j], a);
+      u32x4 a[NP];
+      split_planes<NP>(raw[j], a);
 #pragma unroll
-      for (int pl = 0; pl < 3; ++pl) *reinterpret_cast<u32x4*>(dst + (pl * 8 + j * 4 + w4) * 1024) = a[pl];
+      for (int pl = 0; pl < NP; ++pl) *reinterpret_cast<u32x4*>(dst + (pl * 8 + j * 4 + w4) * 1024) = a[pl];
     }
   };
 
@@ -489,20 +503,20 @@ __global__ __launch_bounds__(256, 2) void cin_dwq_b_kernel(const float* __restri
         pa[e] = row[hh] * row[ff];
         pb[e] = pa[e] * row[so];
       }
-      u32x4 a0[3], a1[3];
-      split3(pa, a0);
-      split3(pb, a1);
-      const unsigned char* sb = hbase + (t & 1) * kDwqbPlaneSlot + lane * 16;
-      u32x4 b[2][3];
+      u32x4 a0[NP], a1[NP];
+      split_planes<NP>(pa, a0);
+      split_planes<NP>(pb, a1);
+      const unsigned char* sb = hbase + (t & 1) * PS + lane * 16;
+      u32x4 b[2][NP];
 #pragma unroll
-      for (int pl = 0; pl < 3; ++pl) b[0][pl] = *reinterpret_cast<const u32x4*>(sb + (pl * 8) * 1024);
+      for (int pl = 0; pl < NP; ++pl) b[0][pl] = *reinterpret_cast<const u32x4*>(sb + (pl * 8) * 1024);
 #pragma unroll
       for (int nb = 0; nb < 8; ++nb) {
         if (nb + 1 < 8) {
 #pragma unroll
-          for (int pl = 0; pl < 3; ++pl) b[(nb + 1) & 1][pl] = *reinterpret_cast<const u32x4*>(sb + (pl * 8 + nb + 1) * 1024);
+          for (int pl = 0; pl < NP; ++pl) b[(nb + 1) & 1][pl] = *reinterpret_cast<const u32x4*>(sb + (pl * 8 + nb + 1) * 1024);
         }
-        acc[nb] = nb < 4 ? mfma_split(a0, b[nb & 1], acc[nb]) : mfma_split(a1, b[nb & 1], acc[nb]);
+        acc[nb] = nb < 4 ? mfma_planes<NP>(a0, b[nb & 1], acc[nb]) : mfma_planes<NP>(a1, b[nb & 1], acc[nb]);
       }
     }
   }
@@ -520,10 +534,10 @@ __global__ __launch_bounds__(256, 2) void cin_dwq_b_kernel(const float* __restri
   }
 }
 
-void cin_launch_dwq_b(hipStream_t st, const DwqbPlan& p, const float* gT, const float* x1T, int HS, const float* xe, int XE, float* part, int M, int F,
+void cin_launch_dwq_b(hipStream_t st, int NP, const DwqbPlan& p, const float* gT, const float* x1T, int HS, const float* xe, int XE, float* part, int M, int F,
                       int symD);
 
-bool cin_launch_fwdq_b(hipStream_t st, int JT, const float* x2T, int XL, const u32x4* Wb, int NT, const float* bias1, const float* wsn, int JTG,
+bool cin_launch_fwdq_b(hipStream_t st, int NP, int JT, const float* x2T, int XL, const u32x4* Wb, int NT, const float* bias1, const float* wsn, int JTG,
                        const float* cvec, float* x1T, float* RT, int HS, float* pool1, float* pool_p, float* pool_L, int M, int F, int H, CinHeadFold hf);
 
 }  // namespace fil

@@ -92,7 +92,8 @@ static __global__ __launch_bounds__(256) void cin_qtail_prep_kernel(const float*
 }
 
 // T in both operand layouts from one launch: [0, nbf) the forward kernel's (cin_pack_wf_sym_body), [nbf, nbf + nbz) the dZ kernel's slot
-// order; split-bf16 mode (nbq > 0): the rest writes the forward's planes of [W1s | Ts] (cin_qs_pack_wb_body, straight from W1 and T)
+// order; split-bf16 mode (nbq > 0): the rest writes the forward's NP planes of [W1s | Ts] (cin_qs_pack_wb_body, straight from W1 and T)
+template <int NP = 3>
 static __global__ __launch_bounds__(256) void cin_qtail_pack_kernel(const float* __restrict__ T, float* __restrict__ Wf, float* __restrict__ Wz, int F,
                                                                     int H, int JTs, int chunks, int nbf, int HS, int tiles, int nbz = -1,
                                                                     const float* __restrict__ W1 = nullptr, int H1 = 0, u32x4* __restrict__ Wb = nullptr,
@@ -100,7 +101,7 @@ static __global__ __launch_bounds__(256) void cin_qtail_pack_kernel(const float*
   if (nbz < 0) nbz = gridDim.x - nbf;
   if ((int)blockIdx.x < nbf) cin_pack_wf_sym_body(T, Wf, F, H, 2 * JTs, chunks, blockIdx.x, nbf);
   else if ((int)blockIdx.x < nbf + nbz) cin_pack_wz_sym_body(T, Wz, F, H, JTs, HS, tiles, blockIdx.x - nbf, nbz);
-  else cin_qs_pack_wb_body(W1, H1, T, H, Wb, NT, F, JTs, blockIdx.x - nbf - nbz, gridDim.x - nbf - nbz);
+  else cin_qs_pack_wb_body<NP>(W1, H1, T, H, Wb, NT, F, JTs, blockIdx.x - nbf - nbz, gridDim.x - nbf - nbz);
 }
 
 // LDS floats of a T workgroup (cin_qtail_t_body; fold: + the column itself) -- and of the cvec workgroup beside them

@@ -1,5 +1,7 @@
 // Split-bf16 ("bf16x3") building blocks shared by the small kernels that pack the weight planes (cin_qtail.h, cin_qmerge.h) and by the
-// GEMM kernels that consume them (cin_qsplit.h, where the mode is described).
+// GEMM kernels that consume them (cin_qsplit.h, where the mode is described).  Everything that handles planes takes their count NP:
+// 3 = the split (each fp32 operand as three exact bf16 pieces, FIL_CIN_BF16X3), 1 = one bf16 value per operand, rounded to nearest
+// even (FIL_CIN_PREC_BF16, one MFMA per product).
 #pragma once
 #include "cin_kernels.h"
 #include "cin_launch.h"
@@ -23,6 +25,14 @@ __device__ __forceinline__ f32x16 mfma_split(const u32x4 (&a)[3], const u32x4 (&
   return c;
 }
 
+// ... or with ONE plane per operand: one MFMA per product
+template <int NP>
+__device__ __forceinline__ f32x16 mfma_planes(const u32x4 (&a)[NP], const u32x4 (&b)[NP], f32x16 c) {
+  static_assert(NP == 1 || NP == 3, "one plane (bf16) or three (bf16x3)");
+  if constexpr (NP == 3) return mfma_split(a, b, c);
+  else return mfma32b(a[0], b[0], c);
+}
+
 // two fp32 values -> their top halves in one dword (element 0 in the low half): a bf16 pair by truncation
 __device__ __forceinline__ unsigned pack_hi(float lo, float hi) {
   return __builtin_amdgcn_perm(__builtin_bit_cast(unsigned, hi), __builtin_bit_cast(unsigned, lo), 0x07060302u);
@@ -38,6 +48,22 @@ __device__ __forceinline__ void split3(const float (&p)[8], u32x4 (&a)[3]) {
     a[0][q] = pack_hi(p0, p1);
     a[1][q] = pack_hi(r0, r1);
     a[2][q] = pack_hi(s0, s1);
+  }
+}
+
+// two fp32 values -> one bf16 pair, each rounded to nearest even (element 0 in the low half; no builtin on gfx950)
+__device__ __forceinline__ unsigned cvt_pk_bf16(float lo, float hi) {
+  unsigned r;
+  asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(r) : "v"(lo), "v"(hi));
+  return r;
+}
+// eight fp32 values -> the NP planes of one MFMA operand: the exact three-piece cut, or one rounded bf16 each (0.5 instructions per value)
+template <int NP>
+__device__ __forceinline__ void split_planes(const float (&p)[8], u32x4 (&a)[NP]) {
+  if constexpr (NP == 3) split3(p, a);
+  else {
+#pragma unroll
+    for (int q = 0; q < 4; ++q) a[0][q] = cvt_pk_bf16(p[2 * q], p[2 * q + 1]);
   }
 }
 
@@ -62,6 +88,7 @@ inline int cin_qs_steps(int F, int JT) {   // MFMA steps of the forward's reduct
 }
 constexpr int kQsStageBytes = 24 * 1024;   // one forward step of B planes: [plane 3][column block 8][lane 64][8 bf16]
 constexpr int kQsStages = 4;
+constexpr int qs_stage_bytes(int NP) { return NP * 8 * 1024; }   // ... with NP planes
 
 // pair weight of slot (h, d) of a pair-symmetric layer (cin_pack_wf_sym_body's rule): W[(h,f)] + W[(f,h)], f = (h + d) mod F; the
 // diagonal once; half the sum where an even F meets a pair from both ends; zero past d = F/2, h = F - 1 and column H - 1
@@ -73,9 +100,10 @@ __device__ __forceinline__ float cin_sym_weight(const float* __restrict__ W, int
   return 2 * d == F ? 0.5f * v : v;
 }
 
-// Forward planes Wb [step t][plane][nb 0..7][lane][8 bf16]: element e of lane (r, half) = the pair weight of slot s = 8 t + e (h = s / JT,
+// Forward planes Wb [step t][plane NP][nb 0..7][lane][8 bf16]: element e of lane (r, half) = the pair weight of slot s = 8 t + e (h = s / JT,
 // d = 2 (s mod JT) + half), column 4 r + (nb & 3) of W1 [F*F][H1] (nb < 4) or of T [F*F][HT] (nb >= 4).  One thread per (t, nb, lane);
 // rides in cin_qtail_pack_kernel's launch (T is complete there).
+template <int NP>
 __device__ __forceinline__ void cin_qs_pack_wb_body(const float* __restrict__ W1, int H1, const float* __restrict__ T, int HT, u32x4* __restrict__ Wb,
                                                     int NT, int F, int JT, int bid, int nblocks) {
   for (int idx = bid * 256 + threadIdx.x; idx < NT * 512; idx += nblocks * 256) {
@@ -89,16 +117,17 @@ __device__ __forceinline__ void cin_qs_pack_wb_body(const float* __restrict__ W1
       const int s = 8 * t + e, h = s / JT;
       p[e] = cin_sym_weight(W, F, H, h, 2 * (s - h * JT) + half, col);
     }
-    u32x4 a[3];
-    split3(p, a);
+    u32x4 a[NP];
+    split_planes<NP>(p, a);
 #pragma unroll
-    for (int pl = 0; pl < 3; ++pl) Wb[((long)(t * 3 + pl) * 8 + nb) * 64 + lane] = a[pl];
+    for (int pl = 0; pl < NP; ++pl) Wb[((long)(t * NP + pl) * 8 + nb) * 64 + lane] = a[pl];
   }
 }
 
-// Data-gradient planes Wzb [tile][step t][plane][lane][8 bf16]: element e of lane (r, half) = the pair weight of slot row r of the tile
+// Data-gradient planes Wzb [tile][step t][plane NP][lane][8 bf16]: element e of lane (r, half) = the pair weight of slot row r of the tile
 // (cin_pack_wz_sym_body's slot order: rr = (r & 3) + 4 (r >> 3), parity (r >> 2) & 1, slot 16 tile + rr), column half*64 + 8 t + e.
 // One thread per (tile, t, lane); rides in cin_qtail_xe_kernel's launch.
+template <int NP>
 __device__ __forceinline__ void cin_qs_pack_wz_body(const float* __restrict__ W, int H, u32x4* __restrict__ Wzb, int tiles, int F, int JT, int bid,
                                                     int nblocks) {
   for (int idx = bid * 256 + threadIdx.x; idx < tiles * 512; idx += nblocks * 256) {
@@ -109,11 +138,11 @@ __device__ __forceinline__ void cin_qs_pack_wz_body(const float* __restrict__ W,
     float p[8];
 #pragma unroll
     for (int e = 0; e < 8; ++e) p[e] = cin_sym_weight(W, F, H, h, d, half * 64 + 8 * t + e);
-    u32x4 a[3];
-    split3(p, a);
-    u32x4* dst = Wzb + ((long)(tile * 8 + t) * 3) * 64 + lane;
+    u32x4 a[NP];
+    split_planes<NP>(p, a);
+    u32x4* dst = Wzb + ((long)(tile * 8 + t) * NP) * 64 + lane;
 #pragma unroll
-    for (int pl = 0; pl < 3; ++pl) dst[pl * 64] = a[pl];
+    for (int pl = 0; pl < NP; ++pl) dst[pl * 64] = a[pl];
   }
 }
 

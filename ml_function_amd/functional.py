@@ -188,6 +188,26 @@ CIN_X_TRANSPOSED = 16   # fil.h FIL_CIN_X_TRANSPOSED: x handed over as [B*K, F] 
 CIN_TAIL_ALWAYS = 64    # fil.h FIL_CIN_TAIL_ALWAYS: the tails wherever they are defined, whatever the batch size (tests, smoke)
 CIN_NOQTAIL = 256       # fil.h FIL_CIN_NOQTAIL: three-layer nets on the F+1-column fused tail instead of the quadratic tail
 CIN_NOQMERGE = 512      # fil.h FIL_CIN_NOQMERGE: round 3's two launches per direction for the quadratic tail (no 256-column forward with the pools and the head in its epilogue, no 256-column dW, no two-pass dZ)
+CIN_PREC_DEFAULT = 0    # fil.h FIL_CIN_PREC_DEFAULT: what `mode` selects
+CIN_PREC_BF16 = 1       # fil.h FIL_CIN_PREC_BF16: the labelled bf16 training mode of the merged quadratic tail's GEMMs (one bf16 MFMA per product)
+_CIN_PRECISIONS = {"f32": CIN_PREC_DEFAULT, "bf16": CIN_PREC_BF16}
+
+
+def _cin_precision_code(precision):
+    if precision not in _CIN_PRECISIONS:
+        raise FilError("cin: precision must be one of %s, got %r" % (sorted(_CIN_PRECISIONS), precision))
+    return _CIN_PRECISIONS[precision]
+
+
+def cin_precision_used(B, F, K, H, mode=0, precision="bf16"):
+    """The precision a CIN call with this shape, mode and precision actually runs (fil_cin_precision_used): "bf16" where the one-plane
+    bf16 kernels of the merged quadratic tail run, else "f32" (the exact kernels)."""
+    lib = _lib.load()
+    code = _cin_precision_code(precision)
+    rc = lib.fil_cin_precision_used(int(B), int(F), int(K), len(H), int_array(list(H)), int(mode), code)
+    if rc < 0:
+        raise FilError("fil_cin_precision_used: %s" % lib.fil_last_error().decode())
+    return "bf16" if rc == CIN_PREC_BF16 else "f32"
 
 
 def cin_grad_ready_points(B, F, K, H, mode=0):
@@ -202,10 +222,12 @@ def cin_grad_ready_points(B, F, K, H, mode=0):
     return [int(v) for v in pts]
 
 
-def cin_forward_raw(x, Ws, bs, dense_w, dense_b, output_dim=1, mode=0, xt=None):
+def cin_forward_raw(x, Ws, bs, dense_w, dense_b, output_dim=1, mode=0, xt=None, precision="f32"):
     """Raw forward through the C ABI.  Returns (out [B,1] or None, pooled [B,L*K], saved uint8 buffer).
-    xt (optional): x already transposed to [B*K, F] by the gather that produced it; the kernels then read it in place."""
+    xt (optional): x already transposed to [B*K, F] by the gather that produced it; the kernels then read it in place.
+    precision: "f32" (fil_cin_fwd) or "bf16" (fil_cin_fwd_p with FIL_CIN_PREC_BF16: the labelled bf16 mode where its kernels run)."""
     lib = _lib.load()
+    prec = _cin_precision_code(precision)
     B, F, K = x.shape
     if xt is not None:
         if tuple(xt.shape) != (B * K, F) or xt.dtype != torch.float32 or not xt.is_contiguous() or xt.device != x.device:
@@ -226,17 +248,22 @@ def cin_forward_raw(x, Ws, bs, dense_w, dense_b, output_dim=1, mode=0, xt=None):
     ws = _scratch(nws, x.device, "cin_fwd")
     pooled = torch.empty((B, L * K), dtype=torch.float32, device=x.device)
     out = torch.empty((B, 1), dtype=torch.float32, device=x.device) if output_dim == 1 else None
-    check(lib.fil_cin_fwd(ptr(xt if xt is not None else x), ptr_array(Ws), ptr_array(bs), ptr(dense_w), ptr(dense_b), ptr(out),
-                          ptr(pooled), ptr(saved), B, F, K, L, Harr, output_dim, mode, ptr(ws), nws, stream_ptr()), "fil_cin_fwd")
+    if prec == CIN_PREC_DEFAULT:
+        check(lib.fil_cin_fwd(ptr(xt if xt is not None else x), ptr_array(Ws), ptr_array(bs), ptr(dense_w), ptr(dense_b), ptr(out),
+                              ptr(pooled), ptr(saved), B, F, K, L, Harr, output_dim, mode, ptr(ws), nws, stream_ptr()), "fil_cin_fwd")
+    else:
+        check(lib.fil_cin_fwd_p(ptr(xt if xt is not None else x), ptr_array(Ws), ptr_array(bs), ptr(dense_w), ptr(dense_b), ptr(out),
+                                ptr(pooled), ptr(saved), B, F, K, L, Harr, output_dim, mode, prec, ptr(ws), nws, stream_ptr()), "fil_cin_fwd_p")
     return out, pooled, saved
 
 
-def cin_backward_raw(x, Ws, bs, dense_w, pooled, saved, g, output_dim=1, mode=0, grads=None, ready_events=None, xt=None):
+def cin_backward_raw(x, Ws, bs, dense_w, pooled, saved, g, output_dim=1, mode=0, grads=None, ready_events=None, xt=None, precision="f32"):
     """Raw backward.  grads (optional): dict with preallocated 'dx','dW'(list),'db'(list),'ddw','ddb' tensors
     (e.g. views into one flat all-reduce bucket).  ready_events (optional): L+1 torch.cuda.Event objects (or None
-    entries), recorded as each layer's / the head's parameter gradients become final (fil.h: grad_ready_events).
-    Returns the dict."""
+    entries), recorded as each layer's / the head's parameter gradients become final (fil.h: grad_ready_events; the same points
+    for either precision).  precision: as cin_forward_raw's (fil_cin_bwd_p for "bf16").  Returns the dict."""
     lib = _lib.load()
+    prec = _cin_precision_code(precision)
     B, F, K = x.shape
     L = len(Ws)
     H = [int(w.shape[1]) for w in Ws]
@@ -257,15 +284,20 @@ def cin_backward_raw(x, Ws, bs, dense_w, pooled, saved, g, output_dim=1, mode=0,
         evs = (ctypes.c_void_p * (L + 1))(*[None if e is None else e.cuda_event for e in ready_events])
     if xt is not None:
         mode |= CIN_X_TRANSPOSED
-    check(lib.fil_cin_bwd(ptr(xt if xt is not None else x), ptr_array(Ws), ptr_array(bs), ptr(dense_w), ptr(pooled), ptr(saved), ptr(g),
-                          ptr(grads["dx"]), ptr_array(grads["dW"]), ptr_array(grads["db"]), ptr(grads["ddw"]),
-                          ptr(grads["ddb"]), B, F, K, L, Harr, output_dim, mode, evs, ptr(ws), nws, stream_ptr()), "fil_cin_bwd")
+    if prec == CIN_PREC_DEFAULT:
+        check(lib.fil_cin_bwd(ptr(xt if xt is not None else x), ptr_array(Ws), ptr_array(bs), ptr(dense_w), ptr(pooled), ptr(saved), ptr(g),
+                              ptr(grads["dx"]), ptr_array(grads["dW"]), ptr_array(grads["db"]), ptr(grads["ddw"]),
+                              ptr(grads["ddb"]), B, F, K, L, Harr, output_dim, mode, evs, ptr(ws), nws, stream_ptr()), "fil_cin_bwd")
+    else:
+        check(lib.fil_cin_bwd_p(ptr(xt if xt is not None else x), ptr_array(Ws), ptr_array(bs), ptr(dense_w), ptr(pooled), ptr(saved), ptr(g),
+                                ptr(grads["dx"]), ptr_array(grads["dW"]), ptr_array(grads["db"]), ptr(grads["ddw"]),
+                                ptr(grads["ddb"]), B, F, K, L, Harr, output_dim, mode, prec, evs, ptr(ws), nws, stream_ptr()), "fil_cin_bwd_p")
     return grads
 
 
 class _CinFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, dense_w, dense_b, output_dim, mode, xt, *params):
+    def forward(ctx, x, dense_w, dense_b, output_dim, mode, xt, precision, *params):
         L = len(params) // 2
         Ws = [_f32c(p) for p in params[:L]]
         bs = [_f32c(p) for p in params[L:]]
@@ -273,29 +305,33 @@ class _CinFn(torch.autograd.Function):
         x = _f32c(x)
         dense_w = _f32c(dense_w)
         dense_b = _f32c(dense_b)
-        out, pooled, saved = cin_forward_raw(x, Ws, bs, dense_w, dense_b, output_dim, mode, xt=xt)
+        out, pooled, saved = cin_forward_raw(x, Ws, bs, dense_w, dense_b, output_dim, mode, xt=xt, precision=precision)
         # xt (the gather's second output, same values as x) goes through save_for_backward too: an in-place edit between the
         # forward and the backward then trips autograd's version check instead of silently feeding stale rows to the kernels
         ctx.save_for_backward(x, dense_w, pooled, saved, *Ws, *bs, *([xt] if xt is not None else []))
-        ctx.cfg = (L, output_dim, mode, xt is not None)
+        ctx.cfg = (L, output_dim, mode, xt is not None, precision)
         return out if output_dim == 1 else pooled
 
     @staticmethod
     def backward(ctx, g):
-        L, output_dim, mode, has_xt = ctx.cfg
+        L, output_dim, mode, has_xt, precision = ctx.cfg
         x, dense_w, pooled, saved = ctx.saved_tensors[:4]
         Ws = list(ctx.saved_tensors[4:4 + L])
         bs = list(ctx.saved_tensors[4 + L:4 + 2 * L])
         xt = ctx.saved_tensors[4 + 2 * L] if has_xt else None
-        gr = cin_backward_raw(x, Ws, bs, dense_w, pooled, saved, _f32c(g), output_dim, mode, xt=xt)
-        return (gr["dx"], gr["ddw"], gr["ddb"], None, None, None, *gr["dW"], *gr["db"])
+        gr = cin_backward_raw(x, Ws, bs, dense_w, pooled, saved, _f32c(g), output_dim, mode, xt=xt, precision=precision)
+        return (gr["dx"], gr["ddw"], gr["ddb"], None, None, None, None, *gr["dW"], *gr["db"])
 
 
-def cin(x, Ws, bs, dense_w=None, dense_b=None, output_dim=1, mode=0, xt=None):
+def cin(x, Ws, bs, dense_w=None, dense_b=None, output_dim=1, mode=0, xt=None, precision="f32"):
     """x [B,F,K]; Ws[l] [H_{l-1}*F, H_l]; bs[l] [H_l]; dense_w [L*K,1]; dense_b [1] -> [B,1] (or pooled [B,L*K]).
     xt (optional) = x transposed to [B*K, F] by the gather that produced x (embed_gather(emit_xt=True) attaches it to its
-    result as `_fil_xt`): the kernels read it in place instead of transposing x again.  Gradients still flow to x."""
-    return _CinFn.apply(x, dense_w, dense_b, output_dim, mode, xt, *Ws, *bs)
+    result as `_fil_xt`): the kernels read it in place instead of transposing x again.  Gradients still flow to x.
+    precision: "f32" (exact, the default) or "bf16" -- the labelled bf16 training mode (include/fil.h fil_cin_fwd_p): the merged
+    quadratic tail's GEMMs on one bf16 value per operand, ~1e-3 relative error; shapes without those kernels run exact
+    (cin_precision_used says which)."""
+    _cin_precision_code(precision)
+    return _CinFn.apply(x, dense_w, dense_b, output_dim, mode, xt, precision, *Ws, *bs)
 
 
 # --------------------------------------------------------------------------------------------- A4  AutoInt

@@ -6,6 +6,7 @@ per-batch arithmetic runs in the HIP kernels behind include/fil.h (no CPU fallba
 Packed [B,F,K] is the native layout; the reference's Python lists of F tensors [B,1,K] are accepted and stacked.
 """
 import os
+import warnings
 
 import torch
 
@@ -247,15 +248,45 @@ class CIN(Layer):
     build creates one Conv1D(size, 1) per entry of conv_size (kernel [1, H_{l-1}*F, H_l] glorot_uniform, bias [H_l]
     zeros; channel c = h*F+f) and, when output_dim == 1, the Dense(1) head (kernel [L*K,1], bias [1]).
     call(x [B,F,K]) -> [B,1] (or the pooled concat [B, L*K] when output_dim != 1).  The sum-pool is over the
-    feature-map axis (reference :322)."""
+    feature-map axis (reference :322).
 
-    def __init__(self, conv_size=None, output_dim=1, mode=0):
+    precision="bf16" (extension): the labelled bf16 training mode (Fn.cin, include/fil.h fil_cin_fwd_p) -- one bf16 rounding per
+    operand in the merged quadratic tail's GEMMs, ~1e-3 relative error.  Where those kernels do not run (other layer widths, small
+    batches, shapes off the kernel menu) the layer warns once and runs the exact fp32 kernels."""
+
+    _BF16_LIMIT = ("the bf16 CIN kernels run only on the merged quadratic tail: 3 layers, H_1 = 128 (one column chunk), "
+                   "F <= 41 with F(F+1)/2-pair kernels in the menu, B*K > 16384 rows")
+
+    def __init__(self, conv_size=None, output_dim=1, mode=0, precision="f32"):
         super().__init__()
         if conv_size is None:
             conv_size = [200, 200, 200]
+        if precision not in ("f32", "bf16"):
+            raise ValueError("CIN precision must be 'f32' or 'bf16', got %r" % (precision,))
         self.conv_size = list(conv_size)
         self.output_dim = output_dim
         self.mode = mode
+        self.precision = precision
+        self._prec_cache = {}
+        self._prec_warned = False
+
+    def _warn_exact(self, why):
+        if not self._prec_warned:
+            self._prec_warned = True
+            warnings.warn("CIN(precision='bf16'): %s; this layer runs the exact fp32 kernels (%s)" % (why, self._BF16_LIMIT), stacklevel=3)
+
+    def _precision_for(self, x):
+        """The precision to hand to Fn.cin for this batch shape: "bf16" where its kernels run, else "f32" (with the one-time warning)."""
+        if self.precision == "f32":
+            return "f32"
+        key = tuple(x.shape)
+        prec = self._prec_cache.get(key)
+        if prec is None:
+            prec = Fn.cin_precision_used(x.shape[0], x.shape[1], x.shape[2], self.conv_size, mode=self.mode, precision="bf16")
+            self._prec_cache[key] = prec
+        if prec != "bf16":
+            self._warn_exact("shape B=%d F=%d K=%d H=%s is outside the bf16 kernels" % (x.shape[0], x.shape[1], x.shape[2], self.conv_size))
+        return prec
 
     def build(self, input_shape):
         _, f, k = input_shape
@@ -281,10 +312,13 @@ class CIN(Layer):
         # gradient into it: six launches and 28 us per xDeepFM step)
         Ws = [w.view(w.shape[1], w.shape[2]) for w in self.conv_kernels]
         if not self.fits_kernel_menu(x):
+            if self.precision == "bf16":
+                self._warn_exact("shape F=%d H=%s is outside the HIP kernels (composed fp32 path)" % (x.shape[1], self.conv_size))
             return self._composed(x, Ws)
+        prec = self._precision_for(x)
         if self.output_dim == 1:
-            return Fn.cin(x, Ws, self.conv_biases, self.logit_kernel, self.logit_bias, output_dim=1, mode=self.mode, xt=xt)
-        return Fn.cin(x, Ws, self.conv_biases, None, None, output_dim=self.output_dim, mode=self.mode, xt=xt)
+            return Fn.cin(x, Ws, self.conv_biases, self.logit_kernel, self.logit_bias, output_dim=1, mode=self.mode, xt=xt, precision=prec)
+        return Fn.cin(x, Ws, self.conv_biases, None, None, output_dim=self.output_dim, mode=self.mode, xt=xt, precision=prec)
 
     def fits_kernel_menu(self, x):
         """fil_cin_*'s limits (include/fil.h): F <= 64, H_l <= 256, L <= 8.  The reference has none (:296-327): a layer outside them

@@ -200,10 +200,11 @@ class DCN(torch.nn.Module):
 class XDeepFM(torch.nn.Module):
     """models.XDeepFM (:121-138).  linear_embed must be one tensor (FeatureInput(useLinear, useAddLinear, useFlattenLinear))."""
 
-    def __init__(self, conv_size=None, hidden_units=None):
+    def __init__(self, conv_size=None, hidden_units=None, precision="f32"):
         super().__init__()
         self.stack = StackLayer()
-        self.cin = CIN(conv_size=conv_size or [200, 200, 200], output_dim=1)
+        # precision="bf16": the CIN's labelled bf16 training mode (layers.CIN); "f32" (the default) is the exact chain
+        self.cin = CIN(conv_size=conv_size or [200, 200, 200], output_dim=1, precision=precision)
         self.dnn = DnnLayer(hidden_units=hidden_units or [256, 128, 64], output_dim=1)
         self.score = ScoreLayer(use_add=True)
 
