@@ -26,7 +26,7 @@ import torch.distributed as dist
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import pandas as pd  # noqa: E402
 
-from ml_function_amd import data, dp, losses, metrics, models  # noqa: E402
+from ml_function_amd import data, dp, losses, metrics, models, optim  # noqa: E402
 from ml_function_amd.data_prepare import data_prepare  # noqa: E402
 from ml_function_amd.layers.base import collect_regularization_loss  # noqa: E402
 
@@ -55,6 +55,11 @@ def main():
     ap.add_argument("--cin-precision", default="f32", choices=["f32", "bf16"],
                     help="XDeepFM only: bf16 = the CIN's labelled bf16 training mode (one bf16 MFMA per product in its three GEMM "
                          "launches, ~1e-3 relative error); f32 = the exact chain")
+    ap.add_argument("--optimizer", default="torch", choices=["torch", "keras", "keras-lazy"],
+                    help="torch = torch.optim.Adam on dense table gradients; keras = ml_function_amd.optim.Adam (Keras' epsilon placement), "
+                         "on one GPU with the tables updated in place from the batch's gradient runs (tableGrad='runs'); keras-lazy = the "
+                         "same with LazyAdam tables (only touched rows change: a labelled deviation from the reference).  Data parallel: "
+                         "the tables keep their dense gradients and the sparse row exchange")
     ap.add_argument("--no-graph", action="store_true",
                     help="run every step eagerly (default on one GPU: the whole step -- forward, backward, Adam -- is captured once "
                          "into a HIP graph and replayed; the C ABI neither allocates nor synchronises, so it is capture-safe)")
@@ -82,8 +87,9 @@ def main():
     lo, hi = rank * per_rank, (rank + 1) * per_rank
     ids_df, dense_df, labels = ids_df.iloc[lo:hi], dense_df.iloc[lo:hi], labels[lo:hi]
     single = args.model == "XDeepFM"
+    keras = args.optimizer != "torch"
     fi = models.FeatureInput(sparseInfo=info, useLinear=args.model != "DCN" and args.model != "AutoInt", useAddLinear=single,
-                             useFlattenLinear=True)
+                             useFlattenLinear=True, tableGrad="runs" if keras and world == 1 else "dense")
     body = {"FM": models.FM, "DeepFM": models.DeepFM, "DCN": models.DCN, "AutoInt": models.AutoInt, "NFM": models.NFM,
             "AFM": models.AFM, "XDeepFM": lambda: models.XDeepFM(conv_size=[128, 128, 128], precision=args.cin_precision)}[args.model]()
     torch.manual_seed(0)  # identical replicas
@@ -97,7 +103,10 @@ def main():
     table_l2 = {id(m.embeddings): m.table_l2_ranges() for m in model.modules() if hasattr(m, "table_l2_ranges") and m.built}
     others = [p for n, p in model.named_parameters() if not n.endswith("embeddings")]
     use_graph = world == 1 and not args.no_graph
-    opt = torch.optim.Adam(model.parameters(), lr=args.lr, eps=1e-7, capturable=use_graph)      # Keras 'adam' (un_seq.py:61)
+    if keras:       # Keras 'adam' (un_seq.py:61) with Keras' numerics; tables in "runs" mode get their l2 inside the update
+        opt = optim.Adam(model.parameters(), learning_rate=args.lr, epsilon=1e-7, lazy_tables=args.optimizer == "keras-lazy")
+    else:
+        opt = torch.optim.Adam(model.parameters(), lr=args.lr, eps=1e-7, capturable=use_graph)      # Keras 'adam' (un_seq.py:61)
     pipe = data.data_pipeline(table, batch_size=args.batch, shuffle_buffer=2048, repeat=2, prefetch=2, seed=rank, device=device)
 
     def train_step(dense, idx, y):
@@ -143,10 +152,13 @@ def main():
                         train_step(*static)
                 torch.cuda.current_stream().wait_stream(side)
                 model.load_state_dict(saved_model)
-                for st_ in opt.state.values():      # Adam's moments and step count back to "never stepped" (in place: the capture keeps these tensors)
-                    for v in st_.values():
-                        if torch.is_tensor(v):
-                            v.zero_()
+                if keras:
+                    opt.reset_()                    # moments, row stamps and the device step counter, in place
+                else:
+                    for st_ in opt.state.values():      # Adam's moments and step count back to "never stepped" (in place: the capture keeps these tensors)
+                        for v in st_.values():
+                            if torch.is_tensor(v):
+                                v.zero_()
                 graph = torch.cuda.CUDAGraph()
                 opt.zero_grad(set_to_none=True)
                 with torch.cuda.graph(graph):

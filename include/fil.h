@@ -38,7 +38,8 @@ typedef enum { FIL_F32 = 0, FIL_BF16 = 1 } fil_dtype;
 
 /* ABI version: bumped on EVERY change of an entry point's argument list or semantics.  fil_version() returns the value the
  * library was compiled with; the ctypes binding (ml_function_amd/_lib.py) refuses a library whose value differs from this
- * header's, so a stale prebuilt .so can never be called with shifted arguments. */
+ * header's, so a stale prebuilt .so can never be called with shifted arguments.  Entry points that are only ADDED leave it as it
+ * is (O1, the Adam entry points, kept 216): the binding already refuses a library that lacks any symbol of its table. */
 #define FIL_ABI_VERSION 216
 int fil_version(void);                 /* == FIL_ABI_VERSION of the header the library was built from */
 const char* fil_last_error(void);      /* thread-local, never NULL */
@@ -333,6 +334,58 @@ int fil_merge_softmax_fwd(const void* const* parts, const int* widths, const int
 int fil_merge_softmax_bwd(const void* const* parts, const int* widths, const int* dtypes, int n_parts, const float* W, const float* out,
                           const float* dout, void* const* dparts, float* dW, float* db, int B, int O, void* workspace, size_t workspace_bytes,
                           void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * O1  Keras-exact Adam -- replaces optimizer='adam' of model.compile (example/ctr_example/un_seq.py:61; TF 2.1 Keras Adam ->
+ *     the ApplyAdam kernel), every tensor fp32:
+ *       t = *step + 1;  b1^t, b2^t = powf(beta_1, (float)t), powf(beta_2, (float)t)   (on the device: Keras' iterations + 1)
+ *       alpha = lr * sqrt(1 - b2^t) / (1 - b1^t)
+ *       m += (g - m) * (1 - beta_1);  v += (g*g - v) * (1 - beta_2);  p -= (m * alpha) / (sqrt(v) + epsilon)
+ *     epsilon is added to the UNCORRECTED sqrt(v) (torch.optim.Adam adds it to sqrt(v / (1 - b2^t)): at t = 1 its epsilon is in
+ *     effect 1/sqrt(1 - beta_2) times Keras').  Keras' defaults: lr 1e-3, beta_1 0.9, beta_2 0.999, epsilon 1e-7.
+ *   step: ONE int64 device counter per optimizer = the number of completed steps (Keras' `iterations`).  Every entry point below
+ *     only reads it; fil_adam_multi(advance = 1) increments it in a one-thread launch queued behind its update, so the last call of
+ *     an optimizer step passes advance = 1 (a captured graph then advances the counter on every replay).
+ *
+ *   fil_adam_multi: every descriptor of `tensors` (a DEVICE array of n entries) in one launch.  grad NULL = a zero gradient;
+ *     l2 != 0 adds 2 * l2 * p to the gradient (Keras' l2(l2) regulariser, applied inside the update: split a tensor into several
+ *     descriptors to give its row ranges different coefficients).  Any numel (>= 0); 16-byte accesses where all four arrays of a
+ *     descriptor are 16-byte aligned, element-wise otherwise and in the tail.  total_numel = the sum of the descriptors' numel (it
+ *     sizes the grid: a wrong value costs speed, never correctness).  n = 0 with advance = 1 only advances the counter.
+ *
+ *   fil_embed_adam_runs: the gradient of an embedding table as fil_embed_run_sum_dt would build it -- (g [R/F rows of F fields][K]
+ *     in g_dtype, perm, sorted_ids) of fil_embed_sort_fields -- applied to table / m / v [V, K] IN PLACE, never materialised: each run
+ *     of equal ids >= 0 is summed in the same order as fil_embed_run_sum (so the row gradient is bit-identical to the dense one),
+ *     gets + 2 * field_l2[f] * p (f = perm % F, the field of the run; field_l2 [F] may be NULL = no l2) and its row takes the update
+ *     above.  Ids -1 (out-of-range ids, frozen fields) are skipped.  No data-dependent size: graph-capturable.  mode:
+ *       FIL_ADAM_KERAS  Keras' dense semantics: the rows it updates are stamped (stamp[row] = low 32 bits of t; stamp [V] int32,
+ *                       caller-owned, zero-initialised once), and fil_embed_adam_sweep then updates every OTHER row of the table.
+ *       FIL_ADAM_LAZY   LABELLED deviation from the reference (TF-Addons LazyAdam): only the touched rows change (bias correction
+ *                       with the global t); no stamps, no sweep.  Never the default.
+ *   fil_embed_adam_sweep: the FIL_ADAM_KERAS rows of the table that are not stamped with the current t take the update with
+ *     g = 2 * field_l2[f] * p (0 without l2): m and v decay and the row moves, as Keras' dense Adam moves every row.  Row r belongs to
+ *     the last field f with offsets[f] <= r (none: no l2); rows of fields with frozen[f] != 0 (frozen [F] may be NULL) are left alone
+ *     (a non-trainable Keras Embedding is not in the optimizer's variable list).  One read and one non-temporal write of p, m, v and a
+ *     read of stamp per row; F <= 1024.
+ */
+typedef struct {
+  float* param;
+  const float* grad;   /* NULL = zero gradient */
+  float* m;
+  float* v;
+  int64_t numel;
+  float l2;            /* g += 2 * l2 * param; 0 = none */
+  int32_t reserved;    /* 0 */
+} fil_adam_tensor;     /* 48 bytes */
+enum { FIL_ADAM_KERAS = 0, FIL_ADAM_LAZY = 1 };
+int fil_adam_multi(const fil_adam_tensor* tensors, int n, int64_t total_numel, int64_t* step, float lr, float beta_1, float beta_2,
+                   float epsilon, int advance, void* stream);
+int fil_embed_adam_runs(const void* g, const int64_t* perm, const int64_t* sorted_ids, long R, int K, int g_dtype, int F,
+                        const float* field_l2, float* table, float* m, float* v, int32_t* stamp, const int64_t* step, float lr,
+                        float beta_1, float beta_2, float epsilon, int mode, void* stream);
+int fil_embed_adam_sweep(float* table, float* m, float* v, const int32_t* stamp, int64_t V, int K, const int64_t* offsets,
+                         const float* field_l2, const unsigned char* frozen, int F, const int64_t* step, float lr, float beta_1,
+                         float beta_2, float epsilon, void* stream);
 
 #ifdef __cplusplus
 }

@@ -26,6 +26,7 @@ LIB_PATH = _lib_path()
 HEADER_PATH = os.path.join(_HERE, "..", "include", "fil.h")
 
 FIL_F32, FIL_BF16 = 0, 1
+FIL_ADAM_KERAS, FIL_ADAM_LAZY = 0, 1
 
 _c = ctypes
 _P = _c.c_void_p
@@ -80,6 +81,9 @@ SIGNATURES = {
     "fil_merge_softmax_bwd_workspace_bytes": (_Z, [_I, _I, _I]),
     "fil_merge_softmax_fwd": (_I, [_P, _P, _P, _I, _P, _P, _P, _I, _I, _P]),
     "fil_merge_softmax_bwd": (_I, [_P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _I, _I, _P, _Z, _P]),
+    "fil_adam_multi": (_I, [_P, _I, _c.c_int64, _P, _F, _F, _F, _F, _I, _P]),
+    "fil_embed_adam_runs": (_I, [_P, _P, _P, _c.c_long, _I, _I, _I, _P, _P, _P, _P, _P, _P, _F, _F, _F, _F, _I, _P]),
+    "fil_embed_adam_sweep": (_I, [_P, _P, _P, _P, _c.c_int64, _I, _P, _P, _P, _I, _P, _F, _F, _F, _F, _P]),
 }
 
 

@@ -1,0 +1,274 @@
+// O1  Keras-exact Adam for gfx950: every dense fp32 tensor of a model in one launch, and the embedding tables updated in place from
+// the batch's gradient runs (no dense [V,K] gradient, no zeroed table).
+//
+// The update is TensorFlow's ApplyAdam as Keras 'adam' (TF 2.1) drives it, in fp32:
+//   t = step + 1;  alpha = lr sqrt(1 - b2^t) / (1 - b1^t);  m += (g - m)(1 - b1);  v += (g^2 - v)(1 - b2);  p -= (m alpha) / (sqrt(v) + eps)
+// with b1^t, b2^t = powf(beta, (float)t) computed on the device from the int64 step counter, so a captured graph advances it on every
+// replay.  Every launch only READS the counter; fil_adam_multi(advance = 1) bumps it in a one-thread launch behind its update.
+//
+// All three kernels are streaming: fil_adam_multi and fil_embed_adam_sweep move 16 bytes per lane and array where the arrays allow it
+// (4 loads + 3 stores of 16 B per lane; 256-lane workgroups, a few per CU: ~64 KiB of loads in flight per CU), scalar otherwise and in
+// the tail.  The sweep's stores are non-temporal (a 2 GB table pass must not evict the MALL).  fil_embed_adam_runs reuses the run sums
+// of fil_embed_run_sum (embed_runs.h): the same order, so a row's gradient is bit-identical to what the dense path materialises.
+#include "common.h"
+#include "embed_runs.h"
+#include <hip/hip_bf16.h>
+
+namespace fil {
+
+static_assert(sizeof(fil_adam_tensor) == 48, "fil_adam_tensor is 48 bytes (fil.h)");
+
+struct AdamCoef {
+  float alpha, omb1, omb2, eps;
+};
+
+__device__ __forceinline__ AdamCoef adam_coef(const int64_t* step, float lr, float b1, float b2, float eps) {
+  const float t = (float)(*step + 1);                 // Keras: local_step = cast(iterations + 1, float32)
+  const float b1p = powf(b1, t), b2p = powf(b2, t);
+  AdamCoef c;
+  c.alpha = lr * sqrtf(1.f - b2p) / (1.f - b1p);
+  c.omb1 = 1.f - b1;
+  c.omb2 = 1.f - b2;
+  c.eps = eps;
+  return c;
+}
+
+// one element of ApplyAdam (Eigen's order of operations)
+__device__ __forceinline__ void adam_elem(float& p, float& m, float& v, float g, const AdamCoef& c) {
+  m += (g - m) * c.omb1;
+  v += (g * g - v) * c.omb2;
+  p -= (m * c.alpha) / (sqrtf(v) + c.eps);
+}
+
+__global__ void adam_step_advance_kernel(int64_t* step) { *step += 1; }
+
+// ---- fil_adam_multi: the descriptors' elements form one index space of 1024-element chunks (a workgroup's 256 lanes x 4), dealt
+// round robin over the grid; a workgroup walks the descriptor list once and takes its chunks of each (grid-stride, balanced over
+// tensors of any size)
+constexpr int kMultiChunk = 1024;
+
+__global__ __launch_bounds__(256) void adam_multi_kernel(const fil_adam_tensor* __restrict__ ts, int n, const int64_t* __restrict__ step,
+                                                         float lr, float b1, float b2, float eps) {
+  const AdamCoef c = adam_coef(step, lr, b1, b2, eps);
+  const long G = gridDim.x;
+  long base = 0;
+  for (int d = 0; d < n; ++d) {
+    float* __restrict__ P = ts[d].param;
+    const float* __restrict__ Gr = ts[d].grad;
+    float* __restrict__ M = ts[d].m;
+    float* __restrict__ V = ts[d].v;
+    const long numel = ts[d].numel;
+    const float l2x2 = 2.f * ts[d].l2;
+    const long nc = (numel + kMultiChunk - 1) / kMultiChunk;
+    const bool vec = ((((uintptr_t)P | (uintptr_t)Gr | (uintptr_t)M | (uintptr_t)V) & 15) == 0);
+    long r = ((long)blockIdx.x - base) % G;
+    if (r < 0) r += G;
+    for (long ch = r; ch < nc; ch += G) {
+      const long e = ch * kMultiChunk + threadIdx.x * 4;
+      if (vec && e + 4 <= numel) {
+        float4 p = *reinterpret_cast<const float4*>(P + e);
+        float4 g = Gr ? *reinterpret_cast<const float4*>(Gr + e) : make_float4(0.f, 0.f, 0.f, 0.f);
+        float4 m = *reinterpret_cast<const float4*>(M + e);
+        float4 v = *reinterpret_cast<const float4*>(V + e);
+        if (l2x2 != 0.f) {
+          g.x += l2x2 * p.x; g.y += l2x2 * p.y; g.z += l2x2 * p.z; g.w += l2x2 * p.w;
+        }
+        adam_elem(p.x, m.x, v.x, g.x, c);
+        adam_elem(p.y, m.y, v.y, g.y, c);
+        adam_elem(p.z, m.z, v.z, g.z, c);
+        adam_elem(p.w, m.w, v.w, g.w, c);
+        *reinterpret_cast<float4*>(P + e) = p;
+        *reinterpret_cast<float4*>(M + e) = m;
+        *reinterpret_cast<float4*>(V + e) = v;
+      } else {
+        for (long i = e; i < e + 4 && i < numel; ++i) {
+          float p = P[i], m = M[i], v = V[i];
+          float g = Gr ? Gr[i] : 0.f;
+          if (l2x2 != 0.f) g += l2x2 * p;
+          adam_elem(p, m, v, g, c);
+          P[i] = p;
+          M[i] = m;
+          V[i] = v;
+        }
+      }
+    }
+    base += nc;
+  }
+}
+
+// ---- fil_embed_adam_runs: the run sums of embed_runs.h with an Adam epilogue.  Row `row` of field f = perm % F takes
+// g = run sum + 2 l2[f] p; Keras mode stamps the row with the step it was updated at (the sweep skips stamped rows).
+template <typename GT>
+__global__ __launch_bounds__(256) void embed_adam_runs_kernel(const GT* __restrict__ g, const int64_t* __restrict__ perm,
+                                                              const int64_t* __restrict__ sorted_ids, long R, int K, int F,
+                                                              const float* __restrict__ field_l2, float* __restrict__ table,
+                                                              float* __restrict__ m, float* __restrict__ v, int32_t* __restrict__ stamp,
+                                                              const int64_t* __restrict__ step, float lr, float b1, float b2, float eps) {
+  const AdamCoef c = adam_coef(step, lr, b1, b2, eps);
+  const int32_t tag = (int32_t)(uint32_t)(*step + 1);
+  embed_run_sums(g, perm, sorted_ids, R, K, [=](int64_t row, int kq, const float (&acc)[4], int64_t first) {
+    const float l2x2 = field_l2 ? 2.f * field_l2[first % F] : 0.f;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      if (kq * 4 + i < K) {
+        const int64_t e = row * K + kq * 4 + i;
+        float p = table[e], mm = m[e], vv = v[e];
+        adam_elem(p, mm, vv, acc[i] + l2x2 * p, c);
+        table[e] = p;
+        m[e] = mm;
+        v[e] = vv;
+      }
+    }
+    if (stamp && kq == 0) stamp[row] = tag;
+  });
+}
+
+// ---- fil_embed_adam_sweep: every row the run pass did not stamp at this step takes g = 2 l2[f] p (or 0); frozen fields are
+// left alone.  The field of a row comes from a binary search of the offsets held in LDS.
+constexpr int kSweepMaxF = 1024;
+
+__device__ __forceinline__ int sweep_field(const int64_t* off, int F, int64_t row) {
+  int lo = 0, hi = F;                      // last f with off[f] <= row, or -1
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    if (off[mid] <= row) lo = mid + 1;
+    else hi = mid;
+  }
+  return lo - 1;
+}
+
+__global__ __launch_bounds__(256) void embed_adam_sweep_kernel(float* __restrict__ table, float* __restrict__ m, float* __restrict__ v,
+                                                               const int32_t* __restrict__ stamp, int64_t V, int K,
+                                                               const int64_t* __restrict__ offsets, const float* __restrict__ field_l2,
+                                                               const unsigned char* __restrict__ frozen, int F,
+                                                               const int64_t* __restrict__ step, float lr, float b1, float b2, float eps,
+                                                               int vec) {
+  __shared__ int64_t s_off[kSweepMaxF];
+  __shared__ float s_l2x2[kSweepMaxF];        // 2 l2[f], or NaN for a frozen field
+  for (int f = threadIdx.x; f < F; f += blockDim.x) {
+    s_off[f] = offsets[f];
+    s_l2x2[f] = (frozen && frozen[f]) ? __builtin_nanf("") : (field_l2 ? 2.f * field_l2[f] : 0.f);
+  }
+  __syncthreads();
+  const AdamCoef c = adam_coef(step, lr, b1, b2, eps);
+  const int32_t tag = (int32_t)(uint32_t)(*step + 1);
+  const int64_t n = V * K;
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  if (vec) {                                  // K % 4 == 0 and 16-byte aligned arrays: a lane moves 4 elements of one row
+    const int64_t nq = n / 4;
+    for (int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; q < nq; q += stride) {
+      const int64_t row = q * 4 / K;
+      if (stamp[row] == tag) continue;
+      const int f = sweep_field(s_off, F, row);
+      const float l2x2 = f >= 0 ? s_l2x2[f] : 0.f;
+      if (l2x2 != l2x2) continue;             // frozen
+      f32x4 p = reinterpret_cast<const f32x4*>(table)[q];
+      f32x4 mm = reinterpret_cast<const f32x4*>(m)[q];
+      f32x4 vv = reinterpret_cast<const f32x4*>(v)[q];
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        float pi = p[i], mi = mm[i], vi = vv[i];
+        adam_elem(pi, mi, vi, l2x2 * pi, c);
+        p[i] = pi;
+        mm[i] = mi;
+        vv[i] = vi;
+      }
+      __builtin_nontemporal_store(p, reinterpret_cast<f32x4*>(table) + q);
+      __builtin_nontemporal_store(mm, reinterpret_cast<f32x4*>(m) + q);
+      __builtin_nontemporal_store(vv, reinterpret_cast<f32x4*>(v) + q);
+    }
+    return;
+  }
+  for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += stride) {
+    const int64_t row = e / K;
+    if (stamp[row] == tag) continue;
+    const int f = sweep_field(s_off, F, row);
+    const float l2x2 = f >= 0 ? s_l2x2[f] : 0.f;
+    if (l2x2 != l2x2) continue;
+    float p = table[e], mm = m[e], vv = v[e];
+    adam_elem(p, mm, vv, l2x2 * p, c);
+    __builtin_nontemporal_store(p, table + e);
+    __builtin_nontemporal_store(mm, m + e);
+    __builtin_nontemporal_store(vv, v + e);
+  }
+}
+
+static int check_hyper(const char* who, float lr, float b1, float b2, float eps) {
+  if (!(lr >= 0.f) || !(b1 >= 0.f && b1 < 1.f) || !(b2 >= 0.f && b2 < 1.f) || !(eps >= 0.f))
+    return fail(FIL_ERR_ARG, "%s: hyper-parameters lr=%g beta_1=%g beta_2=%g epsilon=%g (lr, epsilon >= 0; betas in [0, 1))", who,
+                (double)lr, (double)b1, (double)b2, (double)eps);
+  return FIL_OK;
+}
+
+}  // namespace fil
+
+using namespace fil;
+
+extern "C" int fil_adam_multi(const fil_adam_tensor* tensors, int n, int64_t total_numel, int64_t* step, float lr, float beta_1,
+                              float beta_2, float epsilon, int advance, void* stream) {
+  FIL_CHECK_ARG(n >= 0 && total_numel >= 0);
+  FIL_CHECK_ARG(step != nullptr);
+  FIL_CHECK_ARG(n == 0 || tensors != nullptr);
+  if (int rc = check_hyper("fil_adam_multi", lr, beta_1, beta_2, epsilon)) return rc;
+  if (advance != 0 && advance != 1) return fail(FIL_ERR_ARG, "fil_adam_multi: advance %d (0 or 1)", advance);
+  hipStream_t st = (hipStream_t)stream;
+  if (n > 0) {
+    ProfScope ps("adam_multi", st, 28.0 * (double)total_numel);
+    const long chunks = std::max<long>(1, (long)((total_numel + kMultiChunk - 1) / kMultiChunk));
+    const dim3 grid((int)std::min<long>(chunks, 256 * 8));
+    hipLaunchKernelGGL(adam_multi_kernel, grid, dim3(256), 0, st, tensors, n, step, lr, beta_1, beta_2, epsilon);
+    FIL_CHECK_LAUNCH();
+  }
+  if (advance) {
+    hipLaunchKernelGGL(adam_step_advance_kernel, dim3(1), dim3(1), 0, st, step);
+    FIL_CHECK_LAUNCH();
+  }
+  return FIL_OK;
+}
+
+extern "C" int fil_embed_adam_runs(const void* g, const int64_t* perm, const int64_t* sorted_ids, long R, int K, int g_dtype, int F,
+                                   const float* field_l2, float* table, float* m, float* v, int32_t* stamp, const int64_t* step,
+                                   float lr, float beta_1, float beta_2, float epsilon, int mode, void* stream) {
+  FIL_CHECK_ARG(R >= 0 && K >= 1 && F >= 1);
+  if (g_dtype != FIL_F32 && g_dtype != FIL_BF16) return fail(FIL_ERR_ARG, "fil_embed_adam_runs: g_dtype %d (f32 or bf16)", g_dtype);
+  if (mode != FIL_ADAM_KERAS && mode != FIL_ADAM_LAZY) return fail(FIL_ERR_ARG, "fil_embed_adam_runs: mode %d (FIL_ADAM_KERAS or FIL_ADAM_LAZY)", mode);
+  if (mode == FIL_ADAM_KERAS && stamp == nullptr)
+    return fail(FIL_ERR_ARG, "fil_embed_adam_runs: FIL_ADAM_KERAS needs the row stamps (fil_embed_adam_sweep skips the rows stamped here)");
+  if (K > 256) return fail(FIL_ERR_UNSUPPORTED, "fil_embed_adam_runs: K=%d > 256", K);
+  if (int rc = check_hyper("fil_embed_adam_runs", lr, beta_1, beta_2, epsilon)) return rc;
+  if (R == 0) return FIL_OK;
+  FIL_CHECK_ARG(g && perm && sorted_ids && table && m && v && step);
+  hipStream_t st = (hipStream_t)stream;
+  ProfScope ps("embed_adam_runs", st, (double)R * K * (g_dtype == FIL_F32 ? 4 : 2) + 24.0 * R * K);
+  const int C = 64 / ((K + 3) / 4);
+  const dim3 grid((int)std::min<long>((R + 4 * C - 1) / (4 * C), 256 * 32));
+  if (g_dtype == FIL_F32)
+    hipLaunchKernelGGL(embed_adam_runs_kernel<float>, grid, dim3(256), 0, st, static_cast<const float*>(g), perm, sorted_ids, R, K, F,
+                       field_l2, table, m, v, mode == FIL_ADAM_KERAS ? stamp : nullptr, step, lr, beta_1, beta_2, epsilon);
+  else
+    hipLaunchKernelGGL(embed_adam_runs_kernel<__hip_bfloat16>, grid, dim3(256), 0, st, static_cast<const __hip_bfloat16*>(g), perm,
+                       sorted_ids, R, K, F, field_l2, table, m, v, mode == FIL_ADAM_KERAS ? stamp : nullptr, step, lr, beta_1, beta_2,
+                       epsilon);
+  FIL_CHECK_LAUNCH();
+  return FIL_OK;
+}
+
+extern "C" int fil_embed_adam_sweep(float* table, float* m, float* v, const int32_t* stamp, int64_t V, int K, const int64_t* offsets,
+                                    const float* field_l2, const unsigned char* frozen, int F, const int64_t* step, float lr,
+                                    float beta_1, float beta_2, float epsilon, void* stream) {
+  FIL_CHECK_ARG(V >= 0 && K >= 1 && F >= 1);
+  if (F > kSweepMaxF) return fail(FIL_ERR_UNSUPPORTED, "fil_embed_adam_sweep: F=%d > %d fields", F, kSweepMaxF);
+  if (int rc = check_hyper("fil_embed_adam_sweep", lr, beta_1, beta_2, epsilon)) return rc;
+  if (V == 0) return FIL_OK;
+  FIL_CHECK_ARG(table && m && v && stamp && offsets && step);
+  hipStream_t st = (hipStream_t)stream;
+  const int64_t n = V * K;
+  const int vec = (K % 4 == 0 && ((((uintptr_t)table | (uintptr_t)m | (uintptr_t)v) & 15) == 0)) ? 1 : 0;
+  const int64_t work = vec ? n / 4 : n;
+  ProfScope ps("embed_adam_sweep", st, 24.0 * (double)n + 4.0 * (double)V);
+  const dim3 grid((int)std::max<int64_t>(1, std::min<int64_t>((work + 255) / 256, 256 * 8)));
+  hipLaunchKernelGGL(embed_adam_sweep_kernel, grid, dim3(256), 0, st, table, m, v, stamp, V, K, offsets, field_l2, frozen, F, step, lr,
+                     beta_1, beta_2, epsilon, vec);
+  FIL_CHECK_LAUNCH();
+  return FIL_OK;
+}

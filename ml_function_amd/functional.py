@@ -842,8 +842,14 @@ def embed_grad_rows(offsets, sizes, idx, g, frozen=None, layout_key=None, n_rows
 
 class _EmbedFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, table, offsets, sizes, idx, frozen, sparse_grad, atomic, oob_count, layout_key=None, xt_out=None, out_dtype=None):
+    def forward(ctx, table, offsets, sizes, idx, frozen, sparse_grad, atomic, oob_count, layout_key=None, xt_out=None, out_dtype=None,
+                runs_grad=None):
         _require_cuda(table, offsets, idx)
+        ctx.runs_grad = runs_grad
+        if runs_grad is not None:
+            if sparse_grad or atomic:
+                raise FilError("embed_gather: grad_mode='runs' excludes sparse_grad / atomic")
+            ctx.table_param = table
         table = _f32c(table)
         idx = idx.to(torch.int64).contiguous()
         offsets = offsets.to(torch.int64).contiguous()
@@ -877,7 +883,16 @@ class _EmbedFn(torch.autograd.Function):
         # (a bf16 block's gradient arrives as bf16: the dense deterministic path reads it as it is, the others take fp32)
         g_bf16 = g.dtype == torch.bfloat16 and not atomic and not sparse_grad
         g = g.contiguous() if g_bf16 else _f32c(g)
-        if atomic:      # opt-in: fp32 atomics into a zeroed dense table (order of additions not fixed)
+        if ctx.runs_grad is not None:   # deferred: the optimizer applies the runs in place (optim.Adam, fil_embed_adam_runs)
+            table = ctx.table_param
+            if getattr(table, "_fil_pending_runs", None) is not None:
+                raise FilError("embed_gather(grad_mode='runs'): the table already holds a pending gradient record -- one backward per "
+                               "table per optimizer step (call optimizer.step() or zero_grad() in between)")
+            sorted_ids, perm = _sorted_row_ids(offsets, sizes, frozen, idx, layout_key, table_shape[0], per_field=True)
+            table._fil_pending_runs = dict(g=g, perm=perm, sorted_ids=sorted_ids, R=B * F, K=K, F=F, g_dtype=FIL_BF16 if g_bf16 else FIL_F32,
+                                           **ctx.runs_grad)
+            dtable = None
+        elif atomic:      # opt-in: fp32 atomics into a zeroed dense table (order of additions not fixed)
             dtable = torch.zeros(table_shape, dtype=torch.float32, device=g.device)
             check(_lib.load().fil_embed_scatter_add(ptr(offsets), ptr(sizes), ptr(idx), ptr(g), ptr(dtable), B, F, K, stream_ptr()),
                   "fil_embed_scatter_add")
@@ -892,22 +907,24 @@ class _EmbedFn(torch.autograd.Function):
             dtable = torch.zeros(table_shape, dtype=torch.float32, device=g.device)
             check(lib.fil_embed_run_sum_dt(ptr(g), ptr(perm), ptr(sorted_ids), ptr(dtable), B * F, K, FIL_BF16 if g_bf16 else FIL_F32,
                                            stream_ptr()), "fil_embed_run_sum_dt")
-        return dtable, None, None, None, None, None, None, None, None, None, None
+        return dtable, None, None, None, None, None, None, None, None, None, None, None
 
 
 def embed_gather(table, offsets, idx, sizes=None, frozen=None, sparse_grad=False, atomic=False, oob_count=None, layout_key=None,
-                 emit_xt=False, out_dtype=None):
+                 emit_xt=False, out_dtype=None, runs_grad=None):
     """table [sum V_f, K] (all fields concatenated), offsets [F], idx [B,F] -> packed [B,F,K].
     sizes [F] int64: ids outside [0, V_f) give zero rows (counted in oob_count, an int32 device scalar) and no gradient.
     The gradient is deterministic (sorted segment sums); sparse_grad=True returns it as a sparse COO tensor over the touched
-    rows instead of a dense table; atomic=True selects the fp32-atomic scatter-add instead."""
+    rows instead of a dense table; atomic=True selects the fp32-atomic scatter-add instead.
+    runs_grad (a dict: offsets, frozen, field_l2 [F] fp32 or None): the table gets NO gradient; the backward leaves the sorted runs
+    (g, perm, sorted_ids) on the table as `table._fil_pending_runs` for optim.Adam to apply in place (fil_embed_adam_runs)."""
     if not emit_xt:   # (out_dtype=torch.bfloat16: the block leaves the gather rounded to bf16 and its gradient is read as bf16 -- no cast launches)
-        return _EmbedFn.apply(table, offsets, sizes, idx, frozen, sparse_grad, atomic, oob_count, layout_key, None, out_dtype)
+        return _EmbedFn.apply(table, offsets, sizes, idx, frozen, sparse_grad, atomic, oob_count, layout_key, None, out_dtype, runs_grad)
     # emit_xt: the same launch also writes the block transposed to [B*K, F], the layout the CIN kernels read; it rides on the
     # result as `_fil_xt` (the CIN layer picks it up: no second pass over the block)
     B, F = idx.shape
     xt = torch.empty((B * table.shape[1], F), dtype=torch.float32, device=table.device)
-    out = _EmbedFn.apply(table, offsets, sizes, idx, frozen, sparse_grad, atomic, oob_count, layout_key, xt)
+    out = _EmbedFn.apply(table, offsets, sizes, idx, frozen, sparse_grad, atomic, oob_count, layout_key, xt, None, runs_grad)
     out._fil_xt = xt
     out._fil_xt_version = out._version      # a consumer ignores xt once the block has been modified in place
     return out

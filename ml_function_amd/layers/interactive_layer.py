@@ -367,10 +367,15 @@ class SparseEmbed(Layer):
     Ids are range-checked in the kernel: an id outside [0, word_size) produces a zero row and no gradient (Keras on a GPU);
     ``check_ids=True`` (or FIL_CHECK_IDS=1) additionally raises, like Keras on the CPU does (costs a device sync per call).
     ``sparse_grad=True`` hands the table gradient out as a sparse COO tensor over the touched rows (Keras' IndexedSlices)
-    instead of a dense table; either way it is deterministic (sorted segment sums, no atomics)."""
+    instead of a dense table; either way it is deterministic (sorted segment sums, no atomics).
+    ``grad_mode="runs"`` (extension; default "dense") defers the table gradient to ml_function_amd.optim.Adam: the backward hands
+    the optimizer the batch's sorted gradient runs instead of a [V,K] tensor (the table's .grad stays None), and the optimizer
+    updates table, m and v in place (fil_embed_adam_runs), adding the l2(emb_reg) gradient of table_l2_ranges() itself -- so
+    regularization_losses() then reports the l2 terms DETACHED (the loss value is unchanged, no dense gradient flows).  Needs
+    optim.Adam; any other optimizer would see no gradient for the table."""
 
     def __init__(self, sparse_info: list, is_linear=False, use_flatten=True, use_add=False, seed=2020, support_masking=True,
-                 mask_zero=False, packed=False, check_ids=None, sparse_grad=False, emit_xt=False, out_dtype=None):
+                 mask_zero=False, packed=False, check_ids=None, sparse_grad=False, emit_xt=False, out_dtype=None, grad_mode="dense"):
         super().__init__()
         self.sparse_info = sparse_info
         self.is_linear = is_linear
@@ -384,6 +389,11 @@ class SparseEmbed(Layer):
         self.sparse_grad = sparse_grad
         self.emit_xt = emit_xt      # extension: also emit the block transposed to [B*K, F] for a CIN consumer (fil_embed_gather_xt)
         self.out_dtype = out_dtype  # extension: torch.bfloat16 = the block in bf16 straight out of the gather (a bf16 model's cast, fused)
+        if grad_mode not in ("dense", "runs"):
+            raise ValueError("SparseEmbed: grad_mode %r (dense or runs)" % (grad_mode,))
+        if grad_mode == "runs" and sparse_grad:
+            raise ValueError("SparseEmbed: grad_mode='runs' and sparse_grad=True exclude each other")
+        self.grad_mode = grad_mode
 
     def build(self, input_shape):
         dims = {int(i.linear_unit if self.is_linear else i.cross_unit) for i in self.sparse_info}
@@ -423,12 +433,21 @@ class SparseEmbed(Layer):
         self.register_buffer("frozen", torch.tensor(frozen, dtype=torch.uint8, device=dev) if any(frozen) else None)
         # tables with the same field layout (the embeddings and the linear weights of one model) share the sort of their gradient
         self._layout_key = (tuple(sizes), tuple(frozen) if any(frozen) else None)
+        if self.grad_mode == "runs":
+            # per-field l2 coefficients of table_l2_ranges() (each range is one field's table) for the optimizer's fused update
+            field_l2 = [0.0] * len(sizes)
+            for lo, _, reg in self._reg:
+                field_l2[offsets.index(lo)] = reg
+            self.register_buffer("field_l2", torch.tensor(field_l2, dtype=torch.float32, device=dev) if self._reg else None)
+            self.embeddings._fil_runs_table = True        # optim.Adam: a table whose gradient arrives as runs
         super().build(input_shape)
 
     def regularization_losses(self):
         """tf.keras.regularizers.l2(emb_reg) on each field's table (interactive_layer.py:217): emb_reg * sum(table^2)."""
         if not self.built:
             return []
+        if self.grad_mode == "runs":     # the optimizer adds their gradient (table_l2_ranges): the value only
+            return [reg * self.embeddings.detach()[lo:hi].square().sum() for lo, hi, reg in self._reg]
         return [reg * self.embeddings[lo:hi].square().sum() for lo, hi, reg in self._reg]
 
     def table_l2_ranges(self):
@@ -441,7 +460,9 @@ class SparseEmbed(Layer):
         oob = torch.zeros((), dtype=torch.int32, device=idx.device) if self.check_ids else None
         block = Fn.embed_gather(self.embeddings, self.offsets, idx, sizes=self.sizes, frozen=self.frozen,
                                 sparse_grad=self.sparse_grad, oob_count=oob, layout_key=self._layout_key,
-                                emit_xt=self.emit_xt, out_dtype=self.out_dtype)  # [B,F,K]
+                                emit_xt=self.emit_xt, out_dtype=self.out_dtype,
+                                runs_grad=(dict(offsets=self.offsets, frozen=self.frozen, field_l2=self.field_l2)
+                                           if self.grad_mode == "runs" else None))  # [B,F,K]
         if oob is not None and int(oob) > 0:
             bad = ((idx < 0) | (idx >= self.sizes)).nonzero()[0].tolist()
             raise IndexError("SparseEmbed: %d ids outside their vocabulary, first at sample %d, field %s (id %d, word_size %d)"

@@ -49,17 +49,19 @@ class FeatureInput(Layer):
     optional linear embeddings) and passes the dense columns through as F_d tensors [B,1]."""
 
     def __init__(self, sparseInfo=None, denseInfo=None, useLinear=False, useAddLinear=False, useFlattenLinear=False,
-                 useFlattenSparse=False, emitXT=False, embedDtype=None):
+                 useFlattenSparse=False, emitXT=False, embedDtype=None, tableGrad="dense"):
         super().__init__()
         self.sparse_info = sparseInfo or []
         self.dense_info = denseInfo or []
         self.use_linear = useLinear
         # emitXT (extension): the embedding gather also writes the block in the layout the CIN kernels read (XDeepFM)
         # embedDtype (extension): torch.bfloat16 = the cross embeddings leave the gather as bf16 (a bf16 model's cast of the block, fused)
-        self.sparse_embed = (SparseEmbed(self.sparse_info, use_flatten=useFlattenSparse, emit_xt=emitXT, out_dtype=embedDtype)
-                             if self.sparse_info else None)
-        self.linear_embed = (SparseEmbed(self.sparse_info, use_flatten=useFlattenLinear, is_linear=True, use_add=useAddLinear)
-                             if (useLinear and self.sparse_info) else None)
+        # tableGrad (extension): "runs" = the tables' gradients go to ml_function_amd.optim.Adam as the batch's sorted runs and are
+        # applied in place (SparseEmbed(grad_mode="runs")); "dense" (default) = a [V,K] gradient tensor per table
+        self.sparse_embed = (SparseEmbed(self.sparse_info, use_flatten=useFlattenSparse, emit_xt=emitXT, out_dtype=embedDtype,
+                                         grad_mode=tableGrad) if self.sparse_info else None)
+        self.linear_embed = (SparseEmbed(self.sparse_info, use_flatten=useFlattenLinear, is_linear=True, use_add=useAddLinear,
+                                         grad_mode=tableGrad) if (useLinear and self.sparse_info) else None)
 
     def call(self, inputs, **kwargs):
         dense, sparse_idx = inputs

@@ -1,0 +1,214 @@
+"""Keras' Adam on the HIP path (include/fil.h O1): the optimizer the reference compiles (optimizer='adam', example/ctr_example/
+un_seq.py:61; TF 2.1), with Keras' names, defaults and numerics.
+
+    opt = optim.Adam(model.parameters())                    # learning_rate 1e-3, beta_1 0.9, beta_2 0.999, epsilon 1e-7
+    loss.backward(); opt.step(); opt.zero_grad()
+
+Keras adds epsilon to the UNCORRECTED sqrt(v) and folds the bias correction into the step size (alpha = lr sqrt(1 - b2^t) /
+(1 - b1^t); p -= alpha m / (sqrt(v) + eps)); torch.optim.Adam adds it to the corrected sqrt(v / (1 - b2^t)), which at t = 1 is an
+epsilon 1/sqrt(1 - beta_2) ~ 31.6 times larger -- of the order of an embedding row's gradient.
+
+* Dense parameters with a gradient: ONE fil_adam_multi launch per (parameter group, device) over all of them.  A parameter whose
+  .grad is None is skipped (Keras filters None gradients); the step counter advances anyway.
+* Embedding tables of SparseEmbed(grad_mode="runs") / FeatureInput(tableGrad="runs"): the backward leaves the batch's sorted
+  gradient runs on the table and step() applies them IN PLACE -- fil_embed_adam_runs, plus fil_embed_adam_sweep over every row the
+  batch did not touch (Keras' dense Adam: their m and v decay and they move; l2(emb_reg) of table_l2_ranges() is added inside the
+  update).  No [V,K] gradient is ever built.  lazy_tables=True is the LABELLED deviation from the reference (TF-Addons LazyAdam):
+  only the touched rows change, no sweep.  A table in "dense" mode is an ordinary dense parameter here.
+* The step counter t (Keras' `iterations`) is an int64 on the device, read by every launch and advanced by the last one: a step
+  captured into a HIP graph (capture.capture_step) advances it on every replay.  Learning rate and betas are baked into a capture.
+
+Only fp32 parameters on a GPU are supported: anything else raises (there is no CPU / eager fallback).
+"""
+import ctypes
+
+import torch
+
+from . import _lib
+from ._lib import FIL_ADAM_KERAS, FIL_ADAM_LAZY, FilError, check, ptr, stream_ptr
+
+
+class _Desc(ctypes.Structure):
+    """fil_adam_tensor (include/fil.h)"""
+    _fields_ = [("param", ctypes.c_void_p), ("grad", ctypes.c_void_p), ("m", ctypes.c_void_p), ("v", ctypes.c_void_p),
+                ("numel", ctypes.c_int64), ("l2", ctypes.c_float), ("reserved", ctypes.c_int32)]
+
+
+assert ctypes.sizeof(_Desc) == 48
+
+
+class Adam(torch.optim.Optimizer):
+    def __init__(self, params, learning_rate=1e-3, beta_1=0.9, beta_2=0.999, epsilon=1e-7, lazy_tables=False):
+        if not learning_rate >= 0.0 or not 0.0 <= beta_1 < 1.0 or not 0.0 <= beta_2 < 1.0 or not epsilon >= 0.0:
+            raise ValueError("Adam: learning_rate=%r beta_1=%r beta_2=%r epsilon=%r (rate, epsilon >= 0; betas in [0, 1))"
+                             % (learning_rate, beta_1, beta_2, epsilon))
+        super().__init__(params, dict(learning_rate=float(learning_rate), beta_1=float(beta_1), beta_2=float(beta_2),
+                                      epsilon=float(epsilon)))
+        self.lazy_tables = bool(lazy_tables)
+        self._t = {}            # device -> int64 [1] step counter (Keras' iterations)
+        self._stamps = {}       # runs table -> int32 [V] row stamps of FIL_ADAM_KERAS (valid within one step only: not state)
+        self._descs = {}        # descriptor key -> (device descriptors, pinned host copy)
+        self._pinned = []       # descriptor arrays built during a stream capture: a graph replays them, they are never dropped
+        # pinned staging for descriptors built DURING a capture: a host allocation there would invalidate it, so it is reserved by
+        # the first eager step; a captured copy reads its slice at every replay, so a slice is never handed out twice
+        self._arena, self._arena_off = None, 0
+
+    # -- state ---------------------------------------------------------------------------------------------------
+    def _counter(self, dev):
+        t = self._t.get(dev)
+        if t is None:
+            t = self._t[dev] = torch.zeros(1, dtype=torch.int64, device=dev)
+        return t
+
+    @property
+    def iterations(self):
+        """Completed steps (Keras' optimizer.iterations), as a host int (synchronises)."""
+        return int(next(iter(self._t.values()))[0]) if self._t else 0
+
+    def _moments(self, p):
+        st = self.state[p]
+        if "m" not in st:
+            st["m"] = torch.zeros_like(p, memory_format=torch.contiguous_format)
+            st["v"] = torch.zeros_like(p, memory_format=torch.contiguous_format)
+        return st["m"], st["v"]
+
+    def state_dict(self):
+        sd = super().state_dict()
+        sd["iterations"] = self.iterations
+        return sd
+
+    def load_state_dict(self, state_dict):
+        state_dict = dict(state_dict)
+        it = int(state_dict.pop("iterations", 0))
+        super().load_state_dict(state_dict)
+        for p, st in self.state.items():        # (torch's loader may hand non-contiguous copies back)
+            for k in ("m", "v"):
+                if k in st:
+                    st[k] = st[k].contiguous()
+        for g in self.param_groups:
+            for p in g["params"]:
+                self._counter(p.device)
+        for t in self._t.values():
+            t.fill_(it)
+        for s in self._stamps.values():         # t may go backwards: a stale stamp must never look current
+            s.zero_()
+
+    def reset_(self):
+        """Back to "never stepped" IN PLACE (moments, stamps and counter keep their storage): what a capture's restore needs after
+        warm-up steps (capture.capture_step(..., restore=...))."""
+        for st in self.state.values():
+            for k in ("m", "v"):
+                if k in st:
+                    st[k].zero_()
+        for s in self._stamps.values():
+            s.zero_()
+        for t in self._t.values():
+            t.zero_()
+
+    def zero_grad(self, set_to_none=True):
+        super().zero_grad(set_to_none=set_to_none)
+        for g in self.param_groups:
+            for p in g["params"]:
+                if getattr(p, "_fil_pending_runs", None) is not None:
+                    p._fil_pending_runs = None
+
+    # -- the step ------------------------------------------------------------------------------------------------
+    def _desc_array(self, dev, entries):
+        key = (dev, tuple(entries))
+        hit = self._descs.get(key)
+        if hit is not None:
+            return hit[0]
+        host = (_Desc * len(entries))(*[_Desc(p, g, m, v, n, l2, 0) for p, g, m, v, n, l2 in entries])
+        size = ctypes.sizeof(host)
+        capturing = torch.cuda.is_current_stream_capturing()
+        if capturing:
+            if self._arena is None or self._arena_off + size > self._arena.numel():
+                raise FilError("optim.Adam: no room for the descriptors of a captured step -- run one eager step before capturing "
+                               "(capture.capture_step's warm-up does)")
+            pinned = self._arena[self._arena_off:self._arena_off + size]
+            self._arena_off += (size + 255) // 256 * 256
+        else:
+            if self._arena is None:
+                self._arena = torch.empty(max(1 << 16, 8 * size), dtype=torch.uint8, pin_memory=True)
+            pinned = torch.empty(size, dtype=torch.uint8, pin_memory=True)
+        ctypes.memmove(pinned.data_ptr(), ctypes.addressof(host), size)
+        d = torch.empty(size, dtype=torch.uint8, device=dev)
+        d.copy_(pinned, non_blocking=True)
+        if capturing:
+            self._pinned.append((d, pinned))
+        else:
+            if len(self._descs) >= 16:
+                self._descs.clear()
+            self._descs[key] = (d, pinned)
+        return d
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        lib = _lib.load()
+        calls = []      # (device, hyper, entries) of the fil_adam_multi launches, in group order
+        for group in self.param_groups:
+            hyper = (group["learning_rate"], group["beta_1"], group["beta_2"], group["epsilon"])
+            per_dev = {}
+            for p in group["params"]:
+                pend = getattr(p, "_fil_pending_runs", None)
+                if pend is None and p.grad is None:
+                    continue
+                if p.device.type != "cuda" or p.dtype != torch.float32 or not p.is_contiguous():
+                    raise FilError("optim.Adam: parameter %s %s on %s -- contiguous fp32 GPU tensors only" % (tuple(p.shape), p.dtype, p.device))
+                m, v = self._moments(p)
+                t = self._counter(p.device)
+                if pend is not None:
+                    if p.grad is not None:
+                        raise FilError("optim.Adam: table %s has both a .grad and a pending runs record (a gradient reached the table "
+                                       "outside its gather -- e.g. a regulariser not detached)" % (tuple(p.shape),))
+                    self._apply_runs(lib, p, pend, m, v, t, hyper)
+                    p._fil_pending_runs = None
+                    continue
+                g = p.grad
+                if g.is_sparse or g.dtype != torch.float32 or not g.is_contiguous() or g.shape != p.shape:
+                    raise FilError("optim.Adam: gradient of %s must be a dense contiguous fp32 tensor of its shape" % (tuple(p.shape),))
+                per_dev.setdefault(p.device, []).append((p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel(), 0.0))
+            for dev, entries in per_dev.items():
+                calls.append((dev, hyper, entries))
+        # the last launch on every device advances its counter -- one with no tensors where nothing dense had a gradient
+        devs = set(self._t)
+        for g in self.param_groups:
+            for p in g["params"]:
+                if p.device.type == "cuda":
+                    devs.add(p.device)
+        last = {}
+        for i, (dev, _, _) in enumerate(calls):
+            last[dev] = i
+        for dev in devs:
+            if dev not in last:
+                calls.append((dev, (self.defaults["learning_rate"], self.defaults["beta_1"], self.defaults["beta_2"],
+                                    self.defaults["epsilon"]), []))
+                last[dev] = len(calls) - 1
+        for i, (dev, (lr, b1, b2, eps), entries) in enumerate(calls):
+            with torch.cuda.device(dev):
+                desc = self._desc_array(dev, entries) if entries else None
+                check(lib.fil_adam_multi(ptr(desc), len(entries), sum(e[4] for e in entries), ptr(self._counter(dev)), lr, b1, b2, eps,
+                                         1 if last[dev] == i else 0, stream_ptr()), "fil_adam_multi")
+        return loss
+
+    def _apply_runs(self, lib, p, pend, m, v, t, hyper):
+        lr, b1, b2, eps = hyper
+        V, K = p.shape
+        mode = FIL_ADAM_LAZY if self.lazy_tables else FIL_ADAM_KERAS
+        stamp = None
+        if mode == FIL_ADAM_KERAS:
+            stamp = self._stamps.get(p)
+            if stamp is None:
+                stamp = self._stamps[p] = torch.zeros(V, dtype=torch.int32, device=p.device)
+        with torch.cuda.device(p.device):
+            st = stream_ptr()
+            check(lib.fil_embed_adam_runs(ptr(pend["g"]), ptr(pend["perm"]), ptr(pend["sorted_ids"]), pend["R"], K, pend["g_dtype"],
+                                          pend["F"], ptr(pend["field_l2"]), ptr(p), ptr(m), ptr(v), ptr(stamp), ptr(t), lr, b1, b2, eps,
+                                          mode, st), "fil_embed_adam_runs")
+            if mode == FIL_ADAM_KERAS:
+                check(lib.fil_embed_adam_sweep(ptr(p), ptr(m), ptr(v), ptr(stamp), V, K, ptr(pend["offsets"]), ptr(pend["field_l2"]),
+                                               ptr(pend["frozen"]), pend["F"], ptr(t), lr, b1, b2, eps, st), "fil_embed_adam_sweep")
