@@ -13,7 +13,8 @@ side stream); the loss is Keras' compiled loss: binary cross-entropy + the layer
 of every embedding table, interactive_layer.py:217); the optimiser is Keras' 'adam' (lr 1e-3, epsilon 1e-7).
 Data parallel: every rank trains on its own shard of the table, dense gradients go through one bucketed all-reduce
 (ml_function_amd.dp.allreduce_module_grads), the embedding tables exchange only the rows their shards touched
-(dp.exchange_sparse_rows).  Labels come from a fixed random "teacher" so that the AUC has something to learn.
+(dp.exchange_sparse_rows) -- or, with --optimizer keras --dp-tables runs, their compacted gradient runs (optim.Adam's runs
+exchange).  Labels come from a fixed random "teacher" so that the AUC has something to learn.
 """
 import argparse
 import os
@@ -59,7 +60,12 @@ def main():
                     help="torch = torch.optim.Adam on dense table gradients; keras = ml_function_amd.optim.Adam (Keras' epsilon placement), "
                          "on one GPU with the tables updated in place from the batch's gradient runs (tableGrad='runs'); keras-lazy = the "
                          "same with LazyAdam tables (only touched rows change: a labelled deviation from the reference).  Data parallel: "
-                         "the tables keep their dense gradients and the sparse row exchange")
+                         "the tables keep their dense gradients and the sparse row exchange unless --dp-tables runs")
+    ap.add_argument("--dp-tables", default="dense", choices=["dense", "runs"],
+                    help="data parallel with --optimizer keras|keras-lazy: runs = the tables take tableGrad='runs' and optim.Adam's runs "
+                         "exchange (each rank's compacted gradient runs all-gathered, one merged update per replica, no [V,K] gradient, "
+                         "no host sync after the first step); dense = the dense table gradients and dp.exchange_sparse_rows.  The default "
+                         "stays dense: the runs exchange's all-gather at N > 1 ranks has not been timed on hardware yet (one GPU only)")
     ap.add_argument("--no-graph", action="store_true",
                     help="run every step eagerly (default on one GPU: the whole step -- forward, backward, Adam -- is captured once "
                          "into a HIP graph and replayed; the C ABI neither allocates nor synchronises, so it is capture-safe)")
@@ -89,7 +95,7 @@ def main():
     single = args.model == "XDeepFM"
     keras = args.optimizer != "torch"
     fi = models.FeatureInput(sparseInfo=info, useLinear=args.model != "DCN" and args.model != "AutoInt", useAddLinear=single,
-                             useFlattenLinear=True, tableGrad="runs" if keras and world == 1 else "dense")
+                             useFlattenLinear=True, tableGrad="runs" if keras and (world == 1 or args.dp_tables == "runs") else "dense")
     body = {"FM": models.FM, "DeepFM": models.DeepFM, "DCN": models.DCN, "AutoInt": models.AutoInt, "NFM": models.NFM,
             "AFM": models.AFM, "XDeepFM": lambda: models.XDeepFM(conv_size=[128, 128, 128], precision=args.cin_precision)}[args.model]()
     torch.manual_seed(0)  # identical replicas
@@ -125,7 +131,7 @@ def main():
             offs = fi.sparse_embed.offsets
             rows = (idx + offs).reshape(-1)
             for t in tables:
-                if t.grad is not None:
+                if t.grad is not None:          # (runs tables have no .grad: optim.Adam exchanges their runs and adds their l2 itself)
                     dp.exchange_sparse_rows(t.grad, rows)
         for t in tables:
             if t.grad is not None and table_l2.get(id(t)):

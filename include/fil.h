@@ -366,8 +366,27 @@ int fil_merge_softmax_bwd(const void* const* parts, const int* widths, const int
  *     g = 2 * field_l2[f] * p (0 without l2): m and v decay and the row moves, as Keras' dense Adam moves every row.  Row r belongs to
  *     the last field f with offsets[f] <= r (none: no l2); rows of fields with frozen[f] != 0 (frozen [F] may be NULL) are left alone
  *     (a non-trainable Keras Embedding is not in the optimizer's variable list).  One read and one non-temporal write of p, m, v and a
- *     read of stamp per row; F <= 1024.
+ *     read of stamp per row; F <= 1024. *
+ *   Data parallelism (every rank holds the whole table; each rank's batch shard leaves its own runs record):
+ *   fil_embed_runs_compact: one record -> a compact list.  ids_out [cap] = the distinct row ids >= 0 of sorted_ids in ascending order
+ *     (ids -1 dropped; ascending because offsets[] ascends, as fil_embed_sort_fields requires of a sorted list), values_out [cap, K]
+ *     fp32 = each run's sum in fil_embed_run_sum's order (bit-identical to the dense gradient's row), *count_out (device int64) = the
+ *     number of ids; slots [count, cap) get ids INT64_MAX (a binary search over all cap entries stays valid; their values are left
+ *     as they were).  cap >= R; R < 2^31.  Workspace: fil_embed_runs_compact_workspace_bytes(R).  Three launches, none sized by data
+ *     (capturable); the compaction scan is integer, hence deterministic.
+ *   fil_embed_adam_merged: W such lists gathered back to back -- ids [W][cap], values [W][cap][K], counts [W] (device) -- applied to
+ *     table / m / v [V, K] in place: every row of the union is updated once, by its owner (the lowest list holding it), with
+ *     g = the row's sums added in list order 0 .. W-1 + 2 * field_l2[f] * p (f = the last field with offsets[f] <= row, as in the
+ *     sweep; field_l2 may be NULL) and the update above; FIL_ADAM_KERAS stamps it (then fil_embed_adam_sweep, unchanged).  Every
+ *     replica that applies the same gathered lists computes the same bits; W = 1 is bit-identical to fil_embed_adam_runs on the same
+ *     record.  Rows outside [0, V) are skipped.  F <= 1024, K <= 256.
  */
+size_t fil_embed_runs_compact_workspace_bytes(long R);
+int fil_embed_runs_compact(const void* g, const int64_t* perm, const int64_t* sorted_ids, long R, int K, int g_dtype, int64_t* ids_out,
+                           float* values_out, int64_t* count_out, long cap, void* workspace, size_t workspace_bytes, void* stream);
+int fil_embed_adam_merged(const int64_t* ids, const float* values, const int64_t* counts, int W, long cap, int K, const int64_t* offsets,
+                          const float* field_l2, int F, float* table, float* m, float* v, int32_t* stamp, int64_t V, const int64_t* step,
+                          float lr, float beta_1, float beta_2, float epsilon, int mode, void* stream);
 typedef struct {
   float* param;
   const float* grad;   /* NULL = zero gradient */

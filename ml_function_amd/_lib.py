@@ -84,6 +84,9 @@ SIGNATURES = {
     "fil_adam_multi": (_I, [_P, _I, _c.c_int64, _P, _F, _F, _F, _F, _I, _P]),
     "fil_embed_adam_runs": (_I, [_P, _P, _P, _c.c_long, _I, _I, _I, _P, _P, _P, _P, _P, _P, _F, _F, _F, _F, _I, _P]),
     "fil_embed_adam_sweep": (_I, [_P, _P, _P, _P, _c.c_int64, _I, _P, _P, _P, _I, _P, _F, _F, _F, _F, _P]),
+    "fil_embed_runs_compact_workspace_bytes": (_Z, [_c.c_long]),
+    "fil_embed_runs_compact": (_I, [_P, _P, _P, _c.c_long, _I, _I, _P, _P, _P, _c.c_long, _P, _Z, _P]),
+    "fil_embed_adam_merged": (_I, [_P, _P, _P, _I, _c.c_long, _I, _P, _P, _I, _P, _P, _P, _P, _c.c_int64, _P, _F, _F, _F, _F, _I, _P]),
 }
 
 

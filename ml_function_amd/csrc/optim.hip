@@ -10,6 +10,9 @@
 // (4 loads + 3 stores of 16 B per lane; 256-lane workgroups, a few per CU: ~64 KiB of loads in flight per CU), scalar otherwise and in
 // the tail.  The sweep's stores are non-temporal (a 2 GB table pass must not evict the MALL).  fil_embed_adam_runs reuses the run sums
 // of fil_embed_run_sum (embed_runs.h): the same order, so a row's gradient is bit-identical to what the dense path materialises.
+// Data parallel: fil_embed_runs_compact turns a rank's record into a compact list (distinct ids, their run sums) of fixed capacity,
+// and fil_embed_adam_merged applies the W gathered lists -- every row once, by its lowest rank, summed in rank order -- before the
+// sweep, so every replica computes the same bits.
 #include "common.h"
 #include "embed_runs.h"
 #include <hip/hip_bf16.h>
@@ -193,6 +196,174 @@ __global__ __launch_bounds__(256) void embed_adam_sweep_kernel(float* __restrict
   }
 }
 
+// ---- fil_embed_runs_compact: the run sums of embed_runs.h stored into compact slots.  Three launches, none sized by data:
+//   count  one workgroup per kCompactTile sorted positions counts its run starts (id >= 0, != the id before);
+//   write  every workgroup sums the counts of the tiles before it (and of all tiles: the total), scans its own starts in position
+//          order and writes ids_out[u] = id and slot[perm of the start] = u; the slots [count, cap) get INT64_MAX, count_out the total;
+//   sums   embed_run_sums with an epilogue that stores the row into values_out[slot[perm of the run's first element]].
+// perm holds each position b*F + f exactly once (< R), so the slot map needs R entries.  Integer scans: deterministic.
+constexpr int kCompactPer = 8;
+constexpr int kCompactTile = 256 * kCompactPer;
+
+__device__ __forceinline__ bool run_start_at(const int64_t* __restrict__ sorted_ids, long j) {
+  const int64_t id = sorted_ids[j];
+  return id >= 0 && (j == 0 || sorted_ids[j - 1] != id);
+}
+
+// sum of x over a 256-lane workgroup (s: 4 ints of LDS); every lane gets the total
+__device__ __forceinline__ long block_sum_256(long x, long* s) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o, 64);
+  if ((threadIdx.x & 63) == 0) s[threadIdx.x >> 6] = x;
+  __syncthreads();
+  const long t = (s[0] + s[1]) + (s[2] + s[3]);
+  __syncthreads();
+  return t;
+}
+
+__global__ __launch_bounds__(256) void runs_count_kernel(const int64_t* __restrict__ sorted_ids, long R, int64_t* __restrict__ tile_count) {
+  __shared__ long s[4];
+  const long base = (long)blockIdx.x * kCompactTile + (long)threadIdx.x * kCompactPer;
+  long n = 0;
+#pragma unroll
+  for (int i = 0; i < kCompactPer; ++i)
+    if (base + i < R && run_start_at(sorted_ids, base + i)) ++n;
+  n = block_sum_256(n, s);
+  if (threadIdx.x == 0) tile_count[blockIdx.x] = n;
+}
+
+__global__ __launch_bounds__(256) void runs_write_kernel(const int64_t* __restrict__ sorted_ids, const int64_t* __restrict__ perm, long R,
+                                                         const int64_t* __restrict__ tile_count, int tiles, long cap,
+                                                         int64_t* __restrict__ ids_out, int64_t* __restrict__ count_out,
+                                                         int32_t* __restrict__ slot) {
+  __shared__ long s[4];
+  __shared__ long s_scan[4];
+  long before = 0, all = 0;
+  for (int b = threadIdx.x; b < tiles; b += 256) {
+    const long c = tile_count[b];
+    all += c;
+    before += b < (int)blockIdx.x ? c : 0;
+  }
+  before = block_sum_256(before, s);
+  all = block_sum_256(all, s);
+  // this lane's starts, then an exclusive scan over the workgroup in lane order (= position order)
+  const long base = (long)blockIdx.x * kCompactTile + (long)threadIdx.x * kCompactPer;
+  unsigned flags = 0;
+#pragma unroll
+  for (int i = 0; i < kCompactPer; ++i)
+    if (base + i < R && run_start_at(sorted_ids, base + i)) flags |= 1u << i;
+  const long mine = __builtin_popcount(flags);
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  long incl = mine;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const long y = __shfl_up(incl, o, 64);
+    if (lane >= o) incl += y;
+  }
+  if (lane == 63) s_scan[wave] = incl;
+  __syncthreads();
+  long u = before + incl - mine;
+  for (int w = 0; w < wave; ++w) u += s_scan[w];
+#pragma unroll
+  for (int i = 0; i < kCompactPer; ++i) {
+    if (flags & (1u << i)) {
+      const long j = base + i;
+      const int64_t pj = perm[j];
+      if (u < cap) ids_out[u] = sorted_ids[j];
+      if ((uint64_t)pj < (uint64_t)R) slot[pj] = (int32_t)u;
+      ++u;
+    }
+  }
+  for (long i = all + (long)blockIdx.x * 256 + threadIdx.x; i < cap; i += (long)gridDim.x * 256) ids_out[i] = INT64_MAX;
+  if (blockIdx.x == 0 && threadIdx.x == 0) *count_out = all;
+}
+
+template <typename GT>
+__global__ __launch_bounds__(256) void runs_compact_sums_kernel(const GT* __restrict__ g, const int64_t* __restrict__ perm,
+                                                                const int64_t* __restrict__ sorted_ids, long R, int K,
+                                                                const int32_t* __restrict__ slot, long cap, float* __restrict__ values_out) {
+  embed_run_sums(g, perm, sorted_ids, R, K, [=](int64_t, int kq, const float (&acc)[4], int64_t first) {
+    if ((uint64_t)first >= (uint64_t)R) return;
+    const long u = slot[first];
+    if (u < 0 || u >= cap) return;
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+      if (kq * 4 + i < K) values_out[u * K + kq * 4 + i] = acc[i];
+  });
+}
+
+// ---- fil_embed_adam_merged: one lane per gathered entry (w, i).  The lowest list holding a row owns it; the owner adds the other
+// lists' copies in list order (binary searches: each list is ascending and distinct), adds the field's l2 term and updates the row
+// exactly as embed_adam_runs_kernel does.  K is walked in chunks of kMergeChunk elements (a later chunk repeats the searches).
+constexpr int kMergeChunk = 16;
+
+__device__ __forceinline__ long find_row(const int64_t* __restrict__ list, long n, int64_t row) {
+  long lo = 0, hi = n;
+  while (lo < hi) {
+    const long mid = (lo + hi) >> 1;
+    if (list[mid] < row) lo = mid + 1;
+    else hi = mid;
+  }
+  return lo < n && list[lo] == row ? lo : -1;
+}
+
+__device__ __forceinline__ long list_count(const int64_t* counts, int w, long cap) {
+  const int64_t c = counts[w];
+  return c < 0 ? 0 : (c > cap ? cap : (long)c);
+}
+
+__global__ __launch_bounds__(256) void embed_adam_merged_kernel(const int64_t* __restrict__ ids, const float* __restrict__ values,
+                                                                const int64_t* __restrict__ counts, int W, long cap, int K,
+                                                                const int64_t* __restrict__ offsets, const float* __restrict__ field_l2,
+                                                                int F, float* __restrict__ table, float* __restrict__ m,
+                                                                float* __restrict__ v, int32_t* __restrict__ stamp, int64_t V,
+                                                                const int64_t* __restrict__ step, float lr, float b1, float b2, float eps) {
+  __shared__ int64_t s_off[kSweepMaxF];
+  for (int f = threadIdx.x; f < F; f += blockDim.x) s_off[f] = offsets[f];
+  __syncthreads();
+  const AdamCoef c = adam_coef(step, lr, b1, b2, eps);
+  const int32_t tag = (int32_t)(uint32_t)(*step + 1);
+  const long n = (long)W * cap;
+  for (long q = (long)blockIdx.x * blockDim.x + threadIdx.x; q < n; q += (long)gridDim.x * blockDim.x) {
+    const int w = (int)(q / cap);
+    const long i = q - (long)w * cap;
+    if (i >= list_count(counts, w, cap)) continue;
+    const int64_t row = ids[q];
+    if (row < 0 || row >= V) continue;
+    bool owner = true;
+    for (int w2 = 0; w2 < w && owner; ++w2) owner = find_row(ids + (long)w2 * cap, list_count(counts, w2, cap), row) < 0;
+    if (!owner) continue;
+    const int f = sweep_field(s_off, F, row);
+    const float l2x2 = (field_l2 && f >= 0) ? 2.f * field_l2[f] : 0.f;
+    for (int k0 = 0; k0 < K; k0 += kMergeChunk) {
+      float acc[kMergeChunk];
+      const float* src = values + q * K + k0;
+#pragma unroll
+      for (int e = 0; e < kMergeChunk; ++e) acc[e] = k0 + e < K ? src[e] : 0.f;
+      for (int w2 = w + 1; w2 < W; ++w2) {
+        const long at = find_row(ids + (long)w2 * cap, list_count(counts, w2, cap), row);
+        if (at < 0) continue;
+        const float* o = values + ((long)w2 * cap + at) * K + k0;
+#pragma unroll
+        for (int e = 0; e < kMergeChunk; ++e)
+          if (k0 + e < K) acc[e] += o[e];
+      }
+#pragma unroll
+      for (int e = 0; e < kMergeChunk; ++e) {
+        if (k0 + e < K) {
+          const int64_t x = row * K + k0 + e;
+          float p = table[x], mm = m[x], vv = v[x];
+          adam_elem(p, mm, vv, acc[e] + l2x2 * p, c);
+          table[x] = p;
+          m[x] = mm;
+          v[x] = vv;
+        }
+      }
+    }
+    if (stamp) stamp[row] = tag;
+  }
+}
+
 static int check_hyper(const char* who, float lr, float b1, float b2, float eps) {
   if (!(lr >= 0.f) || !(b1 >= 0.f && b1 < 1.f) || !(b2 >= 0.f && b2 < 1.f) || !(eps >= 0.f))
     return fail(FIL_ERR_ARG, "%s: hyper-parameters lr=%g beta_1=%g beta_2=%g epsilon=%g (lr, epsilon >= 0; betas in [0, 1))", who,
@@ -269,6 +440,77 @@ extern "C" int fil_embed_adam_sweep(float* table, float* m, float* v, const int3
   const dim3 grid((int)std::max<int64_t>(1, std::min<int64_t>((work + 255) / 256, 256 * 8)));
   hipLaunchKernelGGL(embed_adam_sweep_kernel, grid, dim3(256), 0, st, table, m, v, stamp, V, K, offsets, field_l2, frozen, F, step, lr,
                      beta_1, beta_2, epsilon, vec);
+  FIL_CHECK_LAUNCH();
+  return FIL_OK;
+}
+
+
+extern "C" size_t fil_embed_runs_compact_workspace_bytes(long R) {
+  if (R <= 0) return 0;
+  const long tiles = (R + kCompactTile - 1) / kCompactTile;
+  return align_up((size_t)tiles * sizeof(int64_t), 256) + align_up((size_t)R * sizeof(int32_t), 256);
+}
+
+extern "C" int fil_embed_runs_compact(const void* g, const int64_t* perm, const int64_t* sorted_ids, long R, int K, int g_dtype,
+                                      int64_t* ids_out, float* values_out, int64_t* count_out, long cap, void* workspace,
+                                      size_t workspace_bytes, void* stream) {
+  FIL_CHECK_ARG(R >= 0 && K >= 1 && cap >= 0);
+  if (g_dtype != FIL_F32 && g_dtype != FIL_BF16) return fail(FIL_ERR_ARG, "fil_embed_runs_compact: g_dtype %d (f32 or bf16)", g_dtype);
+  if (K > 256) return fail(FIL_ERR_UNSUPPORTED, "fil_embed_runs_compact: K=%d > 256", K);
+  if (cap < R) return fail(FIL_ERR_ARG, "fil_embed_runs_compact: cap %ld < R %ld (a list must hold every run of the record)", cap, R);
+  if (R > (long)INT32_MAX) return fail(FIL_ERR_UNSUPPORTED, "fil_embed_runs_compact: R=%ld > 2^31 - 1", R);
+  FIL_CHECK_ARG(ids_out && count_out);
+  if (workspace_bytes < fil_embed_runs_compact_workspace_bytes(R))
+    return fail(FIL_ERR_ARG, "fil_embed_runs_compact: workspace of %zu bytes < %zu (fil_embed_runs_compact_workspace_bytes)", workspace_bytes,
+                fil_embed_runs_compact_workspace_bytes(R));
+  hipStream_t st = (hipStream_t)stream;
+  if (R == 0) {         // an empty list: count 0, every slot padding (the write kernel with no tiles)
+    hipLaunchKernelGGL(runs_write_kernel, dim3(1), dim3(256), 0, st, sorted_ids, perm, 0L, (const int64_t*)nullptr, 0, cap, ids_out,
+                       count_out, (int32_t*)nullptr);
+    FIL_CHECK_LAUNCH();
+    return FIL_OK;
+  }
+  FIL_CHECK_ARG(g && perm && sorted_ids && values_out && workspace);
+  Carver cv(workspace);
+  const int tiles = (int)((R + kCompactTile - 1) / kCompactTile);
+  int64_t* tile_count = cv.take<int64_t>(tiles);
+  int32_t* slot = cv.take<int32_t>(R);
+  ProfScope ps("embed_runs_compact", st, (double)R * K * (g_dtype == FIL_F32 ? 4 : 2) + 20.0 * R + 4.0 * (double)R * K);
+  hipLaunchKernelGGL(runs_count_kernel, dim3(tiles), dim3(256), 0, st, sorted_ids, R, tile_count);
+  FIL_CHECK_LAUNCH();
+  hipLaunchKernelGGL(runs_write_kernel, dim3(tiles), dim3(256), 0, st, sorted_ids, perm, R, tile_count, tiles, cap, ids_out, count_out, slot);
+  FIL_CHECK_LAUNCH();
+  const int C = 64 / ((K + 3) / 4);
+  const dim3 grid((int)std::min<long>((R + 4 * C - 1) / (4 * C), 256 * 32));
+  if (g_dtype == FIL_F32)
+    hipLaunchKernelGGL(runs_compact_sums_kernel<float>, grid, dim3(256), 0, st, static_cast<const float*>(g), perm, sorted_ids, R, K, slot,
+                       cap, values_out);
+  else
+    hipLaunchKernelGGL(runs_compact_sums_kernel<__hip_bfloat16>, grid, dim3(256), 0, st, static_cast<const __hip_bfloat16*>(g), perm,
+                       sorted_ids, R, K, slot, cap, values_out);
+  FIL_CHECK_LAUNCH();
+  return FIL_OK;
+}
+
+extern "C" int fil_embed_adam_merged(const int64_t* ids, const float* values, const int64_t* counts, int W, long cap, int K,
+                                     const int64_t* offsets, const float* field_l2, int F, float* table, float* m, float* v, int32_t* stamp,
+                                     int64_t V, const int64_t* step, float lr, float beta_1, float beta_2, float epsilon, int mode,
+                                     void* stream) {
+  FIL_CHECK_ARG(W >= 1 && cap >= 0 && K >= 1 && F >= 1 && V >= 0);
+  if (mode != FIL_ADAM_KERAS && mode != FIL_ADAM_LAZY) return fail(FIL_ERR_ARG, "fil_embed_adam_merged: mode %d (FIL_ADAM_KERAS or FIL_ADAM_LAZY)", mode);
+  if (mode == FIL_ADAM_KERAS && stamp == nullptr)
+    return fail(FIL_ERR_ARG, "fil_embed_adam_merged: FIL_ADAM_KERAS needs the row stamps (fil_embed_adam_sweep skips the rows stamped here)");
+  if (K > 256) return fail(FIL_ERR_UNSUPPORTED, "fil_embed_adam_merged: K=%d > 256", K);
+  if (F > kSweepMaxF) return fail(FIL_ERR_UNSUPPORTED, "fil_embed_adam_merged: F=%d > %d fields", F, kSweepMaxF);
+  if (int rc = check_hyper("fil_embed_adam_merged", lr, beta_1, beta_2, epsilon)) return rc;
+  if (cap == 0 || V == 0) return FIL_OK;
+  FIL_CHECK_ARG(ids && values && counts && offsets && table && m && v && step);
+  hipStream_t st = (hipStream_t)stream;
+  const long n = (long)W * cap;
+  ProfScope ps("embed_adam_merged", st, 8.0 * n + 4.0 * (double)n * K + 24.0 * (double)cap * K);
+  const dim3 grid((int)std::max<long>(1, std::min<long>((n + 255) / 256, 256 * 8)));
+  hipLaunchKernelGGL(embed_adam_merged_kernel, grid, dim3(256), 0, st, ids, values, counts, W, cap, K, offsets, field_l2, F, table, m, v,
+                     mode == FIL_ADAM_KERAS ? stamp : nullptr, V, step, lr, beta_1, beta_2, epsilon);
   FIL_CHECK_LAUNCH();
   return FIL_OK;
 }

@@ -235,6 +235,18 @@ def exchange_sparse_rows(grad, touched_rows, group=None):
     return torch.unique(torch.cat([all_rows[r][:counts[r]] for r in range(world)]))
 
 
+def exchange_runs(ids, values, count, ids_all, values_all, counts_all, group=None):
+    """The data-parallel exchange of optim.Adam's runs tables (the compact counterpart of exchange_sparse_rows, which is unchanged):
+    every rank's compact list -- ids [cap] int64 (ascending, INT64_MAX padded), values [cap*K] fp32, count [1] int64, as
+    fil_embed_runs_compact writes them -- is all-gathered into ids_all [W*cap], values_all [W*cap*K], counts_all [W], rank after rank.
+    Fixed sizes (cap is agreed once), no host read, no allocation: fil_embed_adam_merged then applies the same gathered lists on every
+    replica (rows summed in rank order: bit-identical tables)."""
+    dist.all_gather_into_tensor(counts_all, count, group=group)
+    dist.all_gather_into_tensor(ids_all, ids, group=group)
+    dist.all_gather_into_tensor(values_all, values, group=group)
+    return ids_all, values_all, counts_all
+
+
 def add_table_l2_grad_(grad, table, ranges):
     """grad[lo:hi] += 2 * reg * table[lo:hi] for every (lo, hi, reg): the gradient of Keras' l2(reg) = reg * sum(w^2) on those rows
     (SparseEmbed.table_l2_ranges()).  Called by the data-parallel trainer AFTER exchange_sparse_rows, with the same table on

@@ -15,6 +15,13 @@ epsilon 1/sqrt(1 - beta_2) ~ 31.6 times larger -- of the order of an embedding r
   batch did not touch (Keras' dense Adam: their m and v decay and they move; l2(emb_reg) of table_l2_ranges() is added inside the
   update).  No [V,K] gradient is ever built.  lazy_tables=True is the LABELLED deviation from the reference (TF-Addons LazyAdam):
   only the touched rows change, no sweep.  A table in "dense" mode is an ordinary dense parameter here.
+* Data parallelism (process_group, or the default group once torch.distributed is initialised, with more than one rank; or
+  force_exchange=True at any world size): every runs table's record is compacted (fil_embed_runs_compact: distinct row ids + their
+  summed rows), the ranks all-gather the fixed-size lists (dp.exchange_runs) and every rank applies the same merged update
+  (fil_embed_adam_merged: the union's rows, summed in rank order, so the replicas stay bit-identical), then the sweep.  The list
+  capacity `cap` is agreed once per table on the first step (an all-reduce MAX of R, one host read); later steps neither synchronise
+  nor allocate, and a record with R > cap raises.  Without a group of > 1 ranks (and without force_exchange) step() takes the
+  one-GPU path above, unchanged.
 * The step counter t (Keras' `iterations`) is an int64 on the device, read by every launch and advanced by the last one: a step
   captured into a HIP graph (capture.capture_step) advances it on every replay.  Learning rate and betas are baked into a capture.
 
@@ -23,6 +30,7 @@ Only fp32 parameters on a GPU are supported: anything else raises (there is no C
 import ctypes
 
 import torch
+import torch.distributed as dist
 
 from . import _lib
 from ._lib import FIL_ADAM_KERAS, FIL_ADAM_LAZY, FilError, check, ptr, stream_ptr
@@ -38,10 +46,15 @@ assert ctypes.sizeof(_Desc) == 48
 
 
 class Adam(torch.optim.Optimizer):
-    def __init__(self, params, learning_rate=1e-3, beta_1=0.9, beta_2=0.999, epsilon=1e-7, lazy_tables=False):
+    def __init__(self, params, learning_rate=1e-3, beta_1=0.9, beta_2=0.999, epsilon=1e-7, lazy_tables=False, process_group=None,
+                 force_exchange=False):
         if not learning_rate >= 0.0 or not 0.0 <= beta_1 < 1.0 or not 0.0 <= beta_2 < 1.0 or not epsilon >= 0.0:
             raise ValueError("Adam: learning_rate=%r beta_1=%r beta_2=%r epsilon=%r (rate, epsilon >= 0; betas in [0, 1))"
                              % (learning_rate, beta_1, beta_2, epsilon))
+        if process_group is not None and not isinstance(process_group, dist.ProcessGroup):
+            raise TypeError("Adam: process_group must be a torch.distributed.ProcessGroup or None, not %r" % (process_group,))
+        if not isinstance(force_exchange, bool):
+            raise TypeError("Adam: force_exchange must be a bool, not %r" % (force_exchange,))
         super().__init__(params, dict(learning_rate=float(learning_rate), beta_1=float(beta_1), beta_2=float(beta_2),
                                       epsilon=float(epsilon)))
         self.lazy_tables = bool(lazy_tables)
@@ -52,6 +65,9 @@ class Adam(torch.optim.Optimizer):
         # pinned staging for descriptors built DURING a capture: a host allocation there would invalidate it, so it is reserved by
         # the first eager step; a captured copy reads its slice at every replay, so a slice is never handed out twice
         self._arena, self._arena_off = None, 0
+        self.process_group = process_group
+        self.force_exchange = force_exchange
+        self._xbuf = {}         # runs table -> buffers of the data-parallel exchange (cap fixed on the first step, reused after)
 
     # -- state ---------------------------------------------------------------------------------------------------
     def _counter(self, dev):
@@ -206,9 +222,93 @@ class Adam(torch.optim.Optimizer):
                 stamp = self._stamps[p] = torch.zeros(V, dtype=torch.int32, device=p.device)
         with torch.cuda.device(p.device):
             st = stream_ptr()
-            check(lib.fil_embed_adam_runs(ptr(pend["g"]), ptr(pend["perm"]), ptr(pend["sorted_ids"]), pend["R"], K, pend["g_dtype"],
-                                          pend["F"], ptr(pend["field_l2"]), ptr(p), ptr(m), ptr(v), ptr(stamp), ptr(t), lr, b1, b2, eps,
-                                          mode, st), "fil_embed_adam_runs")
+            world = self._exchange_world()
+            if world:
+                self._apply_runs_exchanged(lib, p, pend, m, v, t, stamp, mode, world, hyper, st)
+            else:
+                check(lib.fil_embed_adam_runs(ptr(pend["g"]), ptr(pend["perm"]), ptr(pend["sorted_ids"]), pend["R"], K, pend["g_dtype"],
+                                              pend["F"], ptr(pend["field_l2"]), ptr(p), ptr(m), ptr(v), ptr(stamp), ptr(t), lr, b1, b2,
+                                              eps, mode, st), "fil_embed_adam_runs")
             if mode == FIL_ADAM_KERAS:
                 check(lib.fil_embed_adam_sweep(ptr(p), ptr(m), ptr(v), ptr(stamp), V, K, ptr(pend["offsets"]), ptr(pend["field_l2"]),
                                                ptr(pend["frozen"]), pend["F"], ptr(t), lr, b1, b2, eps, st), "fil_embed_adam_sweep")
+
+    # -- data parallelism ------------------------------------------------------------------------------------------
+    def _exchange_world(self):
+        """The world size of the runs exchange, or 0 for the one-GPU path (no group of > 1 ranks and no force_exchange)."""
+        if dist.is_available() and dist.is_initialized():
+            world = dist.get_world_size(self.process_group)
+            if world > 1 or self.force_exchange:
+                return world
+            return 0
+        if self.process_group is not None:
+            raise FilError("optim.Adam: a process_group was given but torch.distributed is not initialised")
+        return 1 if self.force_exchange else 0
+
+    def _exchange_buffers(self, p, pend, world):
+        V, K = p.shape
+        R = int(pend["R"])
+        buf = self._xbuf.get(p)
+        if buf is None:
+            dev = p.device
+            if world > 1 or dist.is_initialized():      # one all-reduce MAX of R: every rank's lists get the same capacity
+                r = torch.tensor([R], dtype=torch.int64, device=dev)
+                dist.all_reduce(r, op=dist.ReduceOp.MAX, group=self.process_group)
+                cap = int(r.item())
+            else:
+                cap = R
+            cap = max(cap, 1)
+            lib = _lib.load()
+            ids = torch.empty(cap, dtype=torch.int64, device=dev)
+            values = torch.empty(cap * K, dtype=torch.float32, device=dev)
+            count = torch.zeros(1, dtype=torch.int64, device=dev)
+            ws = torch.empty(max(1, int(lib.fil_embed_runs_compact_workspace_bytes(cap))), dtype=torch.uint8, device=dev)
+            if world > 1 or dist.is_initialized():
+                gathered = (torch.empty(world * cap, dtype=torch.int64, device=dev),
+                            torch.empty(world * cap * K, dtype=torch.float32, device=dev),
+                            torch.empty(world, dtype=torch.int64, device=dev))
+            else:
+                gathered = (ids, values, count)        # no process group (force_exchange): the local list IS the gathered one
+            buf = self._xbuf[p] = dict(cap=cap, ids=ids, values=values, count=count, ws=ws, gathered=gathered)
+        if R > buf["cap"]:
+            raise FilError("optim.Adam: runs record of %d entries > the exchange capacity %d agreed on the first step (the first "
+                           "batch must be the largest)" % (R, buf["cap"]))
+        return buf
+
+    def _apply_runs_exchanged(self, lib, p, pend, m, v, t, stamp, mode, world, hyper, st):
+        from . import dp
+        lr, b1, b2, eps = hyper
+        V, K = p.shape
+        buf = self._exchange_buffers(p, pend, world)
+        cap = buf["cap"]
+        check(lib.fil_embed_runs_compact(ptr(pend["g"]), ptr(pend["perm"]), ptr(pend["sorted_ids"]), pend["R"], K, pend["g_dtype"],
+                                         ptr(buf["ids"]), ptr(buf["values"]), ptr(buf["count"]), cap, ptr(buf["ws"]), buf["ws"].numel(),
+                                         st), "fil_embed_runs_compact")
+        ids, values, counts = buf["gathered"]
+        if ids is not buf["ids"]:
+            dp.exchange_runs(buf["ids"], buf["values"], buf["count"], ids, values, counts, group=self.process_group)
+        check(lib.fil_embed_adam_merged(ptr(ids), ptr(values), ptr(counts), world, cap, K, ptr(pend["offsets"]), ptr(pend["field_l2"]),
+                                        pend["F"], ptr(p), ptr(m), ptr(v), ptr(stamp), V, ptr(t), lr, b1, b2, eps, mode, st),
+              "fil_embed_adam_merged")
+
+
+def runs_compact_workspace_bytes(R):
+    """Workspace bytes of runs_compact for a record of R entries."""
+    return int(_lib.load().fil_embed_runs_compact_workspace_bytes(int(R)))
+
+
+def runs_compact(rec, K, ids, values, count, cap, workspace):
+    """fil_embed_runs_compact on a runs record (the dict SparseEmbed(grad_mode="runs") leaves as table._fil_pending_runs, or any
+    dict with g, perm, sorted_ids, R, g_dtype): ids [cap] int64, values [cap*K] fp32, count [1] int64 are written on the device."""
+    check(_lib.load().fil_embed_runs_compact(ptr(rec["g"]), ptr(rec["perm"]), ptr(rec["sorted_ids"]), int(rec["R"]), int(K),
+                                             int(rec["g_dtype"]), ptr(ids), ptr(values), ptr(count), int(cap), ptr(workspace),
+                                             workspace.numel() * workspace.element_size(), stream_ptr()), "fil_embed_runs_compact")
+
+
+def adam_merged(ids, values, counts, W, cap, offsets, field_l2, table, m, v, stamp, step, lr=1e-3, beta_1=0.9, beta_2=0.999,
+                epsilon=1e-7, lazy=False):
+    """fil_embed_adam_merged on W gathered lists (ids [W*cap], values [W*cap*K], counts [W]); table / m / v [V, K] in place."""
+    V, K = table.shape
+    check(_lib.load().fil_embed_adam_merged(ptr(ids), ptr(values), ptr(counts), int(W), int(cap), K, ptr(offsets), ptr(field_l2),
+                                            offsets.numel(), ptr(table), ptr(m), ptr(v), ptr(stamp), V, ptr(step), lr, beta_1, beta_2,
+                                            epsilon, FIL_ADAM_LAZY if lazy else FIL_ADAM_KERAS, stream_ptr()), "fil_embed_adam_merged")
