@@ -66,6 +66,10 @@ def main():
                          "exchange (each rank's compacted gradient runs all-gathered, one merged update per replica, no [V,K] gradient, "
                          "no host sync after the first step); dense = the dense table gradients and dp.exchange_sparse_rows.  The default "
                          "stays dense: the runs exchange's all-gather at N > 1 ranks has not been timed on hardware yet (one GPU only)")
+    ap.add_argument("--sweep-period", type=int, default=None, metavar="N",
+                    help="with --optimizer keras: deferred Keras mode (optim.Adam(sweep_period=N)) -- the untouched table rows catch up "
+                         "on read and in one rolling slice of 1/N of the table per step instead of a whole-table sweep per step; the "
+                         "same bits as keras after a flush (state_dict).  8 is a good choice (DESIGN 6e); default: the per-step sweep")
     ap.add_argument("--no-graph", action="store_true",
                     help="run every step eagerly (default on one GPU: the whole step -- forward, backward, Adam -- is captured once "
                          "into a HIP graph and replayed; the C ABI neither allocates nor synchronises, so it is capture-safe)")
@@ -94,6 +98,10 @@ def main():
     ids_df, dense_df, labels = ids_df.iloc[lo:hi], dense_df.iloc[lo:hi], labels[lo:hi]
     single = args.model == "XDeepFM"
     keras = args.optimizer != "torch"
+    if args.sweep_period is not None and args.optimizer != "keras":
+        ap.error("--sweep-period needs --optimizer keras")
+    if args.sweep_period is not None and world > 1 and args.dp_tables != "runs":
+        ap.error("--sweep-period needs --dp-tables runs when data parallel (dense table gradients are not deferred)")
     fi = models.FeatureInput(sparseInfo=info, useLinear=args.model != "DCN" and args.model != "AutoInt", useAddLinear=single,
                              useFlattenLinear=True, tableGrad="runs" if keras and (world == 1 or args.dp_tables == "runs") else "dense")
     body = {"FM": models.FM, "DeepFM": models.DeepFM, "DCN": models.DCN, "AutoInt": models.AutoInt, "NFM": models.NFM,
@@ -110,7 +118,8 @@ def main():
     others = [p for n, p in model.named_parameters() if not n.endswith("embeddings")]
     use_graph = world == 1 and not args.no_graph
     if keras:       # Keras 'adam' (un_seq.py:61) with Keras' numerics; tables in "runs" mode get their l2 inside the update
-        opt = optim.Adam(model.parameters(), learning_rate=args.lr, epsilon=1e-7, lazy_tables=args.optimizer == "keras-lazy")
+        opt = optim.Adam(model.parameters(), learning_rate=args.lr, epsilon=1e-7, lazy_tables=args.optimizer == "keras-lazy",
+                         sweep_period=args.sweep_period)
     else:
         opt = torch.optim.Adam(model.parameters(), lr=args.lr, eps=1e-7, capturable=use_graph)      # Keras 'adam' (un_seq.py:61)
     pipe = data.data_pipeline(table, batch_size=args.batch, shuffle_buffer=2048, repeat=2, prefetch=2, seed=rank, device=device)

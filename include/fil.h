@@ -387,6 +387,43 @@ int fil_embed_runs_compact(const void* g, const int64_t* perm, const int64_t* so
 int fil_embed_adam_merged(const int64_t* ids, const float* values, const int64_t* counts, int W, long cap, int K, const int64_t* offsets,
                           const float* field_l2, int F, float* table, float* m, float* v, int32_t* stamp, int64_t V, const int64_t* step,
                           float lr, float beta_1, float beta_2, float epsilon, int mode, void* stream);
+/*   Deferred mode (optim.Adam(sweep_period=N)): instead of fil_embed_adam_sweep at every step, a table's untouched rows
+ *   catch up lazily, bit-identical to the per-step sweep (the update of an untouched row, g = 2 l2[f] p, depends on the row's own
+ *   p, m, v, its field's l2 and the step's coefficients only).  State per table, caller-owned:
+ *     stamp [V] int32   stamp[r] = s: row r is current through completed step s (low 32 bits); all = the step count to begin with.
+ *     ring  [D][4] fp32 (16-byte aligned; D = fil_embed_adam_ring_len(N), the power of two >= N + 1): entry t mod D = the
+ *                       coefficients of step t (1-based), or a "skip" entry for a step at which the table had no record (Keras mode
+ *                       leaves such a table alone).  Written by fil_embed_adam_roll of step t only.
+ *   Replayed steps take the sweep's field view (offsets / field_l2 / frozen: frozen fields never move).  No entry point allocates,
+ *   synchronises or sizes a launch by data: a deferred step captures like Keras mode.  1 <= N <= 1023; K <= 256; F <= 1024.
+ *   fil_embed_adam_catchup_runs: the forward's launch.  Every distinct row >= 0 (< V) of a sorted record (sorted_ids of
+ *     fil_embed_sort_fields, R entries) is brought current through the completed steps (*step) in place and stamped; the gather that
+ *     follows reads exactly the values the per-step sweep would have left.
+ *   fil_embed_adam_runs_deferred: fil_embed_adam_runs in FIL_ADAM_KERAS mode, each run's row first caught up through the completed
+ *     steps, then updated with step t = *step + 1 and stamped t.
+ *   fil_embed_adam_merged_deferred: fil_embed_adam_merged in FIL_ADAM_KERAS mode with the same catch-up before each row's update (a
+ *     row another rank touched may be stale on this replica: replicas differ in how stale their memory is, never in what they compute).
+ *   fil_embed_adam_roll: flags FIL_ADAM_ROLL_STEP writes step t's ring entry (FIL_ADAM_ROLL_SKIP: the skip entry) and brings slice
+ *     t mod N (rows [j ceil(V/N), (j + 1) ceil(V/N)) clipped to V) current through step t -- every row at least every N steps; called
+ *     once per step and table, after the runs update and before the counter advances.  FIL_ADAM_ROLL_FLUSH brings EVERY row current
+ *     through the completed steps and writes no entry (a checkpoint, a regulariser value).
+ */
+int fil_embed_adam_ring_len(int sweep_period);       /* D, or 0 when sweep_period is outside 1 ... 1023 */
+enum { FIL_ADAM_ROLL_STEP = 0, FIL_ADAM_ROLL_SKIP = 1, FIL_ADAM_ROLL_FLUSH = 2 };
+int fil_embed_adam_catchup_runs(const int64_t* sorted_ids, long R, int K, float* table, float* m, float* v, int32_t* stamp,
+                                const float* ring, int sweep_period, const int64_t* offsets, const float* field_l2,
+                                const unsigned char* frozen, int F, int64_t V, const int64_t* step, void* stream);
+int fil_embed_adam_runs_deferred(const void* g, const int64_t* perm, const int64_t* sorted_ids, long R, int K, int g_dtype, int F,
+                                 const int64_t* offsets, const float* field_l2, const unsigned char* frozen, float* table, float* m, float* v,
+                                 int32_t* stamp, const float* ring, int sweep_period, int64_t V, const int64_t* step, float lr, float beta_1,
+                                 float beta_2, float epsilon, void* stream);
+int fil_embed_adam_merged_deferred(const int64_t* ids, const float* values, const int64_t* counts, int W, long cap, int K,
+                                   const int64_t* offsets, const float* field_l2, const unsigned char* frozen, int F, float* table, float* m,
+                                   float* v, int32_t* stamp, const float* ring, int sweep_period, int64_t V, const int64_t* step, float lr,
+                                   float beta_1, float beta_2, float epsilon, void* stream);
+int fil_embed_adam_roll(float* table, float* m, float* v, int32_t* stamp, float* ring, int sweep_period, int64_t V, int K,
+                        const int64_t* offsets, const float* field_l2, const unsigned char* frozen, int F, const int64_t* step, float lr,
+                        float beta_1, float beta_2, float epsilon, int flags, void* stream);
 typedef struct {
   float* param;
   const float* grad;   /* NULL = zero gradient */

@@ -27,6 +27,7 @@ HEADER_PATH = os.path.join(_HERE, "..", "include", "fil.h")
 
 FIL_F32, FIL_BF16 = 0, 1
 FIL_ADAM_KERAS, FIL_ADAM_LAZY = 0, 1
+FIL_ADAM_ROLL_STEP, FIL_ADAM_ROLL_SKIP, FIL_ADAM_ROLL_FLUSH = 0, 1, 2
 
 _c = ctypes
 _P = _c.c_void_p
@@ -87,6 +88,13 @@ SIGNATURES = {
     "fil_embed_runs_compact_workspace_bytes": (_Z, [_c.c_long]),
     "fil_embed_runs_compact": (_I, [_P, _P, _P, _c.c_long, _I, _I, _P, _P, _P, _c.c_long, _P, _Z, _P]),
     "fil_embed_adam_merged": (_I, [_P, _P, _P, _I, _c.c_long, _I, _P, _P, _I, _P, _P, _P, _P, _c.c_int64, _P, _F, _F, _F, _F, _I, _P]),
+    "fil_embed_adam_ring_len": (_I, [_I]),
+    "fil_embed_adam_catchup_runs": (_I, [_P, _c.c_long, _I, _P, _P, _P, _P, _P, _I, _P, _P, _P, _I, _c.c_int64, _P, _P]),
+    "fil_embed_adam_runs_deferred": (_I, [_P, _P, _P, _c.c_long, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _I, _c.c_int64, _P, _F, _F,
+                                          _F, _F, _P]),
+    "fil_embed_adam_merged_deferred": (_I, [_P, _P, _P, _I, _c.c_long, _I, _P, _P, _P, _I, _P, _P, _P, _P, _P, _I, _c.c_int64, _P, _F,
+                                            _F, _F, _F, _P]),
+    "fil_embed_adam_roll": (_I, [_P, _P, _P, _P, _P, _I, _c.c_int64, _I, _P, _P, _P, _I, _P, _F, _F, _F, _F, _I, _P]),
 }
 
 

@@ -364,6 +364,409 @@ __global__ __launch_bounds__(256) void embed_adam_merged_kernel(const int64_t* _
   }
 }
 
+// ==== Deferred mode (optim.Adam(sweep_period=N)).  A row the batch did not touch takes g = 2 l2 p: an update that depends
+// on the row's own (p, m, v), its field's l2 and the step's coefficients only.  So the steps a row misses can be applied later, with
+// the same fp32 operations in the same order, and give the sweep's bits.  Persistent state per table:
+//   stamp [V] int32  stamp[r] = s: row r is current through completed step s (low 32 bits of the step count);
+//   ring  [D] AdamCoef (D a power of two >= N + 1): entry t mod D = adam_coef of step t (1-based), or the skip entry of a step at
+//         which the table had no record (Keras mode leaves such a table alone).  Written once, by fil_embed_adam_roll of step t.
+// fil_embed_adam_roll catches up slice (t mod N) of ceil(V/N) rows through step t at every step, so no row is ever more than N steps
+// behind: every replay reads at most the N newest entries, and D >= N + 1 keeps the entry being written out of their way.
+constexpr int kRingMax = 1024;                 // D <= 1024 (the roll keeps the ring in LDS): sweep_period <= 1023
+
+// The replay must give the bits that the Keras-mode kernels give, and those depend on how -ffp-contract fused adam_elem in each
+// context: in fil_embed_adam_sweep's 16-byte path m += (g - m)(1 - b1) became one fma, in its element path (and in the run and merged
+// updates) the SLP vectoriser paired the add with sqrt(v) + eps, so the product is rounded first.  The two helpers below spell out
+// those operations with contraction off and explicit fmas (checked against the gfx950 ISA of the Keras-mode kernels), so the
+// deferred kernels round exactly as they do whatever the compiler makes of their own context.
+//
+// the untouched-row update of the sweep (g = 2 l2[f] p); fused_m: its 16-byte path (K % 4 == 0, 16-byte aligned arrays)
+template <bool fused_m>
+__device__ __forceinline__ void adam_untouched(float& p, float& m, float& v, float l2x2, const AdamCoef& c) {
+#pragma clang fp contract(off)
+  const float g = l2x2 * p;
+  const float d = __builtin_fmaf(l2x2, p, -m);
+  const float gg = __builtin_fmaf(g, g, -v);
+  m = fused_m ? __builtin_fmaf(c.omb1, d, m) : m + c.omb1 * d;
+  v = __builtin_fmaf(c.omb2, gg, v);
+  p = p - (m * c.alpha) / (sqrtf(v) + c.eps);
+}
+
+// the touched-row update of fil_embed_adam_runs / fil_embed_adam_merged: g = (run sum) + 2 l2 p
+__device__ __forceinline__ void adam_touched(float& p, float& m, float& v, float acc, float l2x2, const AdamCoef& c) {
+#pragma clang fp contract(off)
+  const float g = __builtin_fmaf(l2x2, p, acc);
+  const float d = g - m;
+  const float gg = __builtin_fmaf(g, g, -v);
+  m = m + c.omb1 * d;
+  v = __builtin_fmaf(c.omb2, gg, v);
+  p = p - (m * c.alpha) / (sqrtf(v) + c.eps);
+}
+
+__device__ __forceinline__ bool coef_is_skip(const AdamCoef& c) { return c.omb1 != c.omb1; }   // (1 - beta_1 is never NaN)
+
+__device__ __forceinline__ AdamCoef coef_skip() {
+  const float nan = __builtin_nanf("");
+  return AdamCoef{nan, nan, nan, nan};
+}
+
+static int ring_len(int N) {
+  if (N < 1 || N >= kRingMax) return 0;
+  int D = 1;
+  while (D < N + 1) D <<= 1;
+  return D;
+}
+
+// the sweep's view of the fields, in LDS: a row's field is the last f with off[f] <= row; l2x2 = 2 l2[f], NaN for a frozen field
+struct FieldTab {
+  int64_t off[kSweepMaxF];
+  float l2x2[kSweepMaxF];
+};
+
+__device__ __forceinline__ void load_field_tab(FieldTab* s, const int64_t* __restrict__ offsets, const float* __restrict__ field_l2,
+                                               const unsigned char* __restrict__ frozen, int F) {
+  for (int f = threadIdx.x; f < F; f += blockDim.x) {
+    s->off[f] = offsets[f];
+    s->l2x2[f] = (frozen && frozen[f]) ? __builtin_nanf("") : (field_l2 ? 2.f * field_l2[f] : 0.f);
+  }
+}
+
+__device__ __forceinline__ float field_l2x2(const FieldTab* s, int F, int64_t row) {
+  const int f = sweep_field(s->off, F, row);
+  return f >= 0 ? s->l2x2[f] : 0.f;
+}
+
+// the last completed step a row stamped `st` must replay from to reach `to`: `to` itself when it is current.  Never more than N
+// steps back (a longer gap only comes from a broken protocol: the replay stays bounded, it does not hang)
+__device__ __forceinline__ int32_t replay_from(int32_t st, int32_t to, int N) {
+  if (st >= to) return to;
+  return st < to - N ? to - N : st;
+}
+
+// steps (from, to] of the ring (global memory) on NE elements in registers; vec: the sweep would take its 16-byte path on this table
+template <int NE>
+__device__ __forceinline__ void replay(float (&p)[NE], float (&m)[NE], float (&v)[NE], float l2x2, int32_t from, int32_t to,
+                                       const AdamCoef* __restrict__ ring, int D, int vec) {
+  for (int32_t u = from + 1; u <= to; ++u) {
+    const AdamCoef c = ring[u & (D - 1)];
+    if (coef_is_skip(c)) continue;
+    if (vec) {
+#pragma unroll
+      for (int i = 0; i < NE; ++i) adam_untouched<true>(p[i], m[i], v[i], l2x2, c);
+    } else {
+#pragma unroll
+      for (int i = 0; i < NE; ++i) adam_untouched<false>(p[i], m[i], v[i], l2x2, c);
+    }
+  }
+}
+
+// ---- fil_embed_adam_catchup_runs: the forward's launch.  G lanes (a power of two, so a row never straddles a wave) per sorted
+// position; the position that starts a run owns its row, brings it current through the completed steps and stamps it.
+__global__ __launch_bounds__(256) void embed_adam_catchup_kernel(const int64_t* __restrict__ sorted_ids, long R, int K, int lgG,
+                                                                 float* __restrict__ table, float* __restrict__ m, float* __restrict__ v,
+                                                                 int32_t* __restrict__ stamp, const AdamCoef* __restrict__ ring, int D,
+                                                                 int N, const int64_t* __restrict__ offsets,
+                                                                 const float* __restrict__ field_l2, const unsigned char* __restrict__ frozen,
+                                                                 int F, int64_t V, const int64_t* __restrict__ step, int vec) {
+  __shared__ FieldTab s;
+  load_field_tab(&s, offsets, field_l2, frozen, F);
+  __syncthreads();
+  const int32_t to = (int32_t)(uint32_t)(*step);
+  const long total = R << lgG;
+  const int kq = threadIdx.x & ((1 << lgG) - 1);
+  for (long q = (long)blockIdx.x * blockDim.x + threadIdx.x; q < total; q += (long)gridDim.x * blockDim.x) {
+    const long j = q >> lgG;
+    const int64_t row = sorted_ids[j];
+    if (row < 0 || row >= V || (j > 0 && sorted_ids[j - 1] == row)) continue;
+    const float l2x2 = field_l2x2(&s, F, row);
+    if (l2x2 != l2x2) continue;                   // frozen
+    const int32_t from = replay_from(stamp[row], to, N);
+    if (from == to) continue;
+    if (kq * 4 < K) {
+      float p[4], mm[4], vv[4];
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const int64_t e = row * K + kq * 4 + i;
+        const bool in = kq * 4 + i < K;
+        p[i] = in ? table[e] : 0.f;
+        mm[i] = in ? m[e] : 0.f;
+        vv[i] = in ? v[e] : 0.f;
+      }
+      replay<4>(p, mm, vv, l2x2, from, to, ring, D, vec);
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        if (kq * 4 + i < K) {
+          const int64_t e = row * K + kq * 4 + i;
+          table[e] = p[i];
+          m[e] = mm[i];
+          v[e] = vv[i];
+        }
+      }
+    }
+    if (kq == 0) stamp[row] = to;                 // (the row's other lanes read the stamp above: same wave, earlier instruction)
+  }
+}
+
+// ---- the deferred runs update: embed_adam_runs_kernel's epilogue behind a catch-up of the row through the completed steps; the row
+// is then stamped with step t.
+template <typename GT>
+__global__ __launch_bounds__(256) void embed_adam_runs_deferred_kernel(const GT* __restrict__ g, const int64_t* __restrict__ perm,
+                                                                       const int64_t* __restrict__ sorted_ids, long R, int K, int F,
+                                                                       const int64_t* __restrict__ offsets,
+                                                                       const float* __restrict__ field_l2,
+                                                                       const unsigned char* __restrict__ frozen, float* __restrict__ table,
+                                                                       float* __restrict__ m, float* __restrict__ v,
+                                                                       int32_t* __restrict__ stamp, const AdamCoef* __restrict__ ring,
+                                                                       int D, int N, int64_t V, const int64_t* __restrict__ step,
+                                                                       float lr, float b1, float b2, float eps, int vec) {
+  __shared__ FieldTab s;
+  load_field_tab(&s, offsets, field_l2, frozen, F);
+  __syncthreads();
+  const FieldTab* sp = &s;
+  const AdamCoef c = adam_coef(step, lr, b1, b2, eps);
+  const int32_t done = (int32_t)(uint32_t)(*step);
+  embed_run_sums(g, perm, sorted_ids, R, K, [=](int64_t row, int kq, const float (&acc)[4], int64_t first) {
+    if (row >= V) return;
+    const float l2x2 = field_l2 ? 2.f * field_l2[first % F] : 0.f;      // step t's term, as embed_adam_runs_kernel
+    const float r2 = field_l2x2(sp, F, row);                             // the replayed steps' term, as the sweep
+    const int32_t from = r2 == r2 ? replay_from(stamp[row], done, N) : done;
+    float p[4], mm[4], vv[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int64_t e = row * K + kq * 4 + i;
+      const bool in = kq * 4 + i < K;
+      p[i] = in ? table[e] : 0.f;
+      mm[i] = in ? m[e] : 0.f;
+      vv[i] = in ? v[e] : 0.f;
+    }
+    replay<4>(p, mm, vv, r2, from, done, ring, D, vec);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      if (kq * 4 + i < K) {
+        const int64_t e = row * K + kq * 4 + i;
+        adam_touched(p[i], mm[i], vv[i], acc[i], l2x2, c);
+        table[e] = p[i];
+        m[e] = mm[i];
+        v[e] = vv[i];
+      }
+    }
+    if (kq == 0) stamp[row] = done + 1;
+  });
+}
+
+// ---- the deferred merged update: embed_adam_merged_kernel with the owner catching its row up before the update
+__global__ __launch_bounds__(256) void embed_adam_merged_deferred_kernel(const int64_t* __restrict__ ids, const float* __restrict__ values,
+                                                                         const int64_t* __restrict__ counts, int W, long cap, int K,
+                                                                         const int64_t* __restrict__ offsets,
+                                                                         const float* __restrict__ field_l2,
+                                                                         const unsigned char* __restrict__ frozen, int F,
+                                                                         float* __restrict__ table, float* __restrict__ m,
+                                                                         float* __restrict__ v, int32_t* __restrict__ stamp,
+                                                                         const AdamCoef* __restrict__ ring, int D, int N, int64_t V,
+                                                                         const int64_t* __restrict__ step, float lr, float b1, float b2,
+                                                                         float eps, int vec) {
+  __shared__ FieldTab s;
+  load_field_tab(&s, offsets, field_l2, frozen, F);
+  __syncthreads();
+  const AdamCoef c = adam_coef(step, lr, b1, b2, eps);
+  const int32_t done = (int32_t)(uint32_t)(*step);
+  const long n = (long)W * cap;
+  for (long q = (long)blockIdx.x * blockDim.x + threadIdx.x; q < n; q += (long)gridDim.x * blockDim.x) {
+    const int w = (int)(q / cap);
+    const long i = q - (long)w * cap;
+    if (i >= list_count(counts, w, cap)) continue;
+    const int64_t row = ids[q];
+    if (row < 0 || row >= V) continue;
+    bool owner = true;
+    for (int w2 = 0; w2 < w && owner; ++w2) owner = find_row(ids + (long)w2 * cap, list_count(counts, w2, cap), row) < 0;
+    if (!owner) continue;
+    const int f = sweep_field(s.off, F, row);
+    const float l2x2 = (field_l2 && f >= 0) ? 2.f * field_l2[f] : 0.f;
+    const float r2 = f >= 0 ? s.l2x2[f] : 0.f;
+    const int32_t from = r2 == r2 ? replay_from(stamp[row], done, N) : done;
+    for (int k0 = 0; k0 < K; k0 += kMergeChunk) {
+      float acc[kMergeChunk];
+      const float* src = values + q * K + k0;
+#pragma unroll
+      for (int e = 0; e < kMergeChunk; ++e) acc[e] = k0 + e < K ? src[e] : 0.f;
+      for (int w2 = w + 1; w2 < W; ++w2) {
+        const long at = find_row(ids + (long)w2 * cap, list_count(counts, w2, cap), row);
+        if (at < 0) continue;
+        const float* o = values + ((long)w2 * cap + at) * K + k0;
+#pragma unroll
+        for (int e = 0; e < kMergeChunk; ++e)
+          if (k0 + e < K) acc[e] += o[e];
+      }
+#pragma unroll
+      for (int e = 0; e < kMergeChunk; ++e) {
+        if (k0 + e < K) {
+          const int64_t x = row * K + k0 + e;
+          float p[1] = {table[x]}, mm[1] = {m[x]}, vv[1] = {v[x]};
+          replay<1>(p, mm, vv, r2, from, done, ring, D, vec);
+          adam_touched(p[0], mm[0], vv[0], acc[e], l2x2, c);
+          table[x] = p[0];
+          m[x] = mm[0];
+          v[x] = vv[0];
+        }
+      }
+    }
+    stamp[row] = done + 1;
+  }
+}
+
+// ---- fil_embed_adam_roll: step t's ring entry (or the skip entry), then slice t mod N of ceil(V/N) rows brought current through
+// step t; FLUSH: every row through the completed steps, no entry.  VALU-bound by design: the ring sits in LDS and a wave replays
+// from its lowest stamp -- the rows of a slice almost all have the same gap N, so the loop is uniform and its second part runs
+// unmasked.  16-byte accesses where K % 4 == 0 and the arrays allow it, non-temporal stores, as the sweep.
+constexpr int kRollSkip = 1, kRollFlush = 2;
+
+__global__ __launch_bounds__(256) void embed_adam_roll_kernel(float* __restrict__ table, float* __restrict__ m, float* __restrict__ v,
+                                                              int32_t* __restrict__ stamp, AdamCoef* __restrict__ ring, int D, int N,
+                                                              int64_t V, int K, int lgG, int vec, const int64_t* __restrict__ offsets,
+                                                              const float* __restrict__ field_l2, const unsigned char* __restrict__ frozen,
+                                                              int F, const int64_t* __restrict__ step, float lr, float b1, float b2,
+                                                              float eps, int flags) {
+  __shared__ FieldTab s;
+  __shared__ AdamCoef s_ring[kRingMax];
+  const bool flush = (flags & kRollFlush) != 0;
+  const int64_t done = *step;
+  const int32_t to = (int32_t)(uint32_t)(flush ? done : done + 1);
+  load_field_tab(&s, offsets, field_l2, frozen, F);
+  for (int i = threadIdx.x; i < D; i += blockDim.x) s_ring[i] = ring[i];
+  __syncthreads();
+  int64_t lo = 0, hi = V;
+  if (!flush) {
+    // step t's entry: every workgroup holds its own copy (the global one is for later launches only)
+    const AdamCoef ct = (flags & kRollSkip) ? coef_skip() : adam_coef(step, lr, b1, b2, eps);
+    if (threadIdx.x == 0) {
+      s_ring[to & (D - 1)] = ct;
+      if (blockIdx.x == 0) ring[to & (D - 1)] = ct;
+    }
+    __syncthreads();
+    const int64_t S = (V + N - 1) / N;
+    lo = ((done + 1) % N) * S;
+    hi = lo + S < V ? lo + S : V;
+    if (lo > hi) lo = hi;
+  }
+  const int64_t total = (hi - lo) << lgG;
+  const int G = 1 << lgG;
+  const int kq = threadIdx.x & (G - 1);
+  // (a wave-uniform loop: every lane runs the same iterations, so the cross-lane minimum below sees all 64 lanes)
+  for (int64_t base = (int64_t)blockIdx.x * blockDim.x; base < total; base += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t q = base + threadIdx.x;
+    const int64_t row = lo + (q >> lgG);
+    int32_t from = to;
+    float l2x2 = 0.f;
+    if (q < total) {
+      l2x2 = field_l2x2(&s, F, row);
+      if (l2x2 == l2x2) from = replay_from(stamp[row], to, N);
+    }
+    const bool act = from != to;
+    int32_t wlo = from, whi = act ? from : INT32_MIN;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+      wlo = min(wlo, __shfl_xor(wlo, o, 64));
+      whi = max(whi, __shfl_xor(whi, o, 64));
+    }
+    wlo = __builtin_amdgcn_readfirstlane(wlo);
+    whi = __builtin_amdgcn_readfirstlane(whi);
+    if (wlo == to) continue;                      // the whole wave is current
+    const bool mine = act && kq * 4 < K;
+    const int64_t e0 = row * K + kq * 4;
+    float p[4] = {0.f, 0.f, 0.f, 0.f}, mm[4] = {0.f, 0.f, 0.f, 0.f}, vv[4] = {0.f, 0.f, 0.f, 0.f};
+    if (mine) {
+      if (vec) {
+        const f32x4 a = *reinterpret_cast<const f32x4*>(table + e0);
+        const f32x4 b = *reinterpret_cast<const f32x4*>(m + e0);
+        const f32x4 c = *reinterpret_cast<const f32x4*>(v + e0);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          p[i] = a[i];
+          mm[i] = b[i];
+          vv[i] = c[i];
+        }
+      } else {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          if (kq * 4 + i < K) {
+            p[i] = table[e0 + i];
+            mm[i] = m[e0 + i];
+            vv[i] = v[e0 + i];
+          }
+        }
+      }
+    }
+    // steps the wave's rows disagree on (masked per lane), then the ones every row takes (lanes with nothing to do compute on
+    // zeros they never store)
+    int32_t u = wlo + 1;
+    for (; u <= whi; ++u) {
+      const AdamCoef c = s_ring[u & (D - 1)];
+      if (coef_is_skip(c)) continue;
+      if (u > from) {
+        if (vec) {
+#pragma unroll
+          for (int i = 0; i < 4; ++i) adam_untouched<true>(p[i], mm[i], vv[i], l2x2, c);
+        } else {
+#pragma unroll
+          for (int i = 0; i < 4; ++i) adam_untouched<false>(p[i], mm[i], vv[i], l2x2, c);
+        }
+      }
+    }
+    if (vec) {
+      for (; u <= to; ++u) {
+        const AdamCoef c = s_ring[u & (D - 1)];
+        if (coef_is_skip(c)) continue;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) adam_untouched<true>(p[i], mm[i], vv[i], l2x2, c);
+      }
+    } else {
+      for (; u <= to; ++u) {
+        const AdamCoef c = s_ring[u & (D - 1)];
+        if (coef_is_skip(c)) continue;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) adam_untouched<false>(p[i], mm[i], vv[i], l2x2, c);
+      }
+    }
+    if (mine) {
+      if (vec) {
+        __builtin_nontemporal_store(f32x4{p[0], p[1], p[2], p[3]}, reinterpret_cast<f32x4*>(table + e0));
+        __builtin_nontemporal_store(f32x4{mm[0], mm[1], mm[2], mm[3]}, reinterpret_cast<f32x4*>(m + e0));
+        __builtin_nontemporal_store(f32x4{vv[0], vv[1], vv[2], vv[3]}, reinterpret_cast<f32x4*>(v + e0));
+      } else {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          if (kq * 4 + i < K) {
+            __builtin_nontemporal_store(p[i], table + e0 + i);
+            __builtin_nontemporal_store(mm[i], m + e0 + i);
+            __builtin_nontemporal_store(vv[i], v + e0 + i);
+          }
+        }
+      }
+    }
+    if (act && kq == 0) stamp[row] = to;
+  }
+}
+
+// lanes per row of the deferred kernels: the power of two >= ceil(K / 4)
+static int lanes_lg(int K) {
+  int lg = 0;
+  while ((1 << lg) < (K + 3) / 4) ++lg;
+  return lg;
+}
+
+// the path fil_embed_adam_sweep takes on these arrays (its 16-byte path rounds the m update differently: adam_untouched)
+static int sweep_vec(int K, const float* table, const float* m, const float* v) {
+  return (K % 4 == 0 && ((((uintptr_t)table | (uintptr_t)m | (uintptr_t)v) & 15) == 0)) ? 1 : 0;
+}
+
+static int check_deferred(const char* who, int K, int F, int N, const float* ring) {
+  if (K > 256) return fail(FIL_ERR_UNSUPPORTED, "%s: K=%d > 256", who, K);
+  if (F > kSweepMaxF) return fail(FIL_ERR_UNSUPPORTED, "%s: F=%d > %d fields", who, F, kSweepMaxF);
+  if (ring_len(N) == 0) return fail(FIL_ERR_ARG, "%s: sweep_period %d (1 ... %d)", who, N, kRingMax - 1);
+  if (((uintptr_t)ring & 15) != 0) return fail(FIL_ERR_ARG, "%s: the ring must be 16-byte aligned", who);
+  return FIL_OK;
+}
+
 static int check_hyper(const char* who, float lr, float b1, float b2, float eps) {
   if (!(lr >= 0.f) || !(b1 >= 0.f && b1 < 1.f) || !(b2 >= 0.f && b2 < 1.f) || !(eps >= 0.f))
     return fail(FIL_ERR_ARG, "%s: hyper-parameters lr=%g beta_1=%g beta_2=%g epsilon=%g (lr, epsilon >= 0; betas in [0, 1))", who,
@@ -511,6 +914,101 @@ extern "C" int fil_embed_adam_merged(const int64_t* ids, const float* values, co
   const dim3 grid((int)std::max<long>(1, std::min<long>((n + 255) / 256, 256 * 8)));
   hipLaunchKernelGGL(embed_adam_merged_kernel, grid, dim3(256), 0, st, ids, values, counts, W, cap, K, offsets, field_l2, F, table, m, v,
                      mode == FIL_ADAM_KERAS ? stamp : nullptr, V, step, lr, beta_1, beta_2, epsilon);
+  FIL_CHECK_LAUNCH();
+  return FIL_OK;
+}
+
+
+extern "C" int fil_embed_adam_ring_len(int sweep_period) { return ring_len(sweep_period); }
+
+extern "C" int fil_embed_adam_catchup_runs(const int64_t* sorted_ids, long R, int K, float* table, float* m, float* v, int32_t* stamp,
+                                           const float* ring, int sweep_period, const int64_t* offsets, const float* field_l2,
+                                           const unsigned char* frozen, int F, int64_t V, const int64_t* step, void* stream) {
+  FIL_CHECK_ARG(R >= 0 && K >= 1 && F >= 1 && V >= 0);
+  if (int rc = check_deferred("fil_embed_adam_catchup_runs", K, F, sweep_period, ring)) return rc;
+  if (R == 0 || V == 0) return FIL_OK;
+  FIL_CHECK_ARG(sorted_ids && table && m && v && stamp && ring && offsets && step);
+  hipStream_t st = (hipStream_t)stream;
+  const int lg = lanes_lg(K);
+  const long total = R << lg;
+  ProfScope ps("embed_adam_catchup", st, 8.0 * R);
+  const dim3 grid((int)std::max<long>(1, std::min<long>((total + 255) / 256, 256 * 8)));
+  hipLaunchKernelGGL(embed_adam_catchup_kernel, grid, dim3(256), 0, st, sorted_ids, R, K, lg, table, m, v, stamp,
+                     reinterpret_cast<const AdamCoef*>(ring), ring_len(sweep_period), sweep_period, offsets, field_l2, frozen, F, V, step,
+                     sweep_vec(K, table, m, v));
+  FIL_CHECK_LAUNCH();
+  return FIL_OK;
+}
+
+extern "C" int fil_embed_adam_runs_deferred(const void* g, const int64_t* perm, const int64_t* sorted_ids, long R, int K, int g_dtype,
+                                            int F, const int64_t* offsets, const float* field_l2, const unsigned char* frozen, float* table,
+                                            float* m, float* v, int32_t* stamp, const float* ring, int sweep_period, int64_t V,
+                                            const int64_t* step, float lr, float beta_1, float beta_2, float epsilon, void* stream) {
+  FIL_CHECK_ARG(R >= 0 && K >= 1 && F >= 1 && V >= 0);
+  if (g_dtype != FIL_F32 && g_dtype != FIL_BF16) return fail(FIL_ERR_ARG, "fil_embed_adam_runs_deferred: g_dtype %d (f32 or bf16)", g_dtype);
+  if (int rc = check_deferred("fil_embed_adam_runs_deferred", K, F, sweep_period, ring)) return rc;
+  if (int rc = check_hyper("fil_embed_adam_runs_deferred", lr, beta_1, beta_2, epsilon)) return rc;
+  if (R == 0 || V == 0) return FIL_OK;
+  FIL_CHECK_ARG(g && perm && sorted_ids && offsets && table && m && v && stamp && ring && step);
+  hipStream_t st = (hipStream_t)stream;
+  ProfScope ps("embed_adam_runs_deferred", st, (double)R * K * (g_dtype == FIL_F32 ? 4 : 2) + 24.0 * R * K);
+  const int C = 64 / ((K + 3) / 4);
+  const dim3 grid((int)std::min<long>((R + 4 * C - 1) / (4 * C), 256 * 32));
+  const AdamCoef* rg = reinterpret_cast<const AdamCoef*>(ring);
+  const int D = ring_len(sweep_period);
+  if (g_dtype == FIL_F32)
+    hipLaunchKernelGGL(embed_adam_runs_deferred_kernel<float>, grid, dim3(256), 0, st, static_cast<const float*>(g), perm, sorted_ids, R,
+                       K, F, offsets, field_l2, frozen, table, m, v, stamp, rg, D, sweep_period, V, step, lr, beta_1, beta_2, epsilon,
+                       sweep_vec(K, table, m, v));
+  else
+    hipLaunchKernelGGL(embed_adam_runs_deferred_kernel<__hip_bfloat16>, grid, dim3(256), 0, st, static_cast<const __hip_bfloat16*>(g),
+                       perm, sorted_ids, R, K, F, offsets, field_l2, frozen, table, m, v, stamp, rg, D, sweep_period, V, step, lr, beta_1,
+                       beta_2, epsilon, sweep_vec(K, table, m, v));
+  FIL_CHECK_LAUNCH();
+  return FIL_OK;
+}
+
+extern "C" int fil_embed_adam_merged_deferred(const int64_t* ids, const float* values, const int64_t* counts, int W, long cap, int K,
+                                              const int64_t* offsets, const float* field_l2, const unsigned char* frozen, int F,
+                                              float* table, float* m, float* v, int32_t* stamp, const float* ring, int sweep_period,
+                                              int64_t V, const int64_t* step, float lr, float beta_1, float beta_2, float epsilon,
+                                              void* stream) {
+  FIL_CHECK_ARG(W >= 1 && cap >= 0 && K >= 1 && F >= 1 && V >= 0);
+  if (int rc = check_deferred("fil_embed_adam_merged_deferred", K, F, sweep_period, ring)) return rc;
+  if (int rc = check_hyper("fil_embed_adam_merged_deferred", lr, beta_1, beta_2, epsilon)) return rc;
+  if (cap == 0 || V == 0) return FIL_OK;
+  FIL_CHECK_ARG(ids && values && counts && offsets && table && m && v && stamp && ring && step);
+  hipStream_t st = (hipStream_t)stream;
+  const long n = (long)W * cap;
+  ProfScope ps("embed_adam_merged_deferred", st, 8.0 * n + 4.0 * (double)n * K + 24.0 * (double)cap * K);
+  const dim3 grid((int)std::max<long>(1, std::min<long>((n + 255) / 256, 256 * 8)));
+  hipLaunchKernelGGL(embed_adam_merged_deferred_kernel, grid, dim3(256), 0, st, ids, values, counts, W, cap, K, offsets, field_l2, frozen,
+                     F, table, m, v, stamp, reinterpret_cast<const AdamCoef*>(ring), ring_len(sweep_period), sweep_period, V, step, lr,
+                     beta_1, beta_2, epsilon, sweep_vec(K, table, m, v));
+  FIL_CHECK_LAUNCH();
+  return FIL_OK;
+}
+
+extern "C" int fil_embed_adam_roll(float* table, float* m, float* v, int32_t* stamp, float* ring, int sweep_period, int64_t V, int K,
+                                   const int64_t* offsets, const float* field_l2, const unsigned char* frozen, int F, const int64_t* step,
+                                   float lr, float beta_1, float beta_2, float epsilon, int flags, void* stream) {
+  FIL_CHECK_ARG(V >= 0 && K >= 1 && F >= 1);
+  if (flags != FIL_ADAM_ROLL_STEP && flags != FIL_ADAM_ROLL_SKIP && flags != FIL_ADAM_ROLL_FLUSH)
+    return fail(FIL_ERR_ARG, "fil_embed_adam_roll: flags %d (FIL_ADAM_ROLL_STEP, _SKIP or _FLUSH)", flags);
+  if (int rc = check_deferred("fil_embed_adam_roll", K, F, sweep_period, ring)) return rc;
+  if (int rc = check_hyper("fil_embed_adam_roll", lr, beta_1, beta_2, epsilon)) return rc;
+  if (V == 0) return FIL_OK;
+  FIL_CHECK_ARG(table && m && v && stamp && ring && offsets && step);
+  hipStream_t st = (hipStream_t)stream;
+  const int lg = lanes_lg(K);
+  const int64_t rows = flags == FIL_ADAM_ROLL_FLUSH ? V : (V + sweep_period - 1) / sweep_period;
+  const int vec = sweep_vec(K, table, m, v);
+  ProfScope ps(flags == FIL_ADAM_ROLL_FLUSH ? "embed_adam_flush" : "embed_adam_roll", st, 24.0 * (double)rows * K + 4.0 * (double)rows);
+  const int64_t total = rows << lg;
+  const dim3 grid((int)std::max<int64_t>(1, std::min<int64_t>((total + 255) / 256, 256 * 8)));
+  hipLaunchKernelGGL(embed_adam_roll_kernel, grid, dim3(256), 0, st, table, m, v, stamp, reinterpret_cast<AdamCoef*>(ring),
+                     ring_len(sweep_period), sweep_period, V, K, lg, vec, offsets, field_l2, frozen, F, step, lr, beta_1, beta_2, epsilon,
+                     flags == FIL_ADAM_ROLL_STEP ? 0 : (flags == FIL_ADAM_ROLL_SKIP ? kRollSkip : kRollFlush));
   FIL_CHECK_LAUNCH();
   return FIL_OK;
 }

@@ -8,11 +8,13 @@ import ctypes
 import os
 
 import time
+import weakref
 
 import torch
 
 from . import _lib
 from ._lib import FIL_BF16, FIL_F32, FilError, check, int_array, ptr, ptr_array, stream_ptr
+from .optim import deferred_state
 
 
 def _require_cuda(*tensors):
@@ -522,8 +524,14 @@ def product_attention(q, k, v, use_scale=False, mask=None, mask_mod=1):
 # embeddings and the linear weights): their gradients need the same sort.  An entry keeps its idx tensor alive, so an equal
 # (data_ptr, _version) really is the same contents; in-place updates bump the version and miss -- and every gather (forward)
 # empties the cache, so that an entry only ever serves the backward passes that follow the forwards which saw these ids
-# (an update of idx that bypasses the version counter, e.g. through `.data`, cannot meet a stale entry).
+# (an update of idx that bypasses the version counter, e.g. through `.data`, cannot meet a stale entry).  The one exception is a
+# gather from a table in deferred Keras mode, which sorts in the forward: it keeps only the entry that the gather immediately
+# before it, from another table, made for the SAME idx tensor object (the other table of its layout, same forward), so no sort
+# outlives its forward pair either.  An entry records the number of the gather it was made under (_SORT_GEN);
+# _SORT_PREV_TABLE is (a weak reference to) the runs table of the latest gather.
 _SORT_CACHE = []
+_SORT_GEN = [0]
+_SORT_PREV_TABLE = [None]
 
 
 class _ScoreAddSigmoidFn(torch.autograd.Function):
@@ -798,7 +806,7 @@ def _sorted_row_ids(offsets, sizes, frozen, idx, layout_key=None, n_rows=None, p
         check(lib.fil_embed_sort_fields(ptr(offsets), ptr(sizes), ptr(frozen), ptr(idx), ptr(sorted_ids), ptr(perm), B, F,
                                         int(n_rows) if n_rows is not None else 0, stream_ptr()), "fil_embed_sort_fields")
         out = (sorted_ids, perm)
-        _SORT_CACHE.insert(0, (key, (idx, offsets, sizes, frozen), out))
+        _SORT_CACHE.insert(0, (key, (idx, offsets, sizes, frozen, _SORT_GEN[0]), out))
         del _SORT_CACHE[2:]
         return out
     row_ids = torch.empty(B * F, dtype=torch.int64, device=idx.device)
@@ -811,7 +819,7 @@ def _sorted_row_ids(offsets, sizes, frozen, idx, layout_key=None, n_rows=None, p
         out = (s32.to(torch.int64), perm)
     else:
         out = torch.sort(row_ids, stable=True)
-    _SORT_CACHE.insert(0, (key, (idx, offsets, sizes, frozen), out))
+    _SORT_CACHE.insert(0, (key, (idx, offsets, sizes, frozen, _SORT_GEN[0]), out))
     del _SORT_CACHE[2:]
     return out
 
@@ -846,16 +854,32 @@ class _EmbedFn(torch.autograd.Function):
                 runs_grad=None):
         _require_cuda(table, offsets, idx)
         ctx.runs_grad = runs_grad
+        ctx.sorted = None
+        deferred = None
         if runs_grad is not None:
             if sparse_grad or atomic:
                 raise FilError("embed_gather: grad_mode='runs' excludes sparse_grad / atomic")
             ctx.table_param = table
+            deferred = deferred_state(table)
         table = _f32c(table)
         idx = idx.to(torch.int64).contiguous()
         offsets = offsets.to(torch.int64).contiguous()
         B, F = idx.shape
         K = table.shape[1]
-        del _SORT_CACHE[:]
+        _SORT_GEN[0] += 1
+        prev = _SORT_PREV_TABLE[0]() if _SORT_PREV_TABLE[0] is not None else None
+        _SORT_PREV_TABLE[0] = weakref.ref(ctx.table_param) if runs_grad is not None else None
+        if deferred is not None:
+            # deferred Keras mode (optim.Adam(sweep_period=N)): the batch's rows may lag the completed steps in memory -- sort the
+            # batch here and bring its rows current in place before the unchanged gather reads them; the backward reuses the sort.
+            # The cache keeps only what the gather just before this one, from ANOTHER table, sorted for this very idx tensor: the
+            # other table of the same layout in the same forward shares it, and nothing older is ever reused
+            shared = prev is not None and prev is not ctx.table_param
+            _SORT_CACHE[:] = [e for e in _SORT_CACHE if shared and e[1][0] is idx and e[1][4] == _SORT_GEN[0] - 1]
+            ctx.sorted = _sorted_row_ids(offsets, sizes, frozen, idx, layout_key, table.shape[0], per_field=True)
+            deferred.catch_up(ctx.table_param, ctx.sorted[0], runs_grad)
+        else:
+            del _SORT_CACHE[:]
         out_dtype = out_dtype or torch.float32
         if out_dtype not in (torch.float32, torch.bfloat16) or (xt_out is not None and out_dtype != torch.float32):
             raise FilError("embed_gather: out_dtype %s (float32, or bfloat16 without emit_xt)" % out_dtype)
@@ -888,7 +912,8 @@ class _EmbedFn(torch.autograd.Function):
             if getattr(table, "_fil_pending_runs", None) is not None:
                 raise FilError("embed_gather(grad_mode='runs'): the table already holds a pending gradient record -- one backward per "
                                "table per optimizer step (call optimizer.step() or zero_grad() in between)")
-            sorted_ids, perm = _sorted_row_ids(offsets, sizes, frozen, idx, layout_key, table_shape[0], per_field=True)
+            sorted_ids, perm = ctx.sorted if ctx.sorted is not None else _sorted_row_ids(offsets, sizes, frozen, idx, layout_key,
+                                                                                         table_shape[0], per_field=True)
             table._fil_pending_runs = dict(g=g, perm=perm, sorted_ids=sorted_ids, R=B * F, K=K, F=F, g_dtype=FIL_BF16 if g_bf16 else FIL_F32,
                                            **ctx.runs_grad)
             dtable = None

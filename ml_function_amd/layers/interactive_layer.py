@@ -11,6 +11,7 @@ import warnings
 import torch
 
 from .. import functional as Fn
+from ..optim import deferred_state
 from .base import Layer, glorot_uniform_, merge_packed_views
 
 
@@ -350,6 +351,13 @@ class CIN(Layer):
         return pooled
 
 
+def _flush_deferred_table(module, prefix, keep_vars):
+    """SparseEmbed's state-dict pre-hook: a table in deferred Keras mode is flushed first; nothing otherwise."""
+    deferred = module._deferred()
+    if deferred is not None:
+        deferred.flush()
+
+
 class SparseEmbed(Layer):
     """SparseEmbed (interactive_layer.py:189-247): one embedding table per sparse field.
 
@@ -394,6 +402,20 @@ class SparseEmbed(Layer):
         if grad_mode == "runs" and sparse_grad:
             raise ValueError("SparseEmbed: grad_mode='runs' and sparse_grad=True exclude each other")
         self.grad_mode = grad_mode
+        # deferred Keras mode (optim.Adam(sweep_period=N)): rows lag in memory until read -- a state dict is taken flushed
+        self.register_state_dict_pre_hook(_flush_deferred_table)
+
+    def _deferred(self):
+        if not self.built or self.grad_mode != "runs":
+            return None
+        return deferred_state(self.embeddings)
+
+    def __getstate__(self):
+        # pickling the module (torch.save(model)) takes the table's storage as it is: in deferred Keras mode bring it current first
+        deferred = self._deferred()
+        if deferred is not None:
+            deferred.flush()
+        return super().__getstate__()
 
     def build(self, input_shape):
         dims = {int(i.linear_unit if self.is_linear else i.cross_unit) for i in self.sparse_info}
@@ -447,6 +469,9 @@ class SparseEmbed(Layer):
         if not self.built:
             return []
         if self.grad_mode == "runs":     # the optimizer adds their gradient (table_l2_ranges): the value only
+            deferred = self._deferred()
+            if deferred is not None and self._reg:  # deferred Keras mode: the value of the current table
+                deferred.flush()
             return [reg * self.embeddings.detach()[lo:hi].square().sum() for lo, hi, reg in self._reg]
         return [reg * self.embeddings[lo:hi].square().sum() for lo, hi, reg in self._reg]
 

@@ -22,18 +22,32 @@ epsilon 1/sqrt(1 - beta_2) ~ 31.6 times larger -- of the order of an embedding r
   capacity `cap` is agreed once per table on the first step (an all-reduce MAX of R, one host read); later steps neither synchronise
   nor allocate, and a record with R > cap raises.  Without a group of > 1 ranks (and without force_exchange) step() takes the
   one-GPU path above, unchanged.
+* Deferred mode (sweep_period=N, opt-in): the untouched rows are not swept at every step.  Their update (g = 2 l2 p)
+  depends only on the row's own p, m, v, its field's l2 and the step's coefficients, so the steps a row misses are replayed later
+  with the same fp32 operations in the same order -- the same bits.  Per deferred table: int32 [V] row stamps (row r is current
+  through completed step stamp[r]) and a device ring of D >= N + 1 per-step coefficients.  A forward that gathers from the table first
+  catches up the batch's rows (fil_embed_adam_catchup_runs); step() catches up and updates the batch's rows
+  (fil_embed_adam_runs_deferred / fil_embed_adam_merged_deferred), writes the step's ring entry and catches up one slice of ceil(V/N)
+  rows (fil_embed_adam_roll), so no row is ever more than N steps behind.  Everything that leaves the library is bit-identical to
+  Keras mode: gathered rows, losses, and the table, m and v after flush() -- which state_dict(), SparseEmbed's state-dict hook and
+  SparseEmbed.regularization_losses() call, and the optimizer's finaliser (a table never outlives its optimizer lagging).  Only
+  the table in memory between steps lags, for rows nobody has read.  Runs tables attach at construction, through
+  add_param_group, or at their first record.
 * The step counter t (Keras' `iterations`) is an int64 on the device, read by every launch and advanced by the last one: a step
   captured into a HIP graph (capture.capture_step) advances it on every replay.  Learning rate and betas are baked into a capture.
 
 Only fp32 parameters on a GPU are supported: anything else raises (there is no CPU / eager fallback).
 """
 import ctypes
+import weakref
 
 import torch
 import torch.distributed as dist
+from torch.utils.weak import WeakIdKeyDictionary
 
 from . import _lib
-from ._lib import FIL_ADAM_KERAS, FIL_ADAM_LAZY, FilError, check, ptr, stream_ptr
+from ._lib import (FIL_ADAM_KERAS, FIL_ADAM_LAZY, FIL_ADAM_ROLL_FLUSH, FIL_ADAM_ROLL_SKIP, FIL_ADAM_ROLL_STEP, FilError, check, ptr,
+                   stream_ptr)
 
 
 class _Desc(ctypes.Structure):
@@ -45,9 +59,91 @@ class _Desc(ctypes.Structure):
 assert ctypes.sizeof(_Desc) == 48
 
 
+MAX_SWEEP_PERIOD = 1023     # the ring (D >= N + 1 entries, a power of two) sits in LDS in fil_embed_adam_roll: D <= 1024
+
+
+# runs table -> its _Deferred state.  Keyed by identity and weakly: nothing is stored on the Parameter (a pickled module stays
+# picklable) and the registry keeps no table alive.  The state outlives its optimizer until that optimizer is finalised, which
+# flushes the table and removes the entry: a table is never left lagging with nobody to bring it current.
+_DEFERRED = WeakIdKeyDictionary()
+
+
+class _Deferred:
+    """One table's deferred state, shared by its optimizer and the table's readers (the forward's catch-up, SparseEmbed's
+    state-dict hook and regulariser).  Holds the table and the optimizer weakly and everything a catch-up or a flush needs
+    strongly: moments, step counter, stamps, ring, the fields of the last record."""
+
+    def __init__(self, opt, p, m, v, t, N):
+        self.opt = weakref.ref(opt)
+        self.table = weakref.ref(p)
+        self.m, self.v, self.t, self.N = m, v, t, N
+        D = int(_lib.load().fil_embed_adam_ring_len(N))
+        self.stamp = torch.empty(p.shape[0], dtype=torch.int32, device=p.device)
+        self.stamp.copy_(t.expand(p.shape[0]))             # current through the completed steps
+        self.ring = torch.zeros((D, 4), dtype=torch.float32, device=p.device)
+        self.fields = None
+        self.hyper = (opt.defaults["learning_rate"], opt.defaults["beta_1"], opt.defaults["beta_2"], opt.defaults["epsilon"])
+
+    def field_args(self, p, rec=None):
+        """(offsets, field_l2, frozen, F) for the replays: the record's, else the last one seen.  Before any record or forward every
+        step of this table was a skip step, and a replay of those changes nothing: one field without l2 is then exact."""
+        if rec is not None:
+            self.fields = (rec["offsets"], rec.get("field_l2"), rec.get("frozen"))
+        if self.fields is None:
+            self.fields = (torch.zeros(1, dtype=torch.int64, device=p.device), None, None)
+        offsets, field_l2, frozen = self.fields
+        return offsets, field_l2, frozen, int(offsets.numel())
+
+    def catch_up(self, p, sorted_ids, rec):
+        """The forward's launch: the record's rows current through the completed steps, in place (fil_embed_adam_catchup_runs)."""
+        V, K = p.shape
+        offsets, field_l2, frozen, F = self.field_args(p, rec)
+        with torch.cuda.device(p.device):
+            check(_lib.load().fil_embed_adam_catchup_runs(ptr(sorted_ids), sorted_ids.numel(), K, ptr(p), ptr(self.m), ptr(self.v),
+                                                          ptr(self.stamp), ptr(self.ring), self.N, ptr(offsets), ptr(field_l2),
+                                                          ptr(frozen), F, V, ptr(self.t), stream_ptr()), "fil_embed_adam_catchup_runs")
+
+    def roll(self, p, hyper, flags, rec=None):
+        V, K = p.shape
+        offsets, field_l2, frozen, F = self.field_args(p, rec)
+        with torch.cuda.device(p.device):
+            check(_lib.load().fil_embed_adam_roll(ptr(p), ptr(self.m), ptr(self.v), ptr(self.stamp), ptr(self.ring), self.N, V, K,
+                                                  ptr(offsets), ptr(field_l2), ptr(frozen), F, ptr(self.t), *hyper, flags, stream_ptr()),
+                  "fil_embed_adam_roll")
+
+    @torch.no_grad()
+    def flush(self):
+        p = self.table()
+        if p is not None:
+            self.roll(p, self.hyper, FIL_ADAM_ROLL_FLUSH)
+
+
+def _release(states):
+    """An optimizer with deferred tables is finalised: flush every table it still owns and detach it (the table is then current and
+    an ordinary runs table again)."""
+    if torch.cuda.is_available() and torch.cuda.is_current_stream_capturing():
+        return      # (never launch into someone's capture: the states stay registered, and the readers still catch up through them)
+    for st in states:
+        p = st.table()
+        if p is not None and _DEFERRED.get(p) is st:
+            st.flush()
+            del _DEFERRED[p]
+
+
+def deferred_state(table):
+    """The _Deferred state of a table in deferred Keras mode (optim.Adam(sweep_period)), or None."""
+    return _DEFERRED.get(table)
+
+
+def deferred_optimizer(table):
+    """The live deferred optim.Adam a table is attached to (sweep_period), or None."""
+    st = _DEFERRED.get(table)
+    return st.opt() if st is not None else None
+
+
 class Adam(torch.optim.Optimizer):
     def __init__(self, params, learning_rate=1e-3, beta_1=0.9, beta_2=0.999, epsilon=1e-7, lazy_tables=False, process_group=None,
-                 force_exchange=False):
+                 force_exchange=False, sweep_period=None):
         if not learning_rate >= 0.0 or not 0.0 <= beta_1 < 1.0 or not 0.0 <= beta_2 < 1.0 or not epsilon >= 0.0:
             raise ValueError("Adam: learning_rate=%r beta_1=%r beta_2=%r epsilon=%r (rate, epsilon >= 0; betas in [0, 1))"
                              % (learning_rate, beta_1, beta_2, epsilon))
@@ -55,10 +151,24 @@ class Adam(torch.optim.Optimizer):
             raise TypeError("Adam: process_group must be a torch.distributed.ProcessGroup or None, not %r" % (process_group,))
         if not isinstance(force_exchange, bool):
             raise TypeError("Adam: force_exchange must be a bool, not %r" % (force_exchange,))
+        if sweep_period is not None:
+            if isinstance(sweep_period, bool) or not isinstance(sweep_period, int):
+                raise TypeError("Adam: sweep_period must be an int or None, not %r" % (sweep_period,))
+            if not 1 <= sweep_period <= MAX_SWEEP_PERIOD:
+                raise ValueError("Adam: sweep_period %d (1 ... %d)" % (sweep_period, MAX_SWEEP_PERIOD))
+            if lazy_tables:
+                raise ValueError("Adam: sweep_period (deferred Keras mode) and lazy_tables exclude each other")
+        # (set before the base class adds the parameter groups: add_param_group attaches their runs tables)
+        self.sweep_period = sweep_period
+        self._t = {}            # device -> int64 [1] step counter (Keras' iterations)
+        self._defer = {}        # deferred runs table -> its _Deferred state (also in _DEFERRED, for the table's readers)
+        self._released = []     # the same states, for the finaliser (which must not hold the optimizer)
+        if sweep_period is not None:
+            fin = weakref.finalize(self, _release, self._released)
+            fin.atexit = False
         super().__init__(params, dict(learning_rate=float(learning_rate), beta_1=float(beta_1), beta_2=float(beta_2),
                                       epsilon=float(epsilon)))
         self.lazy_tables = bool(lazy_tables)
-        self._t = {}            # device -> int64 [1] step counter (Keras' iterations)
         self._stamps = {}       # runs table -> int32 [V] row stamps of FIL_ADAM_KERAS (valid within one step only: not state)
         self._descs = {}        # descriptor key -> (device descriptors, pinned host copy)
         self._pinned = []       # descriptor arrays built during a stream capture: a graph replays them, they are never dropped
@@ -68,6 +178,13 @@ class Adam(torch.optim.Optimizer):
         self.process_group = process_group
         self.force_exchange = force_exchange
         self._xbuf = {}         # runs table -> buffers of the data-parallel exchange (cap fixed on the first step, reused after)
+
+    def add_param_group(self, param_group):
+        super().add_param_group(param_group)
+        if self.sweep_period is not None:           # deferred mode: the group's runs tables join it now
+            for p in self.param_groups[-1]["params"]:
+                if getattr(p, "_fil_runs_table", False):
+                    self._attach(p)
 
     # -- state ---------------------------------------------------------------------------------------------------
     def _counter(self, dev):
@@ -89,6 +206,7 @@ class Adam(torch.optim.Optimizer):
         return st["m"], st["v"]
 
     def state_dict(self):
+        self.flush()
         sd = super().state_dict()
         sd["iterations"] = self.iterations
         return sd
@@ -108,6 +226,9 @@ class Adam(torch.optim.Optimizer):
             t.fill_(it)
         for s in self._stamps.values():         # t may go backwards: a stale stamp must never look current
             s.zero_()
+        for p, d in self._defer.items():        # deferred: a checkpoint is taken flushed -- every row is current through `it`
+            d.m, d.v = self._moments(p)         # (the loader replaced the moments)
+            d.stamp.fill_(it)
 
     def reset_(self):
         """Back to "never stepped" IN PLACE (moments, stamps and counter keep their storage): what a capture's restore needs after
@@ -118,6 +239,8 @@ class Adam(torch.optim.Optimizer):
                     st[k].zero_()
         for s in self._stamps.values():
             s.zero_()
+        for d in self._defer.values():
+            d.stamp.zero_()
         for t in self._t.values():
             t.zero_()
 
@@ -172,7 +295,15 @@ class Adam(torch.optim.Optimizer):
             for p in group["params"]:
                 pend = getattr(p, "_fil_pending_runs", None)
                 if pend is None and p.grad is None:
+                    if p in self._defer:        # Keras mode leaves the table alone at this step: the ring says so
+                        self._defer[p].roll(p, hyper, FIL_ADAM_ROLL_SKIP)
                     continue
+                if pend is not None and self.sweep_period is not None and p not in self._defer:
+                    # a runs table that was not one when it joined (swept every step so far, so current): deferred from now on
+                    self._attach(p)
+                if pend is None and p in self._defer:
+                    raise FilError("optim.Adam: deferred table %s has a .grad -- with sweep_period its gradient must arrive as runs "
+                                   "(SparseEmbed(grad_mode='runs'))" % (tuple(p.shape),))
                 if p.device.type != "cuda" or p.dtype != torch.float32 or not p.is_contiguous():
                     raise FilError("optim.Adam: parameter %s %s on %s -- contiguous fp32 GPU tensors only" % (tuple(p.shape), p.dtype, p.device))
                 m, v = self._moments(p)
@@ -214,6 +345,9 @@ class Adam(torch.optim.Optimizer):
     def _apply_runs(self, lib, p, pend, m, v, t, hyper):
         lr, b1, b2, eps = hyper
         V, K = p.shape
+        if p in self._defer:
+            self._apply_runs_deferred(lib, p, pend, m, v, t, hyper)
+            return
         mode = FIL_ADAM_LAZY if self.lazy_tables else FIL_ADAM_KERAS
         stamp = None
         if mode == FIL_ADAM_KERAS:
@@ -232,6 +366,49 @@ class Adam(torch.optim.Optimizer):
             if mode == FIL_ADAM_KERAS:
                 check(lib.fil_embed_adam_sweep(ptr(p), ptr(m), ptr(v), ptr(stamp), V, K, ptr(pend["offsets"]), ptr(pend["field_l2"]),
                                                ptr(pend["frozen"]), pend["F"], ptr(t), lr, b1, b2, eps, st), "fil_embed_adam_sweep")
+
+    # -- deferred mode -----------------------------------------------------------------------------------------------
+    def _attach(self, p):
+        """A runs table joins deferred mode: moments now (the forward's catch-up may run before the first step), stamps at the
+        current count, the ring, and its entry in the registry that the forward and SparseEmbed follow."""
+        if p.device.type != "cuda" or p.dtype != torch.float32 or not p.is_contiguous() or p.dim() != 2:
+            raise FilError("optim.Adam: deferred table %s %s on %s -- a contiguous fp32 [V, K] GPU tensor" % (tuple(p.shape), p.dtype,
+                                                                                                               p.device))
+        if p in self._defer:
+            return
+        old = _DEFERRED.get(p)
+        if old is not None:
+            if old.opt() is not None:
+                raise FilError("optim.Adam: table %s already belongs to another deferred optimizer" % (tuple(p.shape),))
+            _release([old])                 # its optimizer is gone but not yet finalised: bring the table current first
+        m, v = self._moments(p)
+        d = self._defer[p] = _Deferred(self, p, m, v, self._counter(p.device), self.sweep_period)
+        self._released.append(d)
+        _DEFERRED[p] = d
+
+    def _apply_runs_deferred(self, lib, p, pend, m, v, t, hyper):
+        lr, b1, b2, eps = hyper
+        V, K = p.shape
+        d = self._defer[p]
+        offsets, field_l2, frozen, F = d.field_args(p, pend)
+        with torch.cuda.device(p.device):
+            st = stream_ptr()
+            world = self._exchange_world()
+            if world:
+                self._apply_runs_exchanged(lib, p, pend, m, v, t, None, FIL_ADAM_KERAS, world, hyper, st)
+            else:
+                check(lib.fil_embed_adam_runs_deferred(ptr(pend["g"]), ptr(pend["perm"]), ptr(pend["sorted_ids"]), pend["R"], K,
+                                                       pend["g_dtype"], F, ptr(offsets), ptr(field_l2), ptr(frozen), ptr(p), ptr(m), ptr(v),
+                                                       ptr(d.stamp), ptr(d.ring), self.sweep_period, V, ptr(t), lr, b1, b2, eps, st),
+                      "fil_embed_adam_runs_deferred")
+        d.roll(p, hyper, FIL_ADAM_ROLL_STEP)
+
+    @torch.no_grad()
+    def flush(self):
+        """Deferred mode: bring every row of every deferred table current (table, m and v then hold exactly what Keras mode holds).
+        A no-op without sweep_period.  Also done when the optimizer is finalised."""
+        for d in self._defer.values():
+            d.flush()
 
     # -- data parallelism ------------------------------------------------------------------------------------------
     def _exchange_world(self):
@@ -287,6 +464,13 @@ class Adam(torch.optim.Optimizer):
         ids, values, counts = buf["gathered"]
         if ids is not buf["ids"]:
             dp.exchange_runs(buf["ids"], buf["values"], buf["count"], ids, values, counts, group=self.process_group)
+        if p in self._defer:
+            d = self._defer[p]
+            offsets, field_l2, frozen, F = d.field_args(p, pend)
+            check(lib.fil_embed_adam_merged_deferred(ptr(ids), ptr(values), ptr(counts), world, cap, K, ptr(offsets), ptr(field_l2),
+                                                     ptr(frozen), F, ptr(p), ptr(m), ptr(v), ptr(d.stamp), ptr(d.ring),
+                                                     self.sweep_period, V, ptr(t), lr, b1, b2, eps, st), "fil_embed_adam_merged_deferred")
+            return
         check(lib.fil_embed_adam_merged(ptr(ids), ptr(values), ptr(counts), world, cap, K, ptr(pend["offsets"]), ptr(pend["field_l2"]),
                                         pend["F"], ptr(p), ptr(m), ptr(v), ptr(stamp), V, ptr(t), lr, b1, b2, eps, mode, st),
               "fil_embed_adam_merged")
