@@ -13,8 +13,8 @@ side stream); the loss is Keras' compiled loss: binary cross-entropy + the layer
 of every embedding table, interactive_layer.py:217); the optimiser is Keras' 'adam' (lr 1e-3, epsilon 1e-7).
 Data parallel: every rank trains on its own shard of the table, dense gradients go through one bucketed all-reduce
 (ml_function_amd.dp.allreduce_module_grads), the embedding tables exchange only the rows their shards touched
-(dp.exchange_sparse_rows) -- or, with --optimizer keras --dp-tables runs, their compacted gradient runs (optim.Adam's runs
-exchange).  Labels come from a fixed random "teacher" so that the AUC has something to learn.
+(dp.exchange_sparse_rows) -- or, with --optimizer keras* --dp-tables runs, their compacted gradient runs (the runs exchange of
+optim.Adam / Adagrad / Ftrl).  Labels come from a fixed random "teacher" so that the AUC has something to learn.
 """
 import argparse
 import os
@@ -56,13 +56,15 @@ def main():
     ap.add_argument("--cin-precision", default="f32", choices=["f32", "bf16"],
                     help="XDeepFM only: bf16 = the CIN's labelled bf16 training mode (one bf16 MFMA per product in its three GEMM "
                          "launches, ~1e-3 relative error); f32 = the exact chain")
-    ap.add_argument("--optimizer", default="torch", choices=["torch", "keras", "keras-lazy"],
+    ap.add_argument("--optimizer", default="torch", choices=["torch", "keras", "keras-lazy", "keras-adagrad", "keras-ftrl"],
                     help="torch = torch.optim.Adam on dense table gradients; keras = ml_function_amd.optim.Adam (Keras' epsilon placement), "
                          "on one GPU with the tables updated in place from the batch's gradient runs (tableGrad='runs'); keras-lazy = the "
-                         "same with LazyAdam tables (only touched rows change: a labelled deviation from the reference).  Data parallel: "
-                         "the tables keep their dense gradients and the sparse row exchange unless --dp-tables runs")
+                         "same with LazyAdam tables (only touched rows change: a labelled deviation from the reference); keras-adagrad / "
+                         "keras-ftrl = ml_function_amd.optim.Adagrad / Ftrl (Keras' defaults and semantics, the tables in place as for "
+                         "keras; Ftrl's strengths: --ftrl-*).  Data parallel: the tables keep their dense gradients and the sparse row "
+                         "exchange unless --dp-tables runs")
     ap.add_argument("--dp-tables", default="dense", choices=["dense", "runs"],
-                    help="data parallel with --optimizer keras|keras-lazy: runs = the tables take tableGrad='runs' and optim.Adam's runs "
+                    help="data parallel with --optimizer keras*: runs = the tables take tableGrad='runs' and the optimizer's runs "
                          "exchange (each rank's compacted gradient runs all-gathered, one merged update per replica, no [V,K] gradient, "
                          "no host sync after the first step); dense = the dense table gradients and dp.exchange_sparse_rows.  The default "
                          "stays dense: the runs exchange's all-gather at N > 1 ranks has not been timed on hardware yet (one GPU only)")
@@ -70,6 +72,10 @@ def main():
                     help="with --optimizer keras: deferred Keras mode (optim.Adam(sweep_period=N)) -- the untouched table rows catch up "
                          "on read and in one rolling slice of 1/N of the table per step instead of a whole-table sweep per step; the "
                          "same bits as keras after a flush (state_dict).  8 is a good choice (DESIGN 6e); default: the per-step sweep")
+    ap.add_argument("--ftrl-lr-power", type=float, default=-0.5, help="--optimizer keras-ftrl: learning_rate_power (<= 0)")
+    ap.add_argument("--ftrl-l1", type=float, default=0.0, help="--optimizer keras-ftrl: l1_regularization_strength")
+    ap.add_argument("--ftrl-l2", type=float, default=0.0, help="--optimizer keras-ftrl: l2_regularization_strength")
+    ap.add_argument("--ftrl-l2-shrinkage", type=float, default=0.0, help="--optimizer keras-ftrl: l2_shrinkage_regularization_strength")
     ap.add_argument("--no-graph", action="store_true",
                     help="run every step eagerly (default on one GPU: the whole step -- forward, backward, Adam -- is captured once "
                          "into a HIP graph and replayed; the C ABI neither allocates nor synchronises, so it is capture-safe)")
@@ -117,7 +123,13 @@ def main():
     table_l2 = {id(m.embeddings): m.table_l2_ranges() for m in model.modules() if hasattr(m, "table_l2_ranges") and m.built}
     others = [p for n, p in model.named_parameters() if not n.endswith("embeddings")]
     use_graph = world == 1 and not args.no_graph
-    if keras:       # Keras 'adam' (un_seq.py:61) with Keras' numerics; tables in "runs" mode get their l2 inside the update
+    if args.optimizer == "keras-adagrad":       # Keras' Adagrad; tables in "runs" mode get their l2 inside the update
+        opt = optim.Adagrad(model.parameters(), learning_rate=args.lr)
+    elif args.optimizer == "keras-ftrl":        # Keras' Ftrl, likewise
+        opt = optim.Ftrl(model.parameters(), learning_rate=args.lr, learning_rate_power=args.ftrl_lr_power,
+                         l1_regularization_strength=args.ftrl_l1, l2_regularization_strength=args.ftrl_l2,
+                         l2_shrinkage_regularization_strength=args.ftrl_l2_shrinkage)
+    elif keras:     # Keras 'adam' (un_seq.py:61) with Keras' numerics; tables in "runs" mode get their l2 inside the update
         opt = optim.Adam(model.parameters(), learning_rate=args.lr, epsilon=1e-7, lazy_tables=args.optimizer == "keras-lazy",
                          sweep_period=args.sweep_period)
     else:
@@ -140,7 +152,7 @@ def main():
             offs = fi.sparse_embed.offsets
             rows = (idx + offs).reshape(-1)
             for t in tables:
-                if t.grad is not None:          # (runs tables have no .grad: optim.Adam exchanges their runs and adds their l2 itself)
+                if t.grad is not None:          # (runs tables have no .grad: the optimizer exchanges their runs and adds their l2 itself)
                     dp.exchange_sparse_rows(t.grad, rows)
         for t in tables:
             if t.grad is not None and table_l2.get(id(t)):
@@ -168,7 +180,7 @@ def main():
                 torch.cuda.current_stream().wait_stream(side)
                 model.load_state_dict(saved_model)
                 if keras:
-                    opt.reset_()                    # moments, row stamps and the device step counter, in place
+                    opt.reset_()                    # slots, row stamps and the device step counter, in place
                 else:
                     for st_ in opt.state.values():      # Adam's moments and step count back to "never stepped" (in place: the capture keeps these tensors)
                         for v in st_.values():

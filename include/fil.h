@@ -443,6 +443,55 @@ int fil_embed_adam_sweep(float* table, float* m, float* v, const int32_t* stamp,
                          const float* field_l2, const unsigned char* frozen, int F, const int64_t* step, float lr, float beta_1,
                          float beta_2, float epsilon, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * O2  Keras-exact Adagrad and Ftrl (TF 2.1 Keras -> ApplyAdagradV2 / ApplyFtrl, ApplyFtrlV2 when l2_shrinkage > 0), every tensor fp32,
+ *     `rule` FIL_OPT_ADAGRAD or FIL_OPT_FTRL, hyper-parameters in a fil_rowopt_hyper read ON THE HOST at the call (a captured graph
+ *     keeps the values it was captured with):
+ *       Adagrad  acc += g*g;  p -= g*lr / (sqrt(acc) + epsilon)                     (Keras: accumulator starts at 0.1, epsilon 1e-7)
+ *       Ftrl     gs = g + 2*l2_shrinkage*p;  n' = n + g*g (the raw g);  a(x) = sqrt(x) if lr_power == -0.5 else pow(x, -lr_power)
+ *                z += gs - (a(n') - a(n))/lr * p;  q = a(n')/lr + 2*l2;  p = |z| > l1 ? (sign(z)*l1 - z)/q : 0;  n = n'
+ *     The accumulator (n) lives in the `m` array of fil_adam_tensor / the `accum` argument, Ftrl's linear slot (z) in `v` / `linear`
+ *     (NULL for Adagrad).  Neither rule reads the step counter; it is kept (Keras' iterations) and used for the row stamps only.
+ *     Requires lr >= 0; Adagrad epsilon >= 0; Ftrl lr_power <= 0, l1, l2, l2_shrinkage >= 0 (FIL_ERR_ARG otherwise).
+ *   Which rows Keras updates (each field a Keras Embedding with l2(emb_reg)): a field with emb_reg > 0 has a dense regulariser
+ *     gradient, so EVERY row moves -- a touched row with g = run sum + 2 emb_reg p, an untouched one with g = 2 emb_reg p; a field
+ *     with emb_reg = 0 gets IndexedSlices, so only the batch's rows change and every other row and its slots keep their bits (for
+ *     Ftrl this is NOT a dense apply with g = 0, which recomputes p from z); a frozen field never changes.  Keras' quirk, reproduced:
+ *     under Ftrl the first step takes every untouched row of a regularised field to about -lr*2*emb_reg*p/sqrt(n), in effect 0 (its
+ *     initial weights are gone) -- the common case, since make_sparse_info's default emb_reg is 1e-8.
+ *   fil_rowopt_multi: fil_adam_multi's contract with the rule: every descriptor in one launch, grad NULL = a zero gradient, l2 adds
+ *     2*l2*p to the gradient, 16-byte accesses where the descriptor's arrays are aligned, advance = 1 increments *step.
+ *   fil_embed_rowopt_runs: fil_embed_adam_runs' contract with the rule: each run of ids >= 0 summed in fil_embed_run_sum's order,
+ *     g = run sum + 2*field_l2[perm % F]*p, the row updated in place; stamp[row] = low 32 bits of *step + 1 when stamp != NULL
+ *     (needed when a sweep follows, i.e. when field_l2 has an entry > 0).  f32 / bf16 g_dtype, K <= 256, capturable.
+ *   fil_embed_rowopt_sweep: the rows of non-frozen fields with field_l2[f] > 0 (f = the last field with offsets[f] <= row) not stamped
+ *     with the current t take the rule with g = 2*field_l2[f]*p; the grid walks those fields' rows only (field_l2 NULL: nothing to
+ *     do, no launch).  Non-temporal stores; F <= 1024.
+ *   fil_embed_rowopt_merged: fil_embed_adam_merged's contract with the rule on W gathered fil_embed_runs_compact lists: each row of
+ *     the union updated once, by its owner (the lowest list holding it), summed in list order; W = 1 is bit-identical to
+ *     fil_embed_rowopt_runs on the same record.  Stamps when stamp != NULL.  F <= 1024, K <= 256.
+ */
+enum { FIL_OPT_ADAGRAD = 1, FIL_OPT_FTRL = 2 };
+typedef struct {
+  float lr;
+  float epsilon;        /* Adagrad */
+  float lr_power;       /* Ftrl: learning_rate_power (<= 0) */
+  float l1;             /* Ftrl: l1_regularization_strength */
+  float l2;             /* Ftrl: l2_regularization_strength */
+  float l2_shrinkage;   /* Ftrl: l2_shrinkage_regularization_strength */
+} fil_rowopt_hyper;     /* 24 bytes */
+int fil_rowopt_multi(const fil_adam_tensor* tensors, int n, int64_t total_numel, int64_t* step, int rule, const fil_rowopt_hyper* hyper,
+                     int advance, void* stream);
+int fil_embed_rowopt_runs(const void* g, const int64_t* perm, const int64_t* sorted_ids, long R, int K, int g_dtype, int F,
+                          const float* field_l2, float* table, float* accum, float* linear, int32_t* stamp, const int64_t* step, int rule,
+                          const fil_rowopt_hyper* hyper, void* stream);
+int fil_embed_rowopt_sweep(float* table, float* accum, float* linear, const int32_t* stamp, int64_t V, int K, const int64_t* offsets,
+                           const float* field_l2, const unsigned char* frozen, int F, const int64_t* step, int rule,
+                           const fil_rowopt_hyper* hyper, void* stream);
+int fil_embed_rowopt_merged(const int64_t* ids, const float* values, const int64_t* counts, int W, long cap, int K, const int64_t* offsets,
+                            const float* field_l2, int F, float* table, float* accum, float* linear, int32_t* stamp, int64_t V,
+                            const int64_t* step, int rule, const fil_rowopt_hyper* hyper, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -28,6 +28,7 @@ HEADER_PATH = os.path.join(_HERE, "..", "include", "fil.h")
 FIL_F32, FIL_BF16 = 0, 1
 FIL_ADAM_KERAS, FIL_ADAM_LAZY = 0, 1
 FIL_ADAM_ROLL_STEP, FIL_ADAM_ROLL_SKIP, FIL_ADAM_ROLL_FLUSH = 0, 1, 2
+FIL_OPT_ADAGRAD, FIL_OPT_FTRL = 1, 2
 
 _c = ctypes
 _P = _c.c_void_p
@@ -95,7 +96,16 @@ SIGNATURES = {
     "fil_embed_adam_merged_deferred": (_I, [_P, _P, _P, _I, _c.c_long, _I, _P, _P, _P, _I, _P, _P, _P, _P, _P, _I, _c.c_int64, _P, _F,
                                             _F, _F, _F, _P]),
     "fil_embed_adam_roll": (_I, [_P, _P, _P, _P, _P, _I, _c.c_int64, _I, _P, _P, _P, _I, _P, _F, _F, _F, _F, _I, _P]),
+    "fil_rowopt_multi": (_I, [_P, _I, _c.c_int64, _P, _I, _P, _I, _P]),
+    "fil_embed_rowopt_runs": (_I, [_P, _P, _P, _c.c_long, _I, _I, _I, _P, _P, _P, _P, _P, _P, _I, _P, _P]),
+    "fil_embed_rowopt_sweep": (_I, [_P, _P, _P, _P, _c.c_int64, _I, _P, _P, _P, _I, _P, _I, _P, _P]),
+    "fil_embed_rowopt_merged": (_I, [_P, _P, _P, _I, _c.c_long, _I, _P, _P, _I, _P, _P, _P, _P, _c.c_int64, _P, _I, _P, _P]),
 }
+
+
+class RowoptHyper(_c.Structure):
+    """fil_rowopt_hyper (include/fil.h O2)"""
+    _fields_ = [("lr", _F), ("epsilon", _F), ("lr_power", _F), ("l1", _F), ("l2", _F), ("l2_shrinkage", _F)]
 
 
 class FilError(RuntimeError):

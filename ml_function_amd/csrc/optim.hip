@@ -15,6 +15,7 @@
 // sweep, so every replica computes the same bits.
 #include "common.h"
 #include "embed_runs.h"
+#include "optim_rows.h"
 #include <hip/hip_bf16.h>
 
 namespace fil {
@@ -127,19 +128,7 @@ __global__ __launch_bounds__(256) void embed_adam_runs_kernel(const GT* __restri
 }
 
 // ---- fil_embed_adam_sweep: every row the run pass did not stamp at this step takes g = 2 l2[f] p (or 0); frozen fields are
-// left alone.  The field of a row comes from a binary search of the offsets held in LDS.
-constexpr int kSweepMaxF = 1024;
-
-__device__ __forceinline__ int sweep_field(const int64_t* off, int F, int64_t row) {
-  int lo = 0, hi = F;                      // last f with off[f] <= row, or -1
-  while (lo < hi) {
-    const int mid = (lo + hi) >> 1;
-    if (off[mid] <= row) lo = mid + 1;
-    else hi = mid;
-  }
-  return lo - 1;
-}
-
+// left alone.  The field of a row comes from a binary search of the offsets held in LDS (sweep_field, optim_rows.h).
 __global__ __launch_bounds__(256) void embed_adam_sweep_kernel(float* __restrict__ table, float* __restrict__ m, float* __restrict__ v,
                                                                const int32_t* __restrict__ stamp, int64_t V, int K,
                                                                const int64_t* __restrict__ offsets, const float* __restrict__ field_l2,
@@ -295,22 +284,8 @@ __global__ __launch_bounds__(256) void runs_compact_sums_kernel(const GT* __rest
 // ---- fil_embed_adam_merged: one lane per gathered entry (w, i).  The lowest list holding a row owns it; the owner adds the other
 // lists' copies in list order (binary searches: each list is ascending and distinct), adds the field's l2 term and updates the row
 // exactly as embed_adam_runs_kernel does.  K is walked in chunks of kMergeChunk elements (a later chunk repeats the searches).
+// (find_row / list_count: optim_rows.h)
 constexpr int kMergeChunk = 16;
-
-__device__ __forceinline__ long find_row(const int64_t* __restrict__ list, long n, int64_t row) {
-  long lo = 0, hi = n;
-  while (lo < hi) {
-    const long mid = (lo + hi) >> 1;
-    if (list[mid] < row) lo = mid + 1;
-    else hi = mid;
-  }
-  return lo < n && list[lo] == row ? lo : -1;
-}
-
-__device__ __forceinline__ long list_count(const int64_t* counts, int w, long cap) {
-  const int64_t c = counts[w];
-  return c < 0 ? 0 : (c > cap ? cap : (long)c);
-}
 
 __global__ __launch_bounds__(256) void embed_adam_merged_kernel(const int64_t* __restrict__ ids, const float* __restrict__ values,
                                                                 const int64_t* __restrict__ counts, int W, long cap, int K,

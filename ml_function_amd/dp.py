@@ -236,11 +236,12 @@ def exchange_sparse_rows(grad, touched_rows, group=None):
 
 
 def exchange_runs(ids, values, count, ids_all, values_all, counts_all, group=None):
-    """The data-parallel exchange of optim.Adam's runs tables (the compact counterpart of exchange_sparse_rows, which is unchanged):
+    """The data-parallel exchange of the runs tables of optim.Adam, optim.Adagrad and optim.Ftrl (the compact counterpart of
+    exchange_sparse_rows, which is unchanged):
     every rank's compact list -- ids [cap] int64 (ascending, INT64_MAX padded), values [cap*K] fp32, count [1] int64, as
     fil_embed_runs_compact writes them -- is all-gathered into ids_all [W*cap], values_all [W*cap*K], counts_all [W], rank after rank.
-    Fixed sizes (cap is agreed once), no host read, no allocation: fil_embed_adam_merged then applies the same gathered lists on every
-    replica (rows summed in rank order: bit-identical tables)."""
+    Fixed sizes (cap is agreed once), no host read, no allocation: fil_embed_adam_merged (fil_embed_rowopt_merged for Adagrad and
+    Ftrl) then applies the same gathered lists on every replica (rows summed in rank order: bit-identical tables)."""
     dist.all_gather_into_tensor(counts_all, count, group=group)
     dist.all_gather_into_tensor(ids_all, ids, group=group)
     dist.all_gather_into_tensor(values_all, values, group=group)

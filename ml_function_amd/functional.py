@@ -907,7 +907,7 @@ class _EmbedFn(torch.autograd.Function):
         # (a bf16 block's gradient arrives as bf16: the dense deterministic path reads it as it is, the others take fp32)
         g_bf16 = g.dtype == torch.bfloat16 and not atomic and not sparse_grad
         g = g.contiguous() if g_bf16 else _f32c(g)
-        if ctx.runs_grad is not None:   # deferred: the optimizer applies the runs in place (optim.Adam, fil_embed_adam_runs)
+        if ctx.runs_grad is not None:   # deferred: the optimizer applies the runs in place (optim.Adam / Adagrad / Ftrl)
             table = ctx.table_param
             if getattr(table, "_fil_pending_runs", None) is not None:
                 raise FilError("embed_gather(grad_mode='runs'): the table already holds a pending gradient record -- one backward per "
@@ -942,7 +942,8 @@ def embed_gather(table, offsets, idx, sizes=None, frozen=None, sparse_grad=False
     The gradient is deterministic (sorted segment sums); sparse_grad=True returns it as a sparse COO tensor over the touched
     rows instead of a dense table; atomic=True selects the fp32-atomic scatter-add instead.
     runs_grad (a dict: offsets, frozen, field_l2 [F] fp32 or None): the table gets NO gradient; the backward leaves the sorted runs
-    (g, perm, sorted_ids) on the table as `table._fil_pending_runs` for optim.Adam to apply in place (fil_embed_adam_runs)."""
+    (g, perm, sorted_ids) on the table as `table._fil_pending_runs` for optim.Adam, optim.Adagrad or optim.Ftrl to apply in place
+    (fil_embed_adam_runs / fil_embed_rowopt_runs)."""
     if not emit_xt:   # (out_dtype=torch.bfloat16: the block leaves the gather rounded to bf16 and its gradient is read as bf16 -- no cast launches)
         return _EmbedFn.apply(table, offsets, sizes, idx, frozen, sparse_grad, atomic, oob_count, layout_key, None, out_dtype, runs_grad)
     # emit_xt: the same launch also writes the block transposed to [B*K, F], the layout the CIN kernels read; it rides on the

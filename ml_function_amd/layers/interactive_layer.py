@@ -376,11 +376,11 @@ class SparseEmbed(Layer):
     ``check_ids=True`` (or FIL_CHECK_IDS=1) additionally raises, like Keras on the CPU does (costs a device sync per call).
     ``sparse_grad=True`` hands the table gradient out as a sparse COO tensor over the touched rows (Keras' IndexedSlices)
     instead of a dense table; either way it is deterministic (sorted segment sums, no atomics).
-    ``grad_mode="runs"`` (extension; default "dense") defers the table gradient to ml_function_amd.optim.Adam: the backward hands
-    the optimizer the batch's sorted gradient runs instead of a [V,K] tensor (the table's .grad stays None), and the optimizer
-    updates table, m and v in place (fil_embed_adam_runs), adding the l2(emb_reg) gradient of table_l2_ranges() itself -- so
-    regularization_losses() then reports the l2 terms DETACHED (the loss value is unchanged, no dense gradient flows).  Needs
-    optim.Adam; any other optimizer would see no gradient for the table."""
+    ``grad_mode="runs"`` (extension; default "dense") defers the table gradient to ml_function_amd.optim.Adam, .Adagrad or .Ftrl:
+    the backward hands the optimizer the batch's sorted gradient runs instead of a [V,K] tensor (the table's .grad stays None), and
+    the optimizer updates the table and its slots in place (fil_embed_adam_runs / fil_embed_rowopt_runs), adding the l2(emb_reg)
+    gradient of table_l2_ranges() itself -- so regularization_losses() then reports the l2 terms DETACHED (the loss value is
+    unchanged, no dense gradient flows).  Needs one of those three optimizers; any other would see no gradient for the table."""
 
     def __init__(self, sparse_info: list, is_linear=False, use_flatten=True, use_add=False, seed=2020, support_masking=True,
                  mask_zero=False, packed=False, check_ids=None, sparse_grad=False, emit_xt=False, out_dtype=None, grad_mode="dense"):
@@ -461,7 +461,7 @@ class SparseEmbed(Layer):
             for lo, _, reg in self._reg:
                 field_l2[offsets.index(lo)] = reg
             self.register_buffer("field_l2", torch.tensor(field_l2, dtype=torch.float32, device=dev) if self._reg else None)
-            self.embeddings._fil_runs_table = True        # optim.Adam: a table whose gradient arrives as runs
+            self.embeddings._fil_runs_table = True        # optim.Adam / Adagrad / Ftrl: a table whose gradient arrives as runs
         super().build(input_shape)
 
     def regularization_losses(self):

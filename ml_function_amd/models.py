@@ -56,8 +56,8 @@ class FeatureInput(Layer):
         self.use_linear = useLinear
         # emitXT (extension): the embedding gather also writes the block in the layout the CIN kernels read (XDeepFM)
         # embedDtype (extension): torch.bfloat16 = the cross embeddings leave the gather as bf16 (a bf16 model's cast of the block, fused)
-        # tableGrad (extension): "runs" = the tables' gradients go to ml_function_amd.optim.Adam as the batch's sorted runs and are
-        # applied in place (SparseEmbed(grad_mode="runs")); "dense" (default) = a [V,K] gradient tensor per table
+        # tableGrad (extension): "runs" = the tables' gradients go to ml_function_amd.optim.Adam, .Adagrad or .Ftrl as the batch's
+        # sorted runs and are applied in place (SparseEmbed(grad_mode="runs")); "dense" (default) = a [V,K] gradient tensor per table
         self.sparse_embed = (SparseEmbed(self.sparse_info, use_flatten=useFlattenSparse, emit_xt=emitXT, out_dtype=embedDtype,
                                          grad_mode=tableGrad) if self.sparse_info else None)
         self.linear_embed = (SparseEmbed(self.sparse_info, use_flatten=useFlattenLinear, is_linear=True, use_add=useAddLinear,

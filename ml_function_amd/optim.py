@@ -1,4 +1,4 @@
-"""Keras' Adam on the HIP path (include/fil.h O1): the optimizer the reference compiles (optimizer='adam', example/ctr_example/
+"""Keras' Adam, Adagrad and Ftrl on the HIP path (include/fil.h O1, O2): the optimizer the reference compiles (optimizer='adam', example/ctr_example/
 un_seq.py:61; TF 2.1), with Keras' names, defaults and numerics.
 
     opt = optim.Adam(model.parameters())                    # learning_rate 1e-3, beta_1 0.9, beta_2 0.999, epsilon 1e-7
@@ -36,6 +36,11 @@ epsilon 1/sqrt(1 - beta_2) ~ 31.6 times larger -- of the order of an embedding r
 * The step counter t (Keras' `iterations`) is an int64 on the device, read by every launch and advanced by the last one: a step
   captured into a HIP graph (capture.capture_step) advances it on every replay.  Learning rate and betas are baked into a capture.
 
+Adagrad and Ftrl (Keras' tf.keras.optimizers.Adagrad / Ftrl, TF 2.1; O2) follow the same contract -- iterations, one dense launch per
+(group, device), runs tables consumed in place, the same data-parallel route, capture after one eager step -- with row-local rules:
+an untouched row has no state that decays, so only the regularised fields (l2(emb_reg) > 0) are swept, over their rows alone, and
+an untouched row of any other field keeps its bits (Keras' IndexedSlices semantics).  No deferred or lazy mode.
+
 Only fp32 parameters on a GPU are supported: anything else raises (there is no CPU / eager fallback).
 """
 import ctypes
@@ -46,8 +51,8 @@ import torch.distributed as dist
 from torch.utils.weak import WeakIdKeyDictionary
 
 from . import _lib
-from ._lib import (FIL_ADAM_KERAS, FIL_ADAM_LAZY, FIL_ADAM_ROLL_FLUSH, FIL_ADAM_ROLL_SKIP, FIL_ADAM_ROLL_STEP, FilError, check, ptr,
-                   stream_ptr)
+from ._lib import (FIL_ADAM_KERAS, FIL_ADAM_LAZY, FIL_ADAM_ROLL_FLUSH, FIL_ADAM_ROLL_SKIP, FIL_ADAM_ROLL_STEP, FIL_OPT_ADAGRAD,
+                   FIL_OPT_FTRL, FilError, RowoptHyper, check, ptr, stream_ptr)
 
 
 class _Desc(ctypes.Structure):
@@ -141,7 +146,120 @@ def deferred_optimizer(table):
     return st.opt() if st is not None else None
 
 
-class Adam(torch.optim.Optimizer):
+class _RunsOptimizer(torch.optim.Optimizer):
+    """What the fused optimizers of this module share: the device step counter (Keras' iterations), the staged descriptor arrays of
+    the one dense launch per (group, device), the pending runs records, and the data-parallel exchange of the runs tables.  A
+    subclass sets _NAME (its name in messages) and, before the base class adds the groups: _t, _descs, _pinned, _arena, _arena_off,
+    _xbuf, process_group, force_exchange."""
+    _NAME = None
+
+    def _counter(self, dev):
+        t = self._t.get(dev)
+        if t is None:
+            t = self._t[dev] = torch.zeros(1, dtype=torch.int64, device=dev)
+        return t
+
+    @property
+    def iterations(self):
+        """Completed steps (Keras' optimizer.iterations), as a host int (synchronises)."""
+        return int(next(iter(self._t.values()))[0]) if self._t else 0
+
+    def zero_grad(self, set_to_none=True):
+        super().zero_grad(set_to_none=set_to_none)
+        for g in self.param_groups:
+            for p in g["params"]:
+                if getattr(p, "_fil_pending_runs", None) is not None:
+                    p._fil_pending_runs = None
+
+    def _desc_array(self, dev, entries):
+        key = (dev, tuple(entries))
+        hit = self._descs.get(key)
+        if hit is not None:
+            return hit[0]
+        host = (_Desc * len(entries))(*[_Desc(p, g, m, v, n, l2, 0) for p, g, m, v, n, l2 in entries])
+        size = ctypes.sizeof(host)
+        capturing = torch.cuda.is_current_stream_capturing()
+        if capturing:
+            if self._arena is None or self._arena_off + size > self._arena.numel():
+                raise FilError("%s: no room for the descriptors of a captured step -- run one eager step before capturing "
+                               "(capture.capture_step's warm-up does)" % self._NAME)
+            pinned = self._arena[self._arena_off:self._arena_off + size]
+            self._arena_off += (size + 255) // 256 * 256
+        else:
+            if self._arena is None:
+                self._arena = torch.empty(max(1 << 16, 8 * size), dtype=torch.uint8, pin_memory=True)
+            pinned = torch.empty(size, dtype=torch.uint8, pin_memory=True)
+        ctypes.memmove(pinned.data_ptr(), ctypes.addressof(host), size)
+        d = torch.empty(size, dtype=torch.uint8, device=dev)
+        d.copy_(pinned, non_blocking=True)
+        if capturing:
+            self._pinned.append((d, pinned))
+        else:
+            if len(self._descs) >= 16:
+                self._descs.clear()
+            self._descs[key] = (d, pinned)
+        return d
+
+    def _exchange_world(self):
+        """The world size of the runs exchange, or 0 for the one-GPU path (no group of > 1 ranks and no force_exchange)."""
+        if dist.is_available() and dist.is_initialized():
+            world = dist.get_world_size(self.process_group)
+            if world > 1 or self.force_exchange:
+                return world
+            return 0
+        if self.process_group is not None:
+            raise FilError("%s: a process_group was given but torch.distributed is not initialised" % self._NAME)
+        return 1 if self.force_exchange else 0
+
+    def _exchange_buffers(self, p, pend, world):
+        V, K = p.shape
+        R = int(pend["R"])
+        buf = self._xbuf.get(p)
+        if buf is None:
+            dev = p.device
+            if world > 1 or dist.is_initialized():      # one all-reduce MAX of R: every rank's lists get the same capacity
+                r = torch.tensor([R], dtype=torch.int64, device=dev)
+                dist.all_reduce(r, op=dist.ReduceOp.MAX, group=self.process_group)
+                cap = int(r.item())
+            else:
+                cap = R
+            cap = max(cap, 1)
+            lib = _lib.load()
+            ids = torch.empty(cap, dtype=torch.int64, device=dev)
+            values = torch.empty(cap * K, dtype=torch.float32, device=dev)
+            count = torch.zeros(1, dtype=torch.int64, device=dev)
+            ws = torch.empty(max(1, int(lib.fil_embed_runs_compact_workspace_bytes(cap))), dtype=torch.uint8, device=dev)
+            if world > 1 or dist.is_initialized():
+                gathered = (torch.empty(world * cap, dtype=torch.int64, device=dev),
+                            torch.empty(world * cap * K, dtype=torch.float32, device=dev),
+                            torch.empty(world, dtype=torch.int64, device=dev))
+            else:
+                gathered = (ids, values, count)        # no process group (force_exchange): the local list IS the gathered one
+            buf = self._xbuf[p] = dict(cap=cap, ids=ids, values=values, count=count, ws=ws, gathered=gathered)
+        if R > buf["cap"]:
+            raise FilError("%s: runs record of %d entries > the exchange capacity %d agreed on the first step (the first "
+                           "batch must be the largest)" % (self._NAME, R, buf["cap"]))
+        return buf
+
+    def _compact_and_exchange(self, lib, p, pend, world, st):
+        """fil_embed_runs_compact of the record, then dp.exchange_runs (nothing to exchange without a process group): the W
+        gathered lists (ids, values, counts) and their capacity."""
+        from . import dp
+        K = p.shape[1]
+        buf = self._exchange_buffers(p, pend, world)
+        cap = buf["cap"]
+        check(lib.fil_embed_runs_compact(ptr(pend["g"]), ptr(pend["perm"]), ptr(pend["sorted_ids"]), pend["R"], K, pend["g_dtype"],
+                                         ptr(buf["ids"]), ptr(buf["values"]), ptr(buf["count"]), cap, ptr(buf["ws"]), buf["ws"].numel(),
+                                         st), "fil_embed_runs_compact")
+        ids, values, counts = buf["gathered"]
+        if ids is not buf["ids"]:
+            dp.exchange_runs(buf["ids"], buf["values"], buf["count"], ids, values, counts, group=self.process_group)
+        return ids, values, counts, cap
+
+
+class Adam(_RunsOptimizer):
+    _NAME = "optim.Adam"
+
     def __init__(self, params, learning_rate=1e-3, beta_1=0.9, beta_2=0.999, epsilon=1e-7, lazy_tables=False, process_group=None,
                  force_exchange=False, sweep_period=None):
         if not learning_rate >= 0.0 or not 0.0 <= beta_1 < 1.0 or not 0.0 <= beta_2 < 1.0 or not epsilon >= 0.0:
@@ -187,17 +305,6 @@ class Adam(torch.optim.Optimizer):
                     self._attach(p)
 
     # -- state ---------------------------------------------------------------------------------------------------
-    def _counter(self, dev):
-        t = self._t.get(dev)
-        if t is None:
-            t = self._t[dev] = torch.zeros(1, dtype=torch.int64, device=dev)
-        return t
-
-    @property
-    def iterations(self):
-        """Completed steps (Keras' optimizer.iterations), as a host int (synchronises)."""
-        return int(next(iter(self._t.values()))[0]) if self._t else 0
-
     def _moments(self, p):
         st = self.state[p]
         if "m" not in st:
@@ -244,43 +351,7 @@ class Adam(torch.optim.Optimizer):
         for t in self._t.values():
             t.zero_()
 
-    def zero_grad(self, set_to_none=True):
-        super().zero_grad(set_to_none=set_to_none)
-        for g in self.param_groups:
-            for p in g["params"]:
-                if getattr(p, "_fil_pending_runs", None) is not None:
-                    p._fil_pending_runs = None
-
     # -- the step ------------------------------------------------------------------------------------------------
-    def _desc_array(self, dev, entries):
-        key = (dev, tuple(entries))
-        hit = self._descs.get(key)
-        if hit is not None:
-            return hit[0]
-        host = (_Desc * len(entries))(*[_Desc(p, g, m, v, n, l2, 0) for p, g, m, v, n, l2 in entries])
-        size = ctypes.sizeof(host)
-        capturing = torch.cuda.is_current_stream_capturing()
-        if capturing:
-            if self._arena is None or self._arena_off + size > self._arena.numel():
-                raise FilError("optim.Adam: no room for the descriptors of a captured step -- run one eager step before capturing "
-                               "(capture.capture_step's warm-up does)")
-            pinned = self._arena[self._arena_off:self._arena_off + size]
-            self._arena_off += (size + 255) // 256 * 256
-        else:
-            if self._arena is None:
-                self._arena = torch.empty(max(1 << 16, 8 * size), dtype=torch.uint8, pin_memory=True)
-            pinned = torch.empty(size, dtype=torch.uint8, pin_memory=True)
-        ctypes.memmove(pinned.data_ptr(), ctypes.addressof(host), size)
-        d = torch.empty(size, dtype=torch.uint8, device=dev)
-        d.copy_(pinned, non_blocking=True)
-        if capturing:
-            self._pinned.append((d, pinned))
-        else:
-            if len(self._descs) >= 16:
-                self._descs.clear()
-            self._descs[key] = (d, pinned)
-        return d
-
     @torch.no_grad()
     def step(self, closure=None):
         loss = None
@@ -411,59 +482,10 @@ class Adam(torch.optim.Optimizer):
             d.flush()
 
     # -- data parallelism ------------------------------------------------------------------------------------------
-    def _exchange_world(self):
-        """The world size of the runs exchange, or 0 for the one-GPU path (no group of > 1 ranks and no force_exchange)."""
-        if dist.is_available() and dist.is_initialized():
-            world = dist.get_world_size(self.process_group)
-            if world > 1 or self.force_exchange:
-                return world
-            return 0
-        if self.process_group is not None:
-            raise FilError("optim.Adam: a process_group was given but torch.distributed is not initialised")
-        return 1 if self.force_exchange else 0
-
-    def _exchange_buffers(self, p, pend, world):
-        V, K = p.shape
-        R = int(pend["R"])
-        buf = self._xbuf.get(p)
-        if buf is None:
-            dev = p.device
-            if world > 1 or dist.is_initialized():      # one all-reduce MAX of R: every rank's lists get the same capacity
-                r = torch.tensor([R], dtype=torch.int64, device=dev)
-                dist.all_reduce(r, op=dist.ReduceOp.MAX, group=self.process_group)
-                cap = int(r.item())
-            else:
-                cap = R
-            cap = max(cap, 1)
-            lib = _lib.load()
-            ids = torch.empty(cap, dtype=torch.int64, device=dev)
-            values = torch.empty(cap * K, dtype=torch.float32, device=dev)
-            count = torch.zeros(1, dtype=torch.int64, device=dev)
-            ws = torch.empty(max(1, int(lib.fil_embed_runs_compact_workspace_bytes(cap))), dtype=torch.uint8, device=dev)
-            if world > 1 or dist.is_initialized():
-                gathered = (torch.empty(world * cap, dtype=torch.int64, device=dev),
-                            torch.empty(world * cap * K, dtype=torch.float32, device=dev),
-                            torch.empty(world, dtype=torch.int64, device=dev))
-            else:
-                gathered = (ids, values, count)        # no process group (force_exchange): the local list IS the gathered one
-            buf = self._xbuf[p] = dict(cap=cap, ids=ids, values=values, count=count, ws=ws, gathered=gathered)
-        if R > buf["cap"]:
-            raise FilError("optim.Adam: runs record of %d entries > the exchange capacity %d agreed on the first step (the first "
-                           "batch must be the largest)" % (R, buf["cap"]))
-        return buf
-
     def _apply_runs_exchanged(self, lib, p, pend, m, v, t, stamp, mode, world, hyper, st):
-        from . import dp
         lr, b1, b2, eps = hyper
         V, K = p.shape
-        buf = self._exchange_buffers(p, pend, world)
-        cap = buf["cap"]
-        check(lib.fil_embed_runs_compact(ptr(pend["g"]), ptr(pend["perm"]), ptr(pend["sorted_ids"]), pend["R"], K, pend["g_dtype"],
-                                         ptr(buf["ids"]), ptr(buf["values"]), ptr(buf["count"]), cap, ptr(buf["ws"]), buf["ws"].numel(),
-                                         st), "fil_embed_runs_compact")
-        ids, values, counts = buf["gathered"]
-        if ids is not buf["ids"]:
-            dp.exchange_runs(buf["ids"], buf["values"], buf["count"], ids, values, counts, group=self.process_group)
+        ids, values, counts, cap = self._compact_and_exchange(lib, p, pend, world, st)
         if p in self._defer:
             d = self._defer[p]
             offsets, field_l2, frozen, F = d.field_args(p, pend)
@@ -474,6 +496,237 @@ class Adam(torch.optim.Optimizer):
         check(lib.fil_embed_adam_merged(ptr(ids), ptr(values), ptr(counts), world, cap, K, ptr(pend["offsets"]), ptr(pend["field_l2"]),
                                         pend["F"], ptr(p), ptr(m), ptr(v), ptr(stamp), V, ptr(t), lr, b1, b2, eps, mode, st),
               "fil_embed_adam_merged")
+
+
+class _Rowwise(_RunsOptimizer):
+    """Keras' Adagrad and Ftrl (include/fil.h O2): optim.Adam's contract with a row-local rule.  Slots: `accumulator` (filled with
+    initial_accumulator_value) and, for Ftrl, `linear` (zeros).  Dense parameters: one fil_rowopt_multi launch per (group, device);
+    runs tables: fil_embed_rowopt_runs (or, data parallel, fil_embed_runs_compact + dp.exchange_runs + fil_embed_rowopt_merged),
+    then fil_embed_rowopt_sweep over the untouched rows of the regularised fields only.  Row stamps exist only for tables with a
+    regularised field."""
+    _RULE = None
+
+    def __init__(self, params, defaults, process_group, force_exchange):
+        if process_group is not None and not isinstance(process_group, dist.ProcessGroup):
+            raise TypeError("%s: process_group must be a torch.distributed.ProcessGroup or None, not %r" % (self._NAME, process_group))
+        if not isinstance(force_exchange, bool):
+            raise TypeError("%s: force_exchange must be a bool, not %r" % (self._NAME, force_exchange))
+        self._t = {}            # device -> int64 [1] step counter (Keras' iterations)
+        self._stamps = {}       # runs table with a regularised field -> int32 [V] row stamps (valid within one step only)
+        self._descs = {}        # descriptor key -> (device descriptors, pinned host copy)
+        self._pinned = []       # descriptor arrays built during a stream capture (a graph replays them: never dropped)
+        self._arena, self._arena_off = None, 0
+        self._xbuf = {}         # runs table -> buffers of the data-parallel exchange
+        self.process_group = process_group
+        self.force_exchange = force_exchange
+        super().__init__(params, defaults)
+
+    def _hyper(self, group):
+        raise NotImplementedError
+
+    # -- state ---------------------------------------------------------------------------------------------------
+    def _slots(self, p, group):
+        st = self.state[p]
+        if "accumulator" not in st:
+            st["accumulator"] = torch.full_like(p, group["initial_accumulator_value"], memory_format=torch.contiguous_format)
+            if self._RULE == FIL_OPT_FTRL:
+                st["linear"] = torch.zeros_like(p, memory_format=torch.contiguous_format)
+        return st["accumulator"], st.get("linear")
+
+    def state_dict(self):
+        sd = super().state_dict()
+        sd["iterations"] = self.iterations
+        return sd
+
+    def load_state_dict(self, state_dict):
+        state_dict = dict(state_dict)
+        it = int(state_dict.pop("iterations", 0))
+        super().load_state_dict(state_dict)
+        for st in self.state.values():          # (torch's loader may hand non-contiguous copies back)
+            for k in ("accumulator", "linear"):
+                if k in st:
+                    st[k] = st[k].contiguous()
+        for g in self.param_groups:
+            for p in g["params"]:
+                self._counter(p.device)
+        for t in self._t.values():
+            t.fill_(it)
+        for s in self._stamps.values():         # t may go backwards: a stale stamp must never look current
+            s.zero_()
+
+    def reset_(self):
+        """Back to "never stepped" IN PLACE (slots, stamps and counter keep their storage): what a capture's restore needs after
+        warm-up steps (capture.capture_step(..., restore=...))."""
+        for group in self.param_groups:
+            for p in group["params"]:
+                st = self.state.get(p, {})
+                if "accumulator" in st:
+                    st["accumulator"].fill_(group["initial_accumulator_value"])
+                if "linear" in st:
+                    st["linear"].zero_()
+        for s in self._stamps.values():
+            s.zero_()
+        for t in self._t.values():
+            t.zero_()
+
+    # -- the step ------------------------------------------------------------------------------------------------
+    @torch.no_grad()
+    def step(self, closure=None):
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        lib = _lib.load()
+        calls = []      # (device, hyper, entries) of the fil_rowopt_multi launches, in group order
+        for group in self.param_groups:
+            hyper = self._hyper(group)
+            per_dev = {}
+            for p in group["params"]:
+                pend = getattr(p, "_fil_pending_runs", None)
+                if pend is None and p.grad is None:
+                    continue                    # (Keras filters None gradients)
+                if deferred_state(p) is not None:
+                    raise FilError("%s: table %s is in optim.Adam's deferred mode (sweep_period) -- drop that optimizer first"
+                                   % (self._NAME, tuple(p.shape)))
+                if p.device.type != "cuda" or p.dtype != torch.float32 or not p.is_contiguous():
+                    raise FilError("%s: parameter %s %s on %s -- contiguous fp32 GPU tensors only" % (self._NAME, tuple(p.shape), p.dtype,
+                                                                                                   p.device))
+                acc, lin = self._slots(p, group)
+                t = self._counter(p.device)
+                if pend is not None:
+                    if p.grad is not None:
+                        raise FilError("%s: table %s has both a .grad and a pending runs record (a gradient reached the table "
+                                       "outside its gather -- e.g. a regulariser not detached)" % (self._NAME, tuple(p.shape)))
+                    self._apply_runs(lib, p, pend, acc, lin, t, hyper)
+                    p._fil_pending_runs = None
+                    continue
+                g = p.grad
+                if g.is_sparse:
+                    raise FilError("%s: sparse gradient of %s -- use SparseEmbed(grad_mode='runs') for the tables" % (self._NAME,
+                                                                                                                    tuple(p.shape)))
+                if g.dtype != torch.float32 or not g.is_contiguous() or g.shape != p.shape:
+                    raise FilError("%s: gradient of %s must be a dense contiguous fp32 tensor of its shape" % (self._NAME, tuple(p.shape)))
+                per_dev.setdefault(p.device, []).append((p.data_ptr(), g.data_ptr(), acc.data_ptr(), ptr(lin), p.numel(), 0.0))
+            for dev, entries in per_dev.items():
+                calls.append((dev, hyper, entries))
+        # the last launch on every device advances its counter -- one with no tensors where nothing dense had a gradient
+        devs = set(self._t)
+        for g in self.param_groups:
+            for p in g["params"]:
+                if p.device.type == "cuda":
+                    devs.add(p.device)
+        last = {}
+        for i, (dev, _, _) in enumerate(calls):
+            last[dev] = i
+        for dev in devs:
+            if dev not in last:
+                calls.append((dev, self._hyper(self.defaults), []))
+                last[dev] = len(calls) - 1
+        for i, (dev, hyper, entries) in enumerate(calls):
+            with torch.cuda.device(dev):
+                desc = self._desc_array(dev, entries) if entries else None
+                check(lib.fil_rowopt_multi(ptr(desc), len(entries), sum(e[4] for e in entries), ptr(self._counter(dev)), self._RULE,
+                                           ctypes.addressof(hyper), 1 if last[dev] == i else 0, stream_ptr()), "fil_rowopt_multi")
+        return loss
+
+    def _apply_runs(self, lib, p, pend, acc, lin, t, hyper):
+        V, K = p.shape
+        h = ctypes.addressof(hyper)
+        field_l2 = pend["field_l2"]
+        stamp = None
+        if field_l2 is not None:            # a regularised field: its untouched rows move too (the sweep), stamps tell them apart
+            stamp = self._stamps.get(p)
+            if stamp is None:
+                stamp = self._stamps[p] = torch.zeros(V, dtype=torch.int32, device=p.device)
+        with torch.cuda.device(p.device):
+            st = stream_ptr()
+            world = self._exchange_world()
+            if world:
+                ids, values, counts, cap = self._compact_and_exchange(lib, p, pend, world, st)
+                check(lib.fil_embed_rowopt_merged(ptr(ids), ptr(values), ptr(counts), world, cap, K, ptr(pend["offsets"]), ptr(field_l2),
+                                                  pend["F"], ptr(p), ptr(acc), ptr(lin), ptr(stamp), V, ptr(t), self._RULE, h, st),
+                      "fil_embed_rowopt_merged")
+            else:
+                check(lib.fil_embed_rowopt_runs(ptr(pend["g"]), ptr(pend["perm"]), ptr(pend["sorted_ids"]), pend["R"], K, pend["g_dtype"],
+                                                pend["F"], ptr(field_l2), ptr(p), ptr(acc), ptr(lin), ptr(stamp), ptr(t), self._RULE, h,
+                                                st), "fil_embed_rowopt_runs")
+            if field_l2 is not None:
+                check(lib.fil_embed_rowopt_sweep(ptr(p), ptr(acc), ptr(lin), ptr(stamp), V, K, ptr(pend["offsets"]), ptr(field_l2),
+                                                 ptr(pend["frozen"]), pend["F"], ptr(t), self._RULE, h, st), "fil_embed_rowopt_sweep")
+
+
+class Adagrad(_Rowwise):
+    """tf.keras.optimizers.Adagrad (TF 2.1; ApplyAdagradV2): acc += g^2;  p -= lr g / (sqrt(acc) + epsilon), with Keras' defaults
+    (initial_accumulator_value 0.1 and epsilon 1e-7, where torch.optim.Adagrad has 0 and 1e-10).  Dense parameters take the rule
+    on every element; runs tables (SparseEmbed(grad_mode="runs")) take Keras' per-field semantics in place: the batch's rows, plus
+    every other row of a field with l2(emb_reg) > 0 (g = 2 emb_reg p); an untouched row of an unregularised field keeps its bits.
+    A table in "dense" mode is an ordinary dense parameter.  process_group / force_exchange: as optim.Adam's."""
+    _NAME = "optim.Adagrad"
+    _RULE = FIL_OPT_ADAGRAD
+
+    def __init__(self, params, learning_rate=0.001, initial_accumulator_value=0.1, epsilon=1e-7, process_group=None,
+                 force_exchange=False):
+        if epsilon is None:
+            epsilon = 1e-7              # Keras: backend.epsilon()
+        if initial_accumulator_value < 0.0:
+            raise ValueError("initial_accumulator_value must be non-negative: %s" % initial_accumulator_value)
+        if not learning_rate >= 0.0 or not epsilon >= 0.0:
+            raise ValueError("Adagrad: learning_rate=%r epsilon=%r (both >= 0)" % (learning_rate, epsilon))
+        super().__init__(params, dict(learning_rate=float(learning_rate), initial_accumulator_value=float(initial_accumulator_value),
+                                      epsilon=float(epsilon)), process_group, force_exchange)
+
+    def _hyper(self, group):
+        return RowoptHyper(group["learning_rate"], group["epsilon"], 0.0, 0.0, 0.0, 0.0)
+
+
+class Ftrl(_Rowwise):
+    """tf.keras.optimizers.Ftrl (TF 2.1; ApplyFtrl, or ApplyFtrlV2 when l2_shrinkage_regularization_strength > 0), with Keras' names,
+    defaults and checks (TF 2.1 has no `beta`).  Slots: accumulator n (initial_accumulator_value) and linear z (0); the rule is in
+    include/fil.h O2.  Runs tables (SparseEmbed(grad_mode="runs")) take Keras' per-field semantics: the batch's rows, plus every other
+    row of a field with l2(emb_reg) > 0 (g = 2 emb_reg p); every other row and its slots keep their bits -- NOT a dense apply with
+    g = 0, which would recompute p from z and zero every untouched row.  Keras' quirk, reproduced: the first step takes the untouched
+    rows of a regularised field to about -lr 2 emb_reg p / sqrt(n), in effect 0 (make_sparse_info's default emb_reg is 1e-8).
+    Everything with a dense .grad -- a tableGrad="dense" table included -- takes the rule on every element: for such a table that is
+    Keras' dense semantics, not its IndexedSlices ones; the exact Keras behaviour of unregularised fields needs tableGrad="runs".
+    process_group / force_exchange: as optim.Adam's."""
+    _NAME = "optim.Ftrl"
+    _RULE = FIL_OPT_FTRL
+
+    def __init__(self, params, learning_rate=0.001, learning_rate_power=-0.5, initial_accumulator_value=0.1,
+                 l1_regularization_strength=0.0, l2_regularization_strength=0.0, l2_shrinkage_regularization_strength=0.0,
+                 process_group=None, force_exchange=False):
+        if initial_accumulator_value < 0.0:
+            raise ValueError("initial_accumulator_value %f needs to be positive or zero" % initial_accumulator_value)
+        if learning_rate_power > 0.0:
+            raise ValueError("learning_rate_power %f needs to be negative or zero" % learning_rate_power)
+        if l1_regularization_strength < 0.0:
+            raise ValueError("l1_regularization_strength %f needs to be positive or zero" % l1_regularization_strength)
+        if l2_regularization_strength < 0.0:
+            raise ValueError("l2_regularization_strength %f needs to be positive or zero" % l2_regularization_strength)
+        if l2_shrinkage_regularization_strength < 0.0:
+            raise ValueError("l2_shrinkage_regularization_strength %f needs to be positive or zero"
+                             % l2_shrinkage_regularization_strength)
+        if not learning_rate >= 0.0:
+            raise ValueError("Ftrl: learning_rate=%r (>= 0)" % (learning_rate,))
+        super().__init__(params, dict(learning_rate=float(learning_rate), learning_rate_power=float(learning_rate_power),
+                                      initial_accumulator_value=float(initial_accumulator_value),
+                                      l1_regularization_strength=float(l1_regularization_strength),
+                                      l2_regularization_strength=float(l2_regularization_strength),
+                                      l2_shrinkage_regularization_strength=float(l2_shrinkage_regularization_strength)),
+                         process_group, force_exchange)
+
+    def _hyper(self, group):
+        return RowoptHyper(group["learning_rate"], 0.0, group["learning_rate_power"], group["l1_regularization_strength"],
+                           group["l2_regularization_strength"], group["l2_shrinkage_regularization_strength"])
+
+
+def rowopt_merged(rule, ids, values, counts, W, cap, offsets, field_l2, table, accum, linear, stamp, step, hyper):
+    """fil_embed_rowopt_merged on W gathered lists (ids [W*cap], values [W*cap*K], counts [W]); table / accum / linear [V, K] in
+    place; rule FIL_OPT_ADAGRAD or FIL_OPT_FTRL, hyper an _lib.RowoptHyper."""
+    V, K = table.shape
+    check(_lib.load().fil_embed_rowopt_merged(ptr(ids), ptr(values), ptr(counts), int(W), int(cap), K, ptr(offsets), ptr(field_l2),
+                                              offsets.numel(), ptr(table), ptr(accum), ptr(linear), ptr(stamp), V, ptr(step), int(rule),
+                                              ctypes.addressof(hyper), stream_ptr()), "fil_embed_rowopt_merged")
 
 
 def runs_compact_workspace_bytes(R):
