@@ -37,67 +37,54 @@ __device__ __forceinline__ AdamCoef adam_coef(const int64_t* step, float lr, flo
   return c;
 }
 
-// one element of ApplyAdam (Eigen's order of operations)
+// The embedding-table kernels, Keras mode and deferred mode alike, update a row through the two helpers below and nothing else: one
+// definition of each update's rounding, written with contraction off and explicit fmas, so the deferred replays give the Keras-mode
+// bits by construction, whatever the compiler makes of each kernel's context.
+//
+// the untouched-row update of the sweep (g = 2 l2[f] p); fused_m: its 16-byte path (K % 4 == 0, 16-byte aligned arrays) rounds
+// m += (g - m)(1 - b1) as one fma, its element path rounds the product first
+template <bool fused_m>
+__device__ __forceinline__ void adam_untouched(float& p, float& m, float& v, float l2x2, const AdamCoef& c) {
+#pragma clang fp contract(off)
+  const float g = l2x2 * p;
+  const float d = __builtin_fmaf(l2x2, p, -m);
+  const float gg = __builtin_fmaf(g, g, -v);
+  m = fused_m ? __builtin_fmaf(c.omb1, d, m) : m + c.omb1 * d;
+  v = __builtin_fmaf(c.omb2, gg, v);
+  p = p - (m * c.alpha) / (sqrtf(v) + c.eps);
+}
+
+// the touched-row update of the runs and merged kernels: g = (run sum) + 2 l2 p
+__device__ __forceinline__ void adam_touched(float& p, float& m, float& v, float acc, float l2x2, const AdamCoef& c) {
+#pragma clang fp contract(off)
+  const float g = __builtin_fmaf(l2x2, p, acc);
+  const float d = g - m;
+  const float gg = __builtin_fmaf(g, g, -v);
+  m = m + c.omb1 * d;
+  v = __builtin_fmaf(c.omb2, gg, v);
+  p = p - (m * c.alpha) / (sqrtf(v) + c.eps);
+}
+
+// one element of ApplyAdam (Eigen's order of operations), left to the compiler's contraction: fil_adam_multi only, whose dense
+// tensors nothing replays
 __device__ __forceinline__ void adam_elem(float& p, float& m, float& v, float g, const AdamCoef& c) {
   m += (g - m) * c.omb1;
   v += (g * g - v) * c.omb2;
   p -= (m * c.alpha) / (sqrtf(v) + c.eps);
 }
 
-__global__ void adam_step_advance_kernel(int64_t* step) { *step += 1; }
+__global__ void step_advance_kernel(int64_t* step) { *step += 1; }
 
-// ---- fil_adam_multi: the descriptors' elements form one index space of 1024-element chunks (a workgroup's 256 lanes x 4), dealt
-// round robin over the grid; a workgroup walks the descriptor list once and takes its chunks of each (grid-stride, balanced over
-// tensors of any size)
-constexpr int kMultiChunk = 1024;
+void launch_step_advance(int64_t* step, hipStream_t st) { hipLaunchKernelGGL(step_advance_kernel, dim3(1), dim3(1), 0, st, step); }
 
+// ---- fil_adam_multi: the dense descriptors (multi_tensor_walk, optim_rows.h), g += 2 l2 p where l2 is set
 __global__ __launch_bounds__(256) void adam_multi_kernel(const fil_adam_tensor* __restrict__ ts, int n, const int64_t* __restrict__ step,
                                                          float lr, float b1, float b2, float eps) {
   const AdamCoef c = adam_coef(step, lr, b1, b2, eps);
-  const long G = gridDim.x;
-  long base = 0;
-  for (int d = 0; d < n; ++d) {
-    float* __restrict__ P = ts[d].param;
-    const float* __restrict__ Gr = ts[d].grad;
-    float* __restrict__ M = ts[d].m;
-    float* __restrict__ V = ts[d].v;
-    const long numel = ts[d].numel;
-    const float l2x2 = 2.f * ts[d].l2;
-    const long nc = (numel + kMultiChunk - 1) / kMultiChunk;
-    const bool vec = ((((uintptr_t)P | (uintptr_t)Gr | (uintptr_t)M | (uintptr_t)V) & 15) == 0);
-    long r = ((long)blockIdx.x - base) % G;
-    if (r < 0) r += G;
-    for (long ch = r; ch < nc; ch += G) {
-      const long e = ch * kMultiChunk + threadIdx.x * 4;
-      if (vec && e + 4 <= numel) {
-        float4 p = *reinterpret_cast<const float4*>(P + e);
-        float4 g = Gr ? *reinterpret_cast<const float4*>(Gr + e) : make_float4(0.f, 0.f, 0.f, 0.f);
-        float4 m = *reinterpret_cast<const float4*>(M + e);
-        float4 v = *reinterpret_cast<const float4*>(V + e);
-        if (l2x2 != 0.f) {
-          g.x += l2x2 * p.x; g.y += l2x2 * p.y; g.z += l2x2 * p.z; g.w += l2x2 * p.w;
-        }
-        adam_elem(p.x, m.x, v.x, g.x, c);
-        adam_elem(p.y, m.y, v.y, g.y, c);
-        adam_elem(p.z, m.z, v.z, g.z, c);
-        adam_elem(p.w, m.w, v.w, g.w, c);
-        *reinterpret_cast<float4*>(P + e) = p;
-        *reinterpret_cast<float4*>(M + e) = m;
-        *reinterpret_cast<float4*>(V + e) = v;
-      } else {
-        for (long i = e; i < e + 4 && i < numel; ++i) {
-          float p = P[i], m = M[i], v = V[i];
-          float g = Gr ? Gr[i] : 0.f;
-          if (l2x2 != 0.f) g += l2x2 * p;
-          adam_elem(p, m, v, g, c);
-          P[i] = p;
-          M[i] = m;
-          V[i] = v;
-        }
-      }
-    }
-    base += nc;
-  }
+  multi_tensor_walk<true>(ts, n, [=](float& p, float& m, float& v, float g, float l2x2) {
+    if (l2x2 != 0.f) g += l2x2 * p;
+    adam_elem(p, m, v, g, c);
+  });
 }
 
 // ---- fil_embed_adam_runs: the run sums of embed_runs.h with an Adam epilogue.  Row `row` of field f = perm % F takes
@@ -117,7 +104,7 @@ __global__ __launch_bounds__(256) void embed_adam_runs_kernel(const GT* __restri
       if (kq * 4 + i < K) {
         const int64_t e = row * K + kq * 4 + i;
         float p = table[e], mm = m[e], vv = v[e];
-        adam_elem(p, mm, vv, acc[i] + l2x2 * p, c);
+        adam_touched(p, mm, vv, acc[i], l2x2, c);
         table[e] = p;
         m[e] = mm;
         v[e] = vv;
@@ -160,7 +147,7 @@ __global__ __launch_bounds__(256) void embed_adam_sweep_kernel(float* __restrict
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
         float pi = p[i], mi = mm[i], vi = vv[i];
-        adam_elem(pi, mi, vi, l2x2 * pi, c);
+        adam_untouched<true>(pi, mi, vi, l2x2, c);
         p[i] = pi;
         mm[i] = mi;
         vv[i] = vi;
@@ -178,7 +165,7 @@ __global__ __launch_bounds__(256) void embed_adam_sweep_kernel(float* __restrict
     const float l2x2 = f >= 0 ? s_l2x2[f] : 0.f;
     if (l2x2 != l2x2) continue;
     float p = table[e], mm = m[e], vv = v[e];
-    adam_elem(p, mm, vv, l2x2 * p, c);
+    adam_untouched<false>(p, mm, vv, l2x2, c);
     __builtin_nontemporal_store(p, table + e);
     __builtin_nontemporal_store(mm, m + e);
     __builtin_nontemporal_store(vv, v + e);
@@ -281,12 +268,8 @@ __global__ __launch_bounds__(256) void runs_compact_sums_kernel(const GT* __rest
   });
 }
 
-// ---- fil_embed_adam_merged: one lane per gathered entry (w, i).  The lowest list holding a row owns it; the owner adds the other
-// lists' copies in list order (binary searches: each list is ascending and distinct), adds the field's l2 term and updates the row
-// exactly as embed_adam_runs_kernel does.  K is walked in chunks of kMergeChunk elements (a later chunk repeats the searches).
-// (find_row / list_count: optim_rows.h)
-constexpr int kMergeChunk = 16;
-
+// ---- fil_embed_adam_merged: the merged walk of the gathered lists (merged_row_sums, optim_rows.h); the owner of a row adds the
+// field's l2 term and updates the row exactly as embed_adam_runs_kernel does.
 __global__ __launch_bounds__(256) void embed_adam_merged_kernel(const int64_t* __restrict__ ids, const float* __restrict__ values,
                                                                 const int64_t* __restrict__ counts, int W, long cap, int K,
                                                                 const int64_t* __restrict__ offsets, const float* __restrict__ field_l2,
@@ -298,45 +281,21 @@ __global__ __launch_bounds__(256) void embed_adam_merged_kernel(const int64_t* _
   __syncthreads();
   const AdamCoef c = adam_coef(step, lr, b1, b2, eps);
   const int32_t tag = (int32_t)(uint32_t)(*step + 1);
-  const long n = (long)W * cap;
-  for (long q = (long)blockIdx.x * blockDim.x + threadIdx.x; q < n; q += (long)gridDim.x * blockDim.x) {
-    const int w = (int)(q / cap);
-    const long i = q - (long)w * cap;
-    if (i >= list_count(counts, w, cap)) continue;
-    const int64_t row = ids[q];
-    if (row < 0 || row >= V) continue;
-    bool owner = true;
-    for (int w2 = 0; w2 < w && owner; ++w2) owner = find_row(ids + (long)w2 * cap, list_count(counts, w2, cap), row) < 0;
-    if (!owner) continue;
-    const int f = sweep_field(s_off, F, row);
-    const float l2x2 = (field_l2 && f >= 0) ? 2.f * field_l2[f] : 0.f;
-    for (int k0 = 0; k0 < K; k0 += kMergeChunk) {
-      float acc[kMergeChunk];
-      const float* src = values + q * K + k0;
+  const auto epi = [=](int64_t row, int f, float l2x2, int k0, const float (&acc)[kMergeChunk]) {
 #pragma unroll
-      for (int e = 0; e < kMergeChunk; ++e) acc[e] = k0 + e < K ? src[e] : 0.f;
-      for (int w2 = w + 1; w2 < W; ++w2) {
-        const long at = find_row(ids + (long)w2 * cap, list_count(counts, w2, cap), row);
-        if (at < 0) continue;
-        const float* o = values + ((long)w2 * cap + at) * K + k0;
-#pragma unroll
-        for (int e = 0; e < kMergeChunk; ++e)
-          if (k0 + e < K) acc[e] += o[e];
-      }
-#pragma unroll
-      for (int e = 0; e < kMergeChunk; ++e) {
-        if (k0 + e < K) {
-          const int64_t x = row * K + k0 + e;
-          float p = table[x], mm = m[x], vv = v[x];
-          adam_elem(p, mm, vv, acc[e] + l2x2 * p, c);
-          table[x] = p;
-          m[x] = mm;
-          v[x] = vv;
-        }
+    for (int e = 0; e < kMergeChunk; ++e) {
+      if (k0 + e < K) {
+        const int64_t x = row * K + k0 + e;
+        float p = table[x], mm = m[x], vv = v[x];
+        adam_touched(p, mm, vv, acc[e], l2x2, c);
+        table[x] = p;
+        m[x] = mm;
+        v[x] = vv;
       }
     }
-    if (stamp) stamp[row] = tag;
-  }
+  };
+  merged_row_sums((long)blockIdx.x * blockDim.x + threadIdx.x, (long)gridDim.x * blockDim.x, ids, values, counts, W, cap, K, V, s_off,
+                  field_l2, F, epi, [=](int64_t row) { if (stamp) stamp[row] = tag; });
 }
 
 // ==== Deferred mode (optim.Adam(sweep_period=N)).  A row the batch did not touch takes g = 2 l2 p: an update that depends
@@ -349,35 +308,7 @@ __global__ __launch_bounds__(256) void embed_adam_merged_kernel(const int64_t* _
 // behind: every replay reads at most the N newest entries, and D >= N + 1 keeps the entry being written out of their way.
 constexpr int kRingMax = 1024;                 // D <= 1024 (the roll keeps the ring in LDS): sweep_period <= 1023
 
-// The replay must give the bits that the Keras-mode kernels give, and those depend on how -ffp-contract fused adam_elem in each
-// context: in fil_embed_adam_sweep's 16-byte path m += (g - m)(1 - b1) became one fma, in its element path (and in the run and merged
-// updates) the SLP vectoriser paired the add with sqrt(v) + eps, so the product is rounded first.  The two helpers below spell out
-// those operations with contraction off and explicit fmas (checked against the gfx950 ISA of the Keras-mode kernels), so the
-// deferred kernels round exactly as they do whatever the compiler makes of their own context.
-//
-// the untouched-row update of the sweep (g = 2 l2[f] p); fused_m: its 16-byte path (K % 4 == 0, 16-byte aligned arrays)
-template <bool fused_m>
-__device__ __forceinline__ void adam_untouched(float& p, float& m, float& v, float l2x2, const AdamCoef& c) {
-#pragma clang fp contract(off)
-  const float g = l2x2 * p;
-  const float d = __builtin_fmaf(l2x2, p, -m);
-  const float gg = __builtin_fmaf(g, g, -v);
-  m = fused_m ? __builtin_fmaf(c.omb1, d, m) : m + c.omb1 * d;
-  v = __builtin_fmaf(c.omb2, gg, v);
-  p = p - (m * c.alpha) / (sqrtf(v) + c.eps);
-}
-
-// the touched-row update of fil_embed_adam_runs / fil_embed_adam_merged: g = (run sum) + 2 l2 p
-__device__ __forceinline__ void adam_touched(float& p, float& m, float& v, float acc, float l2x2, const AdamCoef& c) {
-#pragma clang fp contract(off)
-  const float g = __builtin_fmaf(l2x2, p, acc);
-  const float d = g - m;
-  const float gg = __builtin_fmaf(g, g, -v);
-  m = m + c.omb1 * d;
-  v = __builtin_fmaf(c.omb2, gg, v);
-  p = p - (m * c.alpha) / (sqrtf(v) + c.eps);
-}
-
+// The replays go through adam_untouched, the sweep's own update (above): a replayed step rounds as the sweep would have rounded it.
 __device__ __forceinline__ bool coef_is_skip(const AdamCoef& c) { return c.omb1 != c.omb1; }   // (1 - beta_1 is never NaN)
 
 __device__ __forceinline__ AdamCoef coef_skip() {
@@ -543,50 +474,27 @@ __global__ __launch_bounds__(256) void embed_adam_merged_deferred_kernel(const i
   __shared__ FieldTab s;
   load_field_tab(&s, offsets, field_l2, frozen, F);
   __syncthreads();
+  const FieldTab* sp = &s;
   const AdamCoef c = adam_coef(step, lr, b1, b2, eps);
   const int32_t done = (int32_t)(uint32_t)(*step);
-  const long n = (long)W * cap;
-  for (long q = (long)blockIdx.x * blockDim.x + threadIdx.x; q < n; q += (long)gridDim.x * blockDim.x) {
-    const int w = (int)(q / cap);
-    const long i = q - (long)w * cap;
-    if (i >= list_count(counts, w, cap)) continue;
-    const int64_t row = ids[q];
-    if (row < 0 || row >= V) continue;
-    bool owner = true;
-    for (int w2 = 0; w2 < w && owner; ++w2) owner = find_row(ids + (long)w2 * cap, list_count(counts, w2, cap), row) < 0;
-    if (!owner) continue;
-    const int f = sweep_field(s.off, F, row);
-    const float l2x2 = (field_l2 && f >= 0) ? 2.f * field_l2[f] : 0.f;
-    const float r2 = f >= 0 ? s.l2x2[f] : 0.f;
-    const int32_t from = r2 == r2 ? replay_from(stamp[row], done, N) : done;
-    for (int k0 = 0; k0 < K; k0 += kMergeChunk) {
-      float acc[kMergeChunk];
-      const float* src = values + q * K + k0;
+  const auto epi = [=](int64_t row, int f, float l2x2, int k0, const float (&acc)[kMergeChunk]) {
+    const float r2 = f >= 0 ? sp->l2x2[f] : 0.f;
+    const int32_t from = r2 == r2 ? replay_from(stamp[row], done, N) : done;     // (the stamp moves after the last chunk only)
 #pragma unroll
-      for (int e = 0; e < kMergeChunk; ++e) acc[e] = k0 + e < K ? src[e] : 0.f;
-      for (int w2 = w + 1; w2 < W; ++w2) {
-        const long at = find_row(ids + (long)w2 * cap, list_count(counts, w2, cap), row);
-        if (at < 0) continue;
-        const float* o = values + ((long)w2 * cap + at) * K + k0;
-#pragma unroll
-        for (int e = 0; e < kMergeChunk; ++e)
-          if (k0 + e < K) acc[e] += o[e];
-      }
-#pragma unroll
-      for (int e = 0; e < kMergeChunk; ++e) {
-        if (k0 + e < K) {
-          const int64_t x = row * K + k0 + e;
-          float p[1] = {table[x]}, mm[1] = {m[x]}, vv[1] = {v[x]};
-          replay<1>(p, mm, vv, r2, from, done, ring, D, vec);
-          adam_touched(p[0], mm[0], vv[0], acc[e], l2x2, c);
-          table[x] = p[0];
-          m[x] = mm[0];
-          v[x] = vv[0];
-        }
+    for (int e = 0; e < kMergeChunk; ++e) {
+      if (k0 + e < K) {
+        const int64_t x = row * K + k0 + e;
+        float p[1] = {table[x]}, mm[1] = {m[x]}, vv[1] = {v[x]};
+        replay<1>(p, mm, vv, r2, from, done, ring, D, vec);
+        adam_touched(p[0], mm[0], vv[0], acc[e], l2x2, c);
+        table[x] = p[0];
+        m[x] = mm[0];
+        v[x] = vv[0];
       }
     }
-    stamp[row] = done + 1;
-  }
+  };
+  merged_row_sums((long)blockIdx.x * blockDim.x + threadIdx.x, (long)gridDim.x * blockDim.x, ids, values, counts, W, cap, K, V, s.off,
+                  field_l2, F, epi, [=](int64_t row) { stamp[row] = done + 1; });
 }
 
 // ---- fil_embed_adam_roll: step t's ring entry (or the skip entry), then slice t mod N of ceil(V/N) rows brought current through
@@ -769,7 +677,7 @@ extern "C" int fil_adam_multi(const fil_adam_tensor* tensors, int n, int64_t tot
     FIL_CHECK_LAUNCH();
   }
   if (advance) {
-    hipLaunchKernelGGL(adam_step_advance_kernel, dim3(1), dim3(1), 0, st, step);
+    launch_step_advance(step, st);
     FIL_CHECK_LAUNCH();
   }
   return FIL_OK;

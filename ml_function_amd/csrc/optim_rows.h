@@ -1,5 +1,6 @@
-// Row helpers shared by the table optimizers of optim.hip (Adam) and optim_rowwise.hip (Adagrad, Ftrl): the field of a row, and the
-// look-ups into the gathered compact lists of fil_embed_runs_compact.
+// What the fused optimizers of optim.hip (Adam) and optim_rowwise.hip (Adagrad, Ftrl) share: the walk of the dense descriptors
+// (fil_adam_multi, fil_rowopt_multi), the field of a row, and the walk of the gathered compact lists of fil_embed_runs_compact
+// (the merged updates).  Each rule supplies only its per-element update.
 #pragma once
 #include "common.h"
 
@@ -33,6 +34,108 @@ __device__ __forceinline__ long find_row(const int64_t* __restrict__ list, long 
 __device__ __forceinline__ long list_count(const int64_t* counts, int w, long cap) {
   const int64_t c = counts[w];
   return c < 0 ? 0 : (c > cap ? cap : (long)c);
+}
+
+// the position of `row` in gathered list w2 (the lists of fil_embed_runs_compact, cap entries each, side by side in ids), or -1
+__device__ __forceinline__ long find_in_list(const int64_t* __restrict__ ids, const int64_t* counts, int w2, long cap, int64_t row) {
+  return find_row(ids + (long)w2 * cap, list_count(counts, w2, cap), row);
+}
+
+// ---- the dense launch: the descriptors' elements form one index space of kMultiChunk-element chunks (a workgroup's 256 lanes x 4),
+// dealt round robin over the grid; a workgroup walks the descriptor list once and takes its chunks of each (grid-stride, balanced
+// over tensors of any size).  16-byte accesses where the descriptor's arrays allow it (`v` only counts when the rule has it: kV),
+// element-wise otherwise and in the tail.  elem(p, m, v, g, l2x2) updates one element: g the gradient (0 without one), l2x2 = 2 l2
+// of the descriptor.
+constexpr int kMultiChunk = 1024;
+
+template <bool kV, typename Elem>
+__device__ __forceinline__ void multi_tensor_walk(const fil_adam_tensor* __restrict__ ts, int n, const Elem& elem) {
+  const long G = gridDim.x;
+  long base = 0;
+  for (int d = 0; d < n; ++d) {
+    float* __restrict__ P = ts[d].param;
+    const float* __restrict__ Gr = ts[d].grad;
+    float* __restrict__ M = ts[d].m;
+    float* __restrict__ V = ts[d].v;
+    const long numel = ts[d].numel;
+    const float l2x2 = 2.f * ts[d].l2;
+    const long nc = (numel + kMultiChunk - 1) / kMultiChunk;
+    const bool vec = ((((uintptr_t)P | (uintptr_t)Gr | (uintptr_t)M | (kV ? (uintptr_t)V : 0)) & 15) == 0);
+    long r = ((long)blockIdx.x - base) % G;
+    if (r < 0) r += G;
+    for (long ch = r; ch < nc; ch += G) {
+      const long e = ch * kMultiChunk + threadIdx.x * 4;
+      if (vec && e + 4 <= numel) {
+        float4 p = *reinterpret_cast<const float4*>(P + e);
+        float4 g = Gr ? *reinterpret_cast<const float4*>(Gr + e) : make_float4(0.f, 0.f, 0.f, 0.f);
+        float4 m = *reinterpret_cast<const float4*>(M + e);
+        float4 v = kV ? *reinterpret_cast<const float4*>(V + e) : make_float4(0.f, 0.f, 0.f, 0.f);
+        elem(p.x, m.x, v.x, g.x, l2x2);
+        elem(p.y, m.y, v.y, g.y, l2x2);
+        elem(p.z, m.z, v.z, g.z, l2x2);
+        elem(p.w, m.w, v.w, g.w, l2x2);
+        *reinterpret_cast<float4*>(P + e) = p;
+        *reinterpret_cast<float4*>(M + e) = m;
+        if (kV) *reinterpret_cast<float4*>(V + e) = v;
+      } else {
+        for (long i = e; i < e + 4 && i < numel; ++i) {
+          float p = P[i], m = M[i], v = kV ? V[i] : 0.f;
+          elem(p, m, v, Gr ? Gr[i] : 0.f, l2x2);
+          P[i] = p;
+          M[i] = m;
+          if (kV) V[i] = v;
+        }
+      }
+    }
+    base += nc;
+  }
+}
+
+// launches the one-thread kernel that advances a device step counter behind the dense update (defined once, in optim.hip)
+void launch_step_advance(int64_t* step, hipStream_t st);
+
+// ---- the merged update of W gathered lists: one lane per gathered entry q = (w, i), q0 + k stride (the kernel's grid stride: read
+// there, where blockDim folds to the launch bounds).  The lowest list holding a row owns it; rows outside [0, V) are skipped.  The
+// owner adds the other lists' copies in list order (binary searches: each list is ascending and distinct), K in chunks of
+// kMergeChunk elements (a later chunk repeats the searches), and hands each chunk to epi(row, f, l2x2, k0, acc): f the row's field
+// (sweep_field of the offsets s_off, -1 before the first), l2x2 = 2 field_l2[f] (0 without), acc[e] element k0 + e of the summed
+// row (0 past K).  fin(row) follows the row's last chunk.
+constexpr int kMergeChunk = 16;
+
+template <typename Epi, typename Fin>
+__device__ __forceinline__ void merged_row_sums(long q0, long stride, const int64_t* __restrict__ ids, const float* __restrict__ values,
+                                                const int64_t* __restrict__ counts, int W, long cap, int K, int64_t V,
+                                                const int64_t* s_off, const float* __restrict__ field_l2, int F, const Epi& epi,
+                                                const Fin& fin) {
+  const long n = (long)W * cap;
+  for (long q = q0; q < n; q += stride) {
+    const int w = (int)(q / cap);
+    const long i = q - (long)w * cap;
+    if (i >= list_count(counts, w, cap)) continue;
+    const int64_t row = ids[q];
+    if (row < 0 || row >= V) continue;
+    bool owner = true;
+    for (int w2 = 0; w2 < w && owner; ++w2) owner = find_in_list(ids, counts, w2, cap, row) < 0;
+    if (!owner) continue;
+    const int f = sweep_field(s_off, F, row);
+    const float l2x2 = (field_l2 && f >= 0) ? 2.f * field_l2[f] : 0.f;
+    for (int k0 = 0; k0 < K; k0 += kMergeChunk) {
+      float acc[kMergeChunk];
+      const float* src = values + q * K + k0;
+#pragma unroll
+      for (int e = 0; e < kMergeChunk; ++e) acc[e] = k0 + e < K ? src[e] : 0.f;
+      for (int w2 = w + 1; w2 < W; ++w2) {
+        const long at = find_in_list(ids, counts, w2, cap, row);
+        if (at < 0) continue;
+        const float* o = values + ((long)w2 * cap + at) * K + k0;
+#pragma unroll
+        for (int e = 0; e < kMergeChunk; ++e)
+          if (k0 + e < K) acc[e] += o[e];
+      }
+      epi(row, f, l2x2, k0, acc);
+    }
+    fin(row);
+  }
 }
 
 }  // namespace fil

@@ -59,58 +59,13 @@ __device__ __forceinline__ void rule_elem(float& p, float& s, float& z, float g,
   }
 }
 
-__global__ void rowopt_step_advance_kernel(int64_t* step) { *step += 1; }
-
-// ---- fil_rowopt_multi: adam_multi_kernel's layout -- the descriptors' elements in 1024-element chunks dealt round robin over the
-// grid; 16-byte accesses where the descriptor's arrays allow, element-wise otherwise and in the tail
-constexpr int kRowMultiChunk = 1024;
-
+// ---- fil_rowopt_multi: the dense descriptors (multi_tensor_walk, optim_rows.h) with the rule; Ftrl's linear slot (`v`) joins the
+// 16-byte alignment test, Adagrad has none
 template <int RULE>
 __global__ __launch_bounds__(256) void rowopt_multi_kernel(const fil_adam_tensor* __restrict__ ts, int n, RowHyper h) {
-  constexpr bool kZ = RULE == FIL_OPT_FTRL;
-  const long G = gridDim.x;
-  long base = 0;
-  for (int d = 0; d < n; ++d) {
-    float* __restrict__ P = ts[d].param;
-    const float* __restrict__ Gr = ts[d].grad;
-    float* __restrict__ S = ts[d].m;
-    float* __restrict__ Z = ts[d].v;
-    const long numel = ts[d].numel;
-    const float l2x2 = 2.f * ts[d].l2;
-    const long nc = (numel + kRowMultiChunk - 1) / kRowMultiChunk;
-    const bool vec = ((((uintptr_t)P | (uintptr_t)Gr | (uintptr_t)S | (kZ ? (uintptr_t)Z : 0)) & 15) == 0);
-    long r = ((long)blockIdx.x - base) % G;
-    if (r < 0) r += G;
-    for (long ch = r; ch < nc; ch += G) {
-      const long e = ch * kRowMultiChunk + threadIdx.x * 4;
-      if (vec && e + 4 <= numel) {
-        f32x4 p = *reinterpret_cast<const f32x4*>(P + e);
-        const f32x4 g = Gr ? *reinterpret_cast<const f32x4*>(Gr + e) : f32x4{0.f, 0.f, 0.f, 0.f};
-        f32x4 s = *reinterpret_cast<const f32x4*>(S + e);
-        f32x4 z = kZ ? *reinterpret_cast<const f32x4*>(Z + e) : f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          float pi = p[i], si = s[i], zi = z[i];
-          rule_elem<RULE>(pi, si, zi, with_l2(g[i], l2x2, pi), h);
-          p[i] = pi;
-          s[i] = si;
-          z[i] = zi;
-        }
-        *reinterpret_cast<f32x4*>(P + e) = p;
-        *reinterpret_cast<f32x4*>(S + e) = s;
-        if (kZ) *reinterpret_cast<f32x4*>(Z + e) = z;
-      } else {
-        for (long i = e; i < e + 4 && i < numel; ++i) {
-          float p = P[i], s = S[i], z = kZ ? Z[i] : 0.f;
-          rule_elem<RULE>(p, s, z, with_l2(Gr ? Gr[i] : 0.f, l2x2, p), h);
-          P[i] = p;
-          S[i] = s;
-          if (kZ) Z[i] = z;
-        }
-      }
-    }
-    base += nc;
-  }
+  multi_tensor_walk<RULE == FIL_OPT_FTRL>(ts, n, [=](float& p, float& s, float& z, float g, float l2x2) {
+    rule_elem<RULE>(p, s, z, with_l2(g, l2x2, p), h);
+  });
 }
 
 // one row's K elements (this lane's quad kq) with g = acc + 2 l2 p
@@ -279,10 +234,7 @@ __global__ __launch_bounds__(256) void embed_rowopt_sweep_kernel(float* __restri
   }
 }
 
-// ---- fil_embed_rowopt_merged: embed_adam_merged_kernel with the rule -- one lane per gathered entry (w, i); the lowest list holding
-// a row owns it and adds the other lists' copies in list order; K in chunks of kRowMergeChunk elements.
-constexpr int kRowMergeChunk = 16;
-
+// ---- fil_embed_rowopt_merged: the merged walk of the gathered lists (merged_row_sums, optim_rows.h) with the rule
 template <int RULE>
 __global__ __launch_bounds__(256) void embed_rowopt_merged_kernel(const int64_t* __restrict__ ids, const float* __restrict__ values,
                                                                   const int64_t* __restrict__ counts, int W, long cap, int K,
@@ -294,45 +246,21 @@ __global__ __launch_bounds__(256) void embed_rowopt_merged_kernel(const int64_t*
   for (int f = threadIdx.x; f < F; f += blockDim.x) s_off[f] = offsets[f];
   __syncthreads();
   const int32_t tag = stamp ? (int32_t)(uint32_t)(*step + 1) : 0;
-  const long n = (long)W * cap;
-  for (long q = (long)blockIdx.x * blockDim.x + threadIdx.x; q < n; q += (long)gridDim.x * blockDim.x) {
-    const int w = (int)(q / cap);
-    const long i = q - (long)w * cap;
-    if (i >= list_count(counts, w, cap)) continue;
-    const int64_t row = ids[q];
-    if (row < 0 || row >= V) continue;
-    bool owner = true;
-    for (int w2 = 0; w2 < w && owner; ++w2) owner = find_row(ids + (long)w2 * cap, list_count(counts, w2, cap), row) < 0;
-    if (!owner) continue;
-    const int f = sweep_field(s_off, F, row);
-    const float l2x2 = (field_l2 && f >= 0) ? 2.f * field_l2[f] : 0.f;
-    for (int k0 = 0; k0 < K; k0 += kRowMergeChunk) {
-      float acc[kRowMergeChunk];
-      const float* src = values + q * K + k0;
+  const auto epi = [=](int64_t row, int f, float l2x2, int k0, const float (&acc)[kMergeChunk]) {
 #pragma unroll
-      for (int e = 0; e < kRowMergeChunk; ++e) acc[e] = k0 + e < K ? src[e] : 0.f;
-      for (int w2 = w + 1; w2 < W; ++w2) {
-        const long at = find_row(ids + (long)w2 * cap, list_count(counts, w2, cap), row);
-        if (at < 0) continue;
-        const float* o = values + ((long)w2 * cap + at) * K + k0;
-#pragma unroll
-        for (int e = 0; e < kRowMergeChunk; ++e)
-          if (k0 + e < K) acc[e] += o[e];
-      }
-#pragma unroll
-      for (int e = 0; e < kRowMergeChunk; ++e) {
-        if (k0 + e < K) {
-          const int64_t x = row * K + k0 + e;
-          float p = table[x], s = S[x], z = RULE == FIL_OPT_FTRL ? Z[x] : 0.f;
-          rule_elem<RULE>(p, s, z, with_l2(acc[e], l2x2, p), h);
-          table[x] = p;
-          S[x] = s;
-          if (RULE == FIL_OPT_FTRL) Z[x] = z;
-        }
+    for (int e = 0; e < kMergeChunk; ++e) {
+      if (k0 + e < K) {
+        const int64_t x = row * K + k0 + e;
+        float p = table[x], s = S[x], z = RULE == FIL_OPT_FTRL ? Z[x] : 0.f;
+        rule_elem<RULE>(p, s, z, with_l2(acc[e], l2x2, p), h);
+        table[x] = p;
+        S[x] = s;
+        if (RULE == FIL_OPT_FTRL) Z[x] = z;
       }
     }
-    if (stamp) stamp[row] = tag;
-  }
+  };
+  merged_row_sums((long)blockIdx.x * blockDim.x + threadIdx.x, (long)gridDim.x * blockDim.x, ids, values, counts, W, cap, K, V, s_off,
+                  field_l2, F, epi, [=](int64_t row) { if (stamp) stamp[row] = tag; });
 }
 
 // the rule and its hyper-parameters (read here, on the host: a captured launch keeps the values it was captured with)
@@ -366,14 +294,14 @@ extern "C" int fil_rowopt_multi(const fil_adam_tensor* tensors, int n, int64_t t
   const RowHyper h = row_hyper(*hyper);
   if (n > 0) {
     ProfScope ps(rule == FIL_OPT_FTRL ? "ftrl_multi" : "adagrad_multi", st, (4.0 + 8.0 * rule_arrays(rule)) * (double)total_numel);
-    const long chunks = std::max<long>(1, (long)((total_numel + kRowMultiChunk - 1) / kRowMultiChunk));
+    const long chunks = std::max<long>(1, (long)((total_numel + kMultiChunk - 1) / kMultiChunk));
     const dim3 grid((int)std::min<long>(chunks, 256 * 8));
     if (rule == FIL_OPT_FTRL) hipLaunchKernelGGL(rowopt_multi_kernel<FIL_OPT_FTRL>, grid, dim3(256), 0, st, tensors, n, h);
     else hipLaunchKernelGGL(rowopt_multi_kernel<FIL_OPT_ADAGRAD>, grid, dim3(256), 0, st, tensors, n, h);
     FIL_CHECK_LAUNCH();
   }
   if (advance) {
-    hipLaunchKernelGGL(rowopt_step_advance_kernel, dim3(1), dim3(1), 0, st, step);
+    launch_step_advance(step, st);
     FIL_CHECK_LAUNCH();
   }
   return FIL_OK;

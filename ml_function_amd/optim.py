@@ -148,16 +148,41 @@ def deferred_optimizer(table):
 
 class _RunsOptimizer(torch.optim.Optimizer):
     """What the fused optimizers of this module share: the device step counter (Keras' iterations), the staged descriptor arrays of
-    the one dense launch per (group, device), the pending runs records, and the data-parallel exchange of the runs tables.  A
-    subclass sets _NAME (its name in messages) and, before the base class adds the groups: _t, _descs, _pinned, _arena, _arena_off,
-    _xbuf, process_group, force_exchange."""
+    the one dense launch per (group, device), the pending runs records, the row stamps, the data-parallel exchange of the runs
+    tables, the step loop and the state.  A subclass sets _NAME (its name in messages) and _SLOTS (the state keys of its per-element
+    slots) and supplies _slot_init (their initial values), _hyper, _launch_dense and _apply_runs; Adam's deferred mode hooks in
+    through _skip and _admit."""
     _NAME = None
+    _SLOTS = ()
+
+    def __init__(self, params, defaults, process_group, force_exchange):
+        if process_group is not None and not isinstance(process_group, dist.ProcessGroup):
+            raise TypeError("%s: process_group must be a torch.distributed.ProcessGroup or None, not %r" % (self._NAME, process_group))
+        if not isinstance(force_exchange, bool):
+            raise TypeError("%s: force_exchange must be a bool, not %r" % (self._NAME, force_exchange))
+        self._t = {}            # device -> int64 [1] step counter (Keras' iterations)
+        self._stamps = {}       # runs table -> int32 [V] row stamps of the sweep (valid within one step only: not state)
+        self._descs = {}        # descriptor key -> (device descriptors, pinned host copy)
+        self._pinned = []       # descriptor arrays built during a stream capture: a graph replays them, they are never dropped
+        # pinned staging for descriptors built DURING a capture: a host allocation there would invalidate it, so it is reserved by
+        # the first eager step; a captured copy reads its slice at every replay, so a slice is never handed out twice
+        self._arena, self._arena_off = None, 0
+        self._xbuf = {}         # runs table -> buffers of the data-parallel exchange (cap fixed on the first step, reused after)
+        self.process_group = process_group
+        self.force_exchange = force_exchange
+        super().__init__(params, defaults)
 
     def _counter(self, dev):
         t = self._t.get(dev)
         if t is None:
             t = self._t[dev] = torch.zeros(1, dtype=torch.int64, device=dev)
         return t
+
+    def _stamp(self, p):
+        s = self._stamps.get(p)
+        if s is None:
+            s = self._stamps[p] = torch.zeros(p.shape[0], dtype=torch.int32, device=p.device)
+        return s
 
     @property
     def iterations(self):
@@ -170,6 +195,130 @@ class _RunsOptimizer(torch.optim.Optimizer):
             for p in g["params"]:
                 if getattr(p, "_fil_pending_runs", None) is not None:
                     p._fil_pending_runs = None
+
+    # -- what a subclass supplies ----------------------------------------------------------------------------------
+    def _slot_init(self, group):
+        """The initial values of the _SLOTS of a parameter in `group`."""
+        raise NotImplementedError
+
+    def _hyper(self, group):
+        raise NotImplementedError
+
+    def _launch_dense(self, lib, desc, n, numel, t, hyper, advance):
+        """The dense launch of one (group, device): n descriptors of numel elements in all; advance: the step counter t too."""
+        raise NotImplementedError
+
+    def _apply_runs(self, lib, p, pend, s0, s1, t, hyper):
+        raise NotImplementedError
+
+    def _skip(self, p, hyper):
+        """A parameter without a gradient or a record at this step."""
+
+    def _admit(self, p, pend):
+        """Checks a parameter with a gradient or a record before anything else."""
+
+    # -- state ---------------------------------------------------------------------------------------------------
+    def _slots(self, p, group):
+        """The parameter's two slot tensors, made on first use (None for a slot the rule does not have)."""
+        st = self.state[p]
+        if self._SLOTS[0] not in st:
+            for k, x in zip(self._SLOTS, self._slot_init(group)):
+                st[k] = torch.full_like(p, x, memory_format=torch.contiguous_format)
+        return st[self._SLOTS[0]], (st[self._SLOTS[1]] if len(self._SLOTS) > 1 else None)
+
+    def state_dict(self):
+        sd = super().state_dict()
+        sd["iterations"] = self.iterations
+        return sd
+
+    def load_state_dict(self, state_dict):
+        state_dict = dict(state_dict)
+        it = int(state_dict.pop("iterations", 0))
+        super().load_state_dict(state_dict)
+        for st in self.state.values():          # (torch's loader may hand non-contiguous copies back)
+            for k in self._SLOTS:
+                if k in st:
+                    st[k] = st[k].contiguous()
+        for g in self.param_groups:
+            for p in g["params"]:
+                self._counter(p.device)
+        for t in self._t.values():
+            t.fill_(it)
+        for s in self._stamps.values():         # t may go backwards: a stale stamp must never look current
+            s.zero_()
+
+    def reset_(self):
+        """Back to "never stepped" IN PLACE (slots, stamps and counter keep their storage): what a capture's restore needs after
+        warm-up steps (capture.capture_step(..., restore=...))."""
+        for group in self.param_groups:
+            for p in group["params"]:
+                st = self.state.get(p, {})
+                for k, x in zip(self._SLOTS, self._slot_init(group)):
+                    if k in st:
+                        st[k].fill_(x)
+        for s in self._stamps.values():
+            s.zero_()
+        for t in self._t.values():
+            t.zero_()
+
+    # -- the step ------------------------------------------------------------------------------------------------
+    @torch.no_grad()
+    def step(self, closure=None):
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        lib = _lib.load()
+        calls = []      # (device, hyper, entries) of the dense launches, in group order
+        for group in self.param_groups:
+            hyper = self._hyper(group)
+            per_dev = {}
+            for p in group["params"]:
+                pend = getattr(p, "_fil_pending_runs", None)
+                if pend is None and p.grad is None:
+                    self._skip(p, hyper)        # (Keras filters None gradients)
+                    continue
+                self._admit(p, pend)
+                if p.device.type != "cuda" or p.dtype != torch.float32 or not p.is_contiguous():
+                    raise FilError("%s: parameter %s %s on %s -- contiguous fp32 GPU tensors only" % (self._NAME, tuple(p.shape), p.dtype,
+                                                                                                   p.device))
+                s0, s1 = self._slots(p, group)
+                t = self._counter(p.device)
+                if pend is not None:
+                    if p.grad is not None:
+                        raise FilError("%s: table %s has both a .grad and a pending runs record (a gradient reached the table "
+                                       "outside its gather -- e.g. a regulariser not detached)" % (self._NAME, tuple(p.shape)))
+                    self._apply_runs(lib, p, pend, s0, s1, t, hyper)
+                    p._fil_pending_runs = None
+                    continue
+                g = p.grad
+                if g.is_sparse:
+                    raise FilError("%s: sparse gradient of %s -- use SparseEmbed(grad_mode='runs') for the tables" % (self._NAME,
+                                                                                                                    tuple(p.shape)))
+                if g.dtype != torch.float32 or not g.is_contiguous() or g.shape != p.shape:
+                    raise FilError("%s: gradient of %s must be a dense contiguous fp32 tensor of its shape" % (self._NAME, tuple(p.shape)))
+                per_dev.setdefault(p.device, []).append((p.data_ptr(), g.data_ptr(), s0.data_ptr(), ptr(s1), p.numel(), 0.0))
+            for dev, entries in per_dev.items():
+                calls.append((dev, hyper, entries))
+        # the last launch on every device advances its counter -- one with no tensors where nothing dense had a gradient
+        devs = set(self._t)
+        for g in self.param_groups:
+            for p in g["params"]:
+                if p.device.type == "cuda":
+                    devs.add(p.device)
+        last = {}
+        for i, (dev, _, _) in enumerate(calls):
+            last[dev] = i
+        for dev in devs:
+            if dev not in last:
+                calls.append((dev, self._hyper(self.defaults), []))
+                last[dev] = len(calls) - 1
+        for i, (dev, hyper, entries) in enumerate(calls):
+            with torch.cuda.device(dev):
+                desc = self._desc_array(dev, entries) if entries else None
+                self._launch_dense(lib, desc, len(entries), sum(e[4] for e in entries), self._counter(dev), hyper,
+                                   1 if last[dev] == i else 0)
+        return loss
 
     def _desc_array(self, dev, entries):
         key = (dev, tuple(entries))
@@ -259,16 +408,13 @@ class _RunsOptimizer(torch.optim.Optimizer):
 
 class Adam(_RunsOptimizer):
     _NAME = "optim.Adam"
+    _SLOTS = ("m", "v")
 
     def __init__(self, params, learning_rate=1e-3, beta_1=0.9, beta_2=0.999, epsilon=1e-7, lazy_tables=False, process_group=None,
                  force_exchange=False, sweep_period=None):
         if not learning_rate >= 0.0 or not 0.0 <= beta_1 < 1.0 or not 0.0 <= beta_2 < 1.0 or not epsilon >= 0.0:
             raise ValueError("Adam: learning_rate=%r beta_1=%r beta_2=%r epsilon=%r (rate, epsilon >= 0; betas in [0, 1))"
                              % (learning_rate, beta_1, beta_2, epsilon))
-        if process_group is not None and not isinstance(process_group, dist.ProcessGroup):
-            raise TypeError("Adam: process_group must be a torch.distributed.ProcessGroup or None, not %r" % (process_group,))
-        if not isinstance(force_exchange, bool):
-            raise TypeError("Adam: force_exchange must be a bool, not %r" % (force_exchange,))
         if sweep_period is not None:
             if isinstance(sweep_period, bool) or not isinstance(sweep_period, int):
                 raise TypeError("Adam: sweep_period must be an int or None, not %r" % (sweep_period,))
@@ -278,24 +424,14 @@ class Adam(_RunsOptimizer):
                 raise ValueError("Adam: sweep_period (deferred Keras mode) and lazy_tables exclude each other")
         # (set before the base class adds the parameter groups: add_param_group attaches their runs tables)
         self.sweep_period = sweep_period
-        self._t = {}            # device -> int64 [1] step counter (Keras' iterations)
+        self.lazy_tables = bool(lazy_tables)
         self._defer = {}        # deferred runs table -> its _Deferred state (also in _DEFERRED, for the table's readers)
         self._released = []     # the same states, for the finaliser (which must not hold the optimizer)
         if sweep_period is not None:
             fin = weakref.finalize(self, _release, self._released)
             fin.atexit = False
         super().__init__(params, dict(learning_rate=float(learning_rate), beta_1=float(beta_1), beta_2=float(beta_2),
-                                      epsilon=float(epsilon)))
-        self.lazy_tables = bool(lazy_tables)
-        self._stamps = {}       # runs table -> int32 [V] row stamps of FIL_ADAM_KERAS (valid within one step only: not state)
-        self._descs = {}        # descriptor key -> (device descriptors, pinned host copy)
-        self._pinned = []       # descriptor arrays built during a stream capture: a graph replays them, they are never dropped
-        # pinned staging for descriptors built DURING a capture: a host allocation there would invalidate it, so it is reserved by
-        # the first eager step; a captured copy reads its slice at every replay, so a slice is never handed out twice
-        self._arena, self._arena_off = None, 0
-        self.process_group = process_group
-        self.force_exchange = force_exchange
-        self._xbuf = {}         # runs table -> buffers of the data-parallel exchange (cap fixed on the first step, reused after)
+                                      epsilon=float(epsilon)), process_group, force_exchange)
 
     def add_param_group(self, param_group):
         super().add_param_group(param_group)
@@ -304,114 +440,43 @@ class Adam(_RunsOptimizer):
                 if getattr(p, "_fil_runs_table", False):
                     self._attach(p)
 
-    # -- state ---------------------------------------------------------------------------------------------------
-    def _moments(self, p):
-        st = self.state[p]
-        if "m" not in st:
-            st["m"] = torch.zeros_like(p, memory_format=torch.contiguous_format)
-            st["v"] = torch.zeros_like(p, memory_format=torch.contiguous_format)
-        return st["m"], st["v"]
+    def _slot_init(self, group):
+        return 0.0, 0.0
+
+    def _hyper(self, group):
+        return group["learning_rate"], group["beta_1"], group["beta_2"], group["epsilon"]
+
+    def _launch_dense(self, lib, desc, n, numel, t, hyper, advance):
+        check(lib.fil_adam_multi(ptr(desc), n, numel, ptr(t), *hyper, advance, stream_ptr()), "fil_adam_multi")
 
     def state_dict(self):
         self.flush()
-        sd = super().state_dict()
-        sd["iterations"] = self.iterations
-        return sd
+        return super().state_dict()
 
     def load_state_dict(self, state_dict):
-        state_dict = dict(state_dict)
-        it = int(state_dict.pop("iterations", 0))
         super().load_state_dict(state_dict)
-        for p, st in self.state.items():        # (torch's loader may hand non-contiguous copies back)
-            for k in ("m", "v"):
-                if k in st:
-                    st[k] = st[k].contiguous()
-        for g in self.param_groups:
-            for p in g["params"]:
-                self._counter(p.device)
-        for t in self._t.values():
-            t.fill_(it)
-        for s in self._stamps.values():         # t may go backwards: a stale stamp must never look current
-            s.zero_()
+        it = int(state_dict.get("iterations", 0))
         for p, d in self._defer.items():        # deferred: a checkpoint is taken flushed -- every row is current through `it`
-            d.m, d.v = self._moments(p)         # (the loader replaced the moments)
+            d.m, d.v = self._slots(p, None)    # (the loader replaced the moments)
             d.stamp.fill_(it)
 
     def reset_(self):
-        """Back to "never stepped" IN PLACE (moments, stamps and counter keep their storage): what a capture's restore needs after
-        warm-up steps (capture.capture_step(..., restore=...))."""
-        for st in self.state.values():
-            for k in ("m", "v"):
-                if k in st:
-                    st[k].zero_()
-        for s in self._stamps.values():
-            s.zero_()
+        super().reset_()
         for d in self._defer.values():
             d.stamp.zero_()
-        for t in self._t.values():
-            t.zero_()
 
-    # -- the step ------------------------------------------------------------------------------------------------
-    @torch.no_grad()
-    def step(self, closure=None):
-        loss = None
-        if closure is not None:
-            with torch.enable_grad():
-                loss = closure()
-        lib = _lib.load()
-        calls = []      # (device, hyper, entries) of the fil_adam_multi launches, in group order
-        for group in self.param_groups:
-            hyper = (group["learning_rate"], group["beta_1"], group["beta_2"], group["epsilon"])
-            per_dev = {}
-            for p in group["params"]:
-                pend = getattr(p, "_fil_pending_runs", None)
-                if pend is None and p.grad is None:
-                    if p in self._defer:        # Keras mode leaves the table alone at this step: the ring says so
-                        self._defer[p].roll(p, hyper, FIL_ADAM_ROLL_SKIP)
-                    continue
-                if pend is not None and self.sweep_period is not None and p not in self._defer:
-                    # a runs table that was not one when it joined (swept every step so far, so current): deferred from now on
-                    self._attach(p)
-                if pend is None and p in self._defer:
-                    raise FilError("optim.Adam: deferred table %s has a .grad -- with sweep_period its gradient must arrive as runs "
-                                   "(SparseEmbed(grad_mode='runs'))" % (tuple(p.shape),))
-                if p.device.type != "cuda" or p.dtype != torch.float32 or not p.is_contiguous():
-                    raise FilError("optim.Adam: parameter %s %s on %s -- contiguous fp32 GPU tensors only" % (tuple(p.shape), p.dtype, p.device))
-                m, v = self._moments(p)
-                t = self._counter(p.device)
-                if pend is not None:
-                    if p.grad is not None:
-                        raise FilError("optim.Adam: table %s has both a .grad and a pending runs record (a gradient reached the table "
-                                       "outside its gather -- e.g. a regulariser not detached)" % (tuple(p.shape),))
-                    self._apply_runs(lib, p, pend, m, v, t, hyper)
-                    p._fil_pending_runs = None
-                    continue
-                g = p.grad
-                if g.is_sparse or g.dtype != torch.float32 or not g.is_contiguous() or g.shape != p.shape:
-                    raise FilError("optim.Adam: gradient of %s must be a dense contiguous fp32 tensor of its shape" % (tuple(p.shape),))
-                per_dev.setdefault(p.device, []).append((p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel(), 0.0))
-            for dev, entries in per_dev.items():
-                calls.append((dev, hyper, entries))
-        # the last launch on every device advances its counter -- one with no tensors where nothing dense had a gradient
-        devs = set(self._t)
-        for g in self.param_groups:
-            for p in g["params"]:
-                if p.device.type == "cuda":
-                    devs.add(p.device)
-        last = {}
-        for i, (dev, _, _) in enumerate(calls):
-            last[dev] = i
-        for dev in devs:
-            if dev not in last:
-                calls.append((dev, (self.defaults["learning_rate"], self.defaults["beta_1"], self.defaults["beta_2"],
-                                    self.defaults["epsilon"]), []))
-                last[dev] = len(calls) - 1
-        for i, (dev, (lr, b1, b2, eps), entries) in enumerate(calls):
-            with torch.cuda.device(dev):
-                desc = self._desc_array(dev, entries) if entries else None
-                check(lib.fil_adam_multi(ptr(desc), len(entries), sum(e[4] for e in entries), ptr(self._counter(dev)), lr, b1, b2, eps,
-                                         1 if last[dev] == i else 0, stream_ptr()), "fil_adam_multi")
-        return loss
+    # -- deferred mode hooks of the step -----------------------------------------------------------------------------
+    def _skip(self, p, hyper):
+        if p in self._defer:                    # Keras mode leaves the table alone at this step: the ring says so
+            self._defer[p].roll(p, hyper, FIL_ADAM_ROLL_SKIP)
+
+    def _admit(self, p, pend):
+        if pend is not None and self.sweep_period is not None and p not in self._defer:
+            # a runs table that was not one when it joined (swept every step so far, so current): deferred from now on
+            self._attach(p)
+        if pend is None and p in self._defer:
+            raise FilError("optim.Adam: deferred table %s has a .grad -- with sweep_period its gradient must arrive as runs "
+                           "(SparseEmbed(grad_mode='runs'))" % (tuple(p.shape),))
 
     def _apply_runs(self, lib, p, pend, m, v, t, hyper):
         lr, b1, b2, eps = hyper
@@ -420,11 +485,7 @@ class Adam(_RunsOptimizer):
             self._apply_runs_deferred(lib, p, pend, m, v, t, hyper)
             return
         mode = FIL_ADAM_LAZY if self.lazy_tables else FIL_ADAM_KERAS
-        stamp = None
-        if mode == FIL_ADAM_KERAS:
-            stamp = self._stamps.get(p)
-            if stamp is None:
-                stamp = self._stamps[p] = torch.zeros(V, dtype=torch.int32, device=p.device)
+        stamp = self._stamp(p) if mode == FIL_ADAM_KERAS else None
         with torch.cuda.device(p.device):
             st = stream_ptr()
             world = self._exchange_world()
@@ -452,7 +513,7 @@ class Adam(_RunsOptimizer):
             if old.opt() is not None:
                 raise FilError("optim.Adam: table %s already belongs to another deferred optimizer" % (tuple(p.shape),))
             _release([old])                 # its optimizer is gone but not yet finalised: bring the table current first
-        m, v = self._moments(p)
+        m, v = self._slots(p, None)
         d = self._defer[p] = _Deferred(self, p, m, v, self._counter(p.device), self.sweep_period)
         self._released.append(d)
         _DEFERRED[p] = d
@@ -506,138 +567,24 @@ class _Rowwise(_RunsOptimizer):
     regularised field."""
     _RULE = None
 
-    def __init__(self, params, defaults, process_group, force_exchange):
-        if process_group is not None and not isinstance(process_group, dist.ProcessGroup):
-            raise TypeError("%s: process_group must be a torch.distributed.ProcessGroup or None, not %r" % (self._NAME, process_group))
-        if not isinstance(force_exchange, bool):
-            raise TypeError("%s: force_exchange must be a bool, not %r" % (self._NAME, force_exchange))
-        self._t = {}            # device -> int64 [1] step counter (Keras' iterations)
-        self._stamps = {}       # runs table with a regularised field -> int32 [V] row stamps (valid within one step only)
-        self._descs = {}        # descriptor key -> (device descriptors, pinned host copy)
-        self._pinned = []       # descriptor arrays built during a stream capture (a graph replays them: never dropped)
-        self._arena, self._arena_off = None, 0
-        self._xbuf = {}         # runs table -> buffers of the data-parallel exchange
-        self.process_group = process_group
-        self.force_exchange = force_exchange
-        super().__init__(params, defaults)
+    def _slot_init(self, group):
+        return group["initial_accumulator_value"], 0.0
 
-    def _hyper(self, group):
-        raise NotImplementedError
+    def _launch_dense(self, lib, desc, n, numel, t, hyper, advance):
+        check(lib.fil_rowopt_multi(ptr(desc), n, numel, ptr(t), self._RULE, ctypes.addressof(hyper), advance, stream_ptr()),
+              "fil_rowopt_multi")
 
-    # -- state ---------------------------------------------------------------------------------------------------
-    def _slots(self, p, group):
-        st = self.state[p]
-        if "accumulator" not in st:
-            st["accumulator"] = torch.full_like(p, group["initial_accumulator_value"], memory_format=torch.contiguous_format)
-            if self._RULE == FIL_OPT_FTRL:
-                st["linear"] = torch.zeros_like(p, memory_format=torch.contiguous_format)
-        return st["accumulator"], st.get("linear")
-
-    def state_dict(self):
-        sd = super().state_dict()
-        sd["iterations"] = self.iterations
-        return sd
-
-    def load_state_dict(self, state_dict):
-        state_dict = dict(state_dict)
-        it = int(state_dict.pop("iterations", 0))
-        super().load_state_dict(state_dict)
-        for st in self.state.values():          # (torch's loader may hand non-contiguous copies back)
-            for k in ("accumulator", "linear"):
-                if k in st:
-                    st[k] = st[k].contiguous()
-        for g in self.param_groups:
-            for p in g["params"]:
-                self._counter(p.device)
-        for t in self._t.values():
-            t.fill_(it)
-        for s in self._stamps.values():         # t may go backwards: a stale stamp must never look current
-            s.zero_()
-
-    def reset_(self):
-        """Back to "never stepped" IN PLACE (slots, stamps and counter keep their storage): what a capture's restore needs after
-        warm-up steps (capture.capture_step(..., restore=...))."""
-        for group in self.param_groups:
-            for p in group["params"]:
-                st = self.state.get(p, {})
-                if "accumulator" in st:
-                    st["accumulator"].fill_(group["initial_accumulator_value"])
-                if "linear" in st:
-                    st["linear"].zero_()
-        for s in self._stamps.values():
-            s.zero_()
-        for t in self._t.values():
-            t.zero_()
-
-    # -- the step ------------------------------------------------------------------------------------------------
-    @torch.no_grad()
-    def step(self, closure=None):
-        loss = None
-        if closure is not None:
-            with torch.enable_grad():
-                loss = closure()
-        lib = _lib.load()
-        calls = []      # (device, hyper, entries) of the fil_rowopt_multi launches, in group order
-        for group in self.param_groups:
-            hyper = self._hyper(group)
-            per_dev = {}
-            for p in group["params"]:
-                pend = getattr(p, "_fil_pending_runs", None)
-                if pend is None and p.grad is None:
-                    continue                    # (Keras filters None gradients)
-                if deferred_state(p) is not None:
-                    raise FilError("%s: table %s is in optim.Adam's deferred mode (sweep_period) -- drop that optimizer first"
-                                   % (self._NAME, tuple(p.shape)))
-                if p.device.type != "cuda" or p.dtype != torch.float32 or not p.is_contiguous():
-                    raise FilError("%s: parameter %s %s on %s -- contiguous fp32 GPU tensors only" % (self._NAME, tuple(p.shape), p.dtype,
-                                                                                                   p.device))
-                acc, lin = self._slots(p, group)
-                t = self._counter(p.device)
-                if pend is not None:
-                    if p.grad is not None:
-                        raise FilError("%s: table %s has both a .grad and a pending runs record (a gradient reached the table "
-                                       "outside its gather -- e.g. a regulariser not detached)" % (self._NAME, tuple(p.shape)))
-                    self._apply_runs(lib, p, pend, acc, lin, t, hyper)
-                    p._fil_pending_runs = None
-                    continue
-                g = p.grad
-                if g.is_sparse:
-                    raise FilError("%s: sparse gradient of %s -- use SparseEmbed(grad_mode='runs') for the tables" % (self._NAME,
-                                                                                                                    tuple(p.shape)))
-                if g.dtype != torch.float32 or not g.is_contiguous() or g.shape != p.shape:
-                    raise FilError("%s: gradient of %s must be a dense contiguous fp32 tensor of its shape" % (self._NAME, tuple(p.shape)))
-                per_dev.setdefault(p.device, []).append((p.data_ptr(), g.data_ptr(), acc.data_ptr(), ptr(lin), p.numel(), 0.0))
-            for dev, entries in per_dev.items():
-                calls.append((dev, hyper, entries))
-        # the last launch on every device advances its counter -- one with no tensors where nothing dense had a gradient
-        devs = set(self._t)
-        for g in self.param_groups:
-            for p in g["params"]:
-                if p.device.type == "cuda":
-                    devs.add(p.device)
-        last = {}
-        for i, (dev, _, _) in enumerate(calls):
-            last[dev] = i
-        for dev in devs:
-            if dev not in last:
-                calls.append((dev, self._hyper(self.defaults), []))
-                last[dev] = len(calls) - 1
-        for i, (dev, hyper, entries) in enumerate(calls):
-            with torch.cuda.device(dev):
-                desc = self._desc_array(dev, entries) if entries else None
-                check(lib.fil_rowopt_multi(ptr(desc), len(entries), sum(e[4] for e in entries), ptr(self._counter(dev)), self._RULE,
-                                           ctypes.addressof(hyper), 1 if last[dev] == i else 0, stream_ptr()), "fil_rowopt_multi")
-        return loss
+    def _admit(self, p, pend):
+        if deferred_state(p) is not None:
+            raise FilError("%s: table %s is in optim.Adam's deferred mode (sweep_period) -- drop that optimizer first"
+                           % (self._NAME, tuple(p.shape)))
 
     def _apply_runs(self, lib, p, pend, acc, lin, t, hyper):
         V, K = p.shape
         h = ctypes.addressof(hyper)
         field_l2 = pend["field_l2"]
-        stamp = None
-        if field_l2 is not None:            # a regularised field: its untouched rows move too (the sweep), stamps tell them apart
-            stamp = self._stamps.get(p)
-            if stamp is None:
-                stamp = self._stamps[p] = torch.zeros(V, dtype=torch.int32, device=p.device)
+        # a regularised field: its untouched rows move too (the sweep), stamps tell them apart
+        stamp = self._stamp(p) if field_l2 is not None else None
         with torch.cuda.device(p.device):
             st = stream_ptr()
             world = self._exchange_world()
@@ -663,6 +610,7 @@ class Adagrad(_Rowwise):
     A table in "dense" mode is an ordinary dense parameter.  process_group / force_exchange: as optim.Adam's."""
     _NAME = "optim.Adagrad"
     _RULE = FIL_OPT_ADAGRAD
+    _SLOTS = ("accumulator",)
 
     def __init__(self, params, learning_rate=0.001, initial_accumulator_value=0.1, epsilon=1e-7, process_group=None,
                  force_exchange=False):
@@ -691,6 +639,7 @@ class Ftrl(_Rowwise):
     process_group / force_exchange: as optim.Adam's."""
     _NAME = "optim.Ftrl"
     _RULE = FIL_OPT_FTRL
+    _SLOTS = ("accumulator", "linear")
 
     def __init__(self, params, learning_rate=0.001, learning_rate_power=-0.5, initial_accumulator_value=0.1,
                  l1_regularization_strength=0.0, l2_regularization_strength=0.0, l2_shrinkage_regularization_strength=0.0,
