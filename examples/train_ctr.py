@@ -76,6 +76,10 @@ def main():
     ap.add_argument("--ftrl-l1", type=float, default=0.0, help="--optimizer keras-ftrl: l1_regularization_strength")
     ap.add_argument("--ftrl-l2", type=float, default=0.0, help="--optimizer keras-ftrl: l2_regularization_strength")
     ap.add_argument("--ftrl-l2-shrinkage", type=float, default=0.0, help="--optimizer keras-ftrl: l2_shrinkage_regularization_strength")
+    ap.add_argument("--keras-auc", action="store_true",
+                    help="also keep the reference's compiled metric, tf.keras.metrics.AUC() (metrics.AUC: 200 thresholds, stateful), "
+                         "updated inside the training step -- so inside the captured graph -- over every batch; the log line then "
+                         "prints the running Keras AUC beside the logged batch's exact one (data parallel: the whole group's)")
     ap.add_argument("--no-graph", action="store_true",
                     help="run every step eagerly (default on one GPU: the whole step -- forward, backward, Adam -- is captured once "
                          "into a HIP graph and replayed; the C ABI neither allocates nor synchronises, so it is capture-safe)")
@@ -134,6 +138,7 @@ def main():
                          sweep_period=args.sweep_period)
     else:
         opt = torch.optim.Adam(model.parameters(), lr=args.lr, eps=1e-7, capturable=use_graph)      # Keras 'adam' (un_seq.py:61)
+    keras_auc = metrics.AUC().build(device) if args.keras_auc else None      # the state exists before any capture
     pipe = data.data_pipeline(table, batch_size=args.batch, shuffle_buffer=2048, repeat=2, prefetch=2, seed=rank, device=device)
 
     def train_step(dense, idx, y):
@@ -158,6 +163,8 @@ def main():
             if t.grad is not None and table_l2.get(id(t)):
                 dp.add_table_l2_grad_(t.grad, t.detach(), table_l2[id(t)])
         opt.step()
+        if keras_auc is not None:
+            keras_auc.update_state(y, p)            # one launch, no host synchronisation
         return bce.detach(), p.detach()
 
     graph, static = None, None
@@ -186,6 +193,8 @@ def main():
                         for v in st_.values():
                             if torch.is_tensor(v):
                                 v.zero_()
+                if keras_auc is not None:
+                    keras_auc.reset_states()        # the warm-up batches do not count (in place: the capture keeps the state)
                 graph = torch.cuda.CUDAGraph()
                 opt.zero_grad(set_to_none=True)
                 with torch.cuda.graph(graph):
@@ -196,8 +205,12 @@ def main():
             bce, p = static_out
         else:
             bce, p = train_step(dense, idx, y)
-        if rank == 0 and (step % 20 == 0 or step == len(pipe) - 1):
-            print("step %4d  loss %.4f  auc %.4f" % (step, float(bce), metrics.auc(y, p)), flush=True)
+        if step % 20 == 0 or step == len(pipe) - 1:
+            # (every rank takes part in the group read; result_value() is also where scores outside [0, 1] would raise)
+            running = "" if keras_auc is None else "  keras auc (running) %.4f" % keras_auc.result_value(
+                process_group=dist.group.WORLD if world > 1 else None)
+            if rank == 0:
+                print("step %4d  loss %.4f  auc %.4f%s" % (step, float(bce), metrics.auc(y, p), running), flush=True)
     if world > 1:
         dist.destroy_process_group()
 

@@ -492,6 +492,32 @@ int fil_embed_rowopt_merged(const int64_t* ids, const float* values, const int64
                             const float* field_l2, int F, float* table, float* accum, float* linear, int32_t* stamp, int64_t V,
                             const int64_t* step, int rule, const fil_rowopt_hyper* hyper, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * M1  Keras' streaming AUC (TF 2.1 keras/metrics.py: AUC; keras/utils/metrics_utils.py: update_confusion_matrix_variables) --
+ *     replaces metrics=[tf.keras.metrics.AUC()] of example/ctr_example/un_seq.py:61.  Entry points added only: the ABI version stays.
+ *   State: cm [4][T] fp32 = TP | FP | TN | FN per threshold, as Keras keeps them, and one int64 `invalid`.
+ *   fil_confusion_update: p, y [n] fp32 (y != 0 is a positive label); thr [T] fp32 ascending (duplicates allowed); for every i
+ *     cm[0][i] += #{y != 0, p > thr[i]}, cm[1][i] += #{y == 0, p > thr[i]}, cm[2][i] += #{y == 0, p <= thr[i]},
+ *     cm[3][i] += #{y != 0, p <= thr[i]}: the comparison is fp32 p against the STORED fp32 thr[i]; the batch's counts are integers
+ *     (per-bucket histograms, integer atomics, a suffix sum), so they do not depend on scheduling, and each state entry then takes
+ *     exactly ONE fp32 addition per call (Keras' assign_add: integer-exact below 2^24, an fp32 rounding past it).  Samples with p < 0,
+ *     p > 1 or NaN touch no entry and are counted in *invalid (TF fails an assertion there; a captured step cannot raise).
+ *     n <= FIL_CONFUSION_ONE_LAUNCH_N is one kernel launch and needs no workspace (workspace may be NULL); larger n is a
+ *     partial-histogram launch and a finishing launch with integer partials in the workspace, which needs no initialisation.
+ *     2 <= T <= FIL_CONFUSION_MAX_T (FIL_ERR_UNSUPPORTED otherwise), 1 <= n <= 2^24 (so a call's count is exact in fp32; larger inputs
+ *     are the caller's loop).  p and y need 4-byte alignment only (16-byte loads where the addresses allow).  Repeats from the same
+ *     state on the same inputs are bit-identical.
+ *   fil_auc_result: out[0] = AUC.result() of cm in fp32.  curve 0 ROC, 1 PR; summation 0 interpolation, 1 minoring, 2 majoring
+ *     (PR + interpolation is Keras' interpolate_pr_auc).  Every division is div_no_nan: an empty or one-class state gives 0.
+ *     One small launch, no host round trip.
+ */
+#define FIL_CONFUSION_MAX_T 2048
+#define FIL_CONFUSION_ONE_LAUNCH_N 16384
+size_t fil_confusion_workspace_bytes(int n, int T);
+int fil_confusion_update(const float* p, const float* y, int n, const float* thr, int T, float* cm, long long* invalid,
+                         void* workspace, size_t workspace_bytes, void* stream);
+int fil_auc_result(const float* cm, int T, int curve, int summation, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

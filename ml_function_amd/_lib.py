@@ -29,6 +29,7 @@ FIL_F32, FIL_BF16 = 0, 1
 FIL_ADAM_KERAS, FIL_ADAM_LAZY = 0, 1
 FIL_ADAM_ROLL_STEP, FIL_ADAM_ROLL_SKIP, FIL_ADAM_ROLL_FLUSH = 0, 1, 2
 FIL_OPT_ADAGRAD, FIL_OPT_FTRL = 1, 2
+FIL_CONFUSION_MAX_T, FIL_CONFUSION_ONE_LAUNCH_N = 2048, 16384
 
 _c = ctypes
 _P = _c.c_void_p
@@ -100,6 +101,9 @@ SIGNATURES = {
     "fil_embed_rowopt_runs": (_I, [_P, _P, _P, _c.c_long, _I, _I, _I, _P, _P, _P, _P, _P, _P, _I, _P, _P]),
     "fil_embed_rowopt_sweep": (_I, [_P, _P, _P, _P, _c.c_int64, _I, _P, _P, _P, _I, _P, _I, _P, _P]),
     "fil_embed_rowopt_merged": (_I, [_P, _P, _P, _I, _c.c_long, _I, _P, _P, _I, _P, _P, _P, _P, _c.c_int64, _P, _I, _P, _P]),
+    "fil_confusion_workspace_bytes": (_Z, [_I, _I]),
+    "fil_confusion_update": (_I, [_P, _P, _I, _P, _I, _P, _P, _P, _Z, _P]),
+    "fil_auc_result": (_I, [_P, _I, _I, _I, _P, _P]),
 }
 
 

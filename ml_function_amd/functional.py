@@ -760,6 +760,56 @@ def binary_crossentropy(p, y, eps=1e-7):
     return _BceMeanFn.apply(p, y, eps)
 
 
+# --------------------------------------------------------------------------------------------- M1  Keras' streaming AUC
+AUC_CURVES = {"ROC": 0, "PR": 1}
+AUC_SUMMATIONS = {"interpolation": 0, "minoring": 1, "majoring": 2}
+
+
+def confusion_update(p, y, thr, cm, invalid, workspace=None):
+    """Keras' update_confusion_matrix_variables for one batch (fil_confusion_update): p, y [n] fp32 (n <= 2^24; y != 0 is a positive),
+    thr [T] fp32 ascending, cm [4, T] fp32 = TP | FP | TN | FN and invalid (one int64) updated IN PLACE.  Integer counting, then one
+    fp32 add per state entry; samples with p outside [0, 1] or NaN only count in `invalid`.  No host synchronisation: capturable.
+    workspace: a uint8 tensor of fil_confusion_workspace_bytes(n, T) bytes (none is needed up to _lib.FIL_CONFUSION_ONE_LAUNCH_N
+    samples); allocated here when missing."""
+    _require_cuda(p, y, thr, cm, invalid)
+    if p.dim() != 1 or p.shape != y.shape:
+        raise FilError("confusion_update: p is %s, y is %s (two vectors of one length)" % (tuple(p.shape), tuple(y.shape)))
+    p, y, thr = _f32c(p), _f32c(y), _f32c(thr)
+    T = thr.numel()
+    if cm.dtype != torch.float32 or tuple(cm.shape) != (4, T) or not cm.is_contiguous():
+        raise FilError("confusion_update: cm must be a contiguous float32 [4, %d] tensor, got %s %s" % (T, cm.dtype, tuple(cm.shape)))
+    if invalid.dtype != torch.int64 or invalid.numel() != 1:
+        raise FilError("confusion_update: invalid must be one int64, got %s %s" % (invalid.dtype, tuple(invalid.shape)))
+    n = p.numel()
+    if n == 0:
+        return cm
+    lib = _lib.load()
+    need = lib.fil_confusion_workspace_bytes(n, T) if n <= (1 << 24) else 0
+    if need and workspace is None:
+        workspace = _scratch(need, p.device, "confusion")
+    check(lib.fil_confusion_update(ptr(p), ptr(y), n, ptr(thr), T, ptr(cm), ptr(invalid), ptr(workspace),
+                                   0 if workspace is None else workspace.numel() * workspace.element_size(), stream_ptr()),
+          "fil_confusion_update")
+    return cm
+
+
+def auc_result(cm, curve="ROC", summation="interpolation", out=None):
+    """Keras' AUC.result() of cm [4, T] (fil_auc_result) as a 0-dim fp32 device tensor (a view of `out`, one float32, when given):
+    one small launch, no host synchronisation."""
+    _require_cuda(cm, out)
+    if curve not in AUC_CURVES or summation not in AUC_SUMMATIONS:
+        raise FilError("auc_result: curve %r (ROC, PR), summation %r (interpolation, minoring, majoring)" % (curve, summation))
+    if cm.dtype != torch.float32 or cm.dim() != 2 or cm.shape[0] != 4 or not cm.is_contiguous():
+        raise FilError("auc_result: cm must be a contiguous float32 [4, T] tensor, got %s %s" % (cm.dtype, tuple(cm.shape)))
+    if out is None:
+        out = torch.empty((1,), dtype=torch.float32, device=cm.device)
+    elif out.dtype != torch.float32 or out.numel() != 1:
+        raise FilError("auc_result: out must be one float32, got %s %s" % (out.dtype, tuple(out.shape)))
+    check(_lib.load().fil_auc_result(ptr(cm), cm.shape[1], AUC_CURVES[curve], AUC_SUMMATIONS[summation], ptr(out), stream_ptr()),
+          "fil_auc_result")
+    return out.reshape(())
+
+
 _DISJOINT_CACHE = {}
 
 

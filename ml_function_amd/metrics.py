@@ -1,8 +1,11 @@
 """Evaluation metrics of the reference's training scripts: binary cross-entropy is torch's; AUC
 (example/ctr_example/un_seq.py:61 compiles the model with tf.keras.metrics.AUC) is computed exactly here, as the
 Mann-Whitney statistic with average ranks for ties -- the quantity sklearn.metrics.roc_auc_score returns (Keras' AUC is
-a 200-threshold approximation of the same number)."""
+a 200-threshold approximation of the same number).  `AUC` is that Keras metric itself: stateful, with Keras' thresholds, counts and
+result formulas, updated on the GPU without a host synchronisation, so it can live inside a captured training step."""
 import torch
+
+from . import _lib
 
 
 def auc(y_true, y_score):
@@ -22,3 +25,153 @@ def auc(y_true, y_score):
     ranks = avg_rank[inverse]
     pos_rank_sum = float((ranks * y_true[order]).sum())
     return (pos_rank_sum - n_pos * (n_pos + 1.0) / 2.0) / (n_pos * n_neg)
+
+
+_SLICE = 1 << 24        # fil_confusion_update's limit: one call's counts are exact in fp32
+
+
+class AUC:
+    """tf.keras.metrics.AUC of TensorFlow 2.1 (single label, no sample weights), state on the GPU.
+
+        m = AUC()                                   # 200 thresholds, ROC, interpolation
+        m.update_state(y, p)                        # inside or outside a captured step; no host synchronisation
+        m.result()                                  # 0-dim device tensor, no synchronisation; float(m.result()) is the caller's sync
+        m.result_value()                            # python float; THE call that checks the scores were all in [0, 1]
+
+    State, as in Keras: four float32 vectors of num_thresholds counts (true_positives, false_positives, true_negatives,
+    false_negatives; views of one [4, T] block, `confusion`), each taking ONE fp32 addition per update_state (integer-exact below
+    2^24, rounding like Keras' assign_add past it).  thresholds[i] = i / (num_thresholds - 1) with the end points moved out by
+    K.epsilon() = 1e-7, compared as float32 with a strict `y_pred > threshold`; any non-zero label is positive.
+    The one deviation: TensorFlow fails an assertion on a y_pred outside [0, 1]; a captured step cannot raise, so such scores (and
+    NaN) are left out of the counts and counted in `invalid` (one int64 on the device), and result_value() raises ValueError with the
+    count -- result() and float(result()) do NOT check.  The state is created on the device of the first update_state (or build()),
+    before any capture, and never re-allocated: reset_states() and load_state_dict() write in place."""
+
+    def __init__(self, num_thresholds=200, curve="ROC", summation_method="interpolation", name=None, dtype=None, thresholds=None):
+        from .functional import AUC_CURVES, AUC_SUMMATIONS
+        if isinstance(curve, str) and curve.upper() in AUC_CURVES:          # Keras' AUCCurve.from_str takes 'pr' and 'PR' alike
+            curve = curve.upper()
+        if curve not in AUC_CURVES:
+            raise ValueError('Invalid AUC curve value "%s". Valid values are: %s' % (curve, sorted(AUC_CURVES)))
+        if summation_method not in AUC_SUMMATIONS:
+            raise ValueError('Invalid AUC summation method value "%s". Valid values are: %s' % (summation_method, sorted(AUC_SUMMATIONS)))
+        if dtype not in (None, torch.float32, "float32"):
+            raise ValueError("AUC: dtype %r (the state is float32, as Keras' default)" % (dtype,))
+        if thresholds is not None:
+            thresholds = sorted(float(t) for t in thresholds)
+            if any(not (0.0 <= t <= 1.0) for t in thresholds):
+                raise ValueError("Threshold values must be in [0, 1]. Invalid values: %s" % [t for t in thresholds if not (0.0 <= t <= 1.0)])
+            self.num_thresholds = len(thresholds) + 2
+        else:
+            if num_thresholds <= 1:
+                raise ValueError("`num_thresholds` must be > 1.")
+            self.num_thresholds = int(num_thresholds)
+            thresholds = [(i + 1) * 1.0 / (self.num_thresholds - 1) for i in range(self.num_thresholds - 2)]
+        if self.num_thresholds > _lib.FIL_CONFUSION_MAX_T:
+            raise ValueError("AUC: %d thresholds (at most FIL_CONFUSION_MAX_T = %d)" % (self.num_thresholds, _lib.FIL_CONFUSION_MAX_T))
+        # python floats, as in Keras (K.epsilon() end points); ONE rounding to float32 when they go to the device
+        self.thresholds = [0.0 - 1e-7] + thresholds + [1.0 + 1e-7]
+        self.curve, self.summation_method = curve, summation_method
+        self.name = "auc" if name is None else name
+        self.dtype = torch.float32
+        self.confusion = self.invalid = self._thr = self._out = None
+
+    # ---- state
+    def build(self, device):
+        """Create the state on `device` (update_state does it on its first call).  Do this before capturing a step."""
+        if self.confusion is not None:
+            return self
+        device = torch.device(device)
+        if device.type != "cuda":
+            raise _lib.FilError("ml_function_amd runs on the GPU only (got a %s tensor); there is no CPU fallback" % device.type)
+        self._thr = torch.tensor(self.thresholds, dtype=torch.float64).to(torch.float32).to(device)
+        self.confusion = torch.zeros((4, self.num_thresholds), dtype=torch.float32, device=device)
+        self.invalid = torch.zeros((1,), dtype=torch.int64, device=device)
+        self._out = torch.zeros((1,), dtype=torch.float32, device=device)
+        return self
+
+    true_positives = property(lambda self: None if self.confusion is None else self.confusion[0])
+    false_positives = property(lambda self: None if self.confusion is None else self.confusion[1])
+    true_negatives = property(lambda self: None if self.confusion is None else self.confusion[2])
+    false_negatives = property(lambda self: None if self.confusion is None else self.confusion[3])
+
+    def update_state(self, y_true, y_pred, sample_weight=None):
+        """Add one batch (any shape, flattened; labels of any dtype, non-zero = positive).  Capturable once the state exists."""
+        from . import functional as Fn
+        if sample_weight is not None:
+            raise NotImplementedError("AUC.update_state: sample_weight is not supported (a weighted float32 sum has no order-independent "
+                                      "value, and this library's results repeat bit for bit); pass sample_weight=None")
+        if not (torch.is_tensor(y_true) and torch.is_tensor(y_pred)):
+            raise TypeError("AUC.update_state takes torch tensors")
+        Fn._require_cuda(y_pred, y_true)
+        if y_true.numel() != y_pred.numel():
+            raise ValueError("AUC.update_state: y_true has %d elements, y_pred %d" % (y_true.numel(), y_pred.numel()))
+        self.build(y_pred.device)
+        p = y_pred.detach().reshape(-1)
+        y = y_true.detach().reshape(-1)
+        p = p if p.dtype == torch.float32 else p.to(torch.float32)
+        y = y if y.dtype == torch.float32 else (y != 0).to(torch.float32)          # tf.cast(y_true, bool)
+        for lo in range(0, p.numel(), _SLICE):
+            Fn.confusion_update(p[lo:lo + _SLICE], y[lo:lo + _SLICE], self._thr, self.confusion, self.invalid)
+
+    def reset_states(self):
+        """Zero the state in place (a captured graph keeps its pointers)."""
+        if self.confusion is not None:
+            self.confusion.zero_()
+            self.invalid.zero_()
+
+    def state_dict(self):
+        """The counts for a checkpoint (clones; an AUC that has seen nothing has an empty state)."""
+        d = dict(num_thresholds=self.num_thresholds, thresholds=list(self.thresholds), curve=self.curve, summation_method=self.summation_method)
+        if self.confusion is not None:
+            d.update(confusion=self.confusion.clone(), invalid=self.invalid.clone())
+        return d
+
+    def load_state_dict(self, state, device=None):
+        """Copy a state_dict()'s counts into this metric's state IN PLACE (created first, on `device` or the saved tensors' device, when
+        this metric has none yet).  The thresholds must be the same."""
+        if list(state["thresholds"]) != list(self.thresholds):
+            raise ValueError("AUC.load_state_dict: the checkpoint was taken with other thresholds")
+        if "confusion" not in state:
+            self.reset_states()
+            return
+        if self.confusion is None:
+            self.build(device if device is not None else state["confusion"].device)
+        self.confusion.copy_(state["confusion"])
+        self.invalid.copy_(state["invalid"].reshape(1))
+
+    # ---- reading
+    def _reduced(self, process_group):
+        """SUM over the group of COPIES of the counts and of the invalid counter; the local state is not touched."""
+        import torch.distributed as dist
+        cm, bad = self.confusion.clone(), self.invalid.clone()
+        dist.all_reduce(cm, op=dist.ReduceOp.SUM, group=process_group)
+        dist.all_reduce(bad, op=dist.ReduceOp.SUM, group=process_group)
+        return cm, bad
+
+    def result(self, process_group=None):
+        """Keras' AUC.result() as a 0-dim float32 device tensor; no host synchronisation and NO check of `invalid` (result_value()
+        checks).  Without a group the same static tensor is returned every time (an output of a captured step stays valid across
+        replays).  process_group: the whole group's AUC -- the counts of every rank summed into a copy (all ranks must call; the
+        local state is left as it is, so this can be read mid-epoch, repeatedly)."""
+        from . import functional as Fn
+        if self.confusion is None:
+            if process_group is not None:
+                raise _lib.FilError("AUC.result(process_group=...): this rank has no state yet (call build(device) or update_state first)")
+            return torch.zeros((), dtype=torch.float32)         # Keras: 0.0 before any update
+        if process_group is None:
+            return Fn.auc_result(self.confusion, self.curve, self.summation_method, out=self._out)
+        return Fn.auc_result(self._reduced(process_group)[0], self.curve, self.summation_method)
+
+    def result_value(self, process_group=None):
+        """float(result()) after checking, on the host, that no score was outside [0, 1] (or NaN): raises ValueError with the count
+        otherwise -- where TensorFlow's assertion would have failed in update_state.  Synchronises."""
+        from . import functional as Fn
+        if self.confusion is None:
+            return float(self.result(process_group))
+        cm, bad = (self.confusion, self.invalid) if process_group is None else self._reduced(process_group)
+        out = Fn.auc_result(cm, self.curve, self.summation_method)
+        bad = int(bad.item())
+        if bad:
+            raise ValueError("AUC: %d predictions were outside [0, 1] (or NaN); they were left out of the counts" % bad)
+        return float(out)
