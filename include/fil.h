@@ -493,6 +493,86 @@ int fil_embed_rowopt_merged(const int64_t* ids, const float* values, const int64
                             const int64_t* step, int rule, const fil_rowopt_hyper* hyper, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * O3  Keras' learning-rate schedules (tf.keras.optimizers.schedules, TF 2.1) and the legacy `decay` of OptimizerV2._decayed_lr,
+ *     evaluated ON THE DEVICE from the step counter, so a captured step changes its rate on every replay.  Entry points added only:
+ *     the ABI version stays.
+ *   fil_lr_schedule: a POD descriptor.  step = *step (Keras' iterations: completed steps, 0 at the first step), s = (float)step;
+ *     every constant is fp32 and every operation rounds to fp32 as written (no fused multiply-add), except the two powers, which
+ *     are pow((double)base, (double)p) rounded once to fp32:
+ *       FIL_LR_CONSTANT      lr = initial_lr
+ *       FIL_LR_EXPONENTIAL   p = s / decay_steps (floor(p) when flag);  lr = initial_lr * pow(decay_rate, p)
+ *       FIL_LR_INVERSE_TIME  p as above;  lr = initial_lr / (1 + decay_rate * p)
+ *       FIL_LR_POLYNOMIAL    flag (cycle): d = decay_steps * (s == 0 ? 1 : ceil(s / decay_steps)), else s = min(s, decay_steps),
+ *                            d = decay_steps;  p = s / d;  lr = (initial_lr - end_lr) * pow(1 - p, power) + end_lr
+ *                            (power == 1: the base itself, x ** 1.0 == x)
+ *       FIL_LR_PIECEWISE     lr = values[i] for the first i < n_boundaries with step <= boundaries[i] (int64 comparisons),
+ *                            values[n_boundaries] beyond the last; boundaries non-decreasing, n_boundaries <= 32
+ *     then, when decay > 0:  lr = lr / (1 + decay * s).
+ *   fil_lr_schedule_check: validates a descriptor in HOST memory (kind, decay_steps > 0, n_boundaries, their order, decay >= 0);
+ *     the caller then copies it to the device once.
+ *   fil_lr_schedule_eval: one one-thread launch, lr_out[0] = the rate of the step about to run.  sched, step, lr_out: device memory.
+ *     Queued once per (step, device) before the first update launch; every update launch of the step then reads the same bits.
+ *   The *_lrdev variants are the update entry points of O1 / O2 with the rate read from device memory (lr_dev, one fp32, not
+ *     NULL) in place of the by-value `lr` (fil_rowopt_hyper.lr is ignored); everything else, the kernels included, is unchanged.
+ *     fil_embed_adam_roll_lrdev writes the step's ring entry from *lr_dev: a replayed step takes the rate of the step it replays
+ *     (FIL_ADAM_ROLL_FLUSH and _SKIP read no rate, but lr_dev must still be valid device memory).
+ */
+#define FIL_LR_MAX_BOUNDARIES 32
+enum { FIL_LR_CONSTANT = 0, FIL_LR_EXPONENTIAL = 1, FIL_LR_INVERSE_TIME = 2, FIL_LR_POLYNOMIAL = 3, FIL_LR_PIECEWISE = 4 };
+typedef struct {
+  int32_t kind;
+  int32_t flag;           /* exponential / inverse time: staircase; polynomial: cycle */
+  float initial_lr;
+  float decay_steps;
+  float decay_rate;
+  float end_lr;           /* polynomial */
+  float power;            /* polynomial */
+  float decay;            /* the legacy keyword; 0 = none */
+  int32_t n_boundaries;   /* piecewise */
+  int32_t reserved;       /* 0 */
+  int64_t boundaries[FIL_LR_MAX_BOUNDARIES];
+  float values[FIL_LR_MAX_BOUNDARIES + 1];
+  int32_t reserved2;      /* 0 */
+} fil_lr_schedule;        /* 432 bytes */
+int fil_lr_schedule_check(const fil_lr_schedule* host_sched);
+int fil_lr_schedule_eval(const fil_lr_schedule* sched, const int64_t* step, float* lr_out, void* stream);
+int fil_adam_multi_lrdev(const fil_adam_tensor* tensors, int n, int64_t total_numel, int64_t* step, const float* lr_dev, float beta_1,
+                         float beta_2, float epsilon, int advance, void* stream);
+int fil_embed_adam_runs_lrdev(const void* g, const int64_t* perm, const int64_t* sorted_ids, long R, int K, int g_dtype, int F,
+                              const float* field_l2, float* table, float* m, float* v, int32_t* stamp, const int64_t* step,
+                              const float* lr_dev, float beta_1, float beta_2, float epsilon, int mode, void* stream);
+int fil_embed_adam_sweep_lrdev(float* table, float* m, float* v, const int32_t* stamp, int64_t V, int K, const int64_t* offsets,
+                               const float* field_l2, const unsigned char* frozen, int F, const int64_t* step, const float* lr_dev,
+                               float beta_1, float beta_2, float epsilon, void* stream);
+int fil_embed_adam_merged_lrdev(const int64_t* ids, const float* values, const int64_t* counts, int W, long cap, int K,
+                                const int64_t* offsets, const float* field_l2, int F, float* table, float* m, float* v, int32_t* stamp,
+                                int64_t V, const int64_t* step, const float* lr_dev, float beta_1, float beta_2, float epsilon, int mode,
+                                void* stream);
+int fil_embed_adam_runs_deferred_lrdev(const void* g, const int64_t* perm, const int64_t* sorted_ids, long R, int K, int g_dtype, int F,
+                                       const int64_t* offsets, const float* field_l2, const unsigned char* frozen, float* table, float* m,
+                                       float* v, int32_t* stamp, const float* ring, int sweep_period, int64_t V, const int64_t* step,
+                                       const float* lr_dev, float beta_1, float beta_2, float epsilon, void* stream);
+int fil_embed_adam_merged_deferred_lrdev(const int64_t* ids, const float* values, const int64_t* counts, int W, long cap, int K,
+                                         const int64_t* offsets, const float* field_l2, const unsigned char* frozen, int F, float* table,
+                                         float* m, float* v, int32_t* stamp, const float* ring, int sweep_period, int64_t V,
+                                         const int64_t* step, const float* lr_dev, float beta_1, float beta_2, float epsilon, void* stream);
+int fil_embed_adam_roll_lrdev(float* table, float* m, float* v, int32_t* stamp, float* ring, int sweep_period, int64_t V, int K,
+                              const int64_t* offsets, const float* field_l2, const unsigned char* frozen, int F, const int64_t* step,
+                              const float* lr_dev, float beta_1, float beta_2, float epsilon, int flags, void* stream);
+int fil_rowopt_multi_lrdev(const fil_adam_tensor* tensors, int n, int64_t total_numel, int64_t* step, int rule,
+                           const fil_rowopt_hyper* hyper, const float* lr_dev, int advance, void* stream);
+int fil_embed_rowopt_runs_lrdev(const void* g, const int64_t* perm, const int64_t* sorted_ids, long R, int K, int g_dtype, int F,
+                                const float* field_l2, float* table, float* accum, float* linear, int32_t* stamp, const int64_t* step,
+                                int rule, const fil_rowopt_hyper* hyper, const float* lr_dev, void* stream);
+int fil_embed_rowopt_sweep_lrdev(float* table, float* accum, float* linear, const int32_t* stamp, int64_t V, int K, const int64_t* offsets,
+                                 const float* field_l2, const unsigned char* frozen, int F, const int64_t* step, int rule,
+                                 const fil_rowopt_hyper* hyper, const float* lr_dev, void* stream);
+int fil_embed_rowopt_merged_lrdev(const int64_t* ids, const float* values, const int64_t* counts, int W, long cap, int K,
+                                  const int64_t* offsets, const float* field_l2, int F, float* table, float* accum, float* linear,
+                                  int32_t* stamp, int64_t V, const int64_t* step, int rule, const fil_rowopt_hyper* hyper,
+                                  const float* lr_dev, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * M1  Keras' streaming AUC (TF 2.1 keras/metrics.py: AUC; keras/utils/metrics_utils.py: update_confusion_matrix_variables) --
  *     replaces metrics=[tf.keras.metrics.AUC()] of example/ctr_example/un_seq.py:61.  Entry points added only: the ABI version stays.
  *   State: cm [4][T] fp32 = TP | FP | TN | FN per threshold, as Keras keeps them, and one int64 `invalid`.

@@ -101,6 +101,22 @@ SIGNATURES = {
     "fil_embed_rowopt_runs": (_I, [_P, _P, _P, _c.c_long, _I, _I, _I, _P, _P, _P, _P, _P, _P, _I, _P, _P]),
     "fil_embed_rowopt_sweep": (_I, [_P, _P, _P, _P, _c.c_int64, _I, _P, _P, _P, _I, _P, _I, _P, _P]),
     "fil_embed_rowopt_merged": (_I, [_P, _P, _P, _I, _c.c_long, _I, _P, _P, _I, _P, _P, _P, _P, _c.c_int64, _P, _I, _P, _P]),
+    # O3: the evaluation of a schedule and the device-rate variants (lr_dev in place of lr; beside the hyper for the rowwise rules)
+    "fil_lr_schedule_check": (_I, [_P]),
+    "fil_lr_schedule_eval": (_I, [_P, _P, _P, _P]),
+    "fil_adam_multi_lrdev": (_I, [_P, _I, _c.c_int64, _P, _P, _F, _F, _F, _I, _P]),
+    "fil_embed_adam_runs_lrdev": (_I, [_P, _P, _P, _c.c_long, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _F, _F, _F, _I, _P]),
+    "fil_embed_adam_sweep_lrdev": (_I, [_P, _P, _P, _P, _c.c_int64, _I, _P, _P, _P, _I, _P, _P, _F, _F, _F, _P]),
+    "fil_embed_adam_merged_lrdev": (_I, [_P, _P, _P, _I, _c.c_long, _I, _P, _P, _I, _P, _P, _P, _P, _c.c_int64, _P, _P, _F, _F, _F, _I, _P]),
+    "fil_embed_adam_runs_deferred_lrdev": (_I, [_P, _P, _P, _c.c_long, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _I, _c.c_int64, _P, _P,
+                                                _F, _F, _F, _P]),
+    "fil_embed_adam_merged_deferred_lrdev": (_I, [_P, _P, _P, _I, _c.c_long, _I, _P, _P, _P, _I, _P, _P, _P, _P, _P, _I, _c.c_int64, _P, _P,
+                                                  _F, _F, _F, _P]),
+    "fil_embed_adam_roll_lrdev": (_I, [_P, _P, _P, _P, _P, _I, _c.c_int64, _I, _P, _P, _P, _I, _P, _P, _F, _F, _F, _I, _P]),
+    "fil_rowopt_multi_lrdev": (_I, [_P, _I, _c.c_int64, _P, _I, _P, _P, _I, _P]),
+    "fil_embed_rowopt_runs_lrdev": (_I, [_P, _P, _P, _c.c_long, _I, _I, _I, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P]),
+    "fil_embed_rowopt_sweep_lrdev": (_I, [_P, _P, _P, _P, _c.c_int64, _I, _P, _P, _P, _I, _P, _I, _P, _P, _P]),
+    "fil_embed_rowopt_merged_lrdev": (_I, [_P, _P, _P, _I, _c.c_long, _I, _P, _P, _I, _P, _P, _P, _P, _c.c_int64, _P, _I, _P, _P, _P]),
     "fil_confusion_workspace_bytes": (_Z, [_I, _I]),
     "fil_confusion_update": (_I, [_P, _P, _I, _P, _I, _P, _P, _P, _Z, _P]),
     "fil_auc_result": (_I, [_P, _I, _I, _I, _P, _P]),
@@ -110,6 +126,20 @@ SIGNATURES = {
 class RowoptHyper(_c.Structure):
     """fil_rowopt_hyper (include/fil.h O2)"""
     _fields_ = [("lr", _F), ("epsilon", _F), ("lr_power", _F), ("l1", _F), ("l2", _F), ("l2_shrinkage", _F)]
+
+
+FIL_LR_CONSTANT, FIL_LR_EXPONENTIAL, FIL_LR_INVERSE_TIME, FIL_LR_POLYNOMIAL, FIL_LR_PIECEWISE = 0, 1, 2, 3, 4
+FIL_LR_MAX_BOUNDARIES = 32
+
+
+class LrSchedule(_c.Structure):
+    """fil_lr_schedule (include/fil.h O3)"""
+    _fields_ = [("kind", _c.c_int32), ("flag", _c.c_int32), ("initial_lr", _F), ("decay_steps", _F), ("decay_rate", _F), ("end_lr", _F),
+                ("power", _F), ("decay", _F), ("n_boundaries", _c.c_int32), ("reserved", _c.c_int32),
+                ("boundaries", _c.c_int64 * FIL_LR_MAX_BOUNDARIES), ("values", _F * (FIL_LR_MAX_BOUNDARIES + 1)), ("reserved2", _c.c_int32)]
+
+
+assert _c.sizeof(LrSchedule) == 432
 
 
 class FilError(RuntimeError):

@@ -19,11 +19,24 @@ int fail(int code, const char* fmt, ...);
     if (!(cond)) return ::fil::fail(FIL_ERR_ARG, "%s: bad argument: %s", __func__, #cond); \
   } while (0)
 
+// the same check in a body that several entry points share: `who` names the entry point that was called
+#define FIL_CHECK_ARG_W(who, cond)                                                       \
+  do {                                                                                   \
+    if (!(cond)) return ::fil::fail(FIL_ERR_ARG, "%s: bad argument: %s", who, #cond);      \
+  } while (0)
+
 #define FIL_CHECK_LAUNCH()                                                                          \
   do {                                                                                              \
     hipError_t e__ = hipGetLastError();                                                             \
     if (e__ != hipSuccess)                                                                          \
       return ::fil::fail(FIL_ERR_HIP, "%s: kernel launch failed: %s", __func__, hipGetErrorString(e__)); \
+  } while (0)
+
+#define FIL_CHECK_LAUNCH_W(who)                                                                     \
+  do {                                                                                              \
+    hipError_t e__ = hipGetLastError();                                                             \
+    if (e__ != hipSuccess)                                                                          \
+      return ::fil::fail(FIL_ERR_HIP, "%s: kernel launch failed: %s", who, hipGetErrorString(e__));   \
   } while (0)
 
 static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }

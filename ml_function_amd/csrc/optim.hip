@@ -37,6 +37,10 @@ __device__ __forceinline__ AdamCoef adam_coef(const int64_t* step, float lr, flo
   return c;
 }
 
+// the step's rate: the by-value one, or the word fil_lr_schedule_eval left on the device (the *_lrdev entry points).  A
+// wave-uniform load, once per kernel.
+__device__ __forceinline__ float rate_of(float lr, const float* __restrict__ lr_dev) { return lr_dev ? *lr_dev : lr; }
+
 // The embedding-table kernels, Keras mode and deferred mode alike, update a row through the two helpers below and nothing else: one
 // definition of each update's rounding, written with contraction off and explicit fmas, so the deferred replays give the Keras-mode
 // bits by construction, whatever the compiler makes of each kernel's context.
@@ -79,8 +83,9 @@ void launch_step_advance(int64_t* step, hipStream_t st) { hipLaunchKernelGGL(ste
 
 // ---- fil_adam_multi: the dense descriptors (multi_tensor_walk, optim_rows.h), g += 2 l2 p where l2 is set
 __global__ __launch_bounds__(256) void adam_multi_kernel(const fil_adam_tensor* __restrict__ ts, int n, const int64_t* __restrict__ step,
-                                                         float lr, float b1, float b2, float eps) {
-  const AdamCoef c = adam_coef(step, lr, b1, b2, eps);
+                                                         float lr, float b1, float b2, float eps,
+                                                         const float* __restrict__ lr_dev) {
+  const AdamCoef c = adam_coef(step, rate_of(lr, lr_dev), b1, b2, eps);
   multi_tensor_walk<true>(ts, n, [=](float& p, float& m, float& v, float g, float l2x2) {
     if (l2x2 != 0.f) g += l2x2 * p;
     adam_elem(p, m, v, g, c);
@@ -94,8 +99,9 @@ __global__ __launch_bounds__(256) void embed_adam_runs_kernel(const GT* __restri
                                                               const int64_t* __restrict__ sorted_ids, long R, int K, int F,
                                                               const float* __restrict__ field_l2, float* __restrict__ table,
                                                               float* __restrict__ m, float* __restrict__ v, int32_t* __restrict__ stamp,
-                                                              const int64_t* __restrict__ step, float lr, float b1, float b2, float eps) {
-  const AdamCoef c = adam_coef(step, lr, b1, b2, eps);
+                                                              const int64_t* __restrict__ step, float lr, float b1, float b2, float eps,
+                                                              const float* __restrict__ lr_dev) {
+  const AdamCoef c = adam_coef(step, rate_of(lr, lr_dev), b1, b2, eps);
   const int32_t tag = (int32_t)(uint32_t)(*step + 1);
   embed_run_sums(g, perm, sorted_ids, R, K, [=](int64_t row, int kq, const float (&acc)[4], int64_t first) {
     const float l2x2 = field_l2 ? 2.f * field_l2[first % F] : 0.f;
@@ -121,7 +127,7 @@ __global__ __launch_bounds__(256) void embed_adam_sweep_kernel(float* __restrict
                                                                const int64_t* __restrict__ offsets, const float* __restrict__ field_l2,
                                                                const unsigned char* __restrict__ frozen, int F,
                                                                const int64_t* __restrict__ step, float lr, float b1, float b2, float eps,
-                                                               int vec) {
+                                                               int vec, const float* __restrict__ lr_dev) {
   __shared__ int64_t s_off[kSweepMaxF];
   __shared__ float s_l2x2[kSweepMaxF];        // 2 l2[f], or NaN for a frozen field
   for (int f = threadIdx.x; f < F; f += blockDim.x) {
@@ -129,7 +135,7 @@ __global__ __launch_bounds__(256) void embed_adam_sweep_kernel(float* __restrict
     s_l2x2[f] = (frozen && frozen[f]) ? __builtin_nanf("") : (field_l2 ? 2.f * field_l2[f] : 0.f);
   }
   __syncthreads();
-  const AdamCoef c = adam_coef(step, lr, b1, b2, eps);
+  const AdamCoef c = adam_coef(step, rate_of(lr, lr_dev), b1, b2, eps);
   const int32_t tag = (int32_t)(uint32_t)(*step + 1);
   const int64_t n = V * K;
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
@@ -275,11 +281,12 @@ __global__ __launch_bounds__(256) void embed_adam_merged_kernel(const int64_t* _
                                                                 const int64_t* __restrict__ offsets, const float* __restrict__ field_l2,
                                                                 int F, float* __restrict__ table, float* __restrict__ m,
                                                                 float* __restrict__ v, int32_t* __restrict__ stamp, int64_t V,
-                                                                const int64_t* __restrict__ step, float lr, float b1, float b2, float eps) {
+                                                                const int64_t* __restrict__ step, float lr, float b1, float b2, float eps,
+                                                                const float* __restrict__ lr_dev) {
   __shared__ int64_t s_off[kSweepMaxF];
   for (int f = threadIdx.x; f < F; f += blockDim.x) s_off[f] = offsets[f];
   __syncthreads();
-  const AdamCoef c = adam_coef(step, lr, b1, b2, eps);
+  const AdamCoef c = adam_coef(step, rate_of(lr, lr_dev), b1, b2, eps);
   const int32_t tag = (int32_t)(uint32_t)(*step + 1);
   const auto epi = [=](int64_t row, int f, float l2x2, int k0, const float (&acc)[kMergeChunk]) {
 #pragma unroll
@@ -424,12 +431,13 @@ __global__ __launch_bounds__(256) void embed_adam_runs_deferred_kernel(const GT*
                                                                        float* __restrict__ m, float* __restrict__ v,
                                                                        int32_t* __restrict__ stamp, const AdamCoef* __restrict__ ring,
                                                                        int D, int N, int64_t V, const int64_t* __restrict__ step,
-                                                                       float lr, float b1, float b2, float eps, int vec) {
+                                                                       float lr, float b1, float b2, float eps, int vec,
+                                                                       const float* __restrict__ lr_dev) {
   __shared__ FieldTab s;
   load_field_tab(&s, offsets, field_l2, frozen, F);
   __syncthreads();
   const FieldTab* sp = &s;
-  const AdamCoef c = adam_coef(step, lr, b1, b2, eps);
+  const AdamCoef c = adam_coef(step, rate_of(lr, lr_dev), b1, b2, eps);
   const int32_t done = (int32_t)(uint32_t)(*step);
   embed_run_sums(g, perm, sorted_ids, R, K, [=](int64_t row, int kq, const float (&acc)[4], int64_t first) {
     if (row >= V) return;
@@ -470,12 +478,12 @@ __global__ __launch_bounds__(256) void embed_adam_merged_deferred_kernel(const i
                                                                          float* __restrict__ v, int32_t* __restrict__ stamp,
                                                                          const AdamCoef* __restrict__ ring, int D, int N, int64_t V,
                                                                          const int64_t* __restrict__ step, float lr, float b1, float b2,
-                                                                         float eps, int vec) {
+                                                                         float eps, int vec, const float* __restrict__ lr_dev) {
   __shared__ FieldTab s;
   load_field_tab(&s, offsets, field_l2, frozen, F);
   __syncthreads();
   const FieldTab* sp = &s;
-  const AdamCoef c = adam_coef(step, lr, b1, b2, eps);
+  const AdamCoef c = adam_coef(step, rate_of(lr, lr_dev), b1, b2, eps);
   const int32_t done = (int32_t)(uint32_t)(*step);
   const auto epi = [=](int64_t row, int f, float l2x2, int k0, const float (&acc)[kMergeChunk]) {
     const float r2 = f >= 0 ? sp->l2x2[f] : 0.f;
@@ -508,7 +516,7 @@ __global__ __launch_bounds__(256) void embed_adam_roll_kernel(float* __restrict_
                                                               int64_t V, int K, int lgG, int vec, const int64_t* __restrict__ offsets,
                                                               const float* __restrict__ field_l2, const unsigned char* __restrict__ frozen,
                                                               int F, const int64_t* __restrict__ step, float lr, float b1, float b2,
-                                                              float eps, int flags) {
+                                                              float eps, int flags, const float* __restrict__ lr_dev) {
   __shared__ FieldTab s;
   __shared__ AdamCoef s_ring[kRingMax];
   const bool flush = (flags & kRollFlush) != 0;
@@ -520,7 +528,7 @@ __global__ __launch_bounds__(256) void embed_adam_roll_kernel(float* __restrict_
   int64_t lo = 0, hi = V;
   if (!flush) {
     // step t's entry: every workgroup holds its own copy (the global one is for later launches only)
-    const AdamCoef ct = (flags & kRollSkip) ? coef_skip() : adam_coef(step, lr, b1, b2, eps);
+    const AdamCoef ct = (flags & kRollSkip) ? coef_skip() : adam_coef(step, rate_of(lr, lr_dev), b1, b2, eps);
     if (threadIdx.x == 0) {
       s_ring[to & (D - 1)] = ct;
       if (blockIdx.x == 0) ring[to & (D - 1)] = ct;
@@ -661,63 +669,92 @@ static int check_hyper(const char* who, float lr, float b1, float b2, float eps)
 
 using namespace fil;
 
-extern "C" int fil_adam_multi(const fil_adam_tensor* tensors, int n, int64_t total_numel, int64_t* step, float lr, float beta_1,
-                              float beta_2, float epsilon, int advance, void* stream) {
-  FIL_CHECK_ARG(n >= 0 && total_numel >= 0);
-  FIL_CHECK_ARG(step != nullptr);
-  FIL_CHECK_ARG(n == 0 || tensors != nullptr);
-  if (int rc = check_hyper("fil_adam_multi", lr, beta_1, beta_2, epsilon)) return rc;
-  if (advance != 0 && advance != 1) return fail(FIL_ERR_ARG, "fil_adam_multi: advance %d (0 or 1)", advance);
+static int adam_multi_impl(const char* who, const fil_adam_tensor* tensors, int n, int64_t total_numel, int64_t* step, float lr,
+                           float beta_1,
+                              float beta_2, float epsilon, int advance, void* stream, const float* lr_dev) {
+  FIL_CHECK_ARG_W(who, n >= 0 && total_numel >= 0);
+  FIL_CHECK_ARG_W(who, step != nullptr);
+  FIL_CHECK_ARG_W(who, n == 0 || tensors != nullptr);
+  if (int rc = check_hyper(who, lr, beta_1, beta_2, epsilon)) return rc;
+  if (advance != 0 && advance != 1) return fail(FIL_ERR_ARG, "%s: advance %d (0 or 1)", who, advance);
   hipStream_t st = (hipStream_t)stream;
   if (n > 0) {
     ProfScope ps("adam_multi", st, 28.0 * (double)total_numel);
     const long chunks = std::max<long>(1, (long)((total_numel + kMultiChunk - 1) / kMultiChunk));
     const dim3 grid((int)std::min<long>(chunks, 256 * 8));
-    hipLaunchKernelGGL(adam_multi_kernel, grid, dim3(256), 0, st, tensors, n, step, lr, beta_1, beta_2, epsilon);
-    FIL_CHECK_LAUNCH();
+    hipLaunchKernelGGL(adam_multi_kernel, grid, dim3(256), 0, st, tensors, n, step, lr, beta_1, beta_2, epsilon, lr_dev);
+    FIL_CHECK_LAUNCH_W(who);
   }
   if (advance) {
     launch_step_advance(step, st);
-    FIL_CHECK_LAUNCH();
+    FIL_CHECK_LAUNCH_W(who);
   }
   return FIL_OK;
 }
 
-extern "C" int fil_embed_adam_runs(const void* g, const int64_t* perm, const int64_t* sorted_ids, long R, int K, int g_dtype, int F,
+extern "C" int fil_adam_multi(const fil_adam_tensor* tensors, int n, int64_t total_numel, int64_t* step, float lr, float beta_1,
+                              float beta_2, float epsilon, int advance, void* stream) {
+  return adam_multi_impl("fil_adam_multi", tensors, n, total_numel, step, lr, beta_1, beta_2, epsilon, advance, stream, nullptr);
+}
+
+extern "C" int fil_adam_multi_lrdev(const fil_adam_tensor* tensors, int n, int64_t total_numel, int64_t* step, const float* lr_dev, float beta_1,
+                              float beta_2, float epsilon, int advance, void* stream) {
+  if (lr_dev == nullptr) return fail(FIL_ERR_ARG, "fil_adam_multi_lrdev: no device rate (lr_dev is NULL)");
+  return adam_multi_impl("fil_adam_multi_lrdev", tensors, n, total_numel, step, 0.f, beta_1, beta_2, epsilon, advance, stream, lr_dev);
+}
+
+static int embed_adam_runs_impl(const char* who, const void* g, const int64_t* perm, const int64_t* sorted_ids, long R, int K, int g_dtype,
+                                int F,
                                    const float* field_l2, float* table, float* m, float* v, int32_t* stamp, const int64_t* step,
-                                   float lr, float beta_1, float beta_2, float epsilon, int mode, void* stream) {
-  FIL_CHECK_ARG(R >= 0 && K >= 1 && F >= 1);
-  if (g_dtype != FIL_F32 && g_dtype != FIL_BF16) return fail(FIL_ERR_ARG, "fil_embed_adam_runs: g_dtype %d (f32 or bf16)", g_dtype);
-  if (mode != FIL_ADAM_KERAS && mode != FIL_ADAM_LAZY) return fail(FIL_ERR_ARG, "fil_embed_adam_runs: mode %d (FIL_ADAM_KERAS or FIL_ADAM_LAZY)", mode);
+                                   float lr, float beta_1, float beta_2, float epsilon, int mode, void* stream, const float* lr_dev) {
+  FIL_CHECK_ARG_W(who, R >= 0 && K >= 1 && F >= 1);
+  if (g_dtype != FIL_F32 && g_dtype != FIL_BF16) return fail(FIL_ERR_ARG, "%s: g_dtype %d (f32 or bf16)", who, g_dtype);
+  if (mode != FIL_ADAM_KERAS && mode != FIL_ADAM_LAZY) return fail(FIL_ERR_ARG, "%s: mode %d (FIL_ADAM_KERAS or FIL_ADAM_LAZY)", who, mode);
   if (mode == FIL_ADAM_KERAS && stamp == nullptr)
-    return fail(FIL_ERR_ARG, "fil_embed_adam_runs: FIL_ADAM_KERAS needs the row stamps (fil_embed_adam_sweep skips the rows stamped here)");
-  if (K > 256) return fail(FIL_ERR_UNSUPPORTED, "fil_embed_adam_runs: K=%d > 256", K);
-  if (int rc = check_hyper("fil_embed_adam_runs", lr, beta_1, beta_2, epsilon)) return rc;
+    return fail(FIL_ERR_ARG, "%s: FIL_ADAM_KERAS needs the row stamps (fil_embed_adam_sweep skips the rows stamped here)", who);
+  if (K > 256) return fail(FIL_ERR_UNSUPPORTED, "%s: K=%d > 256", who, K);
+  if (int rc = check_hyper(who, lr, beta_1, beta_2, epsilon)) return rc;
   if (R == 0) return FIL_OK;
-  FIL_CHECK_ARG(g && perm && sorted_ids && table && m && v && step);
+  FIL_CHECK_ARG_W(who, g && perm && sorted_ids && table && m && v && step);
   hipStream_t st = (hipStream_t)stream;
   ProfScope ps("embed_adam_runs", st, (double)R * K * (g_dtype == FIL_F32 ? 4 : 2) + 24.0 * R * K);
   const int C = 64 / ((K + 3) / 4);
   const dim3 grid((int)std::min<long>((R + 4 * C - 1) / (4 * C), 256 * 32));
   if (g_dtype == FIL_F32)
     hipLaunchKernelGGL(embed_adam_runs_kernel<float>, grid, dim3(256), 0, st, static_cast<const float*>(g), perm, sorted_ids, R, K, F,
-                       field_l2, table, m, v, mode == FIL_ADAM_KERAS ? stamp : nullptr, step, lr, beta_1, beta_2, epsilon);
+                       field_l2, table, m, v, mode == FIL_ADAM_KERAS ? stamp : nullptr, step, lr, beta_1, beta_2, epsilon, lr_dev);
   else
     hipLaunchKernelGGL(embed_adam_runs_kernel<__hip_bfloat16>, grid, dim3(256), 0, st, static_cast<const __hip_bfloat16*>(g), perm,
                        sorted_ids, R, K, F, field_l2, table, m, v, mode == FIL_ADAM_KERAS ? stamp : nullptr, step, lr, beta_1, beta_2,
-                       epsilon);
-  FIL_CHECK_LAUNCH();
+                       epsilon, lr_dev);
+  FIL_CHECK_LAUNCH_W(who);
   return FIL_OK;
 }
 
-extern "C" int fil_embed_adam_sweep(float* table, float* m, float* v, const int32_t* stamp, int64_t V, int K, const int64_t* offsets,
+extern "C" int fil_embed_adam_runs(const void* g, const int64_t* perm, const int64_t* sorted_ids, long R, int K, int g_dtype, int F,
+                                   const float* field_l2, float* table, float* m, float* v, int32_t* stamp, const int64_t* step,
+                                   float lr, float beta_1, float beta_2, float epsilon, int mode, void* stream) {
+  return embed_adam_runs_impl("fil_embed_adam_runs", g, perm, sorted_ids, R, K, g_dtype, F, field_l2, table, m, v, stamp, step, lr, beta_1,
+                              beta_2, epsilon, mode, stream, nullptr);
+}
+
+extern "C" int fil_embed_adam_runs_lrdev(const void* g, const int64_t* perm, const int64_t* sorted_ids, long R, int K, int g_dtype, int F,
+                                   const float* field_l2, float* table, float* m, float* v, int32_t* stamp, const int64_t* step,
+                                   const float* lr_dev, float beta_1, float beta_2, float epsilon, int mode, void* stream) {
+  if (lr_dev == nullptr) return fail(FIL_ERR_ARG, "fil_embed_adam_runs_lrdev: no device rate (lr_dev is NULL)");
+  return embed_adam_runs_impl("fil_embed_adam_runs_lrdev", g, perm, sorted_ids, R, K, g_dtype, F, field_l2, table, m, v, stamp, step, 0.f,
+                              beta_1, beta_2, epsilon, mode, stream, lr_dev);
+}
+
+static int embed_adam_sweep_impl(const char* who, float* table, float* m, float* v, const int32_t* stamp, int64_t V, int K,
+                                 const int64_t* offsets,
                                     const float* field_l2, const unsigned char* frozen, int F, const int64_t* step, float lr,
-                                    float beta_1, float beta_2, float epsilon, void* stream) {
-  FIL_CHECK_ARG(V >= 0 && K >= 1 && F >= 1);
-  if (F > kSweepMaxF) return fail(FIL_ERR_UNSUPPORTED, "fil_embed_adam_sweep: F=%d > %d fields", F, kSweepMaxF);
-  if (int rc = check_hyper("fil_embed_adam_sweep", lr, beta_1, beta_2, epsilon)) return rc;
+                                    float beta_1, float beta_2, float epsilon, void* stream, const float* lr_dev) {
+  FIL_CHECK_ARG_W(who, V >= 0 && K >= 1 && F >= 1);
+  if (F > kSweepMaxF) return fail(FIL_ERR_UNSUPPORTED, "%s: F=%d > %d fields", who, F, kSweepMaxF);
+  if (int rc = check_hyper(who, lr, beta_1, beta_2, epsilon)) return rc;
   if (V == 0) return FIL_OK;
-  FIL_CHECK_ARG(table && m && v && stamp && offsets && step);
+  FIL_CHECK_ARG_W(who, table && m && v && stamp && offsets && step);
   hipStream_t st = (hipStream_t)stream;
   const int64_t n = V * K;
   const int vec = (K % 4 == 0 && ((((uintptr_t)table | (uintptr_t)m | (uintptr_t)v) & 15) == 0)) ? 1 : 0;
@@ -725,9 +762,24 @@ extern "C" int fil_embed_adam_sweep(float* table, float* m, float* v, const int3
   ProfScope ps("embed_adam_sweep", st, 24.0 * (double)n + 4.0 * (double)V);
   const dim3 grid((int)std::max<int64_t>(1, std::min<int64_t>((work + 255) / 256, 256 * 8)));
   hipLaunchKernelGGL(embed_adam_sweep_kernel, grid, dim3(256), 0, st, table, m, v, stamp, V, K, offsets, field_l2, frozen, F, step, lr,
-                     beta_1, beta_2, epsilon, vec);
-  FIL_CHECK_LAUNCH();
+                     beta_1, beta_2, epsilon, vec, lr_dev);
+  FIL_CHECK_LAUNCH_W(who);
   return FIL_OK;
+}
+
+extern "C" int fil_embed_adam_sweep(float* table, float* m, float* v, const int32_t* stamp, int64_t V, int K, const int64_t* offsets,
+                                    const float* field_l2, const unsigned char* frozen, int F, const int64_t* step, float lr,
+                                    float beta_1, float beta_2, float epsilon, void* stream) {
+  return embed_adam_sweep_impl("fil_embed_adam_sweep", table, m, v, stamp, V, K, offsets, field_l2, frozen, F, step, lr, beta_1, beta_2,
+                               epsilon, stream, nullptr);
+}
+
+extern "C" int fil_embed_adam_sweep_lrdev(float* table, float* m, float* v, const int32_t* stamp, int64_t V, int K, const int64_t* offsets,
+                                    const float* field_l2, const unsigned char* frozen, int F, const int64_t* step, const float* lr_dev,
+                                    float beta_1, float beta_2, float epsilon, void* stream) {
+  if (lr_dev == nullptr) return fail(FIL_ERR_ARG, "fil_embed_adam_sweep_lrdev: no device rate (lr_dev is NULL)");
+  return embed_adam_sweep_impl("fil_embed_adam_sweep_lrdev", table, m, v, stamp, V, K, offsets, field_l2, frozen, F, step, 0.f, beta_1,
+                               beta_2, epsilon, stream, lr_dev);
 }
 
 
@@ -778,27 +830,44 @@ extern "C" int fil_embed_runs_compact(const void* g, const int64_t* perm, const 
   return FIL_OK;
 }
 
-extern "C" int fil_embed_adam_merged(const int64_t* ids, const float* values, const int64_t* counts, int W, long cap, int K,
+static int embed_adam_merged_impl(const char* who, const int64_t* ids, const float* values, const int64_t* counts, int W, long cap, int K,
                                      const int64_t* offsets, const float* field_l2, int F, float* table, float* m, float* v, int32_t* stamp,
                                      int64_t V, const int64_t* step, float lr, float beta_1, float beta_2, float epsilon, int mode,
-                                     void* stream) {
-  FIL_CHECK_ARG(W >= 1 && cap >= 0 && K >= 1 && F >= 1 && V >= 0);
-  if (mode != FIL_ADAM_KERAS && mode != FIL_ADAM_LAZY) return fail(FIL_ERR_ARG, "fil_embed_adam_merged: mode %d (FIL_ADAM_KERAS or FIL_ADAM_LAZY)", mode);
+                                     void* stream, const float* lr_dev) {
+  FIL_CHECK_ARG_W(who, W >= 1 && cap >= 0 && K >= 1 && F >= 1 && V >= 0);
+  if (mode != FIL_ADAM_KERAS && mode != FIL_ADAM_LAZY) return fail(FIL_ERR_ARG, "%s: mode %d (FIL_ADAM_KERAS or FIL_ADAM_LAZY)", who, mode);
   if (mode == FIL_ADAM_KERAS && stamp == nullptr)
-    return fail(FIL_ERR_ARG, "fil_embed_adam_merged: FIL_ADAM_KERAS needs the row stamps (fil_embed_adam_sweep skips the rows stamped here)");
-  if (K > 256) return fail(FIL_ERR_UNSUPPORTED, "fil_embed_adam_merged: K=%d > 256", K);
-  if (F > kSweepMaxF) return fail(FIL_ERR_UNSUPPORTED, "fil_embed_adam_merged: F=%d > %d fields", F, kSweepMaxF);
-  if (int rc = check_hyper("fil_embed_adam_merged", lr, beta_1, beta_2, epsilon)) return rc;
+    return fail(FIL_ERR_ARG, "%s: FIL_ADAM_KERAS needs the row stamps (fil_embed_adam_sweep skips the rows stamped here)", who);
+  if (K > 256) return fail(FIL_ERR_UNSUPPORTED, "%s: K=%d > 256", who, K);
+  if (F > kSweepMaxF) return fail(FIL_ERR_UNSUPPORTED, "%s: F=%d > %d fields", who, F, kSweepMaxF);
+  if (int rc = check_hyper(who, lr, beta_1, beta_2, epsilon)) return rc;
   if (cap == 0 || V == 0) return FIL_OK;
-  FIL_CHECK_ARG(ids && values && counts && offsets && table && m && v && step);
+  FIL_CHECK_ARG_W(who, ids && values && counts && offsets && table && m && v && step);
   hipStream_t st = (hipStream_t)stream;
   const long n = (long)W * cap;
   ProfScope ps("embed_adam_merged", st, 8.0 * n + 4.0 * (double)n * K + 24.0 * (double)cap * K);
   const dim3 grid((int)std::max<long>(1, std::min<long>((n + 255) / 256, 256 * 8)));
   hipLaunchKernelGGL(embed_adam_merged_kernel, grid, dim3(256), 0, st, ids, values, counts, W, cap, K, offsets, field_l2, F, table, m, v,
-                     mode == FIL_ADAM_KERAS ? stamp : nullptr, V, step, lr, beta_1, beta_2, epsilon);
-  FIL_CHECK_LAUNCH();
+                     mode == FIL_ADAM_KERAS ? stamp : nullptr, V, step, lr, beta_1, beta_2, epsilon, lr_dev);
+  FIL_CHECK_LAUNCH_W(who);
   return FIL_OK;
+}
+
+extern "C" int fil_embed_adam_merged(const int64_t* ids, const float* values, const int64_t* counts, int W, long cap, int K,
+                                     const int64_t* offsets, const float* field_l2, int F, float* table, float* m, float* v, int32_t* stamp,
+                                     int64_t V, const int64_t* step, float lr, float beta_1, float beta_2, float epsilon, int mode,
+                                     void* stream) {
+  return embed_adam_merged_impl("fil_embed_adam_merged", ids, values, counts, W, cap, K, offsets, field_l2, F, table, m, v, stamp, V, step,
+                                lr, beta_1, beta_2, epsilon, mode, stream, nullptr);
+}
+
+extern "C" int fil_embed_adam_merged_lrdev(const int64_t* ids, const float* values, const int64_t* counts, int W, long cap, int K,
+                                     const int64_t* offsets, const float* field_l2, int F, float* table, float* m, float* v, int32_t* stamp,
+                                     int64_t V, const int64_t* step, const float* lr_dev, float beta_1, float beta_2, float epsilon, int mode,
+                                     void* stream) {
+  if (lr_dev == nullptr) return fail(FIL_ERR_ARG, "fil_embed_adam_merged_lrdev: no device rate (lr_dev is NULL)");
+  return embed_adam_merged_impl("fil_embed_adam_merged_lrdev", ids, values, counts, W, cap, K, offsets, field_l2, F, table, m, v, stamp, V,
+                                step, 0.f, beta_1, beta_2, epsilon, mode, stream, lr_dev);
 }
 
 
@@ -823,16 +892,17 @@ extern "C" int fil_embed_adam_catchup_runs(const int64_t* sorted_ids, long R, in
   return FIL_OK;
 }
 
-extern "C" int fil_embed_adam_runs_deferred(const void* g, const int64_t* perm, const int64_t* sorted_ids, long R, int K, int g_dtype,
+static int embed_adam_runs_deferred_impl(const char* who, const void* g, const int64_t* perm, const int64_t* sorted_ids, long R, int K,
+                                         int g_dtype,
                                             int F, const int64_t* offsets, const float* field_l2, const unsigned char* frozen, float* table,
                                             float* m, float* v, int32_t* stamp, const float* ring, int sweep_period, int64_t V,
-                                            const int64_t* step, float lr, float beta_1, float beta_2, float epsilon, void* stream) {
-  FIL_CHECK_ARG(R >= 0 && K >= 1 && F >= 1 && V >= 0);
-  if (g_dtype != FIL_F32 && g_dtype != FIL_BF16) return fail(FIL_ERR_ARG, "fil_embed_adam_runs_deferred: g_dtype %d (f32 or bf16)", g_dtype);
-  if (int rc = check_deferred("fil_embed_adam_runs_deferred", K, F, sweep_period, ring)) return rc;
-  if (int rc = check_hyper("fil_embed_adam_runs_deferred", lr, beta_1, beta_2, epsilon)) return rc;
+                                            const int64_t* step, float lr, float beta_1, float beta_2, float epsilon, void* stream, const float* lr_dev) {
+  FIL_CHECK_ARG_W(who, R >= 0 && K >= 1 && F >= 1 && V >= 0);
+  if (g_dtype != FIL_F32 && g_dtype != FIL_BF16) return fail(FIL_ERR_ARG, "%s: g_dtype %d (f32 or bf16)", who, g_dtype);
+  if (int rc = check_deferred(who, K, F, sweep_period, ring)) return rc;
+  if (int rc = check_hyper(who, lr, beta_1, beta_2, epsilon)) return rc;
   if (R == 0 || V == 0) return FIL_OK;
-  FIL_CHECK_ARG(g && perm && sorted_ids && offsets && table && m && v && stamp && ring && step);
+  FIL_CHECK_ARG_W(who, g && perm && sorted_ids && offsets && table && m && v && stamp && ring && step);
   hipStream_t st = (hipStream_t)stream;
   ProfScope ps("embed_adam_runs_deferred", st, (double)R * K * (g_dtype == FIL_F32 ? 4 : 2) + 24.0 * R * K);
   const int C = 64 / ((K + 3) / 4);
@@ -842,12 +912,52 @@ extern "C" int fil_embed_adam_runs_deferred(const void* g, const int64_t* perm, 
   if (g_dtype == FIL_F32)
     hipLaunchKernelGGL(embed_adam_runs_deferred_kernel<float>, grid, dim3(256), 0, st, static_cast<const float*>(g), perm, sorted_ids, R,
                        K, F, offsets, field_l2, frozen, table, m, v, stamp, rg, D, sweep_period, V, step, lr, beta_1, beta_2, epsilon,
-                       sweep_vec(K, table, m, v));
+                       sweep_vec(K, table, m, v), lr_dev);
   else
     hipLaunchKernelGGL(embed_adam_runs_deferred_kernel<__hip_bfloat16>, grid, dim3(256), 0, st, static_cast<const __hip_bfloat16*>(g),
                        perm, sorted_ids, R, K, F, offsets, field_l2, frozen, table, m, v, stamp, rg, D, sweep_period, V, step, lr, beta_1,
-                       beta_2, epsilon, sweep_vec(K, table, m, v));
-  FIL_CHECK_LAUNCH();
+                       beta_2, epsilon, sweep_vec(K, table, m, v), lr_dev);
+  FIL_CHECK_LAUNCH_W(who);
+  return FIL_OK;
+}
+
+extern "C" int fil_embed_adam_runs_deferred(const void* g, const int64_t* perm, const int64_t* sorted_ids, long R, int K, int g_dtype,
+                                            int F, const int64_t* offsets, const float* field_l2, const unsigned char* frozen, float* table,
+                                            float* m, float* v, int32_t* stamp, const float* ring, int sweep_period, int64_t V,
+                                            const int64_t* step, float lr, float beta_1, float beta_2, float epsilon, void* stream) {
+  return embed_adam_runs_deferred_impl("fil_embed_adam_runs_deferred", g, perm, sorted_ids, R, K, g_dtype, F, offsets, field_l2, frozen,
+                                       table, m, v, stamp, ring, sweep_period, V, step, lr, beta_1, beta_2, epsilon, stream, nullptr);
+}
+
+extern "C" int fil_embed_adam_runs_deferred_lrdev(const void* g, const int64_t* perm, const int64_t* sorted_ids, long R, int K, int g_dtype,
+                                            int F, const int64_t* offsets, const float* field_l2, const unsigned char* frozen, float* table,
+                                            float* m, float* v, int32_t* stamp, const float* ring, int sweep_period, int64_t V,
+                                            const int64_t* step, const float* lr_dev, float beta_1, float beta_2, float epsilon, void* stream) {
+  if (lr_dev == nullptr) return fail(FIL_ERR_ARG, "fil_embed_adam_runs_deferred_lrdev: no device rate (lr_dev is NULL)");
+  return embed_adam_runs_deferred_impl("fil_embed_adam_runs_deferred_lrdev", g, perm, sorted_ids, R, K, g_dtype, F, offsets, field_l2,
+                                       frozen, table, m, v, stamp, ring, sweep_period, V, step, 0.f, beta_1, beta_2, epsilon, stream,
+                                       lr_dev);
+}
+
+static int embed_adam_merged_deferred_impl(const char* who, const int64_t* ids, const float* values, const int64_t* counts, int W, long cap,
+                                           int K,
+                                              const int64_t* offsets, const float* field_l2, const unsigned char* frozen, int F,
+                                              float* table, float* m, float* v, int32_t* stamp, const float* ring, int sweep_period,
+                                              int64_t V, const int64_t* step, float lr, float beta_1, float beta_2, float epsilon,
+                                              void* stream, const float* lr_dev) {
+  FIL_CHECK_ARG_W(who, W >= 1 && cap >= 0 && K >= 1 && F >= 1 && V >= 0);
+  if (int rc = check_deferred(who, K, F, sweep_period, ring)) return rc;
+  if (int rc = check_hyper(who, lr, beta_1, beta_2, epsilon)) return rc;
+  if (cap == 0 || V == 0) return FIL_OK;
+  FIL_CHECK_ARG_W(who, ids && values && counts && offsets && table && m && v && stamp && ring && step);
+  hipStream_t st = (hipStream_t)stream;
+  const long n = (long)W * cap;
+  ProfScope ps("embed_adam_merged_deferred", st, 8.0 * n + 4.0 * (double)n * K + 24.0 * (double)cap * K);
+  const dim3 grid((int)std::max<long>(1, std::min<long>((n + 255) / 256, 256 * 8)));
+  hipLaunchKernelGGL(embed_adam_merged_deferred_kernel, grid, dim3(256), 0, st, ids, values, counts, W, cap, K, offsets, field_l2, frozen,
+                     F, table, m, v, stamp, reinterpret_cast<const AdamCoef*>(ring), ring_len(sweep_period), sweep_period, V, step, lr,
+                     beta_1, beta_2, epsilon, sweep_vec(K, table, m, v), lr_dev);
+  FIL_CHECK_LAUNCH_W(who);
   return FIL_OK;
 }
 
@@ -856,32 +966,31 @@ extern "C" int fil_embed_adam_merged_deferred(const int64_t* ids, const float* v
                                               float* table, float* m, float* v, int32_t* stamp, const float* ring, int sweep_period,
                                               int64_t V, const int64_t* step, float lr, float beta_1, float beta_2, float epsilon,
                                               void* stream) {
-  FIL_CHECK_ARG(W >= 1 && cap >= 0 && K >= 1 && F >= 1 && V >= 0);
-  if (int rc = check_deferred("fil_embed_adam_merged_deferred", K, F, sweep_period, ring)) return rc;
-  if (int rc = check_hyper("fil_embed_adam_merged_deferred", lr, beta_1, beta_2, epsilon)) return rc;
-  if (cap == 0 || V == 0) return FIL_OK;
-  FIL_CHECK_ARG(ids && values && counts && offsets && table && m && v && stamp && ring && step);
-  hipStream_t st = (hipStream_t)stream;
-  const long n = (long)W * cap;
-  ProfScope ps("embed_adam_merged_deferred", st, 8.0 * n + 4.0 * (double)n * K + 24.0 * (double)cap * K);
-  const dim3 grid((int)std::max<long>(1, std::min<long>((n + 255) / 256, 256 * 8)));
-  hipLaunchKernelGGL(embed_adam_merged_deferred_kernel, grid, dim3(256), 0, st, ids, values, counts, W, cap, K, offsets, field_l2, frozen,
-                     F, table, m, v, stamp, reinterpret_cast<const AdamCoef*>(ring), ring_len(sweep_period), sweep_period, V, step, lr,
-                     beta_1, beta_2, epsilon, sweep_vec(K, table, m, v));
-  FIL_CHECK_LAUNCH();
-  return FIL_OK;
+  return embed_adam_merged_deferred_impl("fil_embed_adam_merged_deferred", ids, values, counts, W, cap, K, offsets, field_l2, frozen, F,
+                                         table, m, v, stamp, ring, sweep_period, V, step, lr, beta_1, beta_2, epsilon, stream, nullptr);
 }
 
-extern "C" int fil_embed_adam_roll(float* table, float* m, float* v, int32_t* stamp, float* ring, int sweep_period, int64_t V, int K,
+extern "C" int fil_embed_adam_merged_deferred_lrdev(const int64_t* ids, const float* values, const int64_t* counts, int W, long cap, int K,
+                                              const int64_t* offsets, const float* field_l2, const unsigned char* frozen, int F,
+                                              float* table, float* m, float* v, int32_t* stamp, const float* ring, int sweep_period,
+                                              int64_t V, const int64_t* step, const float* lr_dev, float beta_1, float beta_2, float epsilon,
+                                              void* stream) {
+  if (lr_dev == nullptr) return fail(FIL_ERR_ARG, "fil_embed_adam_merged_deferred_lrdev: no device rate (lr_dev is NULL)");
+  return embed_adam_merged_deferred_impl("fil_embed_adam_merged_deferred_lrdev", ids, values, counts, W, cap, K, offsets, field_l2, frozen,
+                                         F, table, m, v, stamp, ring, sweep_period, V, step, 0.f, beta_1, beta_2, epsilon, stream, lr_dev);
+}
+
+static int embed_adam_roll_impl(const char* who, float* table, float* m, float* v, int32_t* stamp, float* ring, int sweep_period, int64_t V,
+                                int K,
                                    const int64_t* offsets, const float* field_l2, const unsigned char* frozen, int F, const int64_t* step,
-                                   float lr, float beta_1, float beta_2, float epsilon, int flags, void* stream) {
-  FIL_CHECK_ARG(V >= 0 && K >= 1 && F >= 1);
+                                   float lr, float beta_1, float beta_2, float epsilon, int flags, void* stream, const float* lr_dev) {
+  FIL_CHECK_ARG_W(who, V >= 0 && K >= 1 && F >= 1);
   if (flags != FIL_ADAM_ROLL_STEP && flags != FIL_ADAM_ROLL_SKIP && flags != FIL_ADAM_ROLL_FLUSH)
-    return fail(FIL_ERR_ARG, "fil_embed_adam_roll: flags %d (FIL_ADAM_ROLL_STEP, _SKIP or _FLUSH)", flags);
-  if (int rc = check_deferred("fil_embed_adam_roll", K, F, sweep_period, ring)) return rc;
-  if (int rc = check_hyper("fil_embed_adam_roll", lr, beta_1, beta_2, epsilon)) return rc;
+    return fail(FIL_ERR_ARG, "%s: flags %d (FIL_ADAM_ROLL_STEP, _SKIP or _FLUSH)", who, flags);
+  if (int rc = check_deferred(who, K, F, sweep_period, ring)) return rc;
+  if (int rc = check_hyper(who, lr, beta_1, beta_2, epsilon)) return rc;
   if (V == 0) return FIL_OK;
-  FIL_CHECK_ARG(table && m && v && stamp && ring && offsets && step);
+  FIL_CHECK_ARG_W(who, table && m && v && stamp && ring && offsets && step);
   hipStream_t st = (hipStream_t)stream;
   const int lg = lanes_lg(K);
   const int64_t rows = flags == FIL_ADAM_ROLL_FLUSH ? V : (V + sweep_period - 1) / sweep_period;
@@ -891,7 +1000,22 @@ extern "C" int fil_embed_adam_roll(float* table, float* m, float* v, int32_t* st
   const dim3 grid((int)std::max<int64_t>(1, std::min<int64_t>((total + 255) / 256, 256 * 8)));
   hipLaunchKernelGGL(embed_adam_roll_kernel, grid, dim3(256), 0, st, table, m, v, stamp, reinterpret_cast<AdamCoef*>(ring),
                      ring_len(sweep_period), sweep_period, V, K, lg, vec, offsets, field_l2, frozen, F, step, lr, beta_1, beta_2, epsilon,
-                     flags == FIL_ADAM_ROLL_STEP ? 0 : (flags == FIL_ADAM_ROLL_SKIP ? kRollSkip : kRollFlush));
-  FIL_CHECK_LAUNCH();
+                     flags == FIL_ADAM_ROLL_STEP ? 0 : (flags == FIL_ADAM_ROLL_SKIP ? kRollSkip : kRollFlush), lr_dev);
+  FIL_CHECK_LAUNCH_W(who);
   return FIL_OK;
+}
+
+extern "C" int fil_embed_adam_roll(float* table, float* m, float* v, int32_t* stamp, float* ring, int sweep_period, int64_t V, int K,
+                                   const int64_t* offsets, const float* field_l2, const unsigned char* frozen, int F, const int64_t* step,
+                                   float lr, float beta_1, float beta_2, float epsilon, int flags, void* stream) {
+  return embed_adam_roll_impl("fil_embed_adam_roll", table, m, v, stamp, ring, sweep_period, V, K, offsets, field_l2, frozen, F, step, lr,
+                              beta_1, beta_2, epsilon, flags, stream, nullptr);
+}
+
+extern "C" int fil_embed_adam_roll_lrdev(float* table, float* m, float* v, int32_t* stamp, float* ring, int sweep_period, int64_t V, int K,
+                                   const int64_t* offsets, const float* field_l2, const unsigned char* frozen, int F, const int64_t* step,
+                                   const float* lr_dev, float beta_1, float beta_2, float epsilon, int flags, void* stream) {
+  if (lr_dev == nullptr) return fail(FIL_ERR_ARG, "fil_embed_adam_roll_lrdev: no device rate (lr_dev is NULL)");
+  return embed_adam_roll_impl("fil_embed_adam_roll_lrdev", table, m, v, stamp, ring, sweep_period, V, K, offsets, field_l2, frozen, F, step,
+                              0.f, beta_1, beta_2, epsilon, flags, stream, lr_dev);
 }

@@ -39,6 +39,8 @@ __device__ __forceinline__ float with_l2(float acc, float l2x2, float p) {
   return acc + l2x2 * p;
 }
 
+// (the *_lrdev entry points: the kernels take the rate from the word fil_lr_schedule_eval left on the device, `if (lr_dev) h.lr =
+// *lr_dev` -- one wave-uniform load at the top of each kernel; a by-value launch passes NULL)
 // one element of the rule: s = the accumulator, z = Ftrl's linear slot (unused by Adagrad)
 template <int RULE>
 __device__ __forceinline__ void rule_elem(float& p, float& s, float& z, float g, const RowHyper& h) {
@@ -62,7 +64,9 @@ __device__ __forceinline__ void rule_elem(float& p, float& s, float& z, float g,
 // ---- fil_rowopt_multi: the dense descriptors (multi_tensor_walk, optim_rows.h) with the rule; Ftrl's linear slot (`v`) joins the
 // 16-byte alignment test, Adagrad has none
 template <int RULE>
-__global__ __launch_bounds__(256) void rowopt_multi_kernel(const fil_adam_tensor* __restrict__ ts, int n, RowHyper h) {
+__global__ __launch_bounds__(256) void rowopt_multi_kernel(const fil_adam_tensor* __restrict__ ts, int n, RowHyper h,
+                                                           const float* __restrict__ lr_dev) {
+  if (lr_dev) h.lr = *lr_dev;
   multi_tensor_walk<RULE == FIL_OPT_FTRL>(ts, n, [=](float& p, float& s, float& z, float g, float l2x2) {
     rule_elem<RULE>(p, s, z, with_l2(g, l2x2, p), h);
   });
@@ -92,7 +96,9 @@ __global__ __launch_bounds__(256) void embed_rowopt_runs_kernel(const GT* __rest
                                                                 const int64_t* __restrict__ sorted_ids, long R, int K, int F,
                                                                 const float* __restrict__ field_l2, float* __restrict__ table,
                                                                 float* __restrict__ S, float* __restrict__ Z, int32_t* __restrict__ stamp,
-                                                                const int64_t* __restrict__ step, RowHyper h) {
+                                                                const int64_t* __restrict__ step, RowHyper h,
+                                                                const float* __restrict__ lr_dev) {
+  if (lr_dev) h.lr = *lr_dev;
   const int32_t tag = stamp ? (int32_t)(uint32_t)(*step + 1) : 0;
   embed_run_sums(g, perm, sorted_ids, R, K, [=](int64_t row, int kq, const float (&acc)[4], int64_t first) {
     const float l2x2 = field_l2 ? 2.f * field_l2[first % F] : 0.f;
@@ -188,8 +194,10 @@ __global__ __launch_bounds__(256) void embed_rowopt_sweep_kernel(float* __restri
                                                                  const int32_t* __restrict__ stamp, int64_t V, int K,
                                                                  const int64_t* __restrict__ offsets, const float* __restrict__ field_l2,
                                                                  const unsigned char* __restrict__ frozen, int F,
-                                                                 const int64_t* __restrict__ step, RowHyper h, int vec) {
+                                                                 const int64_t* __restrict__ step, RowHyper h, int vec,
+                                                                 const float* __restrict__ lr_dev) {
   constexpr bool kZ = RULE == FIL_OPT_FTRL;
+  if (lr_dev) h.lr = *lr_dev;
   __shared__ RegTab t;
   load_reg_tab(&t, offsets, field_l2, frozen, F, V);
   const int64_t n = t.vbeg[t.n] * K;               // elements of the regularised fields
@@ -241,7 +249,9 @@ __global__ __launch_bounds__(256) void embed_rowopt_merged_kernel(const int64_t*
                                                                   const int64_t* __restrict__ offsets, const float* __restrict__ field_l2,
                                                                   int F, float* __restrict__ table, float* __restrict__ S,
                                                                   float* __restrict__ Z, int32_t* __restrict__ stamp, int64_t V,
-                                                                  const int64_t* __restrict__ step, RowHyper h) {
+                                                                  const int64_t* __restrict__ step, RowHyper h,
+                                                                  const float* __restrict__ lr_dev) {
+  if (lr_dev) h.lr = *lr_dev;
   __shared__ int64_t s_off[kSweepMaxF];
   for (int f = threadIdx.x; f < F; f += blockDim.x) s_off[f] = offsets[f];
   __syncthreads();
@@ -283,40 +293,52 @@ static double rule_arrays(int rule) { return rule == FIL_OPT_FTRL ? 3.0 : 2.0; }
 
 using namespace fil;
 
-extern "C" int fil_rowopt_multi(const fil_adam_tensor* tensors, int n, int64_t total_numel, int64_t* step, int rule,
-                                const fil_rowopt_hyper* hyper, int advance, void* stream) {
-  FIL_CHECK_ARG(n >= 0 && total_numel >= 0);
-  FIL_CHECK_ARG(step != nullptr);
-  FIL_CHECK_ARG(n == 0 || tensors != nullptr);
-  if (int rc = check_rule("fil_rowopt_multi", rule, hyper)) return rc;
-  if (advance != 0 && advance != 1) return fail(FIL_ERR_ARG, "fil_rowopt_multi: advance %d (0 or 1)", advance);
+static int rowopt_multi_impl(const char* who, const fil_adam_tensor* tensors, int n, int64_t total_numel, int64_t* step, int rule,
+                                const fil_rowopt_hyper* hyper, int advance, void* stream, const float* lr_dev) {
+  FIL_CHECK_ARG_W(who, n >= 0 && total_numel >= 0);
+  FIL_CHECK_ARG_W(who, step != nullptr);
+  FIL_CHECK_ARG_W(who, n == 0 || tensors != nullptr);
+  if (int rc = check_rule(who, rule, hyper)) return rc;
+  if (advance != 0 && advance != 1) return fail(FIL_ERR_ARG, "%s: advance %d (0 or 1)", who, advance);
   hipStream_t st = (hipStream_t)stream;
   const RowHyper h = row_hyper(*hyper);
   if (n > 0) {
     ProfScope ps(rule == FIL_OPT_FTRL ? "ftrl_multi" : "adagrad_multi", st, (4.0 + 8.0 * rule_arrays(rule)) * (double)total_numel);
     const long chunks = std::max<long>(1, (long)((total_numel + kMultiChunk - 1) / kMultiChunk));
     const dim3 grid((int)std::min<long>(chunks, 256 * 8));
-    if (rule == FIL_OPT_FTRL) hipLaunchKernelGGL(rowopt_multi_kernel<FIL_OPT_FTRL>, grid, dim3(256), 0, st, tensors, n, h);
-    else hipLaunchKernelGGL(rowopt_multi_kernel<FIL_OPT_ADAGRAD>, grid, dim3(256), 0, st, tensors, n, h);
-    FIL_CHECK_LAUNCH();
+    if (rule == FIL_OPT_FTRL) hipLaunchKernelGGL(rowopt_multi_kernel<FIL_OPT_FTRL>, grid, dim3(256), 0, st, tensors, n, h, lr_dev);
+    else hipLaunchKernelGGL(rowopt_multi_kernel<FIL_OPT_ADAGRAD>, grid, dim3(256), 0, st, tensors, n, h, lr_dev);
+    FIL_CHECK_LAUNCH_W(who);
   }
   if (advance) {
     launch_step_advance(step, st);
-    FIL_CHECK_LAUNCH();
+    FIL_CHECK_LAUNCH_W(who);
   }
   return FIL_OK;
 }
 
-extern "C" int fil_embed_rowopt_runs(const void* g, const int64_t* perm, const int64_t* sorted_ids, long R, int K, int g_dtype, int F,
+extern "C" int fil_rowopt_multi(const fil_adam_tensor* tensors, int n, int64_t total_numel, int64_t* step, int rule,
+                                const fil_rowopt_hyper* hyper, int advance, void* stream) {
+  return rowopt_multi_impl("fil_rowopt_multi", tensors, n, total_numel, step, rule, hyper, advance, stream, nullptr);
+}
+
+extern "C" int fil_rowopt_multi_lrdev(const fil_adam_tensor* tensors, int n, int64_t total_numel, int64_t* step, int rule,
+                                const fil_rowopt_hyper* hyper, const float* lr_dev, int advance, void* stream) {
+  if (lr_dev == nullptr) return fail(FIL_ERR_ARG, "fil_rowopt_multi_lrdev: no device rate (lr_dev is NULL)");
+  return rowopt_multi_impl("fil_rowopt_multi_lrdev", tensors, n, total_numel, step, rule, hyper, advance, stream, lr_dev);
+}
+
+static int embed_rowopt_runs_impl(const char* who, const void* g, const int64_t* perm, const int64_t* sorted_ids, long R, int K, int g_dtype,
+                                  int F,
                                      const float* field_l2, float* table, float* accum, float* linear, int32_t* stamp,
-                                     const int64_t* step, int rule, const fil_rowopt_hyper* hyper, void* stream) {
-  FIL_CHECK_ARG(R >= 0 && K >= 1 && F >= 1);
-  if (g_dtype != FIL_F32 && g_dtype != FIL_BF16) return fail(FIL_ERR_ARG, "fil_embed_rowopt_runs: g_dtype %d (f32 or bf16)", g_dtype);
-  if (K > 256) return fail(FIL_ERR_UNSUPPORTED, "fil_embed_rowopt_runs: K=%d > 256", K);
-  if (int rc = check_rule("fil_embed_rowopt_runs", rule, hyper)) return rc;
+                                     const int64_t* step, int rule, const fil_rowopt_hyper* hyper, void* stream, const float* lr_dev) {
+  FIL_CHECK_ARG_W(who, R >= 0 && K >= 1 && F >= 1);
+  if (g_dtype != FIL_F32 && g_dtype != FIL_BF16) return fail(FIL_ERR_ARG, "%s: g_dtype %d (f32 or bf16)", who, g_dtype);
+  if (K > 256) return fail(FIL_ERR_UNSUPPORTED, "%s: K=%d > 256", who, K);
+  if (int rc = check_rule(who, rule, hyper)) return rc;
   if (R == 0) return FIL_OK;
-  FIL_CHECK_ARG(g && perm && sorted_ids && table && accum && step);
-  if (rule == FIL_OPT_FTRL && linear == nullptr) return fail(FIL_ERR_ARG, "fil_embed_rowopt_runs: Ftrl needs its linear slot");
+  FIL_CHECK_ARG_W(who, g && perm && sorted_ids && table && accum && step);
+  if (rule == FIL_OPT_FTRL && linear == nullptr) return fail(FIL_ERR_ARG, "%s: Ftrl needs its linear slot", who);
   hipStream_t st = (hipStream_t)stream;
   const RowHyper h = row_hyper(*hyper);
   ProfScope ps(rule == FIL_OPT_FTRL ? "embed_ftrl_runs" : "embed_adagrad_runs", st,
@@ -326,7 +348,7 @@ extern "C" int fil_embed_rowopt_runs(const void* g, const int64_t* perm, const i
   float* Z = rule == FIL_OPT_FTRL ? linear : nullptr;
 #define FIL_ROWOPT_RUNS(RULE, GT) \
   hipLaunchKernelGGL((embed_rowopt_runs_kernel<RULE, GT>), grid, dim3(256), 0, st, static_cast<const GT*>(g), perm, sorted_ids, R, K, F, \
-                     field_l2, table, accum, Z, stamp, step, h)
+                     field_l2, table, accum, Z, stamp, step, h, lr_dev)
   if (rule == FIL_OPT_FTRL) {
     if (g_dtype == FIL_F32) FIL_ROWOPT_RUNS(FIL_OPT_FTRL, float);
     else FIL_ROWOPT_RUNS(FIL_OPT_FTRL, __hip_bfloat16);
@@ -335,19 +357,34 @@ extern "C" int fil_embed_rowopt_runs(const void* g, const int64_t* perm, const i
     else FIL_ROWOPT_RUNS(FIL_OPT_ADAGRAD, __hip_bfloat16);
   }
 #undef FIL_ROWOPT_RUNS
-  FIL_CHECK_LAUNCH();
+  FIL_CHECK_LAUNCH_W(who);
   return FIL_OK;
 }
 
-extern "C" int fil_embed_rowopt_sweep(float* table, float* accum, float* linear, const int32_t* stamp, int64_t V, int K,
+extern "C" int fil_embed_rowopt_runs(const void* g, const int64_t* perm, const int64_t* sorted_ids, long R, int K, int g_dtype, int F,
+                                     const float* field_l2, float* table, float* accum, float* linear, int32_t* stamp,
+                                     const int64_t* step, int rule, const fil_rowopt_hyper* hyper, void* stream) {
+  return embed_rowopt_runs_impl("fil_embed_rowopt_runs", g, perm, sorted_ids, R, K, g_dtype, F, field_l2, table, accum, linear, stamp, step,
+                                rule, hyper, stream, nullptr);
+}
+
+extern "C" int fil_embed_rowopt_runs_lrdev(const void* g, const int64_t* perm, const int64_t* sorted_ids, long R, int K, int g_dtype, int F,
+                                     const float* field_l2, float* table, float* accum, float* linear, int32_t* stamp,
+                                     const int64_t* step, int rule, const fil_rowopt_hyper* hyper, const float* lr_dev, void* stream) {
+  if (lr_dev == nullptr) return fail(FIL_ERR_ARG, "fil_embed_rowopt_runs_lrdev: no device rate (lr_dev is NULL)");
+  return embed_rowopt_runs_impl("fil_embed_rowopt_runs_lrdev", g, perm, sorted_ids, R, K, g_dtype, F, field_l2, table, accum, linear, stamp,
+                                step, rule, hyper, stream, lr_dev);
+}
+
+static int embed_rowopt_sweep_impl(const char* who, float* table, float* accum, float* linear, const int32_t* stamp, int64_t V, int K,
                                       const int64_t* offsets, const float* field_l2, const unsigned char* frozen, int F,
-                                      const int64_t* step, int rule, const fil_rowopt_hyper* hyper, void* stream) {
-  FIL_CHECK_ARG(V >= 0 && K >= 1 && F >= 1);
-  if (F > kSweepMaxF) return fail(FIL_ERR_UNSUPPORTED, "fil_embed_rowopt_sweep: F=%d > %d fields", F, kSweepMaxF);
-  if (int rc = check_rule("fil_embed_rowopt_sweep", rule, hyper)) return rc;
+                                      const int64_t* step, int rule, const fil_rowopt_hyper* hyper, void* stream, const float* lr_dev) {
+  FIL_CHECK_ARG_W(who, V >= 0 && K >= 1 && F >= 1);
+  if (F > kSweepMaxF) return fail(FIL_ERR_UNSUPPORTED, "%s: F=%d > %d fields", who, F, kSweepMaxF);
+  if (int rc = check_rule(who, rule, hyper)) return rc;
   if (V == 0 || field_l2 == nullptr) return FIL_OK;          // no regularised field: no untouched row moves
-  FIL_CHECK_ARG(table && accum && stamp && offsets && step);
-  if (rule == FIL_OPT_FTRL && linear == nullptr) return fail(FIL_ERR_ARG, "fil_embed_rowopt_sweep: Ftrl needs its linear slot");
+  FIL_CHECK_ARG_W(who, table && accum && stamp && offsets && step);
+  if (rule == FIL_OPT_FTRL && linear == nullptr) return fail(FIL_ERR_ARG, "%s: Ftrl needs its linear slot", who);
   hipStream_t st = (hipStream_t)stream;
   const RowHyper h = row_hyper(*hyper);
   float* Z = rule == FIL_OPT_FTRL ? linear : nullptr;
@@ -359,25 +396,40 @@ extern "C" int fil_embed_rowopt_sweep(float* table, float* accum, float* linear,
   const dim3 grid((int)std::max<int64_t>(1, std::min<int64_t>((work + 255) / 256, 256 * 8)));
   if (rule == FIL_OPT_FTRL)
     hipLaunchKernelGGL(embed_rowopt_sweep_kernel<FIL_OPT_FTRL>, grid, dim3(256), 0, st, table, accum, Z, stamp, V, K, offsets, field_l2,
-                       frozen, F, step, h, vec);
+                       frozen, F, step, h, vec, lr_dev);
   else
     hipLaunchKernelGGL(embed_rowopt_sweep_kernel<FIL_OPT_ADAGRAD>, grid, dim3(256), 0, st, table, accum, Z, stamp, V, K, offsets,
-                       field_l2, frozen, F, step, h, vec);
-  FIL_CHECK_LAUNCH();
+                       field_l2, frozen, F, step, h, vec, lr_dev);
+  FIL_CHECK_LAUNCH_W(who);
   return FIL_OK;
 }
 
-extern "C" int fil_embed_rowopt_merged(const int64_t* ids, const float* values, const int64_t* counts, int W, long cap, int K,
+extern "C" int fil_embed_rowopt_sweep(float* table, float* accum, float* linear, const int32_t* stamp, int64_t V, int K,
+                                      const int64_t* offsets, const float* field_l2, const unsigned char* frozen, int F,
+                                      const int64_t* step, int rule, const fil_rowopt_hyper* hyper, void* stream) {
+  return embed_rowopt_sweep_impl("fil_embed_rowopt_sweep", table, accum, linear, stamp, V, K, offsets, field_l2, frozen, F, step, rule,
+                                 hyper, stream, nullptr);
+}
+
+extern "C" int fil_embed_rowopt_sweep_lrdev(float* table, float* accum, float* linear, const int32_t* stamp, int64_t V, int K,
+                                      const int64_t* offsets, const float* field_l2, const unsigned char* frozen, int F,
+                                      const int64_t* step, int rule, const fil_rowopt_hyper* hyper, const float* lr_dev, void* stream) {
+  if (lr_dev == nullptr) return fail(FIL_ERR_ARG, "fil_embed_rowopt_sweep_lrdev: no device rate (lr_dev is NULL)");
+  return embed_rowopt_sweep_impl("fil_embed_rowopt_sweep_lrdev", table, accum, linear, stamp, V, K, offsets, field_l2, frozen, F, step, rule,
+                                 hyper, stream, lr_dev);
+}
+
+static int embed_rowopt_merged_impl(const char* who, const int64_t* ids, const float* values, const int64_t* counts, int W, long cap, int K,
                                        const int64_t* offsets, const float* field_l2, int F, float* table, float* accum, float* linear,
                                        int32_t* stamp, int64_t V, const int64_t* step, int rule, const fil_rowopt_hyper* hyper,
-                                       void* stream) {
-  FIL_CHECK_ARG(W >= 1 && cap >= 0 && K >= 1 && F >= 1 && V >= 0);
-  if (K > 256) return fail(FIL_ERR_UNSUPPORTED, "fil_embed_rowopt_merged: K=%d > 256", K);
-  if (F > kSweepMaxF) return fail(FIL_ERR_UNSUPPORTED, "fil_embed_rowopt_merged: F=%d > %d fields", F, kSweepMaxF);
-  if (int rc = check_rule("fil_embed_rowopt_merged", rule, hyper)) return rc;
+                                       void* stream, const float* lr_dev) {
+  FIL_CHECK_ARG_W(who, W >= 1 && cap >= 0 && K >= 1 && F >= 1 && V >= 0);
+  if (K > 256) return fail(FIL_ERR_UNSUPPORTED, "%s: K=%d > 256", who, K);
+  if (F > kSweepMaxF) return fail(FIL_ERR_UNSUPPORTED, "%s: F=%d > %d fields", who, F, kSweepMaxF);
+  if (int rc = check_rule(who, rule, hyper)) return rc;
   if (cap == 0 || V == 0) return FIL_OK;
-  FIL_CHECK_ARG(ids && values && counts && offsets && table && accum && step);
-  if (rule == FIL_OPT_FTRL && linear == nullptr) return fail(FIL_ERR_ARG, "fil_embed_rowopt_merged: Ftrl needs its linear slot");
+  FIL_CHECK_ARG_W(who, ids && values && counts && offsets && table && accum && step);
+  if (rule == FIL_OPT_FTRL && linear == nullptr) return fail(FIL_ERR_ARG, "%s: Ftrl needs its linear slot", who);
   hipStream_t st = (hipStream_t)stream;
   const RowHyper h = row_hyper(*hyper);
   float* Z = rule == FIL_OPT_FTRL ? linear : nullptr;
@@ -387,10 +439,27 @@ extern "C" int fil_embed_rowopt_merged(const int64_t* ids, const float* values, 
   const dim3 grid((int)std::max<long>(1, std::min<long>((n + 255) / 256, 256 * 8)));
   if (rule == FIL_OPT_FTRL)
     hipLaunchKernelGGL(embed_rowopt_merged_kernel<FIL_OPT_FTRL>, grid, dim3(256), 0, st, ids, values, counts, W, cap, K, offsets, field_l2,
-                       F, table, accum, Z, stamp, V, step, h);
+                       F, table, accum, Z, stamp, V, step, h, lr_dev);
   else
     hipLaunchKernelGGL(embed_rowopt_merged_kernel<FIL_OPT_ADAGRAD>, grid, dim3(256), 0, st, ids, values, counts, W, cap, K, offsets,
-                       field_l2, F, table, accum, Z, stamp, V, step, h);
-  FIL_CHECK_LAUNCH();
+                       field_l2, F, table, accum, Z, stamp, V, step, h, lr_dev);
+  FIL_CHECK_LAUNCH_W(who);
   return FIL_OK;
+}
+
+extern "C" int fil_embed_rowopt_merged(const int64_t* ids, const float* values, const int64_t* counts, int W, long cap, int K,
+                                       const int64_t* offsets, const float* field_l2, int F, float* table, float* accum, float* linear,
+                                       int32_t* stamp, int64_t V, const int64_t* step, int rule, const fil_rowopt_hyper* hyper,
+                                       void* stream) {
+  return embed_rowopt_merged_impl("fil_embed_rowopt_merged", ids, values, counts, W, cap, K, offsets, field_l2, F, table, accum, linear,
+                                  stamp, V, step, rule, hyper, stream, nullptr);
+}
+
+extern "C" int fil_embed_rowopt_merged_lrdev(const int64_t* ids, const float* values, const int64_t* counts, int W, long cap, int K,
+                                       const int64_t* offsets, const float* field_l2, int F, float* table, float* accum, float* linear,
+                                       int32_t* stamp, int64_t V, const int64_t* step, int rule, const fil_rowopt_hyper* hyper, const float* lr_dev,
+                                       void* stream) {
+  if (lr_dev == nullptr) return fail(FIL_ERR_ARG, "fil_embed_rowopt_merged_lrdev: no device rate (lr_dev is NULL)");
+  return embed_rowopt_merged_impl("fil_embed_rowopt_merged_lrdev", ids, values, counts, W, cap, K, offsets, field_l2, F, table, accum,
+                                  linear, stamp, V, step, rule, hyper, stream, lr_dev);
 }

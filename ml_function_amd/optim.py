@@ -34,7 +34,16 @@ epsilon 1/sqrt(1 - beta_2) ~ 31.6 times larger -- of the order of an embedding r
   the table in memory between steps lags, for rows nobody has read.  Runs tables attach at construction, through
   add_param_group, or at their first record.
 * The step counter t (Keras' `iterations`) is an int64 on the device, read by every launch and advanced by the last one: a step
-  captured into a HIP graph (capture.capture_step) advances it on every replay.  Learning rate and betas are baked into a capture.
+  captured into a HIP graph (capture.capture_step) advances it on every replay.  Betas and a float learning rate are baked into a
+  capture.
+* learning_rate may be a schedules.LearningRateSchedule (Keras' ExponentialDecay, InverseTimeDecay, PolynomialDecay,
+  PiecewiseConstantDecay), and decay= is Keras' legacy keyword (lr / (1 + decay * iterations), applied after the schedule;
+  OptimizerV2._decayed_lr): with either, step() first enqueues one fil_lr_schedule_eval per (group, device) -- the rate of step t
+  computed on the device from the counter, one fp32 word -- and every update launch of the step reads that word (the *_lrdev entry
+  points, include/fil.h O3), so a captured step changes its rate on every replay, and the deferred ring holds each step's own rate.
+  The rate uses iterations (0 at the first step), Adam's bias correction iterations + 1.  current_learning_rate() reads it without a
+  synchronisation; state_dict() carries the schedule's config.  With a float rate and no decay, step() makes exactly the calls it
+  always made.  Adagrad and Ftrl take both too.
 
 Adagrad and Ftrl (Keras' tf.keras.optimizers.Adagrad / Ftrl, TF 2.1; O2) follow the same contract -- iterations, one dense launch per
 (group, device), runs tables consumed in place, the same data-parallel route, capture after one eager step -- with row-local rules:
@@ -50,7 +59,7 @@ import torch
 import torch.distributed as dist
 from torch.utils.weak import WeakIdKeyDictionary
 
-from . import _lib
+from . import _lib, schedules
 from ._lib import (FIL_ADAM_KERAS, FIL_ADAM_LAZY, FIL_ADAM_ROLL_FLUSH, FIL_ADAM_ROLL_SKIP, FIL_ADAM_ROLL_STEP, FIL_OPT_ADAGRAD,
                    FIL_OPT_FTRL, FilError, RowoptHyper, check, ptr, stream_ptr)
 
@@ -62,6 +71,36 @@ class _Desc(ctypes.Structure):
 
 
 assert ctypes.sizeof(_Desc) == 48
+
+
+def _rated(lib, name, lr):
+    """The entry point `name` for a rate that is a float (by value) or a device tensor (its _lrdev variant, include/fil.h O3):
+    (function, rate argument, name for messages)."""
+    if isinstance(lr, torch.Tensor):
+        return getattr(lib, name + "_lrdev"), lr.data_ptr(), name + "_lrdev"
+    return getattr(lib, name), lr, name
+
+
+def _check_rate(who, learning_rate, decay):
+    if isinstance(learning_rate, schedules.LearningRateSchedule):
+        pass
+    elif not learning_rate >= 0.0:
+        raise ValueError("%s: learning_rate=%r (>= 0, or a schedules.LearningRateSchedule)" % (who, learning_rate))
+    if decay < 0.0:
+        raise ValueError("decay cannot be less than 0: {}".format(decay))
+    return learning_rate if isinstance(learning_rate, schedules.LearningRateSchedule) else float(learning_rate), float(decay)
+
+
+def _decay_entry(decay):
+    """The `decay` entry of an optimizer's defaults: present only when it is used, so an optimizer built without it has the defaults
+    (and the param groups, and the state_dict) it always had."""
+    return {"decay": decay} if decay > 0.0 else {}
+
+
+def _float_rate(group):
+    """The group's by-value rate (0 for a schedule: the launches that take it read no rate)."""
+    lr = group["learning_rate"]
+    return 0.0 if isinstance(lr, schedules.LearningRateSchedule) else lr
 
 
 MAX_SWEEP_PERIOD = 1023     # the ring (D >= N + 1 entries, a power of two) sits in LDS in fil_embed_adam_roll: D <= 1024
@@ -87,7 +126,8 @@ class _Deferred:
         self.stamp.copy_(t.expand(p.shape[0]))             # current through the completed steps
         self.ring = torch.zeros((D, 4), dtype=torch.float32, device=p.device)
         self.fields = None
-        self.hyper = (opt.defaults["learning_rate"], opt.defaults["beta_1"], opt.defaults["beta_2"], opt.defaults["epsilon"])
+        # (for flush(), which reads no rate)
+        self.hyper = (_float_rate(opt.defaults), opt.defaults["beta_1"], opt.defaults["beta_2"], opt.defaults["epsilon"])
 
     def field_args(self, p, rec=None):
         """(offsets, field_l2, frozen, F) for the replays: the record's, else the last one seen.  Before any record or forward every
@@ -111,10 +151,10 @@ class _Deferred:
     def roll(self, p, hyper, flags, rec=None):
         V, K = p.shape
         offsets, field_l2, frozen, F = self.field_args(p, rec)
+        fn, lr, name = _rated(_lib.load(), "fil_embed_adam_roll", hyper[0])
         with torch.cuda.device(p.device):
-            check(_lib.load().fil_embed_adam_roll(ptr(p), ptr(self.m), ptr(self.v), ptr(self.stamp), ptr(self.ring), self.N, V, K,
-                                                  ptr(offsets), ptr(field_l2), ptr(frozen), F, ptr(self.t), *hyper, flags, stream_ptr()),
-                  "fil_embed_adam_roll")
+            check(fn(ptr(p), ptr(self.m), ptr(self.v), ptr(self.stamp), ptr(self.ring), self.N, V, K, ptr(offsets), ptr(field_l2),
+                     ptr(frozen), F, ptr(self.t), lr, *hyper[1:], flags, stream_ptr()), name)
 
     @torch.no_grad()
     def flush(self):
@@ -167,6 +207,7 @@ class _RunsOptimizer(torch.optim.Optimizer):
         # pinned staging for descriptors built DURING a capture: a host allocation there would invalidate it, so it is reserved by
         # the first eager step; a captured copy reads its slice at every replay, so a slice is never handed out twice
         self._arena, self._arena_off = None, 0
+        self._rates = {}        # (group index, device) -> (key, device fil_lr_schedule, fp32 [1] rate of the step): schedules / decay only
         self._xbuf = {}         # runs table -> buffers of the data-parallel exchange (cap fixed on the first step, reused after)
         self.process_group = process_group
         self.force_exchange = force_exchange
@@ -189,6 +230,66 @@ class _RunsOptimizer(torch.optim.Optimizer):
         """Completed steps (Keras' optimizer.iterations), as a host int (synchronises)."""
         return int(next(iter(self._t.values()))[0]) if self._t else 0
 
+    # -- the rate (include/fil.h O3) ---------------------------------------------------------------------------------
+    @staticmethod
+    def _on_device(group):
+        """Is the group's rate computed on the device: a schedule, or the legacy decay."""
+        return isinstance(group["learning_rate"], schedules.LearningRateSchedule) or group.get("decay", 0.0) > 0.0
+
+    def _rate_state(self, gi, group, dev):
+        """The group's descriptor and rate word on `dev`, built on first use (and again when the group's rate was replaced)."""
+        lr, decay = group["learning_rate"], group.get("decay", 0.0)
+        if decay < 0.0:
+            raise ValueError("decay cannot be less than 0: {}".format(decay))
+        key = (schedules.serialize(lr) if isinstance(lr, schedules.LearningRateSchedule) else float(lr), float(decay))
+        hit = self._rates.get((gi, dev))
+        if hit is not None and hit[0] == key:
+            return hit
+        if torch.cuda.is_current_stream_capturing():
+            raise FilError("%s: the learning-rate schedule of a captured step has no descriptor on %s yet -- run one eager step before "
+                           "capturing (capture.capture_step's warm-up does)" % (self._NAME, dev))
+        d = (lr.descriptor(decay) if isinstance(lr, schedules.LearningRateSchedule) else schedules.constant_descriptor(lr, decay))
+        check(_lib.load().fil_lr_schedule_check(ctypes.addressof(d)), "fil_lr_schedule_check")
+        host = torch.frombuffer(bytearray(bytes(d)), dtype=torch.uint8)
+        hit = self._rates[(gi, dev)] = (key, host.to(dev), torch.zeros(1, dtype=torch.float32, device=dev))
+        return hit
+
+    def _eval_rate(self, gi, group, dev, out=None):
+        """Enqueues fil_lr_schedule_eval of the group on `dev`: the rate of the step about to run, into the group's rate word (or
+        `out`); returns the tensor written."""
+        _, desc, word = self._rate_state(gi, group, dev)
+        out = word if out is None else out
+        with torch.cuda.device(dev):
+            check(_lib.load().fil_lr_schedule_eval(ptr(desc), ptr(self._counter(dev)), ptr(out), stream_ptr()), "fil_lr_schedule_eval")
+        return out
+
+    def _step_rates(self):
+        """Per parameter group: None (a float rate, by value) or {device: the rate word}, with one fil_lr_schedule_eval per (group,
+        device) enqueued -- before any update launch of the step, so every one of them reads the same bits."""
+        out = []
+        for gi, group in enumerate(self.param_groups):
+            if not self._on_device(group):
+                out.append(None)
+                continue
+            devs = []
+            for p in group["params"]:
+                if p.device.type == "cuda" and p.device not in devs:
+                    devs.append(p.device)
+            out.append({dev: self._eval_rate(gi, group, dev) for dev in devs})
+        return out
+
+    def current_learning_rate(self, group=0):
+        """Keras' _decayed_lr of parameter group `group` for the step about to run: a 0-dim fp32 device tensor, computed on the
+        device from the step counter without synchronising (float() of it is the caller's synchronisation)."""
+        g = self.param_groups[group]
+        dev = next((p.device for p in g["params"] if p.device.type == "cuda"), None)
+        if dev is None:
+            raise FilError("%s: parameter group %d has no GPU parameter" % (self._NAME, group))
+        if not self._on_device(g):
+            return torch.full((), g["learning_rate"], dtype=torch.float32, device=dev)
+        out = torch.empty(1, dtype=torch.float32, device=dev)
+        return self._eval_rate(group, g, dev, out).reshape(())
+
     def zero_grad(self, set_to_none=True):
         super().zero_grad(set_to_none=set_to_none)
         for g in self.param_groups:
@@ -201,7 +302,8 @@ class _RunsOptimizer(torch.optim.Optimizer):
         """The initial values of the _SLOTS of a parameter in `group`."""
         raise NotImplementedError
 
-    def _hyper(self, group):
+    def _hyper(self, group, lr_dev=None):
+        """The group's hyper-parameters; lr_dev: the device word holding the step's rate (a schedule / decay), else by value."""
         raise NotImplementedError
 
     def _launch_dense(self, lib, desc, n, numel, t, hyper, advance):
@@ -229,11 +331,16 @@ class _RunsOptimizer(torch.optim.Optimizer):
     def state_dict(self):
         sd = super().state_dict()
         sd["iterations"] = self.iterations
+        # a schedule travels as its config ({"class_name", "config"}), not as an object
+        sd["param_groups"] = [dict(g, learning_rate=schedules.serialize(g["learning_rate"]))
+                              if isinstance(g.get("learning_rate"), schedules.LearningRateSchedule) else g for g in sd["param_groups"]]
         return sd
 
     def load_state_dict(self, state_dict):
         state_dict = dict(state_dict)
         it = int(state_dict.pop("iterations", 0))
+        state_dict["param_groups"] = [dict(g, learning_rate=schedules.deserialize(g["learning_rate"]))
+                                      if isinstance(g.get("learning_rate"), dict) else g for g in state_dict["param_groups"]]
         super().load_state_dict(state_dict)
         for st in self.state.values():          # (torch's loader may hand non-contiguous copies back)
             for k in self._SLOTS:
@@ -269,11 +376,15 @@ class _RunsOptimizer(torch.optim.Optimizer):
             with torch.enable_grad():
                 loss = closure()
         lib = _lib.load()
+        rates = self._step_rates()
         calls = []      # (device, hyper, entries) of the dense launches, in group order
-        for group in self.param_groups:
-            hyper = self._hyper(group)
+        for group, rate in zip(self.param_groups, rates):
+            hypers = {}     # device -> the group's hyper-parameters there (they differ by device only in the rate word)
             per_dev = {}
             for p in group["params"]:
+                hyper = hypers.get(p.device)
+                if hyper is None:
+                    hyper = hypers[p.device] = self._hyper(group, rate.get(p.device) if rate else None)
                 pend = getattr(p, "_fil_pending_runs", None)
                 if pend is None and p.grad is None:
                     self._skip(p, hyper)        # (Keras filters None gradients)
@@ -299,7 +410,7 @@ class _RunsOptimizer(torch.optim.Optimizer):
                     raise FilError("%s: gradient of %s must be a dense contiguous fp32 tensor of its shape" % (self._NAME, tuple(p.shape)))
                 per_dev.setdefault(p.device, []).append((p.data_ptr(), g.data_ptr(), s0.data_ptr(), ptr(s1), p.numel(), 0.0))
             for dev, entries in per_dev.items():
-                calls.append((dev, hyper, entries))
+                calls.append((dev, hypers[dev], entries))
         # the last launch on every device advances its counter -- one with no tensors where nothing dense had a gradient
         devs = set(self._t)
         for g in self.param_groups:
@@ -311,7 +422,7 @@ class _RunsOptimizer(torch.optim.Optimizer):
             last[dev] = i
         for dev in devs:
             if dev not in last:
-                calls.append((dev, self._hyper(self.defaults), []))
+                calls.append((dev, self._hyper(dict(self.defaults, learning_rate=_float_rate(self.defaults))), []))  # (reads no rate)
                 last[dev] = len(calls) - 1
         for i, (dev, hyper, entries) in enumerate(calls):
             with torch.cuda.device(dev):
@@ -411,8 +522,9 @@ class Adam(_RunsOptimizer):
     _SLOTS = ("m", "v")
 
     def __init__(self, params, learning_rate=1e-3, beta_1=0.9, beta_2=0.999, epsilon=1e-7, lazy_tables=False, process_group=None,
-                 force_exchange=False, sweep_period=None):
-        if not learning_rate >= 0.0 or not 0.0 <= beta_1 < 1.0 or not 0.0 <= beta_2 < 1.0 or not epsilon >= 0.0:
+                 force_exchange=False, sweep_period=None, decay=0.0):
+        learning_rate, decay = _check_rate("Adam", learning_rate, decay)
+        if not 0.0 <= beta_1 < 1.0 or not 0.0 <= beta_2 < 1.0 or not epsilon >= 0.0:
             raise ValueError("Adam: learning_rate=%r beta_1=%r beta_2=%r epsilon=%r (rate, epsilon >= 0; betas in [0, 1))"
                              % (learning_rate, beta_1, beta_2, epsilon))
         if sweep_period is not None:
@@ -430,8 +542,8 @@ class Adam(_RunsOptimizer):
         if sweep_period is not None:
             fin = weakref.finalize(self, _release, self._released)
             fin.atexit = False
-        super().__init__(params, dict(learning_rate=float(learning_rate), beta_1=float(beta_1), beta_2=float(beta_2),
-                                      epsilon=float(epsilon)), process_group, force_exchange)
+        super().__init__(params, dict(learning_rate=learning_rate, beta_1=float(beta_1), beta_2=float(beta_2),
+                                      epsilon=float(epsilon), **_decay_entry(decay)), process_group, force_exchange)
 
     def add_param_group(self, param_group):
         super().add_param_group(param_group)
@@ -443,11 +555,12 @@ class Adam(_RunsOptimizer):
     def _slot_init(self, group):
         return 0.0, 0.0
 
-    def _hyper(self, group):
-        return group["learning_rate"], group["beta_1"], group["beta_2"], group["epsilon"]
+    def _hyper(self, group, lr_dev=None):
+        return group["learning_rate"] if lr_dev is None else lr_dev, group["beta_1"], group["beta_2"], group["epsilon"]
 
     def _launch_dense(self, lib, desc, n, numel, t, hyper, advance):
-        check(lib.fil_adam_multi(ptr(desc), n, numel, ptr(t), *hyper, advance, stream_ptr()), "fil_adam_multi")
+        fn, lr, name = _rated(lib, "fil_adam_multi", hyper[0])
+        check(fn(ptr(desc), n, numel, ptr(t), lr, *hyper[1:], advance, stream_ptr()), name)
 
     def state_dict(self):
         self.flush()
@@ -492,12 +605,13 @@ class Adam(_RunsOptimizer):
             if world:
                 self._apply_runs_exchanged(lib, p, pend, m, v, t, stamp, mode, world, hyper, st)
             else:
-                check(lib.fil_embed_adam_runs(ptr(pend["g"]), ptr(pend["perm"]), ptr(pend["sorted_ids"]), pend["R"], K, pend["g_dtype"],
-                                              pend["F"], ptr(pend["field_l2"]), ptr(p), ptr(m), ptr(v), ptr(stamp), ptr(t), lr, b1, b2,
-                                              eps, mode, st), "fil_embed_adam_runs")
+                fn, r, name = _rated(lib, "fil_embed_adam_runs", lr)
+                check(fn(ptr(pend["g"]), ptr(pend["perm"]), ptr(pend["sorted_ids"]), pend["R"], K, pend["g_dtype"], pend["F"],
+                         ptr(pend["field_l2"]), ptr(p), ptr(m), ptr(v), ptr(stamp), ptr(t), r, b1, b2, eps, mode, st), name)
             if mode == FIL_ADAM_KERAS:
-                check(lib.fil_embed_adam_sweep(ptr(p), ptr(m), ptr(v), ptr(stamp), V, K, ptr(pend["offsets"]), ptr(pend["field_l2"]),
-                                               ptr(pend["frozen"]), pend["F"], ptr(t), lr, b1, b2, eps, st), "fil_embed_adam_sweep")
+                fn, r, name = _rated(lib, "fil_embed_adam_sweep", lr)
+                check(fn(ptr(p), ptr(m), ptr(v), ptr(stamp), V, K, ptr(pend["offsets"]), ptr(pend["field_l2"]), ptr(pend["frozen"]),
+                         pend["F"], ptr(t), r, b1, b2, eps, st), name)
 
     # -- deferred mode -----------------------------------------------------------------------------------------------
     def _attach(self, p):
@@ -529,10 +643,10 @@ class Adam(_RunsOptimizer):
             if world:
                 self._apply_runs_exchanged(lib, p, pend, m, v, t, None, FIL_ADAM_KERAS, world, hyper, st)
             else:
-                check(lib.fil_embed_adam_runs_deferred(ptr(pend["g"]), ptr(pend["perm"]), ptr(pend["sorted_ids"]), pend["R"], K,
-                                                       pend["g_dtype"], F, ptr(offsets), ptr(field_l2), ptr(frozen), ptr(p), ptr(m), ptr(v),
-                                                       ptr(d.stamp), ptr(d.ring), self.sweep_period, V, ptr(t), lr, b1, b2, eps, st),
-                      "fil_embed_adam_runs_deferred")
+                fn, r, name = _rated(lib, "fil_embed_adam_runs_deferred", lr)
+                check(fn(ptr(pend["g"]), ptr(pend["perm"]), ptr(pend["sorted_ids"]), pend["R"], K, pend["g_dtype"], F, ptr(offsets),
+                         ptr(field_l2), ptr(frozen), ptr(p), ptr(m), ptr(v), ptr(d.stamp), ptr(d.ring), self.sweep_period, V, ptr(t), r,
+                         b1, b2, eps, st), name)
         d.roll(p, hyper, FIL_ADAM_ROLL_STEP)
 
     @torch.no_grad()
@@ -550,13 +664,13 @@ class Adam(_RunsOptimizer):
         if p in self._defer:
             d = self._defer[p]
             offsets, field_l2, frozen, F = d.field_args(p, pend)
-            check(lib.fil_embed_adam_merged_deferred(ptr(ids), ptr(values), ptr(counts), world, cap, K, ptr(offsets), ptr(field_l2),
-                                                     ptr(frozen), F, ptr(p), ptr(m), ptr(v), ptr(d.stamp), ptr(d.ring),
-                                                     self.sweep_period, V, ptr(t), lr, b1, b2, eps, st), "fil_embed_adam_merged_deferred")
+            fn, r, name = _rated(lib, "fil_embed_adam_merged_deferred", lr)
+            check(fn(ptr(ids), ptr(values), ptr(counts), world, cap, K, ptr(offsets), ptr(field_l2), ptr(frozen), F, ptr(p), ptr(m),
+                     ptr(v), ptr(d.stamp), ptr(d.ring), self.sweep_period, V, ptr(t), r, b1, b2, eps, st), name)
             return
-        check(lib.fil_embed_adam_merged(ptr(ids), ptr(values), ptr(counts), world, cap, K, ptr(pend["offsets"]), ptr(pend["field_l2"]),
-                                        pend["F"], ptr(p), ptr(m), ptr(v), ptr(stamp), V, ptr(t), lr, b1, b2, eps, mode, st),
-              "fil_embed_adam_merged")
+        fn, r, name = _rated(lib, "fil_embed_adam_merged", lr)
+        check(fn(ptr(ids), ptr(values), ptr(counts), world, cap, K, ptr(pend["offsets"]), ptr(pend["field_l2"]), pend["F"], ptr(p),
+                 ptr(m), ptr(v), ptr(stamp), V, ptr(t), r, b1, b2, eps, mode, st), name)
 
 
 class _Rowwise(_RunsOptimizer):
@@ -570,9 +684,17 @@ class _Rowwise(_RunsOptimizer):
     def _slot_init(self, group):
         return group["initial_accumulator_value"], 0.0
 
+    @staticmethod
+    def _rate_args(lib, name, hyper):
+        """(entry point, the arguments from the hyper-parameters on, name): hyper = (RowoptHyper, the rate word or None)."""
+        h, lr_dev = hyper
+        if lr_dev is None:
+            return getattr(lib, name), (ctypes.addressof(h),), name
+        return getattr(lib, name + "_lrdev"), (ctypes.addressof(h), lr_dev.data_ptr()), name + "_lrdev"
+
     def _launch_dense(self, lib, desc, n, numel, t, hyper, advance):
-        check(lib.fil_rowopt_multi(ptr(desc), n, numel, ptr(t), self._RULE, ctypes.addressof(hyper), advance, stream_ptr()),
-              "fil_rowopt_multi")
+        fn, h, name = self._rate_args(lib, "fil_rowopt_multi", hyper)
+        check(fn(ptr(desc), n, numel, ptr(t), self._RULE, *h, advance, stream_ptr()), name)
 
     def _admit(self, p, pend):
         if deferred_state(p) is not None:
@@ -581,7 +703,6 @@ class _Rowwise(_RunsOptimizer):
 
     def _apply_runs(self, lib, p, pend, acc, lin, t, hyper):
         V, K = p.shape
-        h = ctypes.addressof(hyper)
         field_l2 = pend["field_l2"]
         # a regularised field: its untouched rows move too (the sweep), stamps tell them apart
         stamp = self._stamp(p) if field_l2 is not None else None
@@ -590,16 +711,17 @@ class _Rowwise(_RunsOptimizer):
             world = self._exchange_world()
             if world:
                 ids, values, counts, cap = self._compact_and_exchange(lib, p, pend, world, st)
-                check(lib.fil_embed_rowopt_merged(ptr(ids), ptr(values), ptr(counts), world, cap, K, ptr(pend["offsets"]), ptr(field_l2),
-                                                  pend["F"], ptr(p), ptr(acc), ptr(lin), ptr(stamp), V, ptr(t), self._RULE, h, st),
-                      "fil_embed_rowopt_merged")
+                fn, h, name = self._rate_args(lib, "fil_embed_rowopt_merged", hyper)
+                check(fn(ptr(ids), ptr(values), ptr(counts), world, cap, K, ptr(pend["offsets"]), ptr(field_l2), pend["F"], ptr(p),
+                         ptr(acc), ptr(lin), ptr(stamp), V, ptr(t), self._RULE, *h, st), name)
             else:
-                check(lib.fil_embed_rowopt_runs(ptr(pend["g"]), ptr(pend["perm"]), ptr(pend["sorted_ids"]), pend["R"], K, pend["g_dtype"],
-                                                pend["F"], ptr(field_l2), ptr(p), ptr(acc), ptr(lin), ptr(stamp), ptr(t), self._RULE, h,
-                                                st), "fil_embed_rowopt_runs")
+                fn, h, name = self._rate_args(lib, "fil_embed_rowopt_runs", hyper)
+                check(fn(ptr(pend["g"]), ptr(pend["perm"]), ptr(pend["sorted_ids"]), pend["R"], K, pend["g_dtype"], pend["F"],
+                         ptr(field_l2), ptr(p), ptr(acc), ptr(lin), ptr(stamp), ptr(t), self._RULE, *h, st), name)
             if field_l2 is not None:
-                check(lib.fil_embed_rowopt_sweep(ptr(p), ptr(acc), ptr(lin), ptr(stamp), V, K, ptr(pend["offsets"]), ptr(field_l2),
-                                                 ptr(pend["frozen"]), pend["F"], ptr(t), self._RULE, h, st), "fil_embed_rowopt_sweep")
+                fn, h, name = self._rate_args(lib, "fil_embed_rowopt_sweep", hyper)
+                check(fn(ptr(p), ptr(acc), ptr(lin), ptr(stamp), V, K, ptr(pend["offsets"]), ptr(field_l2), ptr(pend["frozen"]),
+                         pend["F"], ptr(t), self._RULE, *h, st), name)
 
 
 class Adagrad(_Rowwise):
@@ -613,18 +735,19 @@ class Adagrad(_Rowwise):
     _SLOTS = ("accumulator",)
 
     def __init__(self, params, learning_rate=0.001, initial_accumulator_value=0.1, epsilon=1e-7, process_group=None,
-                 force_exchange=False):
+                 force_exchange=False, decay=0.0):
         if epsilon is None:
             epsilon = 1e-7              # Keras: backend.epsilon()
         if initial_accumulator_value < 0.0:
             raise ValueError("initial_accumulator_value must be non-negative: %s" % initial_accumulator_value)
-        if not learning_rate >= 0.0 or not epsilon >= 0.0:
+        learning_rate, decay = _check_rate("Adagrad", learning_rate, decay)
+        if not epsilon >= 0.0:
             raise ValueError("Adagrad: learning_rate=%r epsilon=%r (both >= 0)" % (learning_rate, epsilon))
-        super().__init__(params, dict(learning_rate=float(learning_rate), initial_accumulator_value=float(initial_accumulator_value),
-                                      epsilon=float(epsilon)), process_group, force_exchange)
+        super().__init__(params, dict(learning_rate=learning_rate, initial_accumulator_value=float(initial_accumulator_value),
+                                      epsilon=float(epsilon), **_decay_entry(decay)), process_group, force_exchange)
 
-    def _hyper(self, group):
-        return RowoptHyper(group["learning_rate"], group["epsilon"], 0.0, 0.0, 0.0, 0.0)
+    def _hyper(self, group, lr_dev=None):
+        return RowoptHyper(_float_rate(group), group["epsilon"], 0.0, 0.0, 0.0, 0.0), lr_dev
 
 
 class Ftrl(_Rowwise):
@@ -643,7 +766,7 @@ class Ftrl(_Rowwise):
 
     def __init__(self, params, learning_rate=0.001, learning_rate_power=-0.5, initial_accumulator_value=0.1,
                  l1_regularization_strength=0.0, l2_regularization_strength=0.0, l2_shrinkage_regularization_strength=0.0,
-                 process_group=None, force_exchange=False):
+                 process_group=None, force_exchange=False, decay=0.0):
         if initial_accumulator_value < 0.0:
             raise ValueError("initial_accumulator_value %f needs to be positive or zero" % initial_accumulator_value)
         if learning_rate_power > 0.0:
@@ -655,18 +778,18 @@ class Ftrl(_Rowwise):
         if l2_shrinkage_regularization_strength < 0.0:
             raise ValueError("l2_shrinkage_regularization_strength %f needs to be positive or zero"
                              % l2_shrinkage_regularization_strength)
-        if not learning_rate >= 0.0:
-            raise ValueError("Ftrl: learning_rate=%r (>= 0)" % (learning_rate,))
-        super().__init__(params, dict(learning_rate=float(learning_rate), learning_rate_power=float(learning_rate_power),
+        learning_rate, decay = _check_rate("Ftrl", learning_rate, decay)
+        super().__init__(params, dict(learning_rate=learning_rate, learning_rate_power=float(learning_rate_power),
                                       initial_accumulator_value=float(initial_accumulator_value),
                                       l1_regularization_strength=float(l1_regularization_strength),
                                       l2_regularization_strength=float(l2_regularization_strength),
-                                      l2_shrinkage_regularization_strength=float(l2_shrinkage_regularization_strength)),
+                                      l2_shrinkage_regularization_strength=float(l2_shrinkage_regularization_strength),
+                                      **_decay_entry(decay)),
                          process_group, force_exchange)
 
-    def _hyper(self, group):
-        return RowoptHyper(group["learning_rate"], 0.0, group["learning_rate_power"], group["l1_regularization_strength"],
-                           group["l2_regularization_strength"], group["l2_shrinkage_regularization_strength"])
+    def _hyper(self, group, lr_dev=None):
+        return RowoptHyper(_float_rate(group), 0.0, group["learning_rate_power"], group["l1_regularization_strength"],
+                           group["l2_regularization_strength"], group["l2_shrinkage_regularization_strength"]), lr_dev
 
 
 def rowopt_merged(rule, ids, values, counts, W, cap, offsets, field_l2, table, accum, linear, stamp, step, hyper):
