@@ -72,12 +72,13 @@ def main():
     ap.add_argument("--cin-precision", default="f32", choices=["f32", "bf16"],
                     help="XDeepFM only: bf16 = the CIN's labelled bf16 training mode (one bf16 MFMA per product in its three GEMM "
                          "launches, ~1e-3 relative error); f32 = the exact chain")
-    ap.add_argument("--optimizer", default="torch", choices=["torch", "keras", "keras-lazy", "keras-adagrad", "keras-ftrl"],
+    ap.add_argument("--optimizer", default="torch", choices=["torch", "keras", "keras-lazy", "keras-adagrad", "keras-ftrl", "keras-sgd", "keras-rmsprop"],
                     help="torch = torch.optim.Adam on dense table gradients; keras = ml_function_amd.optim.Adam (Keras' epsilon placement), "
                          "on one GPU with the tables updated in place from the batch's gradient runs (tableGrad='runs'); keras-lazy = the "
                          "same with LazyAdam tables (only touched rows change: a labelled deviation from the reference); keras-adagrad / "
                          "keras-ftrl = ml_function_amd.optim.Adagrad / Ftrl (Keras' defaults and semantics, the tables in place as for "
-                         "keras; Ftrl's strengths: --ftrl-*).  Data parallel: the tables keep their dense gradients and the sparse row "
+                         "keras; Ftrl's strengths: --ftrl-*); keras-sgd / keras-rmsprop = ml_function_amd.optim.SGD / RMSprop (--momentum, "
+                         "--nesterov, --rho; RMSprop without momentum is what Keras' optimizer='rmsprop' builds).  Data parallel: the tables keep their dense gradients and the sparse row "
                          "exchange unless --dp-tables runs")
     ap.add_argument("--dp-tables", default="dense", choices=["dense", "runs"],
                     help="data parallel with --optimizer keras*: runs = the tables take tableGrad='runs' and the optimizer's runs "
@@ -92,6 +93,9 @@ def main():
     ap.add_argument("--ftrl-l1", type=float, default=0.0, help="--optimizer keras-ftrl: l1_regularization_strength")
     ap.add_argument("--ftrl-l2", type=float, default=0.0, help="--optimizer keras-ftrl: l2_regularization_strength")
     ap.add_argument("--ftrl-l2-shrinkage", type=float, default=0.0, help="--optimizer keras-ftrl: l2_shrinkage_regularization_strength")
+    ap.add_argument("--momentum", type=float, default=0.0, help="--optimizer keras-sgd / keras-rmsprop: momentum, in [0, 1]")
+    ap.add_argument("--nesterov", action="store_true", help="--optimizer keras-sgd: Nesterov momentum")
+    ap.add_argument("--rho", type=float, default=0.9, help="--optimizer keras-rmsprop: rho")
     ap.add_argument("--lr-schedule", default="none", choices=["none", "exponential", "inverse-time", "polynomial", "piecewise"],
                     help="with --optimizer keras*: a Keras learning-rate schedule (ml_function_amd.schedules) starting at --lr, evaluated "
                          "on the GPU from the optimizer's step counter -- it stays inside the captured graph.  exponential / inverse-time: "
@@ -165,6 +169,11 @@ def main():
     use_graph = world == 1 and not args.no_graph
     if args.optimizer == "keras-adagrad":       # Keras' Adagrad; tables in "runs" mode get their l2 inside the update
         opt = optim.Adagrad(model.parameters(), learning_rate=lr, decay=args.lr_decay)
+    elif args.optimizer == "keras-sgd":         # Keras' SGD (plain, momentum, Nesterov), likewise
+        opt = optim.SGD(model.parameters(), learning_rate=lr, momentum=args.momentum, nesterov=args.nesterov, decay=args.lr_decay)
+    elif args.optimizer == "keras-rmsprop":     # Keras' RMSprop; without momentum every row's rms decays at every step (one sweep)
+        opt = optim.RMSprop(model.parameters(), learning_rate=lr, rho=args.rho, momentum=args.momentum, epsilon=1e-7,
+                            decay=args.lr_decay)
     elif args.optimizer == "keras-ftrl":        # Keras' Ftrl, likewise
         opt = optim.Ftrl(model.parameters(), learning_rate=lr, learning_rate_power=args.ftrl_lr_power,
                          l1_regularization_strength=args.ftrl_l1, l2_regularization_strength=args.ftrl_l2,

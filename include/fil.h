@@ -573,6 +573,74 @@ int fil_embed_rowopt_merged_lrdev(const int64_t* ids, const float* values, const
                                   const float* lr_dev, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * O4  Keras-exact SGD and RMSprop (TF 2.1 keras/optimizer_v2/gradient_descent.py, rmsprop.py -> ApplyKerasMomentum, ApplyRMSProp and
+ *     their Sparse twins), every tensor fp32, `rule` FIL_OPT_SGD or FIL_OPT_RMSPROP, hyper-parameters in a fil_momopt_hyper read ON THE
+ *     HOST at the call (a captured graph keeps the values it was captured with).  Entry points added only: the ABI version stays.
+ *     Every operation rounds to fp32 in the order written (no fused multiply-add; correctly rounded division and square root):
+ *       SGD      momentum == 0   p -= g*lr                                              no slot: slot0 / slot1 (m / v) may be NULL
+ *       SGD      momentum  > 0   a = a*momentum - g*lr;  p += a     (FIL_MOMOPT_NESTEROV: p += a*momentum - g*lr)     a in slot0
+ *       RMSprop  momentum == 0   rms = rho*rms + (1 - rho)*(g*g);  p -= lr*g / (sqrt(rms) + epsilon)                 rms in slot0
+ *                                (Keras computes this variant in Python ops: epsilon OUTSIDE the root; 1 - rho formed once in fp32)
+ *       RMSprop  momentum  > 0   the fused ops, epsilon INSIDE the root, rms in slot0, mom in slot1:
+ *                  dense rows    rms += (g*g - rms)*(1 - rho);  mom = mom*momentum + (g*lr) / sqrt(rms + epsilon);  p -= mom
+ *                  touched rows  rms = rms*rho + (g*g)*(1 - rho);  mom = mom*momentum + ((1 / sqrt(rms + epsilon))*lr)*g;  p -= mom
+ *     slot0 lives in the `m` array of fil_adam_tensor, slot1 in `v`; a slot the variant does not have is never read or written.
+ *     Requires lr >= 0, momentum in [0, 1]; RMSprop epsilon >= 0, rho in [0, 1], no Nesterov flag (FIL_ERR_ARG otherwise).  None of the
+ *     rules reads the step counter; it is kept (Keras' iterations) and used for the row stamps only.
+ *   Which rows Keras updates.  All variants but RMSprop with momentum == 0 are row-local, exactly as O2: a touched row takes the touched
+ *     form with g = run sum + 2 emb_reg p; an untouched row of a field with emb_reg > 0 takes the DENSE form with g = 2 emb_reg p (the
+ *     regulariser's gradient is dense: its momentum decays and it moves); every other row and its slots keep their bits; a frozen field
+ *     never changes.  RMSprop with momentum == 0 is not row-local: for IndexedSlices Keras first assigns rms = rms*rho over the WHOLE
+ *     variable, then scatters (g*g)*(1 - rho) at the batch's rows and moves only those.  So there an untouched row of an unregularised,
+ *     non-frozen field takes rms = rms*rho and its p keeps its bits.  (SGD with momentum == 0: Keras scatter-adds each duplicate id on
+ *     its own in an unspecified order; here the run is summed first, in fil_embed_run_sum's order, like every other rule.)
+ *   fil_momopt_multi: fil_rowopt_multi's contract with these rules (dense form).
+ *   fil_embed_momopt_runs: fil_embed_rowopt_runs' contract (touched form); stamps when stamp != NULL -- needed when a sweep follows:
+ *     a regularised field, or RMSprop with momentum == 0 on any table.
+ *   fil_embed_momopt_sweep: the unstamped rows.  Row-local variants: fil_embed_rowopt_sweep's shape, the rows of the regularised,
+ *     non-frozen fields only (field_l2 NULL: nothing to do, no launch).  RMSprop with momentum == 0: one launch over every non-frozen
+ *     field (field_l2 may be NULL) -- an unregularised field's row reads and writes rms alone (8 bytes per element; p, and anything
+ *     else, is not touched), a regularised one takes the full rule (16 bytes per element).  16-byte accesses when K % 4 == 0 and the
+ *     arrays are 16-byte aligned, non-temporal stores, F <= 1024.
+ *   fil_embed_momopt_merged: fil_embed_rowopt_merged's contract (touched form); W = 1 is bit-identical to fil_embed_momopt_runs on the
+ *     same record.  F <= 1024, K <= 256.
+ *   The *_lrdev twins read the rate from device memory (lr_dev, one fp32, not NULL), as in O3; fil_momopt_hyper.lr is then ignored.
+ */
+enum { FIL_OPT_SGD = 3, FIL_OPT_RMSPROP = 4 };
+enum { FIL_MOMOPT_NESTEROV = 1 };
+typedef struct {
+  float lr;
+  float epsilon;        /* RMSprop */
+  float rho;            /* RMSprop */
+  float momentum;       /* 0 = none (no momentum slot) */
+  int32_t flags;        /* SGD: FIL_MOMOPT_NESTEROV */
+  int32_t reserved;     /* 0 */
+} fil_momopt_hyper;     /* 24 bytes */
+int fil_momopt_multi(const fil_adam_tensor* tensors, int n, int64_t total_numel, int64_t* step, int rule, const fil_momopt_hyper* hyper,
+                     int advance, void* stream);
+int fil_embed_momopt_runs(const void* g, const int64_t* perm, const int64_t* sorted_ids, long R, int K, int g_dtype, int F,
+                          const float* field_l2, float* table, float* slot0, float* slot1, int32_t* stamp, const int64_t* step, int rule,
+                          const fil_momopt_hyper* hyper, void* stream);
+int fil_embed_momopt_sweep(float* table, float* slot0, float* slot1, const int32_t* stamp, int64_t V, int K, const int64_t* offsets,
+                           const float* field_l2, const unsigned char* frozen, int F, const int64_t* step, int rule,
+                           const fil_momopt_hyper* hyper, void* stream);
+int fil_embed_momopt_merged(const int64_t* ids, const float* values, const int64_t* counts, int W, long cap, int K, const int64_t* offsets,
+                            const float* field_l2, int F, float* table, float* slot0, float* slot1, int32_t* stamp, int64_t V,
+                            const int64_t* step, int rule, const fil_momopt_hyper* hyper, void* stream);
+int fil_momopt_multi_lrdev(const fil_adam_tensor* tensors, int n, int64_t total_numel, int64_t* step, int rule,
+                           const fil_momopt_hyper* hyper, const float* lr_dev, int advance, void* stream);
+int fil_embed_momopt_runs_lrdev(const void* g, const int64_t* perm, const int64_t* sorted_ids, long R, int K, int g_dtype, int F,
+                                const float* field_l2, float* table, float* slot0, float* slot1, int32_t* stamp, const int64_t* step,
+                                int rule, const fil_momopt_hyper* hyper, const float* lr_dev, void* stream);
+int fil_embed_momopt_sweep_lrdev(float* table, float* slot0, float* slot1, const int32_t* stamp, int64_t V, int K, const int64_t* offsets,
+                                 const float* field_l2, const unsigned char* frozen, int F, const int64_t* step, int rule,
+                                 const fil_momopt_hyper* hyper, const float* lr_dev, void* stream);
+int fil_embed_momopt_merged_lrdev(const int64_t* ids, const float* values, const int64_t* counts, int W, long cap, int K,
+                                  const int64_t* offsets, const float* field_l2, int F, float* table, float* slot0, float* slot1,
+                                  int32_t* stamp, int64_t V, const int64_t* step, int rule, const fil_momopt_hyper* hyper,
+                                  const float* lr_dev, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * M1  Keras' streaming AUC (TF 2.1 keras/metrics.py: AUC; keras/utils/metrics_utils.py: update_confusion_matrix_variables) --
  *     replaces metrics=[tf.keras.metrics.AUC()] of example/ctr_example/un_seq.py:61.  Entry points added only: the ABI version stays.
  *   State: cm [4][T] fp32 = TP | FP | TN | FN per threshold, as Keras keeps them, and one int64 `invalid`.

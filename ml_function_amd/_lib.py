@@ -29,6 +29,8 @@ FIL_F32, FIL_BF16 = 0, 1
 FIL_ADAM_KERAS, FIL_ADAM_LAZY = 0, 1
 FIL_ADAM_ROLL_STEP, FIL_ADAM_ROLL_SKIP, FIL_ADAM_ROLL_FLUSH = 0, 1, 2
 FIL_OPT_ADAGRAD, FIL_OPT_FTRL = 1, 2
+FIL_OPT_SGD, FIL_OPT_RMSPROP = 3, 4
+FIL_MOMOPT_NESTEROV = 1
 FIL_CONFUSION_MAX_T, FIL_CONFUSION_ONE_LAUNCH_N = 2048, 16384
 
 _c = ctypes
@@ -117,6 +119,15 @@ SIGNATURES = {
     "fil_embed_rowopt_runs_lrdev": (_I, [_P, _P, _P, _c.c_long, _I, _I, _I, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P]),
     "fil_embed_rowopt_sweep_lrdev": (_I, [_P, _P, _P, _P, _c.c_int64, _I, _P, _P, _P, _I, _P, _I, _P, _P, _P]),
     "fil_embed_rowopt_merged_lrdev": (_I, [_P, _P, _P, _I, _c.c_long, _I, _P, _P, _I, _P, _P, _P, _P, _c.c_int64, _P, _I, _P, _P, _P]),
+    # O4: SGD / RMSprop -- the argument lists of the O2 entry points, with a fil_momopt_hyper
+    "fil_momopt_multi": (_I, [_P, _I, _c.c_int64, _P, _I, _P, _I, _P]),
+    "fil_embed_momopt_runs": (_I, [_P, _P, _P, _c.c_long, _I, _I, _I, _P, _P, _P, _P, _P, _P, _I, _P, _P]),
+    "fil_embed_momopt_sweep": (_I, [_P, _P, _P, _P, _c.c_int64, _I, _P, _P, _P, _I, _P, _I, _P, _P]),
+    "fil_embed_momopt_merged": (_I, [_P, _P, _P, _I, _c.c_long, _I, _P, _P, _I, _P, _P, _P, _P, _c.c_int64, _P, _I, _P, _P]),
+    "fil_momopt_multi_lrdev": (_I, [_P, _I, _c.c_int64, _P, _I, _P, _P, _I, _P]),
+    "fil_embed_momopt_runs_lrdev": (_I, [_P, _P, _P, _c.c_long, _I, _I, _I, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P]),
+    "fil_embed_momopt_sweep_lrdev": (_I, [_P, _P, _P, _P, _c.c_int64, _I, _P, _P, _P, _I, _P, _I, _P, _P, _P]),
+    "fil_embed_momopt_merged_lrdev": (_I, [_P, _P, _P, _I, _c.c_long, _I, _P, _P, _I, _P, _P, _P, _P, _c.c_int64, _P, _I, _P, _P, _P]),
     "fil_confusion_workspace_bytes": (_Z, [_I, _I]),
     "fil_confusion_update": (_I, [_P, _P, _I, _P, _I, _P, _P, _P, _Z, _P]),
     "fil_auc_result": (_I, [_P, _I, _I, _I, _P, _P]),
@@ -127,6 +138,13 @@ class RowoptHyper(_c.Structure):
     """fil_rowopt_hyper (include/fil.h O2)"""
     _fields_ = [("lr", _F), ("epsilon", _F), ("lr_power", _F), ("l1", _F), ("l2", _F), ("l2_shrinkage", _F)]
 
+
+class MomoptHyper(_c.Structure):
+    """fil_momopt_hyper (include/fil.h O4)"""
+    _fields_ = [("lr", _F), ("epsilon", _F), ("rho", _F), ("momentum", _F), ("flags", _c.c_int32), ("reserved", _c.c_int32)]
+
+
+assert _c.sizeof(MomoptHyper) == 24
 
 FIL_LR_CONSTANT, FIL_LR_EXPONENTIAL, FIL_LR_INVERSE_TIME, FIL_LR_POLYNOMIAL, FIL_LR_PIECEWISE = 0, 1, 2, 3, 4
 FIL_LR_MAX_BOUNDARIES = 32

@@ -1,6 +1,7 @@
-// What the fused optimizers of optim.hip (Adam) and optim_rowwise.hip (Adagrad, Ftrl) share: the walk of the dense descriptors
-// (fil_adam_multi, fil_rowopt_multi), the field of a row, and the walk of the gathered compact lists of fil_embed_runs_compact
-// (the merged updates).  Each rule supplies only its per-element update.
+// What the fused optimizers of optim.hip (Adam), optim_rowwise.hip (Adagrad, Ftrl) and optim_momentum.hip (SGD, RMSprop) share: the
+// walk of the dense descriptors (fil_adam_multi, fil_rowopt_multi, fil_momopt_multi), the field of a row, the walk of the gathered
+// compact lists of fil_embed_runs_compact (the merged updates), the regulariser's gradient and the sweeps' compacted field table.
+// Each rule supplies only its per-element update.
 #pragma once
 #include "common.h"
 
@@ -43,13 +44,13 @@ __device__ __forceinline__ long find_in_list(const int64_t* __restrict__ ids, co
 
 // ---- the dense launch: the descriptors' elements form one index space of kMultiChunk-element chunks (a workgroup's 256 lanes x 4),
 // dealt round robin over the grid; a workgroup walks the descriptor list once and takes its chunks of each (grid-stride, balanced
-// over tensors of any size).  16-byte accesses where the descriptor's arrays allow it (`v` only counts when the rule has it: kV),
-// element-wise otherwise and in the tail.  elem(p, m, v, g, l2x2) updates one element: g the gradient (0 without one), l2x2 = 2 l2
+// over tensors of any size).  16-byte accesses where the descriptor's arrays allow it (`m` and `v` only count when the rule has them:
+// kM, kV -- a slot the rule does not have is neither read nor written and may be NULL), element-wise otherwise and in the tail.  elem(p, m, v, g, l2x2) updates one element: g the gradient (0 without one), l2x2 = 2 l2
 // of the descriptor.
 constexpr int kMultiChunk = 1024;
 
-template <bool kV, typename Elem>
-__device__ __forceinline__ void multi_tensor_walk(const fil_adam_tensor* __restrict__ ts, int n, const Elem& elem) {
+template <bool kM, bool kV, typename Elem>
+__device__ __forceinline__ void multi_tensor_walk_slots(const fil_adam_tensor* __restrict__ ts, int n, const Elem& elem) {
   const long G = gridDim.x;
   long base = 0;
   for (int d = 0; d < n; ++d) {
@@ -60,7 +61,7 @@ __device__ __forceinline__ void multi_tensor_walk(const fil_adam_tensor* __restr
     const long numel = ts[d].numel;
     const float l2x2 = 2.f * ts[d].l2;
     const long nc = (numel + kMultiChunk - 1) / kMultiChunk;
-    const bool vec = ((((uintptr_t)P | (uintptr_t)Gr | (uintptr_t)M | (kV ? (uintptr_t)V : 0)) & 15) == 0);
+    const bool vec = ((((uintptr_t)P | (uintptr_t)Gr | (kM ? (uintptr_t)M : 0) | (kV ? (uintptr_t)V : 0)) & 15) == 0);
     long r = ((long)blockIdx.x - base) % G;
     if (r < 0) r += G;
     for (long ch = r; ch < nc; ch += G) {
@@ -68,27 +69,33 @@ __device__ __forceinline__ void multi_tensor_walk(const fil_adam_tensor* __restr
       if (vec && e + 4 <= numel) {
         float4 p = *reinterpret_cast<const float4*>(P + e);
         float4 g = Gr ? *reinterpret_cast<const float4*>(Gr + e) : make_float4(0.f, 0.f, 0.f, 0.f);
-        float4 m = *reinterpret_cast<const float4*>(M + e);
+        float4 m = kM ? *reinterpret_cast<const float4*>(M + e) : make_float4(0.f, 0.f, 0.f, 0.f);
         float4 v = kV ? *reinterpret_cast<const float4*>(V + e) : make_float4(0.f, 0.f, 0.f, 0.f);
         elem(p.x, m.x, v.x, g.x, l2x2);
         elem(p.y, m.y, v.y, g.y, l2x2);
         elem(p.z, m.z, v.z, g.z, l2x2);
         elem(p.w, m.w, v.w, g.w, l2x2);
         *reinterpret_cast<float4*>(P + e) = p;
-        *reinterpret_cast<float4*>(M + e) = m;
+        if (kM) *reinterpret_cast<float4*>(M + e) = m;
         if (kV) *reinterpret_cast<float4*>(V + e) = v;
       } else {
         for (long i = e; i < e + 4 && i < numel; ++i) {
-          float p = P[i], m = M[i], v = kV ? V[i] : 0.f;
+          float p = P[i], m = kM ? M[i] : 0.f, v = kV ? V[i] : 0.f;
           elem(p, m, v, Gr ? Gr[i] : 0.f, l2x2);
           P[i] = p;
-          M[i] = m;
+          if (kM) M[i] = m;
           if (kV) V[i] = v;
         }
       }
     }
     base += nc;
   }
+}
+
+// the walk of a rule that always has its first slot (Adam, Adagrad, Ftrl)
+template <bool kV, typename Elem>
+__device__ __forceinline__ void multi_tensor_walk(const fil_adam_tensor* __restrict__ ts, int n, const Elem& elem) {
+  multi_tensor_walk_slots<true, kV>(ts, n, elem);
 }
 
 // launches the one-thread kernel that advances a device step counter behind the dense update (defined once, in optim.hip)
@@ -136,6 +143,98 @@ __device__ __forceinline__ void merged_row_sums(long q0, long stride, const int6
     }
     fin(row);
   }
+}
+
+// g = run sum + 2 l2 p of a field's regulariser (rounded as written)
+__device__ __forceinline__ float with_l2(float acc, float l2x2, float p) {
+#pragma clang fp contract(off)
+  return acc + l2x2 * p;
+}
+
+// ---- the sweep's field table.  Only some fields' untouched rows move (the regularised, non-frozen ones; for a rule whose slot decays
+// everywhere, every non-frozen one), so a sweep's grid walks those fields' rows only: every workgroup compacts the field table in LDS
+// into "virtual" row ranges (an integer scan over F <= 1024 fields, a few hundred cycles) and strides over the virtual rows; a virtual
+// row maps back to its table row by a binary search.
+struct RegTab {
+  int64_t vbeg[kSweepMaxF + 1];   // virtual row where compacted field c starts; vbeg[n] = all regularised rows
+  int64_t rbeg[kSweepMaxF];       // its first table row
+  float l2x2[kSweepMaxF];         // 2 field_l2
+  int n;
+};
+
+// exclusive scan of x over a 256-lane workgroup in lane order (s: 4 longs of LDS); *total = the sum over all lanes
+__device__ __forceinline__ long block_scan_256(long x, long* s, long* total) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  long incl = x;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const long y = __shfl_up(incl, o, 64);
+    if (lane >= o) incl += y;
+  }
+  if (lane == 63) s[wave] = incl;
+  __syncthreads();
+  long before = incl - x;
+  for (int w = 0; w < wave; ++w) before += s[w];
+  *total = (s[0] + s[1]) + (s[2] + s[3]);
+  __syncthreads();
+  return before;
+}
+
+// kAll: every non-frozen field joins the table (2 field_l2 = 0 for an unregularised one, field_l2 may then be NULL), not only the
+// regularised ones
+template <bool kAll = false>
+__device__ __forceinline__ void load_reg_tab(RegTab* t, const int64_t* __restrict__ offsets, const float* __restrict__ field_l2,
+                                             const unsigned char* __restrict__ frozen, int F, int64_t V) {
+  __shared__ long s[4];
+  int64_t lo[4], rows[4];
+  long cnt = 0, sum = 0;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const int f = threadIdx.x * 4 + i;
+    lo[i] = 0;
+    rows[i] = 0;
+    if (f < F && !(frozen && frozen[f]) && (kAll || field_l2[f] > 0.f)) {
+      int64_t a = offsets[f], b = f + 1 < F ? offsets[f + 1] : V;
+      a = a < 0 ? 0 : (a > V ? V : a);
+      b = b < a ? a : (b > V ? V : b);
+      if (b > a) {
+        lo[i] = a;
+        rows[i] = b - a;
+        ++cnt;
+        sum += b - a;
+      }
+    }
+  }
+  long nf, total;
+  long c = block_scan_256(cnt, s, &nf);
+  long v = block_scan_256(sum, s, &total);
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    if (rows[i] > 0) {
+      t->vbeg[c] = v;
+      t->rbeg[c] = lo[i];
+      const float l2 = field_l2 ? field_l2[threadIdx.x * 4 + i] : 0.f;
+      t->l2x2[c] = kAll && !(l2 > 0.f) ? 0.f : 2.f * l2;
+      ++c;
+      v += rows[i];
+    }
+  }
+  if (threadIdx.x == 0) {
+    t->n = (int)nf;
+    t->vbeg[nf] = total;
+  }
+  __syncthreads();
+}
+
+// compacted field c holding virtual row vr (vbeg[c] <= vr < vbeg[c + 1])
+__device__ __forceinline__ int reg_field(const RegTab* t, int64_t vr) {
+  int lo = 0, hi = t->n;
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    if (t->vbeg[mid] <= vr) lo = mid + 1;
+    else hi = mid;
+  }
+  return lo - 1;
 }
 
 }  // namespace fil

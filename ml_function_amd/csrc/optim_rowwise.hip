@@ -33,12 +33,6 @@ static RowHyper row_hyper(const fil_rowopt_hyper& h) {
   return r;
 }
 
-// g = run sum + 2 l2 p of a field's regulariser (rounded as written)
-__device__ __forceinline__ float with_l2(float acc, float l2x2, float p) {
-#pragma clang fp contract(off)
-  return acc + l2x2 * p;
-}
-
 // (the *_lrdev entry points: the kernels take the rate from the word fil_lr_schedule_eval left on the device, `if (lr_dev) h.lr =
 // *lr_dev` -- one wave-uniform load at the top of each kernel; a by-value launch passes NULL)
 // one element of the rule: s = the accumulator, z = Ftrl's linear slot (unused by Adagrad)
@@ -111,84 +105,6 @@ __global__ __launch_bounds__(256) void embed_rowopt_runs_kernel(const GT* __rest
 // rows only: every workgroup compacts the field table in LDS into "virtual" row ranges (an integer scan over F <= 1024 fields, a
 // few hundred cycles) and strides over the virtual rows; a virtual row maps back to its table row by a binary search.  The grid is
 // sized by the table (no data-dependent size: capturable); workgroups past the regularised rows leave at once.
-struct RegTab {
-  int64_t vbeg[kSweepMaxF + 1];   // virtual row where compacted field c starts; vbeg[n] = all regularised rows
-  int64_t rbeg[kSweepMaxF];       // its first table row
-  float l2x2[kSweepMaxF];         // 2 field_l2
-  int n;
-};
-
-// exclusive scan of x over a 256-lane workgroup in lane order (s: 4 longs of LDS); *total = the sum over all lanes
-__device__ __forceinline__ long block_scan_256(long x, long* s, long* total) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  long incl = x;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const long y = __shfl_up(incl, o, 64);
-    if (lane >= o) incl += y;
-  }
-  if (lane == 63) s[wave] = incl;
-  __syncthreads();
-  long before = incl - x;
-  for (int w = 0; w < wave; ++w) before += s[w];
-  *total = (s[0] + s[1]) + (s[2] + s[3]);
-  __syncthreads();
-  return before;
-}
-
-__device__ __forceinline__ void load_reg_tab(RegTab* t, const int64_t* __restrict__ offsets, const float* __restrict__ field_l2,
-                                             const unsigned char* __restrict__ frozen, int F, int64_t V) {
-  __shared__ long s[4];
-  int64_t lo[4], rows[4];
-  long cnt = 0, sum = 0;
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const int f = threadIdx.x * 4 + i;
-    lo[i] = 0;
-    rows[i] = 0;
-    if (f < F && !(frozen && frozen[f]) && field_l2[f] > 0.f) {
-      int64_t a = offsets[f], b = f + 1 < F ? offsets[f + 1] : V;
-      a = a < 0 ? 0 : (a > V ? V : a);
-      b = b < a ? a : (b > V ? V : b);
-      if (b > a) {
-        lo[i] = a;
-        rows[i] = b - a;
-        ++cnt;
-        sum += b - a;
-      }
-    }
-  }
-  long nf, total;
-  long c = block_scan_256(cnt, s, &nf);
-  long v = block_scan_256(sum, s, &total);
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    if (rows[i] > 0) {
-      t->vbeg[c] = v;
-      t->rbeg[c] = lo[i];
-      t->l2x2[c] = 2.f * field_l2[threadIdx.x * 4 + i];
-      ++c;
-      v += rows[i];
-    }
-  }
-  if (threadIdx.x == 0) {
-    t->n = (int)nf;
-    t->vbeg[nf] = total;
-  }
-  __syncthreads();
-}
-
-// compacted field c holding virtual row vr (vbeg[c] <= vr < vbeg[c + 1])
-__device__ __forceinline__ int reg_field(const RegTab* t, int64_t vr) {
-  int lo = 0, hi = t->n;
-  while (lo < hi) {
-    const int mid = (lo + hi) >> 1;
-    if (t->vbeg[mid] <= vr) lo = mid + 1;
-    else hi = mid;
-  }
-  return lo - 1;
-}
-
 template <int RULE>
 __global__ __launch_bounds__(256) void embed_rowopt_sweep_kernel(float* __restrict__ table, float* __restrict__ S, float* __restrict__ Z,
                                                                  const int32_t* __restrict__ stamp, int64_t V, int K,

@@ -992,8 +992,8 @@ def embed_gather(table, offsets, idx, sizes=None, frozen=None, sparse_grad=False
     The gradient is deterministic (sorted segment sums); sparse_grad=True returns it as a sparse COO tensor over the touched
     rows instead of a dense table; atomic=True selects the fp32-atomic scatter-add instead.
     runs_grad (a dict: offsets, frozen, field_l2 [F] fp32 or None): the table gets NO gradient; the backward leaves the sorted runs
-    (g, perm, sorted_ids) on the table as `table._fil_pending_runs` for optim.Adam, optim.Adagrad or optim.Ftrl to apply in place
-    (fil_embed_adam_runs / fil_embed_rowopt_runs)."""
+    (g, perm, sorted_ids) on the table as `table._fil_pending_runs` for optim.Adam, Adagrad, Ftrl, SGD or RMSprop to apply in place
+    (fil_embed_adam_runs / fil_embed_rowopt_runs / fil_embed_momopt_runs)."""
     if not emit_xt:   # (out_dtype=torch.bfloat16: the block leaves the gather rounded to bf16 and its gradient is read as bf16 -- no cast launches)
         return _EmbedFn.apply(table, offsets, sizes, idx, frozen, sparse_grad, atomic, oob_count, layout_key, None, out_dtype, runs_grad)
     # emit_xt: the same launch also writes the block transposed to [B*K, F], the layout the CIN kernels read; it rides on the

@@ -1,4 +1,4 @@
-"""Keras' Adam, Adagrad and Ftrl on the HIP path (include/fil.h O1, O2): the optimizer the reference compiles (optimizer='adam', example/ctr_example/
+"""Keras' Adam, Adagrad, Ftrl, SGD and RMSprop on the HIP path (include/fil.h O1, O2, O4): the optimizer the reference compiles (optimizer='adam', example/ctr_example/
 un_seq.py:61; TF 2.1), with Keras' names, defaults and numerics.
 
     opt = optim.Adam(model.parameters())                    # learning_rate 1e-3, beta_1 0.9, beta_2 0.999, epsilon 1e-7
@@ -50,6 +50,13 @@ Adagrad and Ftrl (Keras' tf.keras.optimizers.Adagrad / Ftrl, TF 2.1; O2) follow 
 an untouched row has no state that decays, so only the regularised fields (l2(emb_reg) > 0) are swept, over their rows alone, and
 an untouched row of any other field keeps its bits (Keras' IndexedSlices semantics).  No deferred or lazy mode.
 
+SGD and RMSprop (tf.keras.optimizers.SGD / RMSprop, TF 2.1; O4) take that contract too.  SGD (plain, momentum, Nesterov) and RMSprop
+with momentum > 0 are row-local like Adagrad.  RMSprop with momentum == 0 -- what model.compile(optimizer='rmsprop') builds -- is not:
+Keras decays the `rms` slot of EVERY row of an embedding (rms = rms * rho over the whole variable) and moves the batch's rows only, so
+its sweep walks every non-frozen field of every runs table (rms alone on the unregularised ones) and every such table has row stamps.
+SGD with momentum == 0 has no slot at all: its state holds no tensors and its launches carry NULL slots.  RMSprop(centered=True)
+raises NotImplementedError (a third slot, which the descriptors and the runs entry points do not carry).
+
 Only fp32 parameters on a GPU are supported: anything else raises (there is no CPU / eager fallback).
 """
 import ctypes
@@ -60,8 +67,9 @@ import torch.distributed as dist
 from torch.utils.weak import WeakIdKeyDictionary
 
 from . import _lib, schedules
-from ._lib import (FIL_ADAM_KERAS, FIL_ADAM_LAZY, FIL_ADAM_ROLL_FLUSH, FIL_ADAM_ROLL_SKIP, FIL_ADAM_ROLL_STEP, FIL_OPT_ADAGRAD,
-                   FIL_OPT_FTRL, FilError, RowoptHyper, check, ptr, stream_ptr)
+from ._lib import (FIL_ADAM_KERAS, FIL_ADAM_LAZY, FIL_ADAM_ROLL_FLUSH, FIL_ADAM_ROLL_SKIP, FIL_ADAM_ROLL_STEP, FIL_MOMOPT_NESTEROV,
+                   FIL_OPT_ADAGRAD, FIL_OPT_FTRL, FIL_OPT_RMSPROP, FIL_OPT_SGD, FilError, MomoptHyper, RowoptHyper, check, ptr,
+                   stream_ptr)
 
 
 class _Desc(ctypes.Structure):
@@ -190,7 +198,7 @@ class _RunsOptimizer(torch.optim.Optimizer):
     """What the fused optimizers of this module share: the device step counter (Keras' iterations), the staged descriptor arrays of
     the one dense launch per (group, device), the pending runs records, the row stamps, the data-parallel exchange of the runs
     tables, the step loop and the state.  A subclass sets _NAME (its name in messages) and _SLOTS (the state keys of its per-element
-    slots) and supplies _slot_init (their initial values), _hyper, _launch_dense and _apply_runs; Adam's deferred mode hooks in
+    slots: up to two, none for a rule without state; an instance may set its own) and supplies _slot_init (their initial values), _hyper, _launch_dense and _apply_runs; Adam's deferred mode hooks in
     through _skip and _admit."""
     _NAME = None
     _SLOTS = ()
@@ -322,6 +330,8 @@ class _RunsOptimizer(torch.optim.Optimizer):
     # -- state ---------------------------------------------------------------------------------------------------
     def _slots(self, p, group):
         """The parameter's two slot tensors, made on first use (None for a slot the rule does not have)."""
+        if not self._SLOTS:
+            return None, None
         st = self.state[p]
         if self._SLOTS[0] not in st:
             for k, x in zip(self._SLOTS, self._slot_init(group)):
@@ -408,7 +418,7 @@ class _RunsOptimizer(torch.optim.Optimizer):
                                                                                                                     tuple(p.shape)))
                 if g.dtype != torch.float32 or not g.is_contiguous() or g.shape != p.shape:
                     raise FilError("%s: gradient of %s must be a dense contiguous fp32 tensor of its shape" % (self._NAME, tuple(p.shape)))
-                per_dev.setdefault(p.device, []).append((p.data_ptr(), g.data_ptr(), s0.data_ptr(), ptr(s1), p.numel(), 0.0))
+                per_dev.setdefault(p.device, []).append((p.data_ptr(), g.data_ptr(), ptr(s0), ptr(s1), p.numel(), 0.0))
             for dev, entries in per_dev.items():
                 calls.append((dev, hypers[dev], entries))
         # the last launch on every device advances its counter -- one with no tensors where nothing dense had a gradient
@@ -678,8 +688,10 @@ class _Rowwise(_RunsOptimizer):
     initial_accumulator_value) and, for Ftrl, `linear` (zeros).  Dense parameters: one fil_rowopt_multi launch per (group, device);
     runs tables: fil_embed_rowopt_runs (or, data parallel, fil_embed_runs_compact + dp.exchange_runs + fil_embed_rowopt_merged),
     then fil_embed_rowopt_sweep over the untouched rows of the regularised fields only.  Row stamps exist only for tables with a
-    regularised field."""
+    regularised field.  SGD and RMSprop (O4) take the same calls at their own entry points (_ENTRY: the O4 argument lists are O2's),
+    RMSprop with momentum == 0 with a sweep, hence stamps, for every table (_sweeps)."""
     _RULE = None
+    _ENTRY = ("fil_rowopt_multi", "fil_embed_rowopt_runs", "fil_embed_rowopt_sweep", "fil_embed_rowopt_merged")
 
     def _slot_init(self, group):
         return group["initial_accumulator_value"], 0.0
@@ -693,7 +705,7 @@ class _Rowwise(_RunsOptimizer):
         return getattr(lib, name + "_lrdev"), (ctypes.addressof(h), lr_dev.data_ptr()), name + "_lrdev"
 
     def _launch_dense(self, lib, desc, n, numel, t, hyper, advance):
-        fn, h, name = self._rate_args(lib, "fil_rowopt_multi", hyper)
+        fn, h, name = self._rate_args(lib, self._ENTRY[0], hyper)
         check(fn(ptr(desc), n, numel, ptr(t), self._RULE, *h, advance, stream_ptr()), name)
 
     def _admit(self, p, pend):
@@ -701,25 +713,30 @@ class _Rowwise(_RunsOptimizer):
             raise FilError("%s: table %s is in optim.Adam's deferred mode (sweep_period) -- drop that optimizer first"
                            % (self._NAME, tuple(p.shape)))
 
+    def _sweeps(self, field_l2):
+        """Does a sweep follow the runs update of a table with these per-field l2 (None: no regularised field)."""
+        return field_l2 is not None
+
     def _apply_runs(self, lib, p, pend, acc, lin, t, hyper):
         V, K = p.shape
         field_l2 = pend["field_l2"]
         # a regularised field: its untouched rows move too (the sweep), stamps tell them apart
-        stamp = self._stamp(p) if field_l2 is not None else None
+        sweeps = self._sweeps(field_l2)
+        stamp = self._stamp(p) if sweeps else None
         with torch.cuda.device(p.device):
             st = stream_ptr()
             world = self._exchange_world()
             if world:
                 ids, values, counts, cap = self._compact_and_exchange(lib, p, pend, world, st)
-                fn, h, name = self._rate_args(lib, "fil_embed_rowopt_merged", hyper)
+                fn, h, name = self._rate_args(lib, self._ENTRY[3], hyper)
                 check(fn(ptr(ids), ptr(values), ptr(counts), world, cap, K, ptr(pend["offsets"]), ptr(field_l2), pend["F"], ptr(p),
                          ptr(acc), ptr(lin), ptr(stamp), V, ptr(t), self._RULE, *h, st), name)
             else:
-                fn, h, name = self._rate_args(lib, "fil_embed_rowopt_runs", hyper)
+                fn, h, name = self._rate_args(lib, self._ENTRY[1], hyper)
                 check(fn(ptr(pend["g"]), ptr(pend["perm"]), ptr(pend["sorted_ids"]), pend["R"], K, pend["g_dtype"], pend["F"],
                          ptr(field_l2), ptr(p), ptr(acc), ptr(lin), ptr(stamp), ptr(t), self._RULE, *h, st), name)
-            if field_l2 is not None:
-                fn, h, name = self._rate_args(lib, "fil_embed_rowopt_sweep", hyper)
+            if sweeps:
+                fn, h, name = self._rate_args(lib, self._ENTRY[2], hyper)
                 check(fn(ptr(p), ptr(acc), ptr(lin), ptr(stamp), V, K, ptr(pend["offsets"]), ptr(field_l2), ptr(pend["frozen"]),
                          pend["F"], ptr(t), self._RULE, *h, st), name)
 
@@ -790,6 +807,96 @@ class Ftrl(_Rowwise):
     def _hyper(self, group, lr_dev=None):
         return RowoptHyper(_float_rate(group), 0.0, group["learning_rate_power"], group["l1_regularization_strength"],
                            group["l2_regularization_strength"], group["l2_shrinkage_regularization_strength"]), lr_dev
+
+
+_MOMOPT_ENTRY = ("fil_momopt_multi", "fil_embed_momopt_runs", "fil_embed_momopt_sweep", "fil_embed_momopt_merged")
+
+
+def _check_momentum(momentum):
+    if isinstance(momentum, (int, float)) and (momentum < 0 or momentum > 1):
+        raise ValueError("`momentum` must be between [0, 1].")
+    return float(momentum)
+
+
+class SGD(_Rowwise):
+    """tf.keras.optimizers.SGD (TF 2.1): momentum == 0: p -= g lr; momentum > 0 (ApplyKerasMomentum): a = a momentum - g lr; p += a,
+    or with nesterov p += a momentum - g lr.  The slot `momentum` (zeros) exists only when momentum > 0: plain SGD keeps no state
+    tensors and its launches carry NULL slots.  Runs tables (SparseEmbed(grad_mode="runs")) take Keras' per-field semantics in place:
+    the batch's rows, plus every other row of a field with l2(emb_reg) > 0 (g = 2 emb_reg p: its momentum decays and it moves); an
+    untouched row of an unregularised field keeps its bits, its slot's too.  With momentum == 0 Keras scatter-adds each duplicate id of
+    a batch separately, in an order it does not specify, so there are no bits to match: here the run is summed first, in
+    fil_embed_run_sum's order, like every other rule.  Whether momentum is 0 is fixed at construction (a parameter group may change its
+    value, not that).  process_group / force_exchange / decay / schedules: as optim.Adam's."""
+    _NAME = "optim.SGD"
+    _RULE = FIL_OPT_SGD
+    _ENTRY = _MOMOPT_ENTRY
+
+    def __init__(self, params, learning_rate=0.01, momentum=0.0, nesterov=False, process_group=None, force_exchange=False, decay=0.0):
+        momentum = _check_momentum(momentum)
+        learning_rate, decay = _check_rate("SGD", learning_rate, decay)
+        self._SLOTS = ("momentum",) if momentum > 0.0 else ()
+        super().__init__(params, dict(learning_rate=learning_rate, momentum=momentum, nesterov=bool(nesterov), **_decay_entry(decay)),
+                         process_group, force_exchange)
+
+    def _slot_init(self, group):
+        return (0.0,) * len(self._SLOTS)
+
+    def _hyper(self, group, lr_dev=None):
+        momentum = _check_momentum(group["momentum"])
+        if (momentum > 0.0) != bool(self._SLOTS):
+            raise ValueError("optim.SGD: a parameter group's momentum=%r -- whether momentum is 0 is fixed at construction" % momentum)
+        return MomoptHyper(_float_rate(group), 0.0, 0.0, momentum, FIL_MOMOPT_NESTEROV if group["nesterov"] else 0, 0), lr_dev
+
+
+class RMSprop(_Rowwise):
+    """tf.keras.optimizers.RMSprop (TF 2.1), centered=False.  Slots: `rms` (zeros) and, only when momentum > 0, `momentum` (zeros).
+    momentum == 0 (Keras' Python ops, epsilon outside the root): rms = rho rms + (1 - rho) g^2; p -= lr g / (sqrt(rms) + epsilon).
+    momentum > 0 (ApplyRMSProp / SparseApplyRMSProp, epsilon inside the root): rms, then mom = mom momentum + lr g / sqrt(rms +
+    epsilon); p -= mom (include/fil.h O4 has the two roundings).  Runs tables take Keras' per-field semantics in place.  With
+    momentum > 0 the rule is row-local: the batch's rows, plus the other rows of the fields with l2(emb_reg) > 0.  With momentum == 0
+    Keras decays rms over the whole variable (rms = rms * rho) and moves the batch's rows only: an untouched row of an unregularised
+    field gets rms *= rho and keeps p, an untouched row of a regularised field takes the rule with g = 2 emb_reg p, a frozen field
+    changes nothing -- one sweep per table and step, over every non-frozen field.  centered=True raises NotImplementedError: it needs
+    a third slot (mg), which the dense descriptors (fil_adam_tensor) and the runs entry points do not carry."""
+    _NAME = "optim.RMSprop"
+    _RULE = FIL_OPT_RMSPROP
+    _ENTRY = _MOMOPT_ENTRY
+
+    def __init__(self, params, learning_rate=0.001, rho=0.9, momentum=0.0, epsilon=1e-7, centered=False, process_group=None,
+                 force_exchange=False, decay=0.0):
+        momentum = _check_momentum(momentum)
+        if centered:
+            raise NotImplementedError("optim.RMSprop: centered=True needs a third slot (mg); the dense descriptors (fil_adam_tensor) and "
+                                      "the runs entry points carry two")
+        if epsilon is None:
+            epsilon = 1e-7              # Keras: backend.epsilon()
+        learning_rate, decay = _check_rate("RMSprop", learning_rate, decay)
+        if not 0.0 <= rho <= 1.0 or not epsilon >= 0.0:
+            raise ValueError("RMSprop: rho=%r epsilon=%r (rho in [0, 1], epsilon >= 0)" % (rho, epsilon))
+        self._SLOTS = ("rms", "momentum") if momentum > 0.0 else ("rms",)
+        super().__init__(params, dict(learning_rate=learning_rate, rho=float(rho), momentum=momentum, epsilon=float(epsilon),
+                                      centered=False, **_decay_entry(decay)), process_group, force_exchange)
+
+    def _slot_init(self, group):
+        return (0.0,) * len(self._SLOTS)
+
+    def _sweeps(self, field_l2):
+        return len(self._SLOTS) == 1 or field_l2 is not None         # momentum == 0: rms decays on every row
+
+    def _hyper(self, group, lr_dev=None):
+        momentum = _check_momentum(group["momentum"])
+        if (momentum > 0.0) != (len(self._SLOTS) == 2):
+            raise ValueError("optim.RMSprop: a parameter group's momentum=%r -- whether momentum is 0 is fixed at construction" % momentum)
+        return MomoptHyper(_float_rate(group), group["epsilon"], group["rho"], momentum, 0, 0), lr_dev
+
+
+def momopt_merged(rule, ids, values, counts, W, cap, offsets, field_l2, table, slot0, slot1, stamp, step, hyper):
+    """fil_embed_momopt_merged on W gathered lists (ids [W*cap], values [W*cap*K], counts [W]); table / slot0 / slot1 [V, K] in place
+    (a slot the variant lacks: None); rule FIL_OPT_SGD or FIL_OPT_RMSPROP, hyper an _lib.MomoptHyper."""
+    V, K = table.shape
+    check(_lib.load().fil_embed_momopt_merged(ptr(ids), ptr(values), ptr(counts), int(W), int(cap), K, ptr(offsets), ptr(field_l2),
+                                              offsets.numel(), ptr(table), ptr(slot0), ptr(slot1), ptr(stamp), V, ptr(step), int(rule),
+                                              ctypes.addressof(hyper), stream_ptr()), "fil_embed_momopt_merged")
 
 
 def rowopt_merged(rule, ids, values, counts, W, cap, offsets, field_l2, table, accum, linear, stamp, step, hyper):
