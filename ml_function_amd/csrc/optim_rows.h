@@ -1,7 +1,8 @@
 // What the fused optimizers of optim.hip (Adam), optim_rowwise.hip (Adagrad, Ftrl) and optim_momentum.hip (SGD, RMSprop) share: the
 // walk of the dense descriptors (fil_adam_multi, fil_rowopt_multi, fil_momopt_multi), the field of a row, the walk of the gathered
 // compact lists of fil_embed_runs_compact (the merged updates), the regulariser's gradient and the sweeps' compacted field table.
-// Each rule supplies only its per-element update.
+// optim.hip builds its own kernels on them (its coefficients depend on the step; lazy and deferred modes); the row-rule families get
+// theirs, and their host launchers, from optim_rule.h, which sits on this header: there a rule supplies only its per-element update.
 #pragma once
 #include "common.h"
 

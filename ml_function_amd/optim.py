@@ -890,22 +890,23 @@ class RMSprop(_Rowwise):
         return MomoptHyper(_float_rate(group), group["epsilon"], group["rho"], momentum, 0, 0), lr_dev
 
 
+def _rule_merged(entry, rule, ids, values, counts, W, cap, offsets, field_l2, table, slot0, slot1, stamp, step, hyper):
+    V, K = table.shape
+    check(getattr(_lib.load(), entry)(ptr(ids), ptr(values), ptr(counts), int(W), int(cap), K, ptr(offsets), ptr(field_l2),
+                                      offsets.numel(), ptr(table), ptr(slot0), ptr(slot1), ptr(stamp), V, ptr(step), int(rule),
+                                      ctypes.addressof(hyper), stream_ptr()), entry)
+
+
 def momopt_merged(rule, ids, values, counts, W, cap, offsets, field_l2, table, slot0, slot1, stamp, step, hyper):
     """fil_embed_momopt_merged on W gathered lists (ids [W*cap], values [W*cap*K], counts [W]); table / slot0 / slot1 [V, K] in place
     (a slot the variant lacks: None); rule FIL_OPT_SGD or FIL_OPT_RMSPROP, hyper an _lib.MomoptHyper."""
-    V, K = table.shape
-    check(_lib.load().fil_embed_momopt_merged(ptr(ids), ptr(values), ptr(counts), int(W), int(cap), K, ptr(offsets), ptr(field_l2),
-                                              offsets.numel(), ptr(table), ptr(slot0), ptr(slot1), ptr(stamp), V, ptr(step), int(rule),
-                                              ctypes.addressof(hyper), stream_ptr()), "fil_embed_momopt_merged")
+    _rule_merged("fil_embed_momopt_merged", rule, ids, values, counts, W, cap, offsets, field_l2, table, slot0, slot1, stamp, step, hyper)
 
 
 def rowopt_merged(rule, ids, values, counts, W, cap, offsets, field_l2, table, accum, linear, stamp, step, hyper):
     """fil_embed_rowopt_merged on W gathered lists (ids [W*cap], values [W*cap*K], counts [W]); table / accum / linear [V, K] in
     place; rule FIL_OPT_ADAGRAD or FIL_OPT_FTRL, hyper an _lib.RowoptHyper."""
-    V, K = table.shape
-    check(_lib.load().fil_embed_rowopt_merged(ptr(ids), ptr(values), ptr(counts), int(W), int(cap), K, ptr(offsets), ptr(field_l2),
-                                              offsets.numel(), ptr(table), ptr(accum), ptr(linear), ptr(stamp), V, ptr(step), int(rule),
-                                              ctypes.addressof(hyper), stream_ptr()), "fil_embed_rowopt_merged")
+    _rule_merged("fil_embed_rowopt_merged", rule, ids, values, counts, W, cap, offsets, field_l2, table, accum, linear, stamp, step, hyper)
 
 
 def runs_compact_workspace_bytes(R):
