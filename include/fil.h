@@ -316,7 +316,9 @@ int fil_bce_mean_fwd(const float* p, const float* y, float eps, float* loss, flo
  * are summed in order by a second launch: that is what the workspace is for; a call with an epilogue is never split).
  *   trans_a = 0: A is [M][K] row-major, leading dimension lda >= K;  1: A is [K][M], lda >= M   (dW = x^T dz: A = x, trans_a = 1)
  *   trans_b = 0: B is [K][N] row-major, ldb >= N;                    1: B is [N][K], ldb >= K   (dx = dz W^T: B = W [in][out], trans_b = 1)
- * Any M, N, K; 16-byte operand loads where base and leading dimension allow, element-wise otherwise. */
+ * Any M, N, K; 16-byte operand loads where base and leading dimension allow, element-wise otherwise.  Leading dimensions may be padded
+ * (the padding is neither used nor written) and A, B, C need dword alignment only.  K = 0: C = 0 (+ bias, ReLU) and A, B are not
+ * dereferenced, whatever lda and ldb are (they may be NULL). */
 size_t fil_gemm_f32_workspace_bytes(int M, int N, int K);
 int fil_gemm_f32(const float* A, const float* B, float* C, const float* bias, int M, int N, int K, int lda, int ldb, int ldc, int trans_a,
                  int trans_b, int epilogue, void* workspace, size_t workspace_bytes, void* stream);

@@ -220,6 +220,13 @@ extern "C" int fil_gemm_f32(const float* A, const float* B, float* C, const floa
   FIL_CHECK_ARG(lda >= (trans_a ? M : K) && ldb >= (trans_b ? K : N) && ldc >= N);
   if ((long)(trans_a ? K : M) * lda >= (1L << 29) || (long)(trans_b ? N : K) * ldb >= (1L << 29))
     return fail(FIL_ERR_UNSUPPORTED, "fil_gemm_f32: an operand of 2 GiB or more (32-bit buffer offsets)");
+  if (K == 0) {
+    // an empty reduction: C = 0 (+ bias, ReLU).  The kernel's prologue still issues the loads of its first two stages, and a k-contiguous
+    // operand's resource is rows * ld * 4 bytes long whatever K is -- so the operands get leading dimension 0 here: both resources are
+    // then ZERO bytes long, every load is out of range and returns zero without touching memory, whatever A and B are (NULL included)
+    A = B = nullptr;
+    lda = ldb = 0;
+  }
   hipStream_t st = (hipStream_t)stream;
   const int ns = epilogue != 0 ? 1 : gemm_splits(M, N, K);   // (a call with an epilogue is never split: its tiles finish in one workgroup)
   float* part = nullptr;

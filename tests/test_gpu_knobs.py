@@ -51,3 +51,19 @@ def test_attn_two_waves_per_head_forced_on_fewer_heads():
     tail = "\n".join((r.stdout + r.stderr).strip().splitlines()[-15:])
     assert r.returncode == 0, "FIL_ATTN_WPH=2:\n%s" % tail
     assert " passed" in r.stdout and "no tests ran" not in r.stdout, tail
+
+
+@pytest.mark.gpu
+def test_gemm_edges_with_one_wave_per_tile():
+    """FIL_GEMM_KW=1 (read once per process) launches the dense GEMM with ONE wave per output tile -- the eight
+    gemm_f32_kernel<*, *, *, 1> instantiations, no join of k halves through LDS.  A fresh child runs the constructed-edge cases of
+    tests/test_dense_edges_gpu.py under it, bit for bit against the int64 products: all of the BN = 64 group and of the split-k group
+    (every transposition), and the `kw1` slice of the BN = 32 group."""
+    env = dict(os.environ)
+    env["FIL_GEMM_KW"] = "1"
+    r = subprocess.run([sys.executable, "-m", "pytest", "tests/test_dense_edges_gpu.py", "-x", "-q", "-m", "gpu",
+                        "-k", "gemm_bn64 or gemm_splitk or kw1", "-p", "no:cacheprovider"], cwd=ROOT, env=env, capture_output=True, text=True,
+                       timeout=600)
+    tail = "\n".join((r.stdout + r.stderr).strip().splitlines()[-15:])
+    assert r.returncode == 0, "FIL_GEMM_KW=1:\n%s" % tail
+    assert "44 passed" in r.stdout and "no tests ran" not in r.stdout, tail
