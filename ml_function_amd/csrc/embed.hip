@@ -319,8 +319,7 @@ extern "C" int fil_embed_run_sum_dt(const void* g, const int64_t* perm, const in
   if (K > 256) return fail(FIL_ERR_UNSUPPORTED, "fil_embed_run_sum: K=%d > 256", K);
   if (R == 0) return FIL_OK;
   FIL_CHECK_ARG(g && perm && sorted_ids && dtable);
-  const int C = 64 / ((K + 3) / 4);   // positions per wave and iteration
-  const dim3 grid((int)std::min<long>((R + 4 * C - 1) / (4 * C), 256 * 32));
+  const dim3 grid = run_sums_grid(R, K);
   if (g_dtype == FIL_F32)
     hipLaunchKernelGGL(embed_run_sum_kernel<float>, grid, dim3(256), 0, (hipStream_t)stream, static_cast<const float*>(g), perm, sorted_ids, dtable, R, K);
   else

@@ -1,5 +1,6 @@
-// The run sums behind fil_embed_run_sum (embed.hip) and fil_embed_adam_runs (optim.hip): one definition, so the fused optimizer
-// sums every row's gradient in exactly the order the dense gradient does.
+// The run sums behind fil_embed_run_sum (embed.hip), fil_embed_runs_compact (runs_compact.hip) and the fused optimizers' runs
+// updates (optim.hip, optim_rule.h): one definition, so a fused optimizer sums every row's gradient in exactly the order the dense
+// gradient does; and the grid that walk is launched with.
 #pragma once
 #include "common.h"
 
@@ -133,6 +134,12 @@ __device__ __forceinline__ void embed_run_sums(const GT* __restrict__ g, const i
       if (c == 0) epi(rl, kq, acc, pr0[0]);
     }
   }
+}
+
+// the grid of a kernel that walks R sorted positions with embed_run_sums: a workgroup's 4 waves take C positions each per iteration
+inline dim3 run_sums_grid(long R, int K) {
+  const int C = 64 / ((K + 3) / 4);
+  return dim3((int)std::min<long>((R + 4 * C - 1) / (4 * C), 256 * 32));
 }
 
 }  // namespace fil

@@ -10,9 +10,12 @@
 // (4 loads + 3 stores of 16 B per lane; 256-lane workgroups, a few per CU: ~64 KiB of loads in flight per CU), scalar otherwise and in
 // the tail.  The sweep's stores are non-temporal (a 2 GB table pass must not evict the MALL).  fil_embed_adam_runs reuses the run sums
 // of fil_embed_run_sum (embed_runs.h): the same order, so a row's gradient is bit-identical to what the dense path materialises.
-// Data parallel: fil_embed_runs_compact turns a rank's record into a compact list (distinct ids, their run sums) of fixed capacity,
-// and fil_embed_adam_merged applies the W gathered lists -- every row once, by its lowest rank, summed in rank order -- before the
-// sweep, so every replica computes the same bits.
+// Data parallel: fil_embed_adam_merged applies the W gathered lists of fil_embed_runs_compact (runs_compact.hip) -- every row once,
+// by its lowest rank, summed in rank order -- before the sweep, so every replica computes the same bits.
+// This file is Adam only.  Its kernels sit on a few shared pieces: the field table of a sweep (FieldTab), four elements of a row in
+// and out (row_load4, row_store4), a touched element (adam_touched_at) and one replayed step (replay_step); what the launchers
+// compute the same way as the row-rule optimizers' (grids, the step tag, sweep_vec, the shape check) comes from optim_rows.h and
+// embed_runs.h.
 #include "common.h"
 #include "embed_runs.h"
 #include "optim_rows.h"
@@ -77,6 +80,83 @@ __device__ __forceinline__ void adam_elem(float& p, float& m, float& v, float g,
   p -= (m * c.alpha) / (sqrtf(v) + c.eps);
 }
 
+// the sweep's view of the fields, in LDS: a row's field is the last f with off[f] <= row; l2x2 = 2 l2[f], NaN for a frozen field
+struct FieldTab {
+  int64_t off[kSweepMaxF];
+  float l2x2[kSweepMaxF];
+};
+
+__device__ __forceinline__ void load_field_tab(FieldTab* s, const int64_t* __restrict__ offsets, const float* __restrict__ field_l2,
+                                               const unsigned char* __restrict__ frozen, int F) {
+  for (int f = threadIdx.x; f < F; f += blockDim.x) {
+    s->off[f] = offsets[f];
+    s->l2x2[f] = (frozen && frozen[f]) ? __builtin_nanf("") : (field_l2 ? 2.f * field_l2[f] : 0.f);
+  }
+}
+
+__device__ __forceinline__ float field_l2x2(const FieldTab* s, int F, int64_t row) {
+  const int f = sweep_field(s->off, F, row);
+  return f >= 0 ? s->l2x2[f] : 0.f;
+}
+
+// four elements of a row in and out: lane kq of the row's lane group holds elements kq * 4 ... kq * 4 + 3, those below K (the others
+// read as 0 and are never stored)
+__device__ __forceinline__ void row_load4(const float* __restrict__ table, const float* __restrict__ m, const float* __restrict__ v,
+                                          int64_t row, int K, int kq, float (&p)[4], float (&mm)[4], float (&vv)[4]) {
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const int64_t e = row * K + kq * 4 + i;
+    const bool in = kq * 4 + i < K;
+    p[i] = in ? table[e] : 0.f;
+    mm[i] = in ? m[e] : 0.f;
+    vv[i] = in ? v[e] : 0.f;
+  }
+}
+
+// kNT: non-temporal stores (the roll, as the sweep)
+template <bool kNT>
+__device__ __forceinline__ void row_store4(float* __restrict__ table, float* __restrict__ m, float* __restrict__ v, int64_t row, int K,
+                                           int kq, const float (&p)[4], const float (&mm)[4], const float (&vv)[4]) {
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    if (kq * 4 + i < K) {
+      const int64_t e = row * K + kq * 4 + i;
+      if (kNT) {
+        __builtin_nontemporal_store(p[i], table + e);
+        __builtin_nontemporal_store(mm[i], m + e);
+        __builtin_nontemporal_store(vv[i], v + e);
+      } else {
+        table[e] = p[i];
+        m[e] = mm[i];
+        v[e] = vv[i];
+      }
+    }
+  }
+}
+
+// one element of a touched row in place
+__device__ __forceinline__ void adam_touched_at(float* __restrict__ table, float* __restrict__ m, float* __restrict__ v, int64_t e,
+                                                float acc, float l2x2, const AdamCoef& c) {
+  float p = table[e], mm = m[e], vv = v[e];
+  adam_touched(p, mm, vv, acc, l2x2, c);
+  table[e] = p;
+  m[e] = mm;
+  v[e] = vv;
+}
+
+// one replayed step on NE elements in registers.  vec: the sweep would take its 16-byte path on this table -- the only place that
+// picks the rounding of a replay, which deferred mode's bit-identity to Keras mode rests on
+template <int NE>
+__device__ __forceinline__ void replay_step(float (&p)[NE], float (&m)[NE], float (&v)[NE], float l2x2, const AdamCoef& c, int vec) {
+  if (vec) {
+#pragma unroll
+    for (int i = 0; i < NE; ++i) adam_untouched<true>(p[i], m[i], v[i], l2x2, c);
+  } else {
+#pragma unroll
+    for (int i = 0; i < NE; ++i) adam_untouched<false>(p[i], m[i], v[i], l2x2, c);
+  }
+}
+
 __global__ void step_advance_kernel(int64_t* step) { *step += 1; }
 
 void launch_step_advance(int64_t* step, hipStream_t st) { hipLaunchKernelGGL(step_advance_kernel, dim3(1), dim3(1), 0, st, step); }
@@ -102,41 +182,29 @@ __global__ __launch_bounds__(256) void embed_adam_runs_kernel(const GT* __restri
                                                               const int64_t* __restrict__ step, float lr, float b1, float b2, float eps,
                                                               const float* __restrict__ lr_dev) {
   const AdamCoef c = adam_coef(step, rate_of(lr, lr_dev), b1, b2, eps);
-  const int32_t tag = (int32_t)(uint32_t)(*step + 1);
+  const int32_t tag = step_tag(step);
   embed_run_sums(g, perm, sorted_ids, R, K, [=](int64_t row, int kq, const float (&acc)[4], int64_t first) {
     const float l2x2 = field_l2 ? 2.f * field_l2[first % F] : 0.f;
 #pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      if (kq * 4 + i < K) {
-        const int64_t e = row * K + kq * 4 + i;
-        float p = table[e], mm = m[e], vv = v[e];
-        adam_touched(p, mm, vv, acc[i], l2x2, c);
-        table[e] = p;
-        m[e] = mm;
-        v[e] = vv;
-      }
-    }
+    for (int i = 0; i < 4; ++i)
+      if (kq * 4 + i < K) adam_touched_at(table, m, v, row * K + kq * 4 + i, acc[i], l2x2, c);
     if (stamp && kq == 0) stamp[row] = tag;
   });
 }
 
 // ---- fil_embed_adam_sweep: every row the run pass did not stamp at this step takes g = 2 l2[f] p (or 0); frozen fields are
-// left alone.  The field of a row comes from a binary search of the offsets held in LDS (sweep_field, optim_rows.h).
+// left alone.  The field of a row comes from a binary search of the offsets held in LDS (FieldTab).
 __global__ __launch_bounds__(256) void embed_adam_sweep_kernel(float* __restrict__ table, float* __restrict__ m, float* __restrict__ v,
                                                                const int32_t* __restrict__ stamp, int64_t V, int K,
                                                                const int64_t* __restrict__ offsets, const float* __restrict__ field_l2,
                                                                const unsigned char* __restrict__ frozen, int F,
                                                                const int64_t* __restrict__ step, float lr, float b1, float b2, float eps,
                                                                int vec, const float* __restrict__ lr_dev) {
-  __shared__ int64_t s_off[kSweepMaxF];
-  __shared__ float s_l2x2[kSweepMaxF];        // 2 l2[f], or NaN for a frozen field
-  for (int f = threadIdx.x; f < F; f += blockDim.x) {
-    s_off[f] = offsets[f];
-    s_l2x2[f] = (frozen && frozen[f]) ? __builtin_nanf("") : (field_l2 ? 2.f * field_l2[f] : 0.f);
-  }
+  __shared__ FieldTab s;
+  load_field_tab(&s, offsets, field_l2, frozen, F);
   __syncthreads();
   const AdamCoef c = adam_coef(step, rate_of(lr, lr_dev), b1, b2, eps);
-  const int32_t tag = (int32_t)(uint32_t)(*step + 1);
+  const int32_t tag = step_tag(step);
   const int64_t n = V * K;
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
   if (vec) {                                  // K % 4 == 0 and 16-byte aligned arrays: a lane moves 4 elements of one row
@@ -144,8 +212,7 @@ __global__ __launch_bounds__(256) void embed_adam_sweep_kernel(float* __restrict
     for (int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; q < nq; q += stride) {
       const int64_t row = q * 4 / K;
       if (stamp[row] == tag) continue;
-      const int f = sweep_field(s_off, F, row);
-      const float l2x2 = f >= 0 ? s_l2x2[f] : 0.f;
+      const float l2x2 = field_l2x2(&s, F, row);
       if (l2x2 != l2x2) continue;             // frozen
       f32x4 p = reinterpret_cast<const f32x4*>(table)[q];
       f32x4 mm = reinterpret_cast<const f32x4*>(m)[q];
@@ -167,8 +234,7 @@ __global__ __launch_bounds__(256) void embed_adam_sweep_kernel(float* __restrict
   for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += stride) {
     const int64_t row = e / K;
     if (stamp[row] == tag) continue;
-    const int f = sweep_field(s_off, F, row);
-    const float l2x2 = f >= 0 ? s_l2x2[f] : 0.f;
+    const float l2x2 = field_l2x2(&s, F, row);
     if (l2x2 != l2x2) continue;
     float p = table[e], mm = m[e], vv = v[e];
     adam_untouched<false>(p, mm, vv, l2x2, c);
@@ -176,102 +242,6 @@ __global__ __launch_bounds__(256) void embed_adam_sweep_kernel(float* __restrict
     __builtin_nontemporal_store(mm, m + e);
     __builtin_nontemporal_store(vv, v + e);
   }
-}
-
-// ---- fil_embed_runs_compact: the run sums of embed_runs.h stored into compact slots.  Three launches, none sized by data:
-//   count  one workgroup per kCompactTile sorted positions counts its run starts (id >= 0, != the id before);
-//   write  every workgroup sums the counts of the tiles before it (and of all tiles: the total), scans its own starts in position
-//          order and writes ids_out[u] = id and slot[perm of the start] = u; the slots [count, cap) get INT64_MAX, count_out the total;
-//   sums   embed_run_sums with an epilogue that stores the row into values_out[slot[perm of the run's first element]].
-// perm holds each position b*F + f exactly once (< R), so the slot map needs R entries.  Integer scans: deterministic.
-constexpr int kCompactPer = 8;
-constexpr int kCompactTile = 256 * kCompactPer;
-
-__device__ __forceinline__ bool run_start_at(const int64_t* __restrict__ sorted_ids, long j) {
-  const int64_t id = sorted_ids[j];
-  return id >= 0 && (j == 0 || sorted_ids[j - 1] != id);
-}
-
-// sum of x over a 256-lane workgroup (s: 4 ints of LDS); every lane gets the total
-__device__ __forceinline__ long block_sum_256(long x, long* s) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o, 64);
-  if ((threadIdx.x & 63) == 0) s[threadIdx.x >> 6] = x;
-  __syncthreads();
-  const long t = (s[0] + s[1]) + (s[2] + s[3]);
-  __syncthreads();
-  return t;
-}
-
-__global__ __launch_bounds__(256) void runs_count_kernel(const int64_t* __restrict__ sorted_ids, long R, int64_t* __restrict__ tile_count) {
-  __shared__ long s[4];
-  const long base = (long)blockIdx.x * kCompactTile + (long)threadIdx.x * kCompactPer;
-  long n = 0;
-#pragma unroll
-  for (int i = 0; i < kCompactPer; ++i)
-    if (base + i < R && run_start_at(sorted_ids, base + i)) ++n;
-  n = block_sum_256(n, s);
-  if (threadIdx.x == 0) tile_count[blockIdx.x] = n;
-}
-
-__global__ __launch_bounds__(256) void runs_write_kernel(const int64_t* __restrict__ sorted_ids, const int64_t* __restrict__ perm, long R,
-                                                         const int64_t* __restrict__ tile_count, int tiles, long cap,
-                                                         int64_t* __restrict__ ids_out, int64_t* __restrict__ count_out,
-                                                         int32_t* __restrict__ slot) {
-  __shared__ long s[4];
-  __shared__ long s_scan[4];
-  long before = 0, all = 0;
-  for (int b = threadIdx.x; b < tiles; b += 256) {
-    const long c = tile_count[b];
-    all += c;
-    before += b < (int)blockIdx.x ? c : 0;
-  }
-  before = block_sum_256(before, s);
-  all = block_sum_256(all, s);
-  // this lane's starts, then an exclusive scan over the workgroup in lane order (= position order)
-  const long base = (long)blockIdx.x * kCompactTile + (long)threadIdx.x * kCompactPer;
-  unsigned flags = 0;
-#pragma unroll
-  for (int i = 0; i < kCompactPer; ++i)
-    if (base + i < R && run_start_at(sorted_ids, base + i)) flags |= 1u << i;
-  const long mine = __builtin_popcount(flags);
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  long incl = mine;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const long y = __shfl_up(incl, o, 64);
-    if (lane >= o) incl += y;
-  }
-  if (lane == 63) s_scan[wave] = incl;
-  __syncthreads();
-  long u = before + incl - mine;
-  for (int w = 0; w < wave; ++w) u += s_scan[w];
-#pragma unroll
-  for (int i = 0; i < kCompactPer; ++i) {
-    if (flags & (1u << i)) {
-      const long j = base + i;
-      const int64_t pj = perm[j];
-      if (u < cap) ids_out[u] = sorted_ids[j];
-      if ((uint64_t)pj < (uint64_t)R) slot[pj] = (int32_t)u;
-      ++u;
-    }
-  }
-  for (long i = all + (long)blockIdx.x * 256 + threadIdx.x; i < cap; i += (long)gridDim.x * 256) ids_out[i] = INT64_MAX;
-  if (blockIdx.x == 0 && threadIdx.x == 0) *count_out = all;
-}
-
-template <typename GT>
-__global__ __launch_bounds__(256) void runs_compact_sums_kernel(const GT* __restrict__ g, const int64_t* __restrict__ perm,
-                                                                const int64_t* __restrict__ sorted_ids, long R, int K,
-                                                                const int32_t* __restrict__ slot, long cap, float* __restrict__ values_out) {
-  embed_run_sums(g, perm, sorted_ids, R, K, [=](int64_t, int kq, const float (&acc)[4], int64_t first) {
-    if ((uint64_t)first >= (uint64_t)R) return;
-    const long u = slot[first];
-    if (u < 0 || u >= cap) return;
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-      if (kq * 4 + i < K) values_out[u * K + kq * 4 + i] = acc[i];
-  });
 }
 
 // ---- fil_embed_adam_merged: the merged walk of the gathered lists (merged_row_sums, optim_rows.h); the owner of a row adds the
@@ -287,19 +257,11 @@ __global__ __launch_bounds__(256) void embed_adam_merged_kernel(const int64_t* _
   for (int f = threadIdx.x; f < F; f += blockDim.x) s_off[f] = offsets[f];
   __syncthreads();
   const AdamCoef c = adam_coef(step, rate_of(lr, lr_dev), b1, b2, eps);
-  const int32_t tag = (int32_t)(uint32_t)(*step + 1);
+  const int32_t tag = step_tag(step);
   const auto epi = [=](int64_t row, int f, float l2x2, int k0, const float (&acc)[kMergeChunk]) {
 #pragma unroll
-    for (int e = 0; e < kMergeChunk; ++e) {
-      if (k0 + e < K) {
-        const int64_t x = row * K + k0 + e;
-        float p = table[x], mm = m[x], vv = v[x];
-        adam_touched(p, mm, vv, acc[e], l2x2, c);
-        table[x] = p;
-        m[x] = mm;
-        v[x] = vv;
-      }
-    }
+    for (int e = 0; e < kMergeChunk; ++e)
+      if (k0 + e < K) adam_touched_at(table, m, v, row * K + k0 + e, acc[e], l2x2, c);
   };
   merged_row_sums((long)blockIdx.x * blockDim.x + threadIdx.x, (long)gridDim.x * blockDim.x, ids, values, counts, W, cap, K, V, s_off,
                   field_l2, F, epi, [=](int64_t row) { if (stamp) stamp[row] = tag; });
@@ -330,25 +292,6 @@ static int ring_len(int N) {
   return D;
 }
 
-// the sweep's view of the fields, in LDS: a row's field is the last f with off[f] <= row; l2x2 = 2 l2[f], NaN for a frozen field
-struct FieldTab {
-  int64_t off[kSweepMaxF];
-  float l2x2[kSweepMaxF];
-};
-
-__device__ __forceinline__ void load_field_tab(FieldTab* s, const int64_t* __restrict__ offsets, const float* __restrict__ field_l2,
-                                               const unsigned char* __restrict__ frozen, int F) {
-  for (int f = threadIdx.x; f < F; f += blockDim.x) {
-    s->off[f] = offsets[f];
-    s->l2x2[f] = (frozen && frozen[f]) ? __builtin_nanf("") : (field_l2 ? 2.f * field_l2[f] : 0.f);
-  }
-}
-
-__device__ __forceinline__ float field_l2x2(const FieldTab* s, int F, int64_t row) {
-  const int f = sweep_field(s->off, F, row);
-  return f >= 0 ? s->l2x2[f] : 0.f;
-}
-
 // the last completed step a row stamped `st` must replay from to reach `to`: `to` itself when it is current.  Never more than N
 // steps back (a longer gap only comes from a broken protocol: the replay stays bounded, it does not hang)
 __device__ __forceinline__ int32_t replay_from(int32_t st, int32_t to, int N) {
@@ -356,20 +299,14 @@ __device__ __forceinline__ int32_t replay_from(int32_t st, int32_t to, int N) {
   return st < to - N ? to - N : st;
 }
 
-// steps (from, to] of the ring (global memory) on NE elements in registers; vec: the sweep would take its 16-byte path on this table
+// steps (from, to] of the ring (global memory) on NE elements in registers
 template <int NE>
 __device__ __forceinline__ void replay(float (&p)[NE], float (&m)[NE], float (&v)[NE], float l2x2, int32_t from, int32_t to,
                                        const AdamCoef* __restrict__ ring, int D, int vec) {
   for (int32_t u = from + 1; u <= to; ++u) {
     const AdamCoef c = ring[u & (D - 1)];
     if (coef_is_skip(c)) continue;
-    if (vec) {
-#pragma unroll
-      for (int i = 0; i < NE; ++i) adam_untouched<true>(p[i], m[i], v[i], l2x2, c);
-    } else {
-#pragma unroll
-      for (int i = 0; i < NE; ++i) adam_untouched<false>(p[i], m[i], v[i], l2x2, c);
-    }
+    replay_step(p, m, v, l2x2, c, vec);
   }
 }
 
@@ -397,24 +334,9 @@ __global__ __launch_bounds__(256) void embed_adam_catchup_kernel(const int64_t* 
     if (from == to) continue;
     if (kq * 4 < K) {
       float p[4], mm[4], vv[4];
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const int64_t e = row * K + kq * 4 + i;
-        const bool in = kq * 4 + i < K;
-        p[i] = in ? table[e] : 0.f;
-        mm[i] = in ? m[e] : 0.f;
-        vv[i] = in ? v[e] : 0.f;
-      }
-      replay<4>(p, mm, vv, l2x2, from, to, ring, D, vec);
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        if (kq * 4 + i < K) {
-          const int64_t e = row * K + kq * 4 + i;
-          table[e] = p[i];
-          m[e] = mm[i];
-          v[e] = vv[i];
-        }
-      }
+      row_load4(table, m, v, row, K, kq, p, mm, vv);
+      replay(p, mm, vv, l2x2, from, to, ring, D, vec);
+      row_store4<false>(table, m, v, row, K, kq, p, mm, vv);
     }
     if (kq == 0) stamp[row] = to;                 // (the row's other lanes read the stamp above: same wave, earlier instruction)
   }
@@ -445,25 +367,12 @@ __global__ __launch_bounds__(256) void embed_adam_runs_deferred_kernel(const GT*
     const float r2 = field_l2x2(sp, F, row);                             // the replayed steps' term, as the sweep
     const int32_t from = r2 == r2 ? replay_from(stamp[row], done, N) : done;
     float p[4], mm[4], vv[4];
+    row_load4(table, m, v, row, K, kq, p, mm, vv);
+    replay(p, mm, vv, r2, from, done, ring, D, vec);
 #pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int64_t e = row * K + kq * 4 + i;
-      const bool in = kq * 4 + i < K;
-      p[i] = in ? table[e] : 0.f;
-      mm[i] = in ? m[e] : 0.f;
-      vv[i] = in ? v[e] : 0.f;
-    }
-    replay<4>(p, mm, vv, r2, from, done, ring, D, vec);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      if (kq * 4 + i < K) {
-        const int64_t e = row * K + kq * 4 + i;
-        adam_touched(p[i], mm[i], vv[i], acc[i], l2x2, c);
-        table[e] = p[i];
-        m[e] = mm[i];
-        v[e] = vv[i];
-      }
-    }
+    for (int i = 0; i < 4; ++i)
+      if (kq * 4 + i < K) adam_touched(p[i], mm[i], vv[i], acc[i], l2x2, c);
+    row_store4<false>(table, m, v, row, K, kq, p, mm, vv);
     if (kq == 0) stamp[row] = done + 1;
   });
 }
@@ -488,12 +397,13 @@ __global__ __launch_bounds__(256) void embed_adam_merged_deferred_kernel(const i
   const auto epi = [=](int64_t row, int f, float l2x2, int k0, const float (&acc)[kMergeChunk]) {
     const float r2 = f >= 0 ? sp->l2x2[f] : 0.f;
     const int32_t from = r2 == r2 ? replay_from(stamp[row], done, N) : done;     // (the stamp moves after the last chunk only)
+    // (element by element: four at a time on the row helpers costs 33 registers and three waves of occupancy)
 #pragma unroll
     for (int e = 0; e < kMergeChunk; ++e) {
       if (k0 + e < K) {
         const int64_t x = row * K + k0 + e;
         float p[1] = {table[x]}, mm[1] = {m[x]}, vv[1] = {v[x]};
-        replay<1>(p, mm, vv, r2, from, done, ring, D, vec);
+        replay(p, mm, vv, r2, from, done, ring, D, vec);
         adam_touched(p[0], mm[0], vv[0], acc[e], l2x2, c);
         table[x] = p[0];
         m[x] = mm[0];
@@ -577,14 +487,7 @@ __global__ __launch_bounds__(256) void embed_adam_roll_kernel(float* __restrict_
           vv[i] = c[i];
         }
       } else {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          if (kq * 4 + i < K) {
-            p[i] = table[e0 + i];
-            mm[i] = m[e0 + i];
-            vv[i] = v[e0 + i];
-          }
-        }
+        row_load4(table, m, v, row, K, kq, p, mm, vv);
       }
     }
     // steps the wave's rows disagree on (masked per lane), then the ones every row takes (lanes with nothing to do compute on
@@ -593,30 +496,12 @@ __global__ __launch_bounds__(256) void embed_adam_roll_kernel(float* __restrict_
     for (; u <= whi; ++u) {
       const AdamCoef c = s_ring[u & (D - 1)];
       if (coef_is_skip(c)) continue;
-      if (u > from) {
-        if (vec) {
-#pragma unroll
-          for (int i = 0; i < 4; ++i) adam_untouched<true>(p[i], mm[i], vv[i], l2x2, c);
-        } else {
-#pragma unroll
-          for (int i = 0; i < 4; ++i) adam_untouched<false>(p[i], mm[i], vv[i], l2x2, c);
-        }
-      }
+      if (u > from) replay_step(p, mm, vv, l2x2, c, vec);
     }
-    if (vec) {
-      for (; u <= to; ++u) {
-        const AdamCoef c = s_ring[u & (D - 1)];
-        if (coef_is_skip(c)) continue;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) adam_untouched<true>(p[i], mm[i], vv[i], l2x2, c);
-      }
-    } else {
-      for (; u <= to; ++u) {
-        const AdamCoef c = s_ring[u & (D - 1)];
-        if (coef_is_skip(c)) continue;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) adam_untouched<false>(p[i], mm[i], vv[i], l2x2, c);
-      }
+    for (; u <= to; ++u) {
+      const AdamCoef c = s_ring[u & (D - 1)];
+      if (coef_is_skip(c)) continue;
+      replay_step(p, mm, vv, l2x2, c, vec);
     }
     if (mine) {
       if (vec) {
@@ -624,14 +509,7 @@ __global__ __launch_bounds__(256) void embed_adam_roll_kernel(float* __restrict_
         __builtin_nontemporal_store(f32x4{mm[0], mm[1], mm[2], mm[3]}, reinterpret_cast<f32x4*>(m + e0));
         __builtin_nontemporal_store(f32x4{vv[0], vv[1], vv[2], vv[3]}, reinterpret_cast<f32x4*>(v + e0));
       } else {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          if (kq * 4 + i < K) {
-            __builtin_nontemporal_store(p[i], table + e0 + i);
-            __builtin_nontemporal_store(mm[i], m + e0 + i);
-            __builtin_nontemporal_store(vv[i], v + e0 + i);
-          }
-        }
+        row_store4<true>(table, m, v, row, K, kq, p, mm, vv);
       }
     }
     if (act && kq == 0) stamp[row] = to;
@@ -645,16 +523,18 @@ static int lanes_lg(int K) {
   return lg;
 }
 
-// the path fil_embed_adam_sweep takes on these arrays (its 16-byte path rounds the m update differently: adam_untouched)
-static int sweep_vec(int K, const float* table, const float* m, const float* v) {
-  return (K % 4 == 0 && ((((uintptr_t)table | (uintptr_t)m | (uintptr_t)v) & 15) == 0)) ? 1 : 0;
-}
-
 static int check_deferred(const char* who, int K, int F, int N, const float* ring) {
-  if (K > 256) return fail(FIL_ERR_UNSUPPORTED, "%s: K=%d > 256", who, K);
-  if (F > kSweepMaxF) return fail(FIL_ERR_UNSUPPORTED, "%s: F=%d > %d fields", who, F, kSweepMaxF);
+  if (int rc = check_table_shape(who, K, F)) return rc;
   if (ring_len(N) == 0) return fail(FIL_ERR_ARG, "%s: sweep_period %d (1 ... %d)", who, N, kRingMax - 1);
   if (((uintptr_t)ring & 15) != 0) return fail(FIL_ERR_ARG, "%s: the ring must be 16-byte aligned", who);
+  return FIL_OK;
+}
+
+// the Keras / lazy mode of the runs and merged updates
+static int check_mode(const char* who, int mode, const int32_t* stamp) {
+  if (mode != FIL_ADAM_KERAS && mode != FIL_ADAM_LAZY) return fail(FIL_ERR_ARG, "%s: mode %d (FIL_ADAM_KERAS or FIL_ADAM_LAZY)", who, mode);
+  if (mode == FIL_ADAM_KERAS && stamp == nullptr)
+    return fail(FIL_ERR_ARG, "%s: FIL_ADAM_KERAS needs the row stamps (fil_embed_adam_sweep skips the rows stamped here)", who);
   return FIL_OK;
 }
 
@@ -670,8 +550,7 @@ static int check_hyper(const char* who, float lr, float b1, float b2, float eps)
 using namespace fil;
 
 static int adam_multi_impl(const char* who, const fil_adam_tensor* tensors, int n, int64_t total_numel, int64_t* step, float lr,
-                           float beta_1,
-                              float beta_2, float epsilon, int advance, void* stream, const float* lr_dev) {
+                           float beta_1, float beta_2, float epsilon, int advance, void* stream, const float* lr_dev) {
   FIL_CHECK_ARG_W(who, n >= 0 && total_numel >= 0);
   FIL_CHECK_ARG_W(who, step != nullptr);
   FIL_CHECK_ARG_W(who, n == 0 || tensors != nullptr);
@@ -704,22 +583,18 @@ extern "C" int fil_adam_multi_lrdev(const fil_adam_tensor* tensors, int n, int64
 }
 
 static int embed_adam_runs_impl(const char* who, const void* g, const int64_t* perm, const int64_t* sorted_ids, long R, int K, int g_dtype,
-                                int F,
-                                   const float* field_l2, float* table, float* m, float* v, int32_t* stamp, const int64_t* step,
-                                   float lr, float beta_1, float beta_2, float epsilon, int mode, void* stream, const float* lr_dev) {
+                                int F, const float* field_l2, float* table, float* m, float* v, int32_t* stamp, const int64_t* step,
+                                float lr, float beta_1, float beta_2, float epsilon, int mode, void* stream, const float* lr_dev) {
   FIL_CHECK_ARG_W(who, R >= 0 && K >= 1 && F >= 1);
   if (g_dtype != FIL_F32 && g_dtype != FIL_BF16) return fail(FIL_ERR_ARG, "%s: g_dtype %d (f32 or bf16)", who, g_dtype);
-  if (mode != FIL_ADAM_KERAS && mode != FIL_ADAM_LAZY) return fail(FIL_ERR_ARG, "%s: mode %d (FIL_ADAM_KERAS or FIL_ADAM_LAZY)", who, mode);
-  if (mode == FIL_ADAM_KERAS && stamp == nullptr)
-    return fail(FIL_ERR_ARG, "%s: FIL_ADAM_KERAS needs the row stamps (fil_embed_adam_sweep skips the rows stamped here)", who);
-  if (K > 256) return fail(FIL_ERR_UNSUPPORTED, "%s: K=%d > 256", who, K);
+  if (int rc = check_mode(who, mode, stamp)) return rc;
+  if (int rc = check_table_shape(who, K, 0)) return rc;
   if (int rc = check_hyper(who, lr, beta_1, beta_2, epsilon)) return rc;
   if (R == 0) return FIL_OK;
   FIL_CHECK_ARG_W(who, g && perm && sorted_ids && table && m && v && step);
   hipStream_t st = (hipStream_t)stream;
   ProfScope ps("embed_adam_runs", st, (double)R * K * (g_dtype == FIL_F32 ? 4 : 2) + 24.0 * R * K);
-  const int C = 64 / ((K + 3) / 4);
-  const dim3 grid((int)std::min<long>((R + 4 * C - 1) / (4 * C), 256 * 32));
+  const dim3 grid = run_sums_grid(R, K);
   if (g_dtype == FIL_F32)
     hipLaunchKernelGGL(embed_adam_runs_kernel<float>, grid, dim3(256), 0, st, static_cast<const float*>(g), perm, sorted_ids, R, K, F,
                        field_l2, table, m, v, mode == FIL_ADAM_KERAS ? stamp : nullptr, step, lr, beta_1, beta_2, epsilon, lr_dev);
@@ -747,20 +622,19 @@ extern "C" int fil_embed_adam_runs_lrdev(const void* g, const int64_t* perm, con
 }
 
 static int embed_adam_sweep_impl(const char* who, float* table, float* m, float* v, const int32_t* stamp, int64_t V, int K,
-                                 const int64_t* offsets,
-                                    const float* field_l2, const unsigned char* frozen, int F, const int64_t* step, float lr,
-                                    float beta_1, float beta_2, float epsilon, void* stream, const float* lr_dev) {
+                                 const int64_t* offsets, const float* field_l2, const unsigned char* frozen, int F, const int64_t* step,
+                                 float lr, float beta_1, float beta_2, float epsilon, void* stream, const float* lr_dev) {
   FIL_CHECK_ARG_W(who, V >= 0 && K >= 1 && F >= 1);
-  if (F > kSweepMaxF) return fail(FIL_ERR_UNSUPPORTED, "%s: F=%d > %d fields", who, F, kSweepMaxF);
+  if (int rc = check_table_shape(who, 0, F)) return rc;
   if (int rc = check_hyper(who, lr, beta_1, beta_2, epsilon)) return rc;
   if (V == 0) return FIL_OK;
   FIL_CHECK_ARG_W(who, table && m && v && stamp && offsets && step);
   hipStream_t st = (hipStream_t)stream;
   const int64_t n = V * K;
-  const int vec = (K % 4 == 0 && ((((uintptr_t)table | (uintptr_t)m | (uintptr_t)v) & 15) == 0)) ? 1 : 0;
+  const int vec = sweep_vec(K, table, m, v);
   const int64_t work = vec ? n / 4 : n;
   ProfScope ps("embed_adam_sweep", st, 24.0 * (double)n + 4.0 * (double)V);
-  const dim3 grid((int)std::max<int64_t>(1, std::min<int64_t>((work + 255) / 256, 256 * 8)));
+  const dim3 grid = stride_grid(work);
   hipLaunchKernelGGL(embed_adam_sweep_kernel, grid, dim3(256), 0, st, table, m, v, stamp, V, K, offsets, field_l2, frozen, F, step, lr,
                      beta_1, beta_2, epsilon, vec, lr_dev);
   FIL_CHECK_LAUNCH_W(who);
@@ -783,70 +657,20 @@ extern "C" int fil_embed_adam_sweep_lrdev(float* table, float* m, float* v, cons
 }
 
 
-extern "C" size_t fil_embed_runs_compact_workspace_bytes(long R) {
-  if (R <= 0) return 0;
-  const long tiles = (R + kCompactTile - 1) / kCompactTile;
-  return align_up((size_t)tiles * sizeof(int64_t), 256) + align_up((size_t)R * sizeof(int32_t), 256);
-}
-
-extern "C" int fil_embed_runs_compact(const void* g, const int64_t* perm, const int64_t* sorted_ids, long R, int K, int g_dtype,
-                                      int64_t* ids_out, float* values_out, int64_t* count_out, long cap, void* workspace,
-                                      size_t workspace_bytes, void* stream) {
-  FIL_CHECK_ARG(R >= 0 && K >= 1 && cap >= 0);
-  if (g_dtype != FIL_F32 && g_dtype != FIL_BF16) return fail(FIL_ERR_ARG, "fil_embed_runs_compact: g_dtype %d (f32 or bf16)", g_dtype);
-  if (K > 256) return fail(FIL_ERR_UNSUPPORTED, "fil_embed_runs_compact: K=%d > 256", K);
-  if (cap < R) return fail(FIL_ERR_ARG, "fil_embed_runs_compact: cap %ld < R %ld (a list must hold every run of the record)", cap, R);
-  if (R > (long)INT32_MAX) return fail(FIL_ERR_UNSUPPORTED, "fil_embed_runs_compact: R=%ld > 2^31 - 1", R);
-  FIL_CHECK_ARG(ids_out && count_out);
-  if (workspace_bytes < fil_embed_runs_compact_workspace_bytes(R))
-    return fail(FIL_ERR_ARG, "fil_embed_runs_compact: workspace of %zu bytes < %zu (fil_embed_runs_compact_workspace_bytes)", workspace_bytes,
-                fil_embed_runs_compact_workspace_bytes(R));
-  hipStream_t st = (hipStream_t)stream;
-  if (R == 0) {         // an empty list: count 0, every slot padding (the write kernel with no tiles)
-    hipLaunchKernelGGL(runs_write_kernel, dim3(1), dim3(256), 0, st, sorted_ids, perm, 0L, (const int64_t*)nullptr, 0, cap, ids_out,
-                       count_out, (int32_t*)nullptr);
-    FIL_CHECK_LAUNCH();
-    return FIL_OK;
-  }
-  FIL_CHECK_ARG(g && perm && sorted_ids && values_out && workspace);
-  Carver cv(workspace);
-  const int tiles = (int)((R + kCompactTile - 1) / kCompactTile);
-  int64_t* tile_count = cv.take<int64_t>(tiles);
-  int32_t* slot = cv.take<int32_t>(R);
-  ProfScope ps("embed_runs_compact", st, (double)R * K * (g_dtype == FIL_F32 ? 4 : 2) + 20.0 * R + 4.0 * (double)R * K);
-  hipLaunchKernelGGL(runs_count_kernel, dim3(tiles), dim3(256), 0, st, sorted_ids, R, tile_count);
-  FIL_CHECK_LAUNCH();
-  hipLaunchKernelGGL(runs_write_kernel, dim3(tiles), dim3(256), 0, st, sorted_ids, perm, R, tile_count, tiles, cap, ids_out, count_out, slot);
-  FIL_CHECK_LAUNCH();
-  const int C = 64 / ((K + 3) / 4);
-  const dim3 grid((int)std::min<long>((R + 4 * C - 1) / (4 * C), 256 * 32));
-  if (g_dtype == FIL_F32)
-    hipLaunchKernelGGL(runs_compact_sums_kernel<float>, grid, dim3(256), 0, st, static_cast<const float*>(g), perm, sorted_ids, R, K, slot,
-                       cap, values_out);
-  else
-    hipLaunchKernelGGL(runs_compact_sums_kernel<__hip_bfloat16>, grid, dim3(256), 0, st, static_cast<const __hip_bfloat16*>(g), perm,
-                       sorted_ids, R, K, slot, cap, values_out);
-  FIL_CHECK_LAUNCH();
-  return FIL_OK;
-}
-
 static int embed_adam_merged_impl(const char* who, const int64_t* ids, const float* values, const int64_t* counts, int W, long cap, int K,
-                                     const int64_t* offsets, const float* field_l2, int F, float* table, float* m, float* v, int32_t* stamp,
-                                     int64_t V, const int64_t* step, float lr, float beta_1, float beta_2, float epsilon, int mode,
-                                     void* stream, const float* lr_dev) {
+                                  const int64_t* offsets, const float* field_l2, int F, float* table, float* m, float* v, int32_t* stamp,
+                                  int64_t V, const int64_t* step, float lr, float beta_1, float beta_2, float epsilon, int mode,
+                                  void* stream, const float* lr_dev) {
   FIL_CHECK_ARG_W(who, W >= 1 && cap >= 0 && K >= 1 && F >= 1 && V >= 0);
-  if (mode != FIL_ADAM_KERAS && mode != FIL_ADAM_LAZY) return fail(FIL_ERR_ARG, "%s: mode %d (FIL_ADAM_KERAS or FIL_ADAM_LAZY)", who, mode);
-  if (mode == FIL_ADAM_KERAS && stamp == nullptr)
-    return fail(FIL_ERR_ARG, "%s: FIL_ADAM_KERAS needs the row stamps (fil_embed_adam_sweep skips the rows stamped here)", who);
-  if (K > 256) return fail(FIL_ERR_UNSUPPORTED, "%s: K=%d > 256", who, K);
-  if (F > kSweepMaxF) return fail(FIL_ERR_UNSUPPORTED, "%s: F=%d > %d fields", who, F, kSweepMaxF);
+  if (int rc = check_mode(who, mode, stamp)) return rc;
+  if (int rc = check_table_shape(who, K, F)) return rc;
   if (int rc = check_hyper(who, lr, beta_1, beta_2, epsilon)) return rc;
   if (cap == 0 || V == 0) return FIL_OK;
   FIL_CHECK_ARG_W(who, ids && values && counts && offsets && table && m && v && step);
   hipStream_t st = (hipStream_t)stream;
   const long n = (long)W * cap;
   ProfScope ps("embed_adam_merged", st, 8.0 * n + 4.0 * (double)n * K + 24.0 * (double)cap * K);
-  const dim3 grid((int)std::max<long>(1, std::min<long>((n + 255) / 256, 256 * 8)));
+  const dim3 grid = stride_grid(n);
   hipLaunchKernelGGL(embed_adam_merged_kernel, grid, dim3(256), 0, st, ids, values, counts, W, cap, K, offsets, field_l2, F, table, m, v,
                      mode == FIL_ADAM_KERAS ? stamp : nullptr, V, step, lr, beta_1, beta_2, epsilon, lr_dev);
   FIL_CHECK_LAUNCH_W(who);
@@ -870,7 +694,6 @@ extern "C" int fil_embed_adam_merged_lrdev(const int64_t* ids, const float* valu
                                 step, 0.f, beta_1, beta_2, epsilon, mode, stream, lr_dev);
 }
 
-
 extern "C" int fil_embed_adam_ring_len(int sweep_period) { return ring_len(sweep_period); }
 
 extern "C" int fil_embed_adam_catchup_runs(const int64_t* sorted_ids, long R, int K, float* table, float* m, float* v, int32_t* stamp,
@@ -884,7 +707,7 @@ extern "C" int fil_embed_adam_catchup_runs(const int64_t* sorted_ids, long R, in
   const int lg = lanes_lg(K);
   const long total = R << lg;
   ProfScope ps("embed_adam_catchup", st, 8.0 * R);
-  const dim3 grid((int)std::max<long>(1, std::min<long>((total + 255) / 256, 256 * 8)));
+  const dim3 grid = stride_grid(total);
   hipLaunchKernelGGL(embed_adam_catchup_kernel, grid, dim3(256), 0, st, sorted_ids, R, K, lg, table, m, v, stamp,
                      reinterpret_cast<const AdamCoef*>(ring), ring_len(sweep_period), sweep_period, offsets, field_l2, frozen, F, V, step,
                      sweep_vec(K, table, m, v));
@@ -893,10 +716,10 @@ extern "C" int fil_embed_adam_catchup_runs(const int64_t* sorted_ids, long R, in
 }
 
 static int embed_adam_runs_deferred_impl(const char* who, const void* g, const int64_t* perm, const int64_t* sorted_ids, long R, int K,
-                                         int g_dtype,
-                                            int F, const int64_t* offsets, const float* field_l2, const unsigned char* frozen, float* table,
-                                            float* m, float* v, int32_t* stamp, const float* ring, int sweep_period, int64_t V,
-                                            const int64_t* step, float lr, float beta_1, float beta_2, float epsilon, void* stream, const float* lr_dev) {
+                                         int g_dtype, int F, const int64_t* offsets, const float* field_l2, const unsigned char* frozen,
+                                         float* table, float* m, float* v, int32_t* stamp, const float* ring, int sweep_period, int64_t V,
+                                         const int64_t* step, float lr, float beta_1, float beta_2, float epsilon, void* stream,
+                                         const float* lr_dev) {
   FIL_CHECK_ARG_W(who, R >= 0 && K >= 1 && F >= 1 && V >= 0);
   if (g_dtype != FIL_F32 && g_dtype != FIL_BF16) return fail(FIL_ERR_ARG, "%s: g_dtype %d (f32 or bf16)", who, g_dtype);
   if (int rc = check_deferred(who, K, F, sweep_period, ring)) return rc;
@@ -905,8 +728,7 @@ static int embed_adam_runs_deferred_impl(const char* who, const void* g, const i
   FIL_CHECK_ARG_W(who, g && perm && sorted_ids && offsets && table && m && v && stamp && ring && step);
   hipStream_t st = (hipStream_t)stream;
   ProfScope ps("embed_adam_runs_deferred", st, (double)R * K * (g_dtype == FIL_F32 ? 4 : 2) + 24.0 * R * K);
-  const int C = 64 / ((K + 3) / 4);
-  const dim3 grid((int)std::min<long>((R + 4 * C - 1) / (4 * C), 256 * 32));
+  const dim3 grid = run_sums_grid(R, K);
   const AdamCoef* rg = reinterpret_cast<const AdamCoef*>(ring);
   const int D = ring_len(sweep_period);
   if (g_dtype == FIL_F32)
@@ -940,11 +762,10 @@ extern "C" int fil_embed_adam_runs_deferred_lrdev(const void* g, const int64_t* 
 }
 
 static int embed_adam_merged_deferred_impl(const char* who, const int64_t* ids, const float* values, const int64_t* counts, int W, long cap,
-                                           int K,
-                                              const int64_t* offsets, const float* field_l2, const unsigned char* frozen, int F,
-                                              float* table, float* m, float* v, int32_t* stamp, const float* ring, int sweep_period,
-                                              int64_t V, const int64_t* step, float lr, float beta_1, float beta_2, float epsilon,
-                                              void* stream, const float* lr_dev) {
+                                           int K, const int64_t* offsets, const float* field_l2, const unsigned char* frozen, int F,
+                                           float* table, float* m, float* v, int32_t* stamp, const float* ring, int sweep_period,
+                                           int64_t V, const int64_t* step, float lr, float beta_1, float beta_2, float epsilon,
+                                           void* stream, const float* lr_dev) {
   FIL_CHECK_ARG_W(who, W >= 1 && cap >= 0 && K >= 1 && F >= 1 && V >= 0);
   if (int rc = check_deferred(who, K, F, sweep_period, ring)) return rc;
   if (int rc = check_hyper(who, lr, beta_1, beta_2, epsilon)) return rc;
@@ -953,7 +774,7 @@ static int embed_adam_merged_deferred_impl(const char* who, const int64_t* ids, 
   hipStream_t st = (hipStream_t)stream;
   const long n = (long)W * cap;
   ProfScope ps("embed_adam_merged_deferred", st, 8.0 * n + 4.0 * (double)n * K + 24.0 * (double)cap * K);
-  const dim3 grid((int)std::max<long>(1, std::min<long>((n + 255) / 256, 256 * 8)));
+  const dim3 grid = stride_grid(n);
   hipLaunchKernelGGL(embed_adam_merged_deferred_kernel, grid, dim3(256), 0, st, ids, values, counts, W, cap, K, offsets, field_l2, frozen,
                      F, table, m, v, stamp, reinterpret_cast<const AdamCoef*>(ring), ring_len(sweep_period), sweep_period, V, step, lr,
                      beta_1, beta_2, epsilon, sweep_vec(K, table, m, v), lr_dev);
@@ -981,9 +802,8 @@ extern "C" int fil_embed_adam_merged_deferred_lrdev(const int64_t* ids, const fl
 }
 
 static int embed_adam_roll_impl(const char* who, float* table, float* m, float* v, int32_t* stamp, float* ring, int sweep_period, int64_t V,
-                                int K,
-                                   const int64_t* offsets, const float* field_l2, const unsigned char* frozen, int F, const int64_t* step,
-                                   float lr, float beta_1, float beta_2, float epsilon, int flags, void* stream, const float* lr_dev) {
+                                int K, const int64_t* offsets, const float* field_l2, const unsigned char* frozen, int F, const int64_t* step,
+                                float lr, float beta_1, float beta_2, float epsilon, int flags, void* stream, const float* lr_dev) {
   FIL_CHECK_ARG_W(who, V >= 0 && K >= 1 && F >= 1);
   if (flags != FIL_ADAM_ROLL_STEP && flags != FIL_ADAM_ROLL_SKIP && flags != FIL_ADAM_ROLL_FLUSH)
     return fail(FIL_ERR_ARG, "%s: flags %d (FIL_ADAM_ROLL_STEP, _SKIP or _FLUSH)", who, flags);
@@ -997,7 +817,7 @@ static int embed_adam_roll_impl(const char* who, float* table, float* m, float* 
   const int vec = sweep_vec(K, table, m, v);
   ProfScope ps(flags == FIL_ADAM_ROLL_FLUSH ? "embed_adam_flush" : "embed_adam_roll", st, 24.0 * (double)rows * K + 4.0 * (double)rows);
   const int64_t total = rows << lg;
-  const dim3 grid((int)std::max<int64_t>(1, std::min<int64_t>((total + 255) / 256, 256 * 8)));
+  const dim3 grid = stride_grid(total);
   hipLaunchKernelGGL(embed_adam_roll_kernel, grid, dim3(256), 0, st, table, m, v, stamp, reinterpret_cast<AdamCoef*>(ring),
                      ring_len(sweep_period), sweep_period, V, K, lg, vec, offsets, field_l2, frozen, F, step, lr, beta_1, beta_2, epsilon,
                      flags == FIL_ADAM_ROLL_STEP ? 0 : (flags == FIL_ADAM_ROLL_SKIP ? kRollSkip : kRollFlush), lr_dev);

@@ -1,6 +1,8 @@
 // What the fused optimizers of optim.hip (Adam), optim_rowwise.hip (Adagrad, Ftrl) and optim_momentum.hip (SGD, RMSprop) share: the
 // walk of the dense descriptors (fil_adam_multi, fil_rowopt_multi, fil_momopt_multi), the field of a row, the walk of the gathered
-// compact lists of fil_embed_runs_compact (the merged updates), the regulariser's gradient and the sweeps' compacted field table.
+// compact lists of fil_embed_runs_compact (runs_compact.hip; the merged updates), the regulariser's gradient, the sweeps' compacted
+// field table, the workgroup sum and scan, and what every launcher computes the same way: the row tag of a step, the sweep's 16-byte
+// predicate, the grid-stride grid and the table-shape check.
 // optim.hip builds its own kernels on them (its coefficients depend on the step; lazy and deferred modes); the row-rule families get
 // theirs, and their host launchers, from optim_rule.h, which sits on this header: there a rule supplies only its per-element update.
 #pragma once
@@ -9,6 +11,26 @@
 namespace fil {
 
 constexpr int kSweepMaxF = 1024;
+
+// the tag of the rows updated at the step in progress: the low 32 bits of its 1-based count
+__device__ __forceinline__ int32_t step_tag(const int64_t* __restrict__ step) { return (int32_t)(uint32_t)(*step + 1); }
+
+// does a sweep of these arrays take its 16-byte path (K % 4 == 0 and every array the rule has 16-byte aligned; NULL: not one of
+// them).  Adam's 16-byte path rounds differently (adam_untouched, optim.hip), so its deferred kernels ask here too.
+inline int sweep_vec(int K, const float* a, const float* b, const float* c) {
+  return (K % 4 == 0 && ((((uintptr_t)a | (uintptr_t)b | (uintptr_t)c) & 15) == 0)) ? 1 : 0;
+}
+
+// the grid of a grid-stride kernel over `work` lanes' worth of items, 256 lanes a workgroup
+inline dim3 stride_grid(int64_t work) { return dim3((int)std::max<int64_t>(1, std::min<int64_t>((work + 255) / 256, 256 * 8))); }
+
+// a lane group of a wave holds a row (K <= 256) and the field table sits in LDS (F <= kSweepMaxF); K = 0 / F = 0: the caller's
+// kernels have no such limit
+inline int check_table_shape(const char* who, int K, int F) {
+  if (K > 256) return fail(FIL_ERR_UNSUPPORTED, "%s: K=%d > 256", who, K);
+  if (F > kSweepMaxF) return fail(FIL_ERR_UNSUPPORTED, "%s: F=%d > %d fields", who, F, kSweepMaxF);
+  return FIL_OK;
+}
 
 // the last f with off[f] <= row, or -1
 __device__ __forceinline__ int sweep_field(const int64_t* off, int F, int64_t row) {
@@ -162,6 +184,17 @@ struct RegTab {
   float l2x2[kSweepMaxF];         // 2 field_l2
   int n;
 };
+
+// sum of x over a 256-lane workgroup (s: 4 longs of LDS); every lane gets the total
+__device__ __forceinline__ long block_sum_256(long x, long* s) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o, 64);
+  if ((threadIdx.x & 63) == 0) s[threadIdx.x >> 6] = x;
+  __syncthreads();
+  const long t = (s[0] + s[1]) + (s[2] + s[3]);
+  __syncthreads();
+  return t;
+}
 
 // exclusive scan of x over a 256-lane workgroup in lane order (s: 4 longs of LDS); *total = the sum over all lanes
 __device__ __forceinline__ long block_scan_256(long x, long* s, long* total) {

@@ -60,7 +60,7 @@ __global__ __launch_bounds__(256) void embed_rule_runs_kernel(const GT* __restri
                                                               const int64_t* __restrict__ step, typename Rule::Hyper h,
                                                               const float* __restrict__ lr_dev) {
   if (lr_dev) h.lr = *lr_dev;
-  const int32_t tag = stamp ? (int32_t)(uint32_t)(*step + 1) : 0;
+  const int32_t tag = stamp ? step_tag(step) : 0;
   embed_run_sums(g, perm, sorted_ids, R, K, [=](int64_t row, int kq, const float (&acc)[4], int64_t first) {
     const float l2x2 = field_l2 ? 2.f * field_l2[first % F] : 0.f;
 #pragma unroll
@@ -87,7 +87,7 @@ __global__ __launch_bounds__(256) void embed_rule_sweep_kernel(float* __restrict
   __shared__ RegTab t;
   load_reg_tab<kAll>(&t, offsets, field_l2, frozen, F, V);
   const int64_t n = t.vbeg[t.n] * K;               // elements of the walked fields
-  const int32_t tag = (int32_t)(uint32_t)(*step + 1);
+  const int32_t tag = step_tag(step);
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
   if (vec) {                                        // K % 4 == 0 and 16-byte aligned arrays: a lane moves 4 elements of one row
     for (int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; q < n / 4; q += stride) {
@@ -156,7 +156,7 @@ __global__ __launch_bounds__(256) void embed_rule_merged_kernel(const int64_t* _
   __shared__ int64_t s_off[kSweepMaxF];
   for (int f = threadIdx.x; f < F; f += blockDim.x) s_off[f] = offsets[f];
   __syncthreads();
-  const int32_t tag = stamp ? (int32_t)(uint32_t)(*step + 1) : 0;
+  const int32_t tag = stamp ? step_tag(step) : 0;
   const auto epi = [=](int64_t row, int f, float l2x2, int k0, const float (&acc)[kMergeChunk]) {
 #pragma unroll
     for (int e = 0; e < kMergeChunk; ++e)
@@ -204,7 +204,7 @@ int embed_rule_runs_launch(const char* who, const void* g, const int64_t* perm, 
                            const typename Fam::Raw* hyper, void* stream, const float* lr_dev) {
   FIL_CHECK_ARG_W(who, R >= 0 && K >= 1 && F >= 1);
   if (g_dtype != FIL_F32 && g_dtype != FIL_BF16) return fail(FIL_ERR_ARG, "%s: g_dtype %d (f32 or bf16)", who, g_dtype);
-  if (K > 256) return fail(FIL_ERR_UNSUPPORTED, "%s: K=%d > 256", who, K);
+  if (int rc = check_table_shape(who, K, 0)) return rc;
   int var = 0;
   if (int rc = Fam::resolve(who, rule, hyper, &var)) return rc;
   if (R == 0) return FIL_OK;
@@ -212,8 +212,7 @@ int embed_rule_runs_launch(const char* who, const void* g, const int64_t* perm, 
   if (int rc = Fam::check_slots(who, var, slot0, slot1)) return rc;
   hipStream_t st = (hipStream_t)stream;
   const auto h = Fam::device(*hyper);
-  const int C = 64 / ((K + 3) / 4);
-  const dim3 grid((int)std::min<long>((R + 4 * C - 1) / (4 * C), 256 * 32));
+  const dim3 grid = run_sums_grid(R, K);
   return Fam::dispatch(var, [&](auto r) -> int {
     using Rule = decltype(r);
     ProfScope ps(Rule::scope(SC_RUNS), st, (double)R * K * (g_dtype == FIL_F32 ? 4 : 2) + 8.0 * rule_arrays<Rule>() * R * K);
@@ -235,7 +234,7 @@ int embed_rule_sweep_launch(const char* who, float* table, float* slot0, float* 
                             const int64_t* offsets, const float* field_l2, const unsigned char* frozen, int F, const int64_t* step, int rule,
                             const typename Fam::Raw* hyper, void* stream, const float* lr_dev) {
   FIL_CHECK_ARG_W(who, V >= 0 && K >= 1 && F >= 1);
-  if (F > kSweepMaxF) return fail(FIL_ERR_UNSUPPORTED, "%s: F=%d > %d fields", who, F, kSweepMaxF);
+  if (int rc = check_table_shape(who, 0, F)) return rc;
   int var = 0;
   if (int rc = Fam::resolve(who, rule, hyper, &var)) return rc;
   return Fam::dispatch(var, [&](auto r) -> int {
@@ -249,11 +248,11 @@ int embed_rule_sweep_launch(const char* who, float* table, float* slot0, float* 
     float* S = Rule::kHasS ? slot0 : nullptr;
     float* Z = Rule::kHasZ ? slot1 : nullptr;
     const int64_t n = V * K;
-    const int vec = (K % 4 == 0 && ((((uintptr_t)table | (uintptr_t)S | (uintptr_t)Z) & 15) == 0)) ? 1 : 0;
+    const int vec = sweep_vec(K, table, S, Z);
     const int64_t work = vec ? n / 4 : n;
     // (bytes of a whole-table sweep at the full rule: the kernel moves only the walked fields' share, 8 per element where it only decays)
     ProfScope ps(Rule::scope(SC_SWEEP), st, 8.0 * rule_arrays<Rule>() * (double)n + 4.0 * (double)V);
-    const dim3 grid((int)std::max<int64_t>(1, std::min<int64_t>((work + 255) / 256, 256 * 8)));
+    const dim3 grid = stride_grid(work);
     hipLaunchKernelGGL(embed_rule_sweep_kernel<Rule>, grid, dim3(256), 0, st, table, S, Z, stamp, V, K, offsets, field_l2, frozen, F, step, h,
                        vec, lr_dev);
     FIL_CHECK_LAUNCH_W(who);
@@ -266,8 +265,7 @@ int embed_rule_merged_launch(const char* who, const int64_t* ids, const float* v
                              const int64_t* offsets, const float* field_l2, int F, float* table, float* slot0, float* slot1, int32_t* stamp,
                              int64_t V, const int64_t* step, int rule, const typename Fam::Raw* hyper, void* stream, const float* lr_dev) {
   FIL_CHECK_ARG_W(who, W >= 1 && cap >= 0 && K >= 1 && F >= 1 && V >= 0);
-  if (K > 256) return fail(FIL_ERR_UNSUPPORTED, "%s: K=%d > 256", who, K);
-  if (F > kSweepMaxF) return fail(FIL_ERR_UNSUPPORTED, "%s: F=%d > %d fields", who, F, kSweepMaxF);
+  if (int rc = check_table_shape(who, K, F)) return rc;
   int var = 0;
   if (int rc = Fam::resolve(who, rule, hyper, &var)) return rc;
   if (cap == 0 || V == 0) return FIL_OK;
@@ -276,7 +274,7 @@ int embed_rule_merged_launch(const char* who, const int64_t* ids, const float* v
   hipStream_t st = (hipStream_t)stream;
   const auto h = Fam::device(*hyper);
   const long n = (long)W * cap;
-  const dim3 grid((int)std::max<long>(1, std::min<long>((n + 255) / 256, 256 * 8)));
+  const dim3 grid = stride_grid(n);
   return Fam::dispatch(var, [&](auto r) -> int {
     using Rule = decltype(r);
     ProfScope ps(Rule::scope(SC_MERGED), st, 8.0 * n + 4.0 * (double)n * K + 8.0 * rule_arrays<Rule>() * (double)cap * K);

@@ -602,23 +602,43 @@ class Adam(_RunsOptimizer):
                            "(SparseEmbed(grad_mode='runs'))" % (tuple(p.shape),))
 
     def _apply_runs(self, lib, p, pend, m, v, t, hyper):
+        """One table's step from its runs record.  The update: fil_embed_adam_runs, or with an exchange (data parallel,
+        force_exchange) fil_embed_adam_merged of the gathered lists; either in its _deferred form for a deferred table.  Then the rows
+        the batch did not touch: a deferred table's roll, Keras mode's sweep, nothing in lazy mode."""
         lr, b1, b2, eps = hyper
         V, K = p.shape
-        if p in self._defer:
-            self._apply_runs_deferred(lib, p, pend, m, v, t, hyper)
-            return
-        mode = FIL_ADAM_LAZY if self.lazy_tables else FIL_ADAM_KERAS
-        stamp = self._stamp(p) if mode == FIL_ADAM_KERAS else None
+        d = self._defer.get(p)
+        if d is not None:
+            offsets, field_l2, frozen, F = d.field_args(p, pend)
+            stamp = d.stamp
+        else:
+            mode = FIL_ADAM_LAZY if self.lazy_tables else FIL_ADAM_KERAS
+            stamp = self._stamp(p) if mode == FIL_ADAM_KERAS else None
         with torch.cuda.device(p.device):
             st = stream_ptr()
             world = self._exchange_world()
             if world:
-                self._apply_runs_exchanged(lib, p, pend, m, v, t, stamp, mode, world, hyper, st)
+                ids, values, counts, cap = self._compact_and_exchange(lib, p, pend, world, st)
+                if d is not None:
+                    fn, r, name = _rated(lib, "fil_embed_adam_merged_deferred", lr)
+                    check(fn(ptr(ids), ptr(values), ptr(counts), world, cap, K, ptr(offsets), ptr(field_l2), ptr(frozen), F, ptr(p),
+                             ptr(m), ptr(v), ptr(stamp), ptr(d.ring), self.sweep_period, V, ptr(t), r, b1, b2, eps, st), name)
+                else:
+                    fn, r, name = _rated(lib, "fil_embed_adam_merged", lr)
+                    check(fn(ptr(ids), ptr(values), ptr(counts), world, cap, K, ptr(pend["offsets"]), ptr(pend["field_l2"]), pend["F"],
+                             ptr(p), ptr(m), ptr(v), ptr(stamp), V, ptr(t), r, b1, b2, eps, mode, st), name)
+            elif d is not None:
+                fn, r, name = _rated(lib, "fil_embed_adam_runs_deferred", lr)
+                check(fn(ptr(pend["g"]), ptr(pend["perm"]), ptr(pend["sorted_ids"]), pend["R"], K, pend["g_dtype"], F, ptr(offsets),
+                         ptr(field_l2), ptr(frozen), ptr(p), ptr(m), ptr(v), ptr(stamp), ptr(d.ring), self.sweep_period, V, ptr(t), r,
+                         b1, b2, eps, st), name)
             else:
                 fn, r, name = _rated(lib, "fil_embed_adam_runs", lr)
                 check(fn(ptr(pend["g"]), ptr(pend["perm"]), ptr(pend["sorted_ids"]), pend["R"], K, pend["g_dtype"], pend["F"],
                          ptr(pend["field_l2"]), ptr(p), ptr(m), ptr(v), ptr(stamp), ptr(t), r, b1, b2, eps, mode, st), name)
-            if mode == FIL_ADAM_KERAS:
+            if d is not None:
+                d.roll(p, hyper, FIL_ADAM_ROLL_STEP)
+            elif mode == FIL_ADAM_KERAS:
                 fn, r, name = _rated(lib, "fil_embed_adam_sweep", lr)
                 check(fn(ptr(p), ptr(m), ptr(v), ptr(stamp), V, K, ptr(pend["offsets"]), ptr(pend["field_l2"]), ptr(pend["frozen"]),
                          pend["F"], ptr(t), r, b1, b2, eps, st), name)
@@ -642,45 +662,12 @@ class Adam(_RunsOptimizer):
         self._released.append(d)
         _DEFERRED[p] = d
 
-    def _apply_runs_deferred(self, lib, p, pend, m, v, t, hyper):
-        lr, b1, b2, eps = hyper
-        V, K = p.shape
-        d = self._defer[p]
-        offsets, field_l2, frozen, F = d.field_args(p, pend)
-        with torch.cuda.device(p.device):
-            st = stream_ptr()
-            world = self._exchange_world()
-            if world:
-                self._apply_runs_exchanged(lib, p, pend, m, v, t, None, FIL_ADAM_KERAS, world, hyper, st)
-            else:
-                fn, r, name = _rated(lib, "fil_embed_adam_runs_deferred", lr)
-                check(fn(ptr(pend["g"]), ptr(pend["perm"]), ptr(pend["sorted_ids"]), pend["R"], K, pend["g_dtype"], F, ptr(offsets),
-                         ptr(field_l2), ptr(frozen), ptr(p), ptr(m), ptr(v), ptr(d.stamp), ptr(d.ring), self.sweep_period, V, ptr(t), r,
-                         b1, b2, eps, st), name)
-        d.roll(p, hyper, FIL_ADAM_ROLL_STEP)
-
     @torch.no_grad()
     def flush(self):
         """Deferred mode: bring every row of every deferred table current (table, m and v then hold exactly what Keras mode holds).
         A no-op without sweep_period.  Also done when the optimizer is finalised."""
         for d in self._defer.values():
             d.flush()
-
-    # -- data parallelism ------------------------------------------------------------------------------------------
-    def _apply_runs_exchanged(self, lib, p, pend, m, v, t, stamp, mode, world, hyper, st):
-        lr, b1, b2, eps = hyper
-        V, K = p.shape
-        ids, values, counts, cap = self._compact_and_exchange(lib, p, pend, world, st)
-        if p in self._defer:
-            d = self._defer[p]
-            offsets, field_l2, frozen, F = d.field_args(p, pend)
-            fn, r, name = _rated(lib, "fil_embed_adam_merged_deferred", lr)
-            check(fn(ptr(ids), ptr(values), ptr(counts), world, cap, K, ptr(offsets), ptr(field_l2), ptr(frozen), F, ptr(p), ptr(m),
-                     ptr(v), ptr(d.stamp), ptr(d.ring), self.sweep_period, V, ptr(t), r, b1, b2, eps, st), name)
-            return
-        fn, r, name = _rated(lib, "fil_embed_adam_merged", lr)
-        check(fn(ptr(ids), ptr(values), ptr(counts), world, cap, K, ptr(pend["offsets"]), ptr(pend["field_l2"]), pend["F"], ptr(p),
-                 ptr(m), ptr(v), ptr(stamp), V, ptr(t), r, b1, b2, eps, mode, st), name)
 
 
 class _Rowwise(_RunsOptimizer):

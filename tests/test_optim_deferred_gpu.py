@@ -27,21 +27,21 @@ def _layer(K, reg, out_dtype=None, vocab=VOCAB, seed=3):
     return SparseEmbed(info, packed=True, check_ids=False, grad_mode="runs", out_dtype=out_dtype)
 
 
-def _batches(steps, K, seed, vocab=VOCAB):
+def _batches(steps, K, seed, vocab=VOCAB, batch=B):
     """Zipf(1.1) ids (a few hot rows, most rows untouched for many steps), some out of range, fixed upstream gradients."""
     rng = np.random.default_rng(seed)
     out = []
     for _ in range(steps):
-        idx = np.stack([np.minimum(rng.zipf(1.1, B) - 1, v - 1) for v in vocab], 1)
+        idx = np.stack([np.minimum(rng.zipf(1.1, batch) - 1, v - 1) for v in vocab], 1)
         idx[rng.random(idx.shape) < 0.01] = -1
-        out.append((torch.tensor(idx, device="cuda"), torch.tensor(rng.standard_normal((B, len(vocab), K)) * 1e-2, device="cuda")))
+        out.append((torch.tensor(idx, device="cuda"), torch.tensor(rng.standard_normal((batch, len(vocab), K)) * 1e-2, device="cuda")))
     return out
 
 
-def _pair(K, reg, N, out_dtype=None):
+def _pair(K, reg, N, out_dtype=None, vocab=VOCAB, batch=B):
     """Two identical layers: one under Keras mode, one deferred."""
-    emb_k, emb_d = _layer(K, reg, out_dtype), _layer(K, reg, out_dtype)
-    first = _batches(1, K, 99)[0][0]
+    emb_k, emb_d = _layer(K, reg, out_dtype, vocab), _layer(K, reg, out_dtype, vocab)
+    first = _batches(1, K, 99, vocab, batch)[0][0]
     emb_k(first), emb_d(first)                  # build
     assert torch.equal(emb_k.embeddings, emb_d.embeddings)
     return emb_k, optim.Adam([emb_k.embeddings]), emb_d, optim.Adam([emb_d.embeddings], sweep_period=N)
@@ -84,6 +84,32 @@ def test_deferred_is_bitwise_keras_mode(N, out_dtype, reg, K):
     before = emb_d.embeddings.detach().clone()
     opt_d.flush()
     assert torch.equal(before, emb_d.embeddings)
+
+
+EDGE_VOCAB = [37, 5, 64, 9, 3]              # 118 rows, so every step's slice holds rows of several fields; field 4 is the frozen one
+
+
+@pytest.mark.parametrize("K", [1, 3, 4, 5, 252, 256])
+def test_deferred_is_bitwise_keras_mode_at_edge_widths(K):
+    """The widths at which four elements of a row per lane can go wrong: K = 1 and 3 are one lane per row with a masked tail, K = 5
+    two lanes of which the second holds one element, K = 4 and K = 252 / 256 the 16-byte path at the smallest and the largest lane
+    group.  l2 fields and a frozen one; N = 3, so 8 steps cover a skipped slice and a wrap of the ring (4 entries)."""
+    N = 3
+    emb_k, opt_k, emb_d, opt_d = _pair(K, True, N, vocab=EDGE_VOCAB, batch=32)
+    frozen_rows = slice(int(emb_k.offsets[FROZEN]), int(emb_k.offsets[FROZEN]) + EDGE_VOCAB[FROZEN])
+    start = emb_k.embeddings.detach().clone()
+    for s, (idx, g) in enumerate(_batches(8, K, seed=100 + K, vocab=EDGE_VOCAB, batch=32)):
+        if s == 4:                      # the table has no record at this step
+            for o in (opt_k, opt_d):
+                o.zero_grad()
+                o.step()
+            continue
+        bk = _train_step(emb_k, opt_k, idx, g)
+        bd = _train_step(emb_d, opt_d, idx, g)
+        assert torch.equal(bk, bd), s
+    assert opt_k.iterations == opt_d.iterations == 8
+    _assert_state_equal(emb_k, opt_k, emb_d, opt_d)
+    assert torch.equal(emb_d.embeddings[frozen_rows], start[frozen_rows])
 
 
 def test_deferred_really_defers():
