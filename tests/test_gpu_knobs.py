@@ -67,3 +67,22 @@ def test_gemm_edges_with_one_wave_per_tile():
     tail = "\n".join((r.stdout + r.stderr).strip().splitlines()[-15:])
     assert r.returncode == 0, "FIL_GEMM_KW=1:\n%s" % tail
     assert "44 passed" in r.stdout and "no tests ran" not in r.stdout, tail
+
+
+@pytest.mark.gpu
+def test_dcn_edges_with_a_two_workgroup_grid():
+    """FIL_DCN_GRID=2 (read once per process) caps the register-resident DCN kernels at two workgroups: 8 forward and 16 backward waves.
+    A fresh child runs three groups of tests/test_dcn_edges_gpu.py under it.  The `walk` cases -- every menu shape with a
+    register-resident direction at B = 37 -- are the ones where every forward wave loops (5 or 4 samples) and every backward wave walks
+    3 or 2 samples through its prefetch chain, at every menu instantiation; they assert those trip counts when the grid is forced.  The
+    grid cases with B <= 257 (`le257`) walk up to 17 samples per wave at <8, 4, 2> with one or two partials to reduce.  The path / menu
+    cases (B <= 9) stay at one sample per wave: they show that the forced grid changes no result.  The cases size the workspace with the
+    same override (tests/dcn_edge_cases.py reads the variable), so the child also proves that the library saw it."""
+    env = dict(os.environ)
+    env["FIL_DCN_GRID"] = "2"
+    r = subprocess.run([sys.executable, "-m", "pytest", "tests/test_dcn_edges_gpu.py", "-x", "-q", "-m", "gpu",
+                        "-k", "path_and_menu or le257 or walk", "-p", "no:cacheprovider"], cwd=ROOT, env=env, capture_output=True, text=True,
+                       timeout=600)
+    tail = "\n".join((r.stdout + r.stderr).strip().splitlines()[-15:])
+    assert r.returncode == 0, "FIL_DCN_GRID=2:\n%s" % tail
+    assert "47 passed" in r.stdout and "no tests ran" not in r.stdout, tail

@@ -109,6 +109,30 @@ def test_workspace_sizes(lib):
     assert lib.fil_cin_bwd_workspace_bytes(0, F, K, 3, H) >= 0
 
 
+def test_dcn_workspace_size_follows_the_predicted_backward_path(lib):
+    """fil_dcn_bwd_workspace_bytes at every (B, D, L) of tests/dcn_edge_cases.py equals the formula of the backward path that dcn_paths
+    predicts -- the register path's one partial per workgroup, or the generic path's ds + chunk partials -- and the tables' own path
+    columns agree with dcn_paths.  (tests/test_dcn_edges_gpu.py runs the same cases on the GPU.)"""
+    from tests import dcn_edge_cases as dc
+    assert not dc.forced_grid(), "FIL_DCN_GRID is set"
+    for (B, D, L), (fwd, bwd, npl, vec) in dc.PATH_CASES.items():
+        p = dc.dcn_paths(D, L)
+        assert (p.fwd, p.bwd, p.npl, p.vec) == (fwd, bwd, npl, vec), (B, D, L, p)
+    assert [dc.grid_bwd(B) for B in dc.REG_GRID_B] == list(dc.REG_GRID_B.values())
+    assert [dc.generic_parts(B)[0] for B in dc.GEN_GRID_B] == list(dc.GEN_GRID_B.values())
+    cases = dc.all_cases()
+    assert len(cases) == len(set(cases)) == 15 + 2 * 10 + 6 + 13
+    seen = set()
+    for B, D, L in cases:
+        bwd = dc.dcn_paths(D, L).bwd
+        seen.add(bwd)
+        want = (dc.align256(dc.grid_bwd(B) * ((L + 1) * D + 8) * 4) if bwd == "register" else
+                dc.align256(4 * B * L) + dc.align256(dc.generic_chunks(B) * 2 * L * D * 4))
+        assert want == dc.workspace_bytes(B, D, L)
+        assert lib.fil_dcn_bwd_workspace_bytes(B, D, L) == want, (B, D, L, bwd, lib.fil_dcn_bwd_workspace_bytes(B, D, L), want)
+    assert seen == {"register", "generic"}
+
+
 def test_constructor_surface_matches_reference():
     sig = lambda c: {k: v.default for k, v in inspect.signature(c.__init__).parameters.items() if k not in ("self", "kwargs")}
     assert sig(layers.InnerLayer) == dict(use_inner=True, mod=1, seed=2020, perm=None, use_add=False)
