@@ -643,6 +643,62 @@ int fil_embed_momopt_merged_lrdev(const int64_t* ids, const float* values, const
                                   const float* lr_dev, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * O5  Keras-exact Adadelta and Adamax (TF 2.1 keras/optimizer_v2/adadelta.py, adamax.py -> ApplyAdadelta / SparseApplyAdadelta,
+ *     ApplyAdaMax and adamax.py's Python for IndexedSlices), every tensor fp32, `rule` FIL_OPT_ADADELTA or FIL_OPT_ADAMAX,
+ *     hyper-parameters in a fil_adaopt_hyper read ON THE HOST at the call (a captured graph keeps the values it was captured with).
+ *     Entry points added only: the ABI version stays.  Every operation rounds to fp32 in the order written (no fused multiply-add;
+ *     correctly rounded division and square root; 1 - rho and 1 - beta_1 formed once in fp32):
+ *       Adadelta  dense and touched rows   ag = ag*rho + (g*g)*(1 - rho);  upd = (sqrt(av + epsilon)*(1 / sqrt(ag + epsilon)))*g;
+ *                                          p = p - upd*lr;  av = av*rho + (upd*upd)*(1 - rho)       accum_grad in slot0, accum_var in slot1
+ *       Adamax    dense rows      m += (g - m)*(1 - beta_1);  v = max(beta_2*v, |g|);  p -= c*(m / (v + epsilon))       m in slot0, v in slot1
+ *                 touched rows    m = m*beta_1 + g*(1 - beta_1);  v = max(v*beta_2, |g|);  p += (-c)*(m / (v + epsilon))
+ *                 c = lr / (1 - powf(beta_1, (float)(*step + 1))), computed ON THE DEVICE once per kernel from the step counter and the
+ *                 step's rate (lr, or *lr_dev in the _lrdev twins): a captured step takes each replay's coefficient.  powf is the
+ *                 device's, so Adamax is Keras-exact within optim.Adam's bars, not bit-exact; Adadelta reads no step and is bit-exact.
+ *     slot0 lives in the `m` array of fil_adam_tensor, slot1 in `v`; both rules need both (FIL_ERR_ARG for a NULL one).
+ *     Requires lr, epsilon >= 0; Adadelta rho in [0, 1]; Adamax beta_1, beta_2 in [0, 1) (FIL_ERR_ARG otherwise).
+ *   Which rows Keras updates: both rules are row-local, exactly as O2 -- a touched row takes the touched form with g = run sum +
+ *     2 emb_reg p; an untouched row of a field with emb_reg > 0 takes the DENSE form with g = 2 emb_reg p; every other row and its slots
+ *     keep their bits; a frozen field never changes.
+ *   fil_adaopt_multi / fil_embed_adaopt_runs / fil_embed_adaopt_sweep / fil_embed_adaopt_merged: the contracts, argument lists and
+ *     errors of their fil_momopt_* counterparts (O4) with these rules: the sweep walks the regularised, non-frozen fields only
+ *     (field_l2 NULL: nothing to do, no launch); W = 1 merged is bit-identical to runs on the same record; F <= 1024, K <= 256
+ *     (FIL_ERR_UNSUPPORTED otherwise); R = 0, V = 0 or cap = 0 return FIL_OK before any pointer is looked at.
+ *   The *_lrdev twins read the rate from device memory (lr_dev, one fp32, not NULL), as in O3; fil_adaopt_hyper.lr is then ignored.
+ */
+enum { FIL_OPT_ADADELTA = 5, FIL_OPT_ADAMAX = 6 };
+typedef struct {
+  float lr;
+  float rho;            /* Adadelta */
+  float beta_1;         /* Adamax */
+  float beta_2;         /* Adamax */
+  float epsilon;
+} fil_adaopt_hyper;     /* 20 bytes */
+int fil_adaopt_multi(const fil_adam_tensor* tensors, int n, int64_t total_numel, int64_t* step, int rule, const fil_adaopt_hyper* hyper,
+                     int advance, void* stream);
+int fil_embed_adaopt_runs(const void* g, const int64_t* perm, const int64_t* sorted_ids, long R, int K, int g_dtype, int F,
+                          const float* field_l2, float* table, float* slot0, float* slot1, int32_t* stamp, const int64_t* step, int rule,
+                          const fil_adaopt_hyper* hyper, void* stream);
+int fil_embed_adaopt_sweep(float* table, float* slot0, float* slot1, const int32_t* stamp, int64_t V, int K, const int64_t* offsets,
+                           const float* field_l2, const unsigned char* frozen, int F, const int64_t* step, int rule,
+                           const fil_adaopt_hyper* hyper, void* stream);
+int fil_embed_adaopt_merged(const int64_t* ids, const float* values, const int64_t* counts, int W, long cap, int K, const int64_t* offsets,
+                            const float* field_l2, int F, float* table, float* slot0, float* slot1, int32_t* stamp, int64_t V,
+                            const int64_t* step, int rule, const fil_adaopt_hyper* hyper, void* stream);
+int fil_adaopt_multi_lrdev(const fil_adam_tensor* tensors, int n, int64_t total_numel, int64_t* step, int rule,
+                           const fil_adaopt_hyper* hyper, const float* lr_dev, int advance, void* stream);
+int fil_embed_adaopt_runs_lrdev(const void* g, const int64_t* perm, const int64_t* sorted_ids, long R, int K, int g_dtype, int F,
+                                const float* field_l2, float* table, float* slot0, float* slot1, int32_t* stamp, const int64_t* step,
+                                int rule, const fil_adaopt_hyper* hyper, const float* lr_dev, void* stream);
+int fil_embed_adaopt_sweep_lrdev(float* table, float* slot0, float* slot1, const int32_t* stamp, int64_t V, int K, const int64_t* offsets,
+                                 const float* field_l2, const unsigned char* frozen, int F, const int64_t* step, int rule,
+                                 const fil_adaopt_hyper* hyper, const float* lr_dev, void* stream);
+int fil_embed_adaopt_merged_lrdev(const int64_t* ids, const float* values, const int64_t* counts, int W, long cap, int K,
+                                  const int64_t* offsets, const float* field_l2, int F, float* table, float* slot0, float* slot1,
+                                  int32_t* stamp, int64_t V, const int64_t* step, int rule, const fil_adaopt_hyper* hyper,
+                                  const float* lr_dev, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * M1  Keras' streaming AUC (TF 2.1 keras/metrics.py: AUC; keras/utils/metrics_utils.py: update_confusion_matrix_variables) --
  *     replaces metrics=[tf.keras.metrics.AUC()] of example/ctr_example/un_seq.py:61.  Entry points added only: the ABI version stays.
  *   State: cm [4][T] fp32 = TP | FP | TN | FN per threshold, as Keras keeps them, and one int64 `invalid`.

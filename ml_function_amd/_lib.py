@@ -31,6 +31,7 @@ FIL_ADAM_ROLL_STEP, FIL_ADAM_ROLL_SKIP, FIL_ADAM_ROLL_FLUSH = 0, 1, 2
 FIL_OPT_ADAGRAD, FIL_OPT_FTRL = 1, 2
 FIL_OPT_SGD, FIL_OPT_RMSPROP = 3, 4
 FIL_MOMOPT_NESTEROV = 1
+FIL_OPT_ADADELTA, FIL_OPT_ADAMAX = 5, 6
 FIL_CONFUSION_MAX_T, FIL_CONFUSION_ONE_LAUNCH_N = 2048, 16384
 
 _c = ctypes
@@ -128,6 +129,15 @@ SIGNATURES = {
     "fil_embed_momopt_runs_lrdev": (_I, [_P, _P, _P, _c.c_long, _I, _I, _I, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P]),
     "fil_embed_momopt_sweep_lrdev": (_I, [_P, _P, _P, _P, _c.c_int64, _I, _P, _P, _P, _I, _P, _I, _P, _P, _P]),
     "fil_embed_momopt_merged_lrdev": (_I, [_P, _P, _P, _I, _c.c_long, _I, _P, _P, _I, _P, _P, _P, _P, _c.c_int64, _P, _I, _P, _P, _P]),
+    # O5: Adadelta / Adamax -- the argument lists of the O4 entry points, with a fil_adaopt_hyper
+    "fil_adaopt_multi": (_I, [_P, _I, _c.c_int64, _P, _I, _P, _I, _P]),
+    "fil_embed_adaopt_runs": (_I, [_P, _P, _P, _c.c_long, _I, _I, _I, _P, _P, _P, _P, _P, _P, _I, _P, _P]),
+    "fil_embed_adaopt_sweep": (_I, [_P, _P, _P, _P, _c.c_int64, _I, _P, _P, _P, _I, _P, _I, _P, _P]),
+    "fil_embed_adaopt_merged": (_I, [_P, _P, _P, _I, _c.c_long, _I, _P, _P, _I, _P, _P, _P, _P, _c.c_int64, _P, _I, _P, _P]),
+    "fil_adaopt_multi_lrdev": (_I, [_P, _I, _c.c_int64, _P, _I, _P, _P, _I, _P]),
+    "fil_embed_adaopt_runs_lrdev": (_I, [_P, _P, _P, _c.c_long, _I, _I, _I, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P]),
+    "fil_embed_adaopt_sweep_lrdev": (_I, [_P, _P, _P, _P, _c.c_int64, _I, _P, _P, _P, _I, _P, _I, _P, _P, _P]),
+    "fil_embed_adaopt_merged_lrdev": (_I, [_P, _P, _P, _I, _c.c_long, _I, _P, _P, _I, _P, _P, _P, _P, _c.c_int64, _P, _I, _P, _P, _P]),
     "fil_confusion_workspace_bytes": (_Z, [_I, _I]),
     "fil_confusion_update": (_I, [_P, _P, _I, _P, _I, _P, _P, _P, _Z, _P]),
     "fil_auc_result": (_I, [_P, _I, _I, _I, _P, _P]),
@@ -145,6 +155,14 @@ class MomoptHyper(_c.Structure):
 
 
 assert _c.sizeof(MomoptHyper) == 24
+
+
+class AdaoptHyper(_c.Structure):
+    """fil_adaopt_hyper (include/fil.h O5)"""
+    _fields_ = [("lr", _F), ("rho", _F), ("beta_1", _F), ("beta_2", _F), ("epsilon", _F)]
+
+
+assert _c.sizeof(AdaoptHyper) == 20
 
 FIL_LR_CONSTANT, FIL_LR_EXPONENTIAL, FIL_LR_INVERSE_TIME, FIL_LR_POLYNOMIAL, FIL_LR_PIECEWISE = 0, 1, 2, 3, 4
 FIL_LR_MAX_BOUNDARIES = 32

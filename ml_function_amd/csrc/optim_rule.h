@@ -1,11 +1,15 @@
-// The row-rule optimizers (optim_rowwise.hip: Adagrad, Ftrl; optim_momentum.hip: SGD, RMSprop), each kernel shape and each host
-// launcher written once on the walks of optim_rows.h.  A rule is a per-element update whose coefficients do not depend on the step
-// (Adam's do: optim.hip stays apart); its file supplies a Rule per variant and one Family:
+// The row-rule optimizers (optim_rowwise.hip: Adagrad, Ftrl; optim_momentum.hip: SGD, RMSprop; optim_adaptive.hip: Adadelta, Adamax),
+// each kernel shape and each host launcher written once on the walks of optim_rows.h.  A rule is a row-local per-element update whose
+// coefficients do not depend on the step, or (kStepped) depend on it through one wave-uniform prepare() per kernel (Adam's sweep is not
+// row-local: optim.hip stays apart); its file supplies a Rule per variant and one Family:
 //   Rule    Hyper                        the device hyper-parameters, passed by value; `lr` is a member (the device rate replaces it)
 //           kHasS, kHasZ                 the rule has the first / the second slot: one it lacks is never dereferenced and may be NULL
 //           kSweepAll                    the sweep walks every non-frozen field, an unstamped row of an unregularised one takes decay()
 //           elem<kTouched>(p, s, z, g, h)  one element, contraction off; kTouched: the row came with the batch (the Sparse op's form)
 //           decay(s, h)                  -> the decayed first slot; only where kSweepAll
+//           kStepped, prepare(h, it)     opt-in (a rule without the member is not stepped): every kernel replaces its hyper-parameters by
+//                                        prepare(h, *step) once at its top, after the device rate has replaced lr -- `it` is the count of
+//                                        completed steps (Keras' iterations), the same in every launch of a step: the counter advances last
 //           scope(SC_*)                  the profile scope name of each launch (string literals: the profiler keeps the pointer)
 //   Family  Raw                          the hyper-parameter struct of fil.h
 //           resolve(who, rule, raw, &var)  checks rule and hyper-parameters (on the host: a capture keeps the values) -> the variant
@@ -18,10 +22,23 @@
 #include "embed_runs.h"
 #include "optim_rows.h"
 #include <hip/hip_bf16.h>
+#include <type_traits>
 
 namespace fil {
 
 enum { SC_MULTI = 0, SC_RUNS = 1, SC_SWEEP = 2, SC_MERGED = 3 };
+
+template <typename Rule, typename = void>
+struct rule_stepped : std::false_type {};
+template <typename Rule>
+struct rule_stepped<Rule, std::void_t<decltype(Rule::kStepped)>> : std::bool_constant<Rule::kStepped> {};
+
+// the top of every kernel: the step's rate, then the step's coefficients (nothing is read or computed for a rule that is not stepped)
+template <typename Rule>
+__device__ __forceinline__ void rule_hyper_of_step(typename Rule::Hyper& h, const float* __restrict__ lr_dev, const int64_t* __restrict__ step) {
+  if (lr_dev) h.lr = *lr_dev;
+  if constexpr (rule_stepped<Rule>::value) h = Rule::prepare(h, *step);
+}
 
 template <typename Rule>
 constexpr double rule_arrays() { return 1.0 + (Rule::kHasS ? 1.0 : 0.0) + (Rule::kHasZ ? 1.0 : 0.0); }
@@ -32,8 +49,8 @@ constexpr double rule_arrays() { return 1.0 + (Rule::kHasS ? 1.0 : 0.0) + (Rule:
 // ---- the dense launch: the descriptors (multi_tensor_walk_slots) with the rule in its dense form; `m` is the first slot, `v` the second
 template <typename Rule>
 __global__ __launch_bounds__(256) void rule_multi_kernel(const fil_adam_tensor* __restrict__ ts, int n, typename Rule::Hyper h,
-                                                         const float* __restrict__ lr_dev) {
-  if (lr_dev) h.lr = *lr_dev;
+                                                         const float* __restrict__ lr_dev, const int64_t* __restrict__ step) {
+  rule_hyper_of_step<Rule>(h, lr_dev, step);
   multi_tensor_walk_slots<Rule::kHasS, Rule::kHasZ>(ts, n, [=](float& p, float& s, float& z, float g, float l2x2) {
     Rule::template elem<false>(p, s, z, with_l2(g, l2x2, p), h);
   });
@@ -59,7 +76,7 @@ __global__ __launch_bounds__(256) void embed_rule_runs_kernel(const GT* __restri
                                                               float* __restrict__ S, float* __restrict__ Z, int32_t* __restrict__ stamp,
                                                               const int64_t* __restrict__ step, typename Rule::Hyper h,
                                                               const float* __restrict__ lr_dev) {
-  if (lr_dev) h.lr = *lr_dev;
+  rule_hyper_of_step<Rule>(h, lr_dev, step);
   const int32_t tag = stamp ? step_tag(step) : 0;
   embed_run_sums(g, perm, sorted_ids, R, K, [=](int64_t row, int kq, const float (&acc)[4], int64_t first) {
     const float l2x2 = field_l2 ? 2.f * field_l2[first % F] : 0.f;
@@ -83,7 +100,7 @@ __global__ __launch_bounds__(256) void embed_rule_sweep_kernel(float* __restrict
                                                                const int64_t* __restrict__ step, typename Rule::Hyper h, int vec,
                                                                const float* __restrict__ lr_dev) {
   constexpr bool kM = Rule::kHasS, kZ = Rule::kHasZ, kAll = Rule::kSweepAll;
-  if (lr_dev) h.lr = *lr_dev;
+  rule_hyper_of_step<Rule>(h, lr_dev, step);
   __shared__ RegTab t;
   load_reg_tab<kAll>(&t, offsets, field_l2, frozen, F, V);
   const int64_t n = t.vbeg[t.n] * K;               // elements of the walked fields
@@ -152,7 +169,7 @@ __global__ __launch_bounds__(256) void embed_rule_merged_kernel(const int64_t* _
                                                                 float* __restrict__ Z, int32_t* __restrict__ stamp, int64_t V,
                                                                 const int64_t* __restrict__ step, typename Rule::Hyper h,
                                                                 const float* __restrict__ lr_dev) {
-  if (lr_dev) h.lr = *lr_dev;
+  rule_hyper_of_step<Rule>(h, lr_dev, step);
   __shared__ int64_t s_off[kSweepMaxF];
   for (int f = threadIdx.x; f < F; f += blockDim.x) s_off[f] = offsets[f];
   __syncthreads();
@@ -185,7 +202,7 @@ int rule_multi_launch(const char* who, const fil_adam_tensor* tensors, int n, in
     if (int rc = Fam::dispatch(var, [&](auto r) -> int {
           using Rule = decltype(r);
           ProfScope ps(Rule::scope(SC_MULTI), st, (4.0 + 8.0 * rule_arrays<Rule>()) * (double)total_numel);
-          hipLaunchKernelGGL(rule_multi_kernel<Rule>, grid, dim3(256), 0, st, tensors, n, h, lr_dev);
+          hipLaunchKernelGGL(rule_multi_kernel<Rule>, grid, dim3(256), 0, st, tensors, n, h, lr_dev, step);
           FIL_CHECK_LAUNCH_W(who);
           return FIL_OK;
         }))

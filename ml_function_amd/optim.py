@@ -1,4 +1,4 @@
-"""Keras' Adam, Adagrad, Ftrl, SGD and RMSprop on the HIP path (include/fil.h O1, O2, O4): the optimizer the reference compiles (optimizer='adam', example/ctr_example/
+"""Keras' Adam, Adagrad, Ftrl, SGD, RMSprop, Adadelta and Adamax on the HIP path (include/fil.h O1, O2, O4, O5): the optimizer the reference compiles (optimizer='adam', example/ctr_example/
 un_seq.py:61; TF 2.1), with Keras' names, defaults and numerics.
 
     opt = optim.Adam(model.parameters())                    # learning_rate 1e-3, beta_1 0.9, beta_2 0.999, epsilon 1e-7
@@ -57,6 +57,13 @@ its sweep walks every non-frozen field of every runs table (rms alone on the unr
 SGD with momentum == 0 has no slot at all: its state holds no tensors and its launches carry NULL slots.  RMSprop(centered=True)
 raises NotImplementedError (a third slot, which the descriptors and the runs entry points do not carry).
 
+Adadelta and Adamax (tf.keras.optimizers.Adadelta / Adamax, TF 2.1; O5) take that contract as well, both row-local with two slots
+(accum_grad / accum_var; m / v).  Adadelta reads no step and is bit-exact.  Adamax' step size c = lr / (1 - beta_1^t), t = iterations
++ 1, is formed on the device at the top of every launch from the step counter and the step's rate (a float, a schedule's word, or
+decay=), so a captured step takes each replay's own coefficient; beta_1^t is the device's powf, as in Adam, so it is Keras-exact
+within Adam's bars rather than bit-exact.  Nadam is not offered: its sparse apply decays m and v over the whole variable and carries
+a running momentum-cache product -- Adam's shape, not a row rule's.
+
 Only fp32 parameters on a GPU are supported: anything else raises (there is no CPU / eager fallback).
 """
 import ctypes
@@ -68,8 +75,8 @@ from torch.utils.weak import WeakIdKeyDictionary
 
 from . import _lib, schedules
 from ._lib import (FIL_ADAM_KERAS, FIL_ADAM_LAZY, FIL_ADAM_ROLL_FLUSH, FIL_ADAM_ROLL_SKIP, FIL_ADAM_ROLL_STEP, FIL_MOMOPT_NESTEROV,
-                   FIL_OPT_ADAGRAD, FIL_OPT_FTRL, FIL_OPT_RMSPROP, FIL_OPT_SGD, FilError, MomoptHyper, RowoptHyper, check, ptr,
-                   stream_ptr)
+                   FIL_OPT_ADADELTA, FIL_OPT_ADAGRAD, FIL_OPT_ADAMAX, FIL_OPT_FTRL, FIL_OPT_RMSPROP, FIL_OPT_SGD, AdaoptHyper, FilError,
+                   MomoptHyper, RowoptHyper, check, ptr, stream_ptr)
 
 
 class _Desc(ctypes.Structure):
@@ -676,7 +683,7 @@ class _Rowwise(_RunsOptimizer):
     runs tables: fil_embed_rowopt_runs (or, data parallel, fil_embed_runs_compact + dp.exchange_runs + fil_embed_rowopt_merged),
     then fil_embed_rowopt_sweep over the untouched rows of the regularised fields only.  Row stamps exist only for tables with a
     regularised field.  SGD and RMSprop (O4) take the same calls at their own entry points (_ENTRY: the O4 argument lists are O2's),
-    RMSprop with momentum == 0 with a sweep, hence stamps, for every table (_sweeps)."""
+    RMSprop with momentum == 0 with a sweep, hence stamps, for every table (_sweeps); Adadelta and Adamax (O5) likewise."""
     _RULE = None
     _ENTRY = ("fil_rowopt_multi", "fil_embed_rowopt_runs", "fil_embed_rowopt_sweep", "fil_embed_rowopt_merged")
 
@@ -877,6 +884,68 @@ class RMSprop(_Rowwise):
         return MomoptHyper(_float_rate(group), group["epsilon"], group["rho"], momentum, 0, 0), lr_dev
 
 
+_ADAOPT_ENTRY = ("fil_adaopt_multi", "fil_embed_adaopt_runs", "fil_embed_adaopt_sweep", "fil_embed_adaopt_merged")
+
+
+class Adadelta(_Rowwise):
+    """tf.keras.optimizers.Adadelta (TF 2.1; ApplyAdadelta / SparseApplyAdadelta, one rule for both): accum_grad = accum_grad rho +
+    g^2 (1 - rho); upd = sqrt(accum_var + epsilon) / sqrt(accum_grad + epsilon) g; p -= lr upd; accum_var = accum_var rho + upd^2
+    (1 - rho) (include/fil.h O5 has the rounding), with Keras' defaults (learning_rate 1e-3 and epsilon 1e-7, where
+    torch.optim.Adadelta has 1.0 and 1e-6).  Slots: `accum_grad` and `accum_var` (zeros).  Runs tables (SparseEmbed(grad_mode="runs"))
+    take Keras' per-field semantics in place: the batch's rows, plus every other row of a field with l2(emb_reg) > 0 (g = 2 emb_reg p);
+    an untouched row of an unregularised field keeps its bits, its slots' too.  Reads no step: bit-exact.  process_group /
+    force_exchange / decay / schedules: as optim.Adam's."""
+    _NAME = "optim.Adadelta"
+    _RULE = FIL_OPT_ADADELTA
+    _ENTRY = _ADAOPT_ENTRY
+    _SLOTS = ("accum_grad", "accum_var")
+
+    def __init__(self, params, learning_rate=0.001, rho=0.95, epsilon=1e-7, process_group=None, force_exchange=False, decay=0.0):
+        if epsilon is None:
+            epsilon = 1e-7              # Keras: backend.epsilon()
+        learning_rate, decay = _check_rate("Adadelta", learning_rate, decay)
+        if not 0.0 <= rho <= 1.0 or not epsilon >= 0.0:
+            raise ValueError("Adadelta: rho=%r epsilon=%r (rho in [0, 1], epsilon >= 0)" % (rho, epsilon))
+        super().__init__(params, dict(learning_rate=learning_rate, rho=float(rho), epsilon=float(epsilon), **_decay_entry(decay)),
+                         process_group, force_exchange)
+
+    def _slot_init(self, group):
+        return 0.0, 0.0
+
+    def _hyper(self, group, lr_dev=None):
+        return AdaoptHyper(_float_rate(group), group["rho"], 0.0, 0.0, group["epsilon"]), lr_dev
+
+
+class Adamax(_Rowwise):
+    """tf.keras.optimizers.Adamax (TF 2.1; ApplyAdaMax, and adamax.py's Python for IndexedSlices): m = beta_1 m + (1 - beta_1) g;
+    v = max(beta_2 v, |g|); p -= c m / (v + epsilon) with c = lr / (1 - beta_1^t), t = iterations + 1 (include/fil.h O5 has the two
+    roundings).  Slots: `m` and `v` (zeros).  Row-local, unlike Keras' Adam: runs tables take the batch's rows, plus every other row of
+    a field with l2(emb_reg) > 0 (g = 2 emb_reg p); an untouched row of an unregularised field keeps its bits, its slots' too.  c is
+    formed on the device in every launch, from the step counter and the step's rate, so schedules, decay= and captured steps work as
+    for the other optimizers; beta_1^t is the device's powf: Keras-exact within optim.Adam's bars.  process_group / force_exchange /
+    decay / schedules: as optim.Adam's."""
+    _NAME = "optim.Adamax"
+    _RULE = FIL_OPT_ADAMAX
+    _ENTRY = _ADAOPT_ENTRY
+    _SLOTS = ("m", "v")
+
+    def __init__(self, params, learning_rate=0.001, beta_1=0.9, beta_2=0.999, epsilon=1e-7, process_group=None, force_exchange=False,
+                 decay=0.0):
+        if epsilon is None:
+            epsilon = 1e-7              # Keras: backend.epsilon()
+        learning_rate, decay = _check_rate("Adamax", learning_rate, decay)
+        if not 0.0 <= beta_1 < 1.0 or not 0.0 <= beta_2 < 1.0 or not epsilon >= 0.0:
+            raise ValueError("Adamax: beta_1=%r beta_2=%r epsilon=%r (betas in [0, 1), epsilon >= 0)" % (beta_1, beta_2, epsilon))
+        super().__init__(params, dict(learning_rate=learning_rate, beta_1=float(beta_1), beta_2=float(beta_2), epsilon=float(epsilon),
+                                      **_decay_entry(decay)), process_group, force_exchange)
+
+    def _slot_init(self, group):
+        return 0.0, 0.0
+
+    def _hyper(self, group, lr_dev=None):
+        return AdaoptHyper(_float_rate(group), 0.0, group["beta_1"], group["beta_2"], group["epsilon"]), lr_dev
+
+
 def _rule_merged(entry, rule, ids, values, counts, W, cap, offsets, field_l2, table, slot0, slot1, stamp, step, hyper):
     V, K = table.shape
     check(getattr(_lib.load(), entry)(ptr(ids), ptr(values), ptr(counts), int(W), int(cap), K, ptr(offsets), ptr(field_l2),
@@ -888,6 +957,12 @@ def momopt_merged(rule, ids, values, counts, W, cap, offsets, field_l2, table, s
     """fil_embed_momopt_merged on W gathered lists (ids [W*cap], values [W*cap*K], counts [W]); table / slot0 / slot1 [V, K] in place
     (a slot the variant lacks: None); rule FIL_OPT_SGD or FIL_OPT_RMSPROP, hyper an _lib.MomoptHyper."""
     _rule_merged("fil_embed_momopt_merged", rule, ids, values, counts, W, cap, offsets, field_l2, table, slot0, slot1, stamp, step, hyper)
+
+
+def adaopt_merged(rule, ids, values, counts, W, cap, offsets, field_l2, table, slot0, slot1, stamp, step, hyper):
+    """fil_embed_adaopt_merged on W gathered lists (ids [W*cap], values [W*cap*K], counts [W]); table / slot0 / slot1 [V, K] in place;
+    rule FIL_OPT_ADADELTA or FIL_OPT_ADAMAX, hyper an _lib.AdaoptHyper."""
+    _rule_merged("fil_embed_adaopt_merged", rule, ids, values, counts, W, cap, offsets, field_l2, table, slot0, slot1, stamp, step, hyper)
 
 
 def rowopt_merged(rule, ids, values, counts, W, cap, offsets, field_l2, table, accum, linear, stamp, step, hyper):
