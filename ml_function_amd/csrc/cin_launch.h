@@ -41,6 +41,9 @@ void cin_launch_dz3_sym(hipStream_t st, int MB, int JT, int NHMAX, dim3 grid, co
 inline int cin_gcd(int a, int b) { return b == 0 ? a : cin_gcd(b, a % b); }
 inline int cin_dz_tiles_per_period(int JT) { return JT / cin_gcd(16, JT); }
 inline int cin_dz_h_per_period(int JT) { return 16 * cin_dz_tiles_per_period(JT) / JT; }
+// tiles of a layer's weights in the dZ kernel's slot order: whole periods over its nh input maps, and one tile past the end
+inline int cin_dz_periods(int nh, int JT) { return (nh + cin_dz_h_per_period(JT) - 1) / cin_dz_h_per_period(JT); }
+inline int cin_slot_tiles(int nh, int JT) { return cin_dz_periods(nh, JT) * cin_dz_tiles_per_period(JT) + 1; }
 
 // LDS field rows of the symmetric dZ kernel: h + 2j + half stays below F + rows for every (padded) slot
 inline int cin_dz_sym_rows(int F, int JT) { return F > cin_dz_h_per_period(JT) + 2 * JT ? F : cin_dz_h_per_period(JT) + 2 * JT; }
