@@ -32,8 +32,8 @@ __global__ __launch_bounds__(256) void score_add_sigmoid_bwd_kernel(const float*
 }
 
 // loss = mean_i -(y log(pc + eps) + (1-y) log(1 - pc + eps)), pc = clip(p, eps, 1-eps);  dp[i] = d loss / d p[i] (0 where the clip
-// is active, as the gradient of clip_by_value is).  One workgroup: thread t sums i = t, t + 1024, ... in order, the 1024 sums are folded by a
-// fixed tree -- bit-identical repeats.
+// is active or p[i] is NaN, as the gradient of clip_by_value is; a NaN in p or y makes the loss NaN).  One workgroup: thread t sums
+// i = t, t + 1024, ... in order, the 1024 sums are folded by a fixed tree -- bit-identical repeats.
 __global__ __launch_bounds__(1024) void bce_mean_fwd_kernel(const float* __restrict__ p, const float* __restrict__ y, float eps,
                                                             float* __restrict__ loss, float* __restrict__ dp, int n) {
   __shared__ float red[1024];
@@ -41,7 +41,9 @@ __global__ __launch_bounds__(1024) void bce_mean_fwd_kernel(const float* __restr
   float t = 0.f;
   for (int i = threadIdx.x; i < n; i += 1024) {
     const float pi = p[i], yi = y[i];
-    const float pc = fminf(fmaxf(pi, eps), 1.0f - eps);
+    // (fmaxf / fminf return their other operand for a NaN: a NaN prediction must stay one, as clip_by_value leaves it, so that the loss
+    // of a diverged model is NaN; its dp is 0 below, as the gradient of the clip is)
+    const float pc = pi != pi ? pi : fminf(fmaxf(pi, eps), 1.0f - eps);
     const float u = pc + eps, v = 1.0f - pc + eps;
     t -= yi * logf(u) + (1.0f - yi) * logf(v);
     if (dp != nullptr) {

@@ -235,7 +235,11 @@ static int pdims(const char* fn, int N, int Fq, int Fk, int A, int Av, int mask_
 template <typename KernelT>
 static int pallow(KernelT kernel, size_t sh) {
   if (sh > 160 * 1024) return FIL_ERR_UNSUPPORTED;
-  if (sh > 48 * 1024) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh);
+  if (sh > 48 * 1024 &&
+      hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh) != hipSuccess) {
+    (void)hipGetLastError();
+    return FIL_ERR_HIP;
+  }
   return FIL_OK;
 }
 
@@ -251,7 +255,9 @@ extern "C" int fil_pattn_fwd(const float* q, const float* k, const float* v, con
   if (N == 0) return FIL_OK;
   FIL_CHECK_ARG(q && k && v && out);
   const size_t sh = (size_t)(d.NA + d.NV) * d.KP * kPRS * sizeof(float);
-  if (pallow(pattn_q_kernel<0>, sh) != FIL_OK) return fail(FIL_ERR_UNSUPPORTED, "fil_pattn_fwd: Fk=%d needs %zu bytes of LDS (> 160 KiB)", Fk, sh);
+  rc = pallow(pattn_q_kernel<0>, sh);
+  if (rc == FIL_ERR_HIP) return fail(FIL_ERR_HIP, "fil_pattn_fwd: the opt-in to %zu bytes of dynamic LDS was refused", sh);
+  if (rc != FIL_OK) return fail(FIL_ERR_UNSUPPORTED, "fil_pattn_fwd: Fk=%d needs %zu bytes of LDS (> 160 KiB)", Fk, sh);
   ProfScope ps("pattn_fwd", (hipStream_t)stream, (double)N * 2.0 * Fq * (double)Fk * (A + Av));
   hipLaunchKernelGGL(pattn_q_kernel<0>, dim3(N), dim3(256), sh, (hipStream_t)stream, q, k, v, mask, nullptr, out, d, scale);
   FIL_CHECK_LAUNCH();
@@ -267,8 +273,9 @@ extern "C" int fil_pattn_bwd(const float* q, const float* k, const float* v, con
   FIL_CHECK_ARG(q && k && v && dout && dq && dk && dv);
   const size_t sh1 = (size_t)(d.NA + d.NV) * d.KP * kPRS * sizeof(float);
   const size_t sh2 = (size_t)(d.NA + d.NV) * d.QP * kPRS * sizeof(float);
+  if (sh1 > 160 * 1024 || sh2 > 160 * 1024) return fail(FIL_ERR_UNSUPPORTED, "fil_pattn_bwd: Fq=%d Fk=%d need more than 160 KiB of LDS", Fq, Fk);
   if (pallow(pattn_q_kernel<1>, sh1) != FIL_OK || pallow(pattn_bwd_kv_kernel, sh2) != FIL_OK)
-    return fail(FIL_ERR_UNSUPPORTED, "fil_pattn_bwd: Fq=%d Fk=%d need more than 160 KiB of LDS", Fq, Fk);
+    return fail(FIL_ERR_HIP, "fil_pattn_bwd: the opt-in to %zu / %zu bytes of dynamic LDS was refused", sh1, sh2);
   ProfScope ps("pattn_bwd", (hipStream_t)stream, (double)N * 2.0 * Fq * (double)Fk * (4.0 * A + 4.0 * Av));
   hipLaunchKernelGGL(pattn_q_kernel<1>, dim3(N), dim3(256), sh1, (hipStream_t)stream, q, k, v, mask, dout, dq, d, scale);
   FIL_CHECK_LAUNCH();

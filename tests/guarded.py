@@ -1,6 +1,6 @@
 """Poisoned inputs and guarded outputs for tests that call the C ABI directly on flat tensors (tests/test_fm_edges_gpu.py,
-tests/test_dcn_edges_gpu.py).  Every payload starts 16-byte aligned: an input at the start of its allocation with TAIL words of the payload
-NaN behind it (a read past the end turns up in the results), an output GUARD_BYTES into a sentinel-filled allocation whose words in front
+tests/test_dcn_edges_gpu.py, tests/test_head_edges_gpu.py, tests/test_pattn_edges_gpu.py).  Every payload starts 16-byte aligned: an input at
+the start of its allocation with TAIL words of the payload NaN behind it (a read past the end turns up in the results), an output GUARD_BYTES into a sentinel-filled allocation whose words in front
 of and behind the payload must hold the sentinel's bits after the call.  Words are uint32 (fp32) or uint16 (bf16)."""
 import numpy as np
 import torch
@@ -49,3 +49,13 @@ def workspace(nbytes):
 
 def assert_workspace_guard(ws, nbytes, what):
     assert (ws[nbytes:].cpu().numpy() == WS_FILL).all(), "%s: a store behind the workspace's %d bytes" % (what, nbytes)
+
+
+def bf16_words(a):
+    """fp32 values -> their bf16 words, rounded to nearest even (exact where the values are bf16 values already)."""
+    return torch.tensor(np.ascontiguousarray(a, dtype=np.float32)).bfloat16().view(torch.int16).numpy().view(np.uint16).copy()
+
+
+def words_f32(words):
+    """The fp32 values that uint32 (fp32) or uint16 (bf16) words stand for."""
+    return words.view(np.float32) if words.dtype == np.uint32 else (words.astype(np.uint32) << 16).view(np.float32)
