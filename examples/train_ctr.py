@@ -73,14 +73,15 @@ def main():
                     help="XDeepFM only: bf16 = the CIN's labelled bf16 training mode (one bf16 MFMA per product in its three GEMM "
                          "launches, ~1e-3 relative error); f32 = the exact chain")
     ap.add_argument("--optimizer", default="torch", choices=["torch", "keras", "keras-lazy", "keras-adagrad", "keras-ftrl", "keras-sgd", "keras-rmsprop",
-                                                                     "keras-adadelta", "keras-adamax"],
+                                                                     "keras-adadelta", "keras-adamax", "keras-nadam"],
                     help="torch = torch.optim.Adam on dense table gradients; keras = ml_function_amd.optim.Adam (Keras' epsilon placement), "
                          "on one GPU with the tables updated in place from the batch's gradient runs (tableGrad='runs'); keras-lazy = the "
                          "same with LazyAdam tables (only touched rows change: a labelled deviation from the reference); keras-adagrad / "
                          "keras-ftrl = ml_function_amd.optim.Adagrad / Ftrl (Keras' defaults and semantics, the tables in place as for "
                          "keras; Ftrl's strengths: --ftrl-*); keras-sgd / keras-rmsprop = ml_function_amd.optim.SGD / RMSprop (--momentum, "
                          "--nesterov, --rho; RMSprop without momentum is what Keras' optimizer='rmsprop' builds); keras-adadelta / keras-adamax = "
-                         "ml_function_amd.optim.Adadelta / Adamax (--rho; --beta-1, --beta-2).  Data parallel: the tables keep their dense gradients and the sparse row "
+                         "ml_function_amd.optim.Adadelta / Adamax (--rho; --beta-1, --beta-2); keras-nadam = ml_function_amd.optim.Nadam (--beta-1, "
+                         "--beta-2, --schedule-decay; like Keras' it takes no schedule and no decay).  Data parallel: the tables keep their dense gradients and the sparse row "
                          "exchange unless --dp-tables runs")
     ap.add_argument("--dp-tables", default="dense", choices=["dense", "runs"],
                     help="data parallel with --optimizer keras*: runs = the tables take tableGrad='runs' and the optimizer's runs "
@@ -98,8 +99,9 @@ def main():
     ap.add_argument("--momentum", type=float, default=0.0, help="--optimizer keras-sgd / keras-rmsprop: momentum, in [0, 1]")
     ap.add_argument("--nesterov", action="store_true", help="--optimizer keras-sgd: Nesterov momentum")
     ap.add_argument("--rho", type=float, default=None, help="--optimizer keras-rmsprop / keras-adadelta: rho (Keras' defaults: 0.9 / 0.95)")
-    ap.add_argument("--beta-1", type=float, default=0.9, help="--optimizer keras-adamax: beta_1")
-    ap.add_argument("--beta-2", type=float, default=0.999, help="--optimizer keras-adamax: beta_2")
+    ap.add_argument("--beta-1", type=float, default=0.9, help="--optimizer keras-adamax / keras-nadam: beta_1")
+    ap.add_argument("--beta-2", type=float, default=0.999, help="--optimizer keras-adamax / keras-nadam: beta_2")
+    ap.add_argument("--schedule-decay", type=float, default=0.004, help="--optimizer keras-nadam: schedule_decay")
     ap.add_argument("--lr-schedule", default="none", choices=["none", "exponential", "inverse-time", "polynomial", "piecewise"],
                     help="with --optimizer keras*: a Keras learning-rate schedule (ml_function_amd.schedules) starting at --lr, evaluated "
                          "on the GPU from the optimizer's step counter -- it stays inside the captured graph.  exponential / inverse-time: "
@@ -185,6 +187,11 @@ def main():
     elif args.optimizer == "keras-adamax":      # Keras' Adamax, likewise; its step size is formed on the GPU from the step counter
         opt = optim.Adamax(model.parameters(), learning_rate=lr, beta_1=args.beta_1, beta_2=args.beta_2, epsilon=1e-7,
                            decay=args.lr_decay)
+    elif args.optimizer == "keras-nadam":       # Keras' Nadam: m and v of every row decay at every step (one sweep), a number as rate
+        if args.lr_schedule != "none" or args.lr_decay != 0.0:
+            ap.error("--optimizer keras-nadam takes neither --lr-schedule nor --lr-decay (Keras' Nadam refuses both)")
+        opt = optim.Nadam(model.parameters(), learning_rate=lr, beta_1=args.beta_1, beta_2=args.beta_2, epsilon=1e-7,
+                          schedule_decay=args.schedule_decay)
     elif args.optimizer == "keras-ftrl":        # Keras' Ftrl, likewise
         opt = optim.Ftrl(model.parameters(), learning_rate=lr, learning_rate_power=args.ftrl_lr_power,
                          l1_regularization_strength=args.ftrl_l1, l2_regularization_strength=args.ftrl_l2,

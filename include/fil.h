@@ -699,6 +699,56 @@ int fil_embed_adaopt_merged_lrdev(const int64_t* ids, const float* values, const
                                   const float* lr_dev, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * O6  Keras-exact Nadam (TF 2.1 keras/optimizer_v2/nadam.py), every tensor fp32, `rule` FIL_OPT_NADAM, hyper-parameters in a
+ *     fil_nadam_hyper read ON THE HOST at the call (a captured graph keeps the values it was captured with, the m_cache pointer too).
+ *     Entry points added only: the ABI version stays.  Every operation rounds to fp32 in the order written (no fused multiply-add;
+ *     correctly rounded division and square root).  Per step, computed ON THE DEVICE once per kernel from the step counter and the
+ *     momentum cache, with it = *step, t = (float)(it + 1), n = (float)(it + 2), sd = schedule_decay, cache = *m_cache (one fp32 word on
+ *     the device, 1.0 before the first step):
+ *       mt   = beta_1*(1 - 0.5*powf(0.96f, sd*t))       mt1 = beta_1*(1 - 0.5*powf(0.96f, sd*n))       msn = cache*mt      msx = msn*mt1
+ *       omm  = 1 - mt;  omsn = 1 - msn;  omsx = 1 - msx;  vden = 1 - powf(beta_2, t);  omb1 = 1 - beta_1;  omb2 = 1 - beta_2
+ *     and per element, with gradient g:
+ *       gp = g / omsn;  m = beta_1*m + omb1*g;  mp = m / omsx;  v = beta_2*v + omb2*(g*g);  vp = v / vden        m in slot0, v in slot1
+ *       mbar = omm*gp + mt1*mp;  p = p - (lr*mbar) / (sqrt(vp) + epsilon)
+ *     Keras' dense form and its IndexedSlices form round to the same bits (the products commute, and p + (-lr*mbar)/d == p -
+ *     (lr*mbar)/d), so there is ONE form.  powf is the device's: Keras-exact within optim.Adam's bars, bit-exact in m and v, and
+ *     fully bit-exact once both powers have left the coefficients (large t).  lr is the plain hyper-parameter: Keras' Nadam applies no
+ *     decay and takes no schedule, so there are no _lrdev twins.
+ *     Requires m_cache != NULL, reserved == 0, lr, epsilon, schedule_decay >= 0, beta_1 and beta_2 in [0, 1), both slots
+ *     (FIL_ERR_ARG otherwise, a NaN included).
+ *   Which rows Keras updates: m = m*beta_1 and v = v*beta_2 are assigned over the WHOLE variable, the batch's rows are scattered, so
+ *     (as RMSprop with momentum == 0, O4) a touched row takes the rule with g = run sum + 2 emb_reg p; an untouched row of a field
+ *     with emb_reg > 0 takes it with g = 2 emb_reg p; an untouched row of an unregularised field gets m *= beta_1, v *= beta_2 and
+ *     keeps the bits of p; a frozen field never changes.
+ *   fil_nadam_multi / fil_embed_nadam_runs / fil_embed_nadam_sweep / fil_embed_nadam_merged: the contracts, argument lists and errors
+ *     of their fil_momopt_* counterparts (O4): the sweep walks every non-frozen field and launches even when field_l2 is NULL; W = 1
+ *     merged is bit-identical to runs on the same record; F <= 1024, K <= 256 (FIL_ERR_UNSUPPORTED otherwise); R = 0, V = 0 or cap = 0
+ *     return FIL_OK before any pointer is looked at.  Every launch reads *m_cache and *step; fil_nadam_multi(advance = 1) ends with
+ *     ONE one-thread launch that writes *m_cache = *m_cache * mt(it) and then *step = it + 1 (with n = 0 it is the only launch).
+ */
+enum { FIL_OPT_NADAM = 7 };
+typedef struct {
+  float lr;
+  float beta_1;
+  float beta_2;
+  float epsilon;
+  float schedule_decay;
+  int32_t reserved;     /* 0 */
+  float* m_cache;       /* device, one fp32: the momentum cache (the product of the completed steps' mt) */
+} fil_nadam_hyper;      /* 32 bytes */
+int fil_nadam_multi(const fil_adam_tensor* tensors, int n, int64_t total_numel, int64_t* step, int rule, const fil_nadam_hyper* hyper,
+                    int advance, void* stream);
+int fil_embed_nadam_runs(const void* g, const int64_t* perm, const int64_t* sorted_ids, long R, int K, int g_dtype, int F,
+                         const float* field_l2, float* table, float* slot0, float* slot1, int32_t* stamp, const int64_t* step, int rule,
+                         const fil_nadam_hyper* hyper, void* stream);
+int fil_embed_nadam_sweep(float* table, float* slot0, float* slot1, const int32_t* stamp, int64_t V, int K, const int64_t* offsets,
+                          const float* field_l2, const unsigned char* frozen, int F, const int64_t* step, int rule,
+                          const fil_nadam_hyper* hyper, void* stream);
+int fil_embed_nadam_merged(const int64_t* ids, const float* values, const int64_t* counts, int W, long cap, int K, const int64_t* offsets,
+                           const float* field_l2, int F, float* table, float* slot0, float* slot1, int32_t* stamp, int64_t V,
+                           const int64_t* step, int rule, const fil_nadam_hyper* hyper, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * M1  Keras' streaming AUC (TF 2.1 keras/metrics.py: AUC; keras/utils/metrics_utils.py: update_confusion_matrix_variables) --
  *     replaces metrics=[tf.keras.metrics.AUC()] of example/ctr_example/un_seq.py:61.  Entry points added only: the ABI version stays.
  *   State: cm [4][T] fp32 = TP | FP | TN | FN per threshold, as Keras keeps them, and one int64 `invalid`.

@@ -32,6 +32,7 @@ FIL_OPT_ADAGRAD, FIL_OPT_FTRL = 1, 2
 FIL_OPT_SGD, FIL_OPT_RMSPROP = 3, 4
 FIL_MOMOPT_NESTEROV = 1
 FIL_OPT_ADADELTA, FIL_OPT_ADAMAX = 5, 6
+FIL_OPT_NADAM = 7
 FIL_CONFUSION_MAX_T, FIL_CONFUSION_ONE_LAUNCH_N = 2048, 16384
 
 _c = ctypes
@@ -138,6 +139,11 @@ SIGNATURES = {
     "fil_embed_adaopt_runs_lrdev": (_I, [_P, _P, _P, _c.c_long, _I, _I, _I, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P]),
     "fil_embed_adaopt_sweep_lrdev": (_I, [_P, _P, _P, _P, _c.c_int64, _I, _P, _P, _P, _I, _P, _I, _P, _P, _P]),
     "fil_embed_adaopt_merged_lrdev": (_I, [_P, _P, _P, _I, _c.c_long, _I, _P, _P, _I, _P, _P, _P, _P, _c.c_int64, _P, _I, _P, _P, _P]),
+    # O6: Nadam -- the argument lists of the O4 entry points, with a fil_nadam_hyper; no _lrdev twins
+    "fil_nadam_multi": (_I, [_P, _I, _c.c_int64, _P, _I, _P, _I, _P]),
+    "fil_embed_nadam_runs": (_I, [_P, _P, _P, _c.c_long, _I, _I, _I, _P, _P, _P, _P, _P, _P, _I, _P, _P]),
+    "fil_embed_nadam_sweep": (_I, [_P, _P, _P, _P, _c.c_int64, _I, _P, _P, _P, _I, _P, _I, _P, _P]),
+    "fil_embed_nadam_merged": (_I, [_P, _P, _P, _I, _c.c_long, _I, _P, _P, _I, _P, _P, _P, _P, _c.c_int64, _P, _I, _P, _P]),
     "fil_confusion_workspace_bytes": (_Z, [_I, _I]),
     "fil_confusion_update": (_I, [_P, _P, _I, _P, _I, _P, _P, _P, _Z, _P]),
     "fil_auc_result": (_I, [_P, _I, _I, _I, _P, _P]),
@@ -163,6 +169,15 @@ class AdaoptHyper(_c.Structure):
 
 
 assert _c.sizeof(AdaoptHyper) == 20
+
+
+class NadamHyper(_c.Structure):
+    """fil_nadam_hyper (include/fil.h O6); m_cache: the device address of the momentum cache word"""
+    _fields_ = [("lr", _F), ("beta_1", _F), ("beta_2", _F), ("epsilon", _F), ("schedule_decay", _F), ("reserved", _c.c_int32),
+                ("m_cache", _P)]
+
+
+assert _c.sizeof(NadamHyper) == 32
 
 FIL_LR_CONSTANT, FIL_LR_EXPONENTIAL, FIL_LR_INVERSE_TIME, FIL_LR_POLYNOMIAL, FIL_LR_PIECEWISE = 0, 1, 2, 3, 4
 FIL_LR_MAX_BOUNDARIES = 32

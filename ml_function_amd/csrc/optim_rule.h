@@ -1,4 +1,5 @@
-// The row-rule optimizers (optim_rowwise.hip: Adagrad, Ftrl; optim_momentum.hip: SGD, RMSprop; optim_adaptive.hip: Adadelta, Adamax),
+// The row-rule optimizers (optim_rowwise.hip: Adagrad, Ftrl; optim_momentum.hip: SGD, RMSprop; optim_adaptive.hip: Adadelta, Adamax;
+// optim_nadam.hip: Nadam),
 // each kernel shape and each host launcher written once on the walks of optim_rows.h.  A rule is a row-local per-element update whose
 // coefficients do not depend on the step, or (kStepped) depend on it through one wave-uniform prepare() per kernel (Adam's sweep is not
 // row-local: optim.hip stays apart); its file supplies a Rule per variant and one Family:
@@ -7,6 +8,8 @@
 //           kSweepAll                    the sweep walks every non-frozen field, an unstamped row of an unregularised one takes decay()
 //           elem<kTouched>(p, s, z, g, h)  one element, contraction off; kTouched: the row came with the batch (the Sparse op's form)
 //           decay(s, h)                  -> the decayed first slot; only where kSweepAll
+//           kDecayZ, decay_z(z, h)       opt-in (a rule without the member decays its first slot only), only where kSweepAll: a decay-only
+//                                        row decays the second slot too -- one more 16-byte load and non-temporal store beside S's
 //           kStepped, prepare(h, it)     opt-in (a rule without the member is not stepped): every kernel replaces its hyper-parameters by
 //                                        prepare(h, *step) once at its top, after the device rate has replaced lr -- `it` is the count of
 //                                        completed steps (Keras' iterations), the same in every launch of a step: the counter advances last
@@ -16,6 +19,8 @@
 //           device(raw)                  -> Hyper
 //           check_slots(who, var, s, z)  reports a slot the variant needs and did not get
 //           dispatch(var, f)             returns f(Rule{}) of the variant's Rule
+//           advance(step, raw, stream)   opt-in (a family without the member advances the counter with launch_step_advance): the ONE
+//                                        one-thread launch that ends a step, for a family that keeps device state beside the counter
 // The bytes a launch is charged for count 8 per element and array: the parameter and the slots the rule has.
 #pragma once
 #include "common.h"
@@ -32,6 +37,16 @@ template <typename Rule, typename = void>
 struct rule_stepped : std::false_type {};
 template <typename Rule>
 struct rule_stepped<Rule, std::void_t<decltype(Rule::kStepped)>> : std::bool_constant<Rule::kStepped> {};
+
+template <typename Rule, typename = void>
+struct rule_decays_z : std::false_type {};
+template <typename Rule>
+struct rule_decays_z<Rule, std::void_t<decltype(Rule::kDecayZ)>> : std::bool_constant<Rule::kDecayZ> {};
+
+template <typename Fam, typename = void>
+struct family_advances : std::false_type {};
+template <typename Fam>
+struct family_advances<Fam, std::void_t<decltype(&Fam::advance)>> : std::true_type {};
 
 // the top of every kernel: the step's rate, then the step's coefficients (nothing is read or computed for a rule that is not stepped)
 template <typename Rule>
@@ -90,8 +105,9 @@ __global__ __launch_bounds__(256) void embed_rule_runs_kernel(const GT* __restri
 // ---- the sweep: the untouched rows that move.  The grid strides over the virtual rows of the sweep's field table (RegTab,
 // optim_rows.h): the regularised, non-frozen fields, whose unstamped rows take the dense rule with g = 2 l2 p; with kSweepAll every
 // non-frozen field, where an unstamped row of an unregularised field takes decay() and nothing but its first slot is read or written
-// (one 16-byte load and one non-temporal 16-byte store per lane).  The branch is uniform per row (K / 4 neighbouring lanes).  The
-// grid is sized by the table (no data-dependent size: capturable); workgroups past the walked rows leave at once.
+// (one 16-byte load and one non-temporal 16-byte store per lane; with kDecayZ the same for its second slot).  The branch is uniform
+// per row (K / 4 neighbouring lanes).  The grid is sized by the table (no data-dependent size: capturable); workgroups past the
+// walked rows leave at once.
 template <typename Rule>
 __global__ __launch_bounds__(256) void embed_rule_sweep_kernel(float* __restrict__ table, float* __restrict__ S, float* __restrict__ Z,
                                                                const int32_t* __restrict__ stamp, int64_t V, int K,
@@ -117,6 +133,12 @@ __global__ __launch_bounds__(256) void embed_rule_sweep_kernel(float* __restrict
       if constexpr (kAll) {
         if (l2x2 == 0.f) {                          // decay only
           f32x4 s = *reinterpret_cast<const f32x4*>(S + e);
+          if constexpr (rule_decays_z<Rule>::value) {  // both loads in flight before either store
+            f32x4 z = *reinterpret_cast<const f32x4*>(Z + e);
+#pragma unroll
+            for (int i = 0; i < 4; ++i) z[i] = Rule::decay_z(z[i], h);
+            __builtin_nontemporal_store(z, reinterpret_cast<f32x4*>(Z + e));
+          }
 #pragma unroll
           for (int i = 0; i < 4; ++i) s[i] = Rule::decay(s[i], h);
           __builtin_nontemporal_store(s, reinterpret_cast<f32x4*>(S + e));
@@ -149,6 +171,7 @@ __global__ __launch_bounds__(256) void embed_rule_sweep_kernel(float* __restrict
     if constexpr (kAll) {
       if (t.l2x2[c] == 0.f) {
         __builtin_nontemporal_store(Rule::decay(S[e], h), S + e);
+        if constexpr (rule_decays_z<Rule>::value) __builtin_nontemporal_store(Rule::decay_z(Z[e], h), Z + e);
         continue;
       }
     }
@@ -209,7 +232,8 @@ int rule_multi_launch(const char* who, const fil_adam_tensor* tensors, int n, in
       return rc;
   }
   if (advance) {
-    launch_step_advance(step, st);
+    if constexpr (family_advances<Fam>::value) Fam::advance(step, *hyper, st);
+    else launch_step_advance(step, st);
     FIL_CHECK_LAUNCH_W(who);
   }
   return FIL_OK;

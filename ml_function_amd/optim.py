@@ -1,4 +1,4 @@
-"""Keras' Adam, Adagrad, Ftrl, SGD, RMSprop, Adadelta and Adamax on the HIP path (include/fil.h O1, O2, O4, O5): the optimizer the reference compiles (optimizer='adam', example/ctr_example/
+"""Keras' Adam, Adagrad, Ftrl, SGD, RMSprop, Adadelta, Adamax and Nadam on the HIP path (include/fil.h O1, O2, O4, O5, O6): the optimizer the reference compiles (optimizer='adam', example/ctr_example/
 un_seq.py:61; TF 2.1), with Keras' names, defaults and numerics.
 
     opt = optim.Adam(model.parameters())                    # learning_rate 1e-3, beta_1 0.9, beta_2 0.999, epsilon 1e-7
@@ -61,8 +61,15 @@ Adadelta and Adamax (tf.keras.optimizers.Adadelta / Adamax, TF 2.1; O5) take tha
 (accum_grad / accum_var; m / v).  Adadelta reads no step and is bit-exact.  Adamax' step size c = lr / (1 - beta_1^t), t = iterations
 + 1, is formed on the device at the top of every launch from the step counter and the step's rate (a float, a schedule's word, or
 decay=), so a captured step takes each replay's own coefficient; beta_1^t is the device's powf, as in Adam, so it is Keras-exact
-within Adam's bars rather than bit-exact.  Nadam is not offered: its sparse apply decays m and v over the whole variable and carries
-a running momentum-cache product -- Adam's shape, not a row rule's.
+within Adam's bars rather than bit-exact.
+
+Nadam (tf.keras.optimizers.Nadam, TF 2.1; O6) takes the contract too, although it is not row-local: its sparse apply decays m and v
+over the whole variable, so -- like RMSprop with momentum == 0 -- its sweep walks every non-frozen field of every runs table (m and v
+alone on the unregularised ones) and every such table has row stamps.  Its running momentum-cache product is one fp32 word per
+device beside the step counter (`momentum_cache`), read by every launch and multiplied by the step's momentum in the launch that
+advances the counter, so a captured step moves both on every replay.  The step's coefficients are formed on the device from the two
+words; its powers are the device's powf, so it is Keras-exact within Adam's bars, bit-exact in m and v.  Keras' Nadam takes neither a
+schedule nor decay=, and neither does this one.
 
 Only fp32 parameters on a GPU are supported: anything else raises (there is no CPU / eager fallback).
 """
@@ -75,8 +82,8 @@ from torch.utils.weak import WeakIdKeyDictionary
 
 from . import _lib, schedules
 from ._lib import (FIL_ADAM_KERAS, FIL_ADAM_LAZY, FIL_ADAM_ROLL_FLUSH, FIL_ADAM_ROLL_SKIP, FIL_ADAM_ROLL_STEP, FIL_MOMOPT_NESTEROV,
-                   FIL_OPT_ADADELTA, FIL_OPT_ADAGRAD, FIL_OPT_ADAMAX, FIL_OPT_FTRL, FIL_OPT_RMSPROP, FIL_OPT_SGD, AdaoptHyper, FilError,
-                   MomoptHyper, RowoptHyper, check, ptr, stream_ptr)
+                   FIL_OPT_ADADELTA, FIL_OPT_ADAGRAD, FIL_OPT_ADAMAX, FIL_OPT_FTRL, FIL_OPT_NADAM, FIL_OPT_RMSPROP, FIL_OPT_SGD, AdaoptHyper,
+                   FilError, MomoptHyper, NadamHyper, RowoptHyper, check, ptr, stream_ptr)
 
 
 class _Desc(ctypes.Structure):
@@ -317,8 +324,9 @@ class _RunsOptimizer(torch.optim.Optimizer):
         """The initial values of the _SLOTS of a parameter in `group`."""
         raise NotImplementedError
 
-    def _hyper(self, group, lr_dev=None):
-        """The group's hyper-parameters; lr_dev: the device word holding the step's rate (a schedule / decay), else by value."""
+    def _hyper(self, group, lr_dev=None, dev=None):
+        """The group's hyper-parameters; lr_dev: the device word holding the step's rate (a schedule / decay), else by value; dev: the
+        device of the launches that will take them (for a rule that keeps a device word of its own there; the others ignore it)."""
         raise NotImplementedError
 
     def _launch_dense(self, lib, desc, n, numel, t, hyper, advance):
@@ -401,7 +409,7 @@ class _RunsOptimizer(torch.optim.Optimizer):
             for p in group["params"]:
                 hyper = hypers.get(p.device)
                 if hyper is None:
-                    hyper = hypers[p.device] = self._hyper(group, rate.get(p.device) if rate else None)
+                    hyper = hypers[p.device] = self._hyper(group, rate.get(p.device) if rate else None, p.device)
                 pend = getattr(p, "_fil_pending_runs", None)
                 if pend is None and p.grad is None:
                     self._skip(p, hyper)        # (Keras filters None gradients)
@@ -439,7 +447,7 @@ class _RunsOptimizer(torch.optim.Optimizer):
             last[dev] = i
         for dev in devs:
             if dev not in last:
-                calls.append((dev, self._hyper(dict(self.defaults, learning_rate=_float_rate(self.defaults))), []))  # (reads no rate)
+                calls.append((dev, self._hyper(dict(self.defaults, learning_rate=_float_rate(self.defaults)), None, dev), []))  # (reads no rate)
                 last[dev] = len(calls) - 1
         for i, (dev, hyper, entries) in enumerate(calls):
             with torch.cuda.device(dev):
@@ -572,7 +580,7 @@ class Adam(_RunsOptimizer):
     def _slot_init(self, group):
         return 0.0, 0.0
 
-    def _hyper(self, group, lr_dev=None):
+    def _hyper(self, group, lr_dev=None, dev=None):
         return group["learning_rate"] if lr_dev is None else lr_dev, group["beta_1"], group["beta_2"], group["epsilon"]
 
     def _launch_dense(self, lib, desc, n, numel, t, hyper, advance):
@@ -683,7 +691,8 @@ class _Rowwise(_RunsOptimizer):
     runs tables: fil_embed_rowopt_runs (or, data parallel, fil_embed_runs_compact + dp.exchange_runs + fil_embed_rowopt_merged),
     then fil_embed_rowopt_sweep over the untouched rows of the regularised fields only.  Row stamps exist only for tables with a
     regularised field.  SGD and RMSprop (O4) take the same calls at their own entry points (_ENTRY: the O4 argument lists are O2's),
-    RMSprop with momentum == 0 with a sweep, hence stamps, for every table (_sweeps); Adadelta and Adamax (O5) likewise."""
+    RMSprop with momentum == 0 with a sweep, hence stamps, for every table (_sweeps); Adadelta and Adamax (O5) likewise, and Nadam
+    (O6), which always sweeps."""
     _RULE = None
     _ENTRY = ("fil_rowopt_multi", "fil_embed_rowopt_runs", "fil_embed_rowopt_sweep", "fil_embed_rowopt_merged")
 
@@ -757,7 +766,7 @@ class Adagrad(_Rowwise):
         super().__init__(params, dict(learning_rate=learning_rate, initial_accumulator_value=float(initial_accumulator_value),
                                       epsilon=float(epsilon), **_decay_entry(decay)), process_group, force_exchange)
 
-    def _hyper(self, group, lr_dev=None):
+    def _hyper(self, group, lr_dev=None, dev=None):
         return RowoptHyper(_float_rate(group), group["epsilon"], 0.0, 0.0, 0.0, 0.0), lr_dev
 
 
@@ -798,7 +807,7 @@ class Ftrl(_Rowwise):
                                       **_decay_entry(decay)),
                          process_group, force_exchange)
 
-    def _hyper(self, group, lr_dev=None):
+    def _hyper(self, group, lr_dev=None, dev=None):
         return RowoptHyper(_float_rate(group), 0.0, group["learning_rate_power"], group["l1_regularization_strength"],
                            group["l2_regularization_strength"], group["l2_shrinkage_regularization_strength"]), lr_dev
 
@@ -835,7 +844,7 @@ class SGD(_Rowwise):
     def _slot_init(self, group):
         return (0.0,) * len(self._SLOTS)
 
-    def _hyper(self, group, lr_dev=None):
+    def _hyper(self, group, lr_dev=None, dev=None):
         momentum = _check_momentum(group["momentum"])
         if (momentum > 0.0) != bool(self._SLOTS):
             raise ValueError("optim.SGD: a parameter group's momentum=%r -- whether momentum is 0 is fixed at construction" % momentum)
@@ -877,7 +886,7 @@ class RMSprop(_Rowwise):
     def _sweeps(self, field_l2):
         return len(self._SLOTS) == 1 or field_l2 is not None         # momentum == 0: rms decays on every row
 
-    def _hyper(self, group, lr_dev=None):
+    def _hyper(self, group, lr_dev=None, dev=None):
         momentum = _check_momentum(group["momentum"])
         if (momentum > 0.0) != (len(self._SLOTS) == 2):
             raise ValueError("optim.RMSprop: a parameter group's momentum=%r -- whether momentum is 0 is fixed at construction" % momentum)
@@ -912,7 +921,7 @@ class Adadelta(_Rowwise):
     def _slot_init(self, group):
         return 0.0, 0.0
 
-    def _hyper(self, group, lr_dev=None):
+    def _hyper(self, group, lr_dev=None, dev=None):
         return AdaoptHyper(_float_rate(group), group["rho"], 0.0, 0.0, group["epsilon"]), lr_dev
 
 
@@ -942,8 +951,97 @@ class Adamax(_Rowwise):
     def _slot_init(self, group):
         return 0.0, 0.0
 
-    def _hyper(self, group, lr_dev=None):
+    def _hyper(self, group, lr_dev=None, dev=None):
         return AdaoptHyper(_float_rate(group), 0.0, group["beta_1"], group["beta_2"], group["epsilon"]), lr_dev
+
+
+_NADAM_ENTRY = ("fil_nadam_multi", "fil_embed_nadam_runs", "fil_embed_nadam_sweep", "fil_embed_nadam_merged")
+
+
+class Nadam(_Rowwise):
+    """tf.keras.optimizers.Nadam (TF 2.1; keras/optimizer_v2/nadam.py): with t = iterations + 1, mt = beta_1 (1 - 0.5 0.96^(schedule_decay
+    t)), mt1 the same at t + 1, and the momentum cache msn = (the product of mt over the steps so far, this one included), msx = msn mt1:
+    gp = g / (1 - msn); m = beta_1 m + (1 - beta_1) g; mp = m / (1 - msx); v = beta_2 v + (1 - beta_2) g^2; vp = v / (1 - beta_2^t);
+    p -= lr ((1 - mt) gp + mt1 mp) / (sqrt(vp) + epsilon) (include/fil.h O6 has the rounding; the dense and the IndexedSlices form are
+    the same bits).  Slots: `m` and `v` (zeros).  `momentum_cache` is the product of the completed steps' mt (1.0 before the first):
+    one fp32 word per device beside the step counter, advanced with it by the step's last launch, carried by state_dict() and put back
+    to 1.0 by reset_().  Runs tables take Keras' per-field semantics in place, and Keras decays m and v over the whole variable: an
+    untouched row of an unregularised field gets m *= beta_1, v *= beta_2 and keeps p, an untouched row of a regularised field takes
+    the rule with g = 2 emb_reg p, a frozen field changes nothing -- one sweep per table and step, over every non-frozen field.
+    learning_rate is a number: Keras' Nadam refuses a LearningRateSchedule and overwrites `decay` with schedule_decay, so there is no
+    decay= here.  beta_1 and schedule_decay are optimizer-wide (the cache has one recurrence); learning_rate, beta_2 and epsilon may
+    differ by parameter group.  The powers are the device's powf: Keras-exact within optim.Adam's bars, bit-exact in m and v.
+    process_group / force_exchange: as optim.Adam's."""
+    _NAME = "optim.Nadam"
+    _RULE = FIL_OPT_NADAM
+    _ENTRY = _NADAM_ENTRY
+    _SLOTS = ("m", "v")
+
+    def __init__(self, params, learning_rate=0.001, beta_1=0.9, beta_2=0.999, epsilon=1e-7, schedule_decay=0.004, process_group=None,
+                 force_exchange=False):
+        if epsilon is None:
+            epsilon = 1e-7              # Keras: backend.epsilon()
+        if isinstance(learning_rate, schedules.LearningRateSchedule):
+            raise ValueError("The Nadam optimizer does not support tf.keras.optimizers.LearningRateSchedules as the learning rate.")
+        if not learning_rate >= 0.0:
+            raise ValueError("Nadam: learning_rate=%r (>= 0)" % (learning_rate,))
+        if not 0.0 <= beta_1 < 1.0 or not 0.0 <= beta_2 < 1.0 or not epsilon >= 0.0 or not schedule_decay >= 0.0:
+            raise ValueError("Nadam: beta_1=%r beta_2=%r epsilon=%r schedule_decay=%r (betas in [0, 1); epsilon, schedule_decay >= 0)"
+                             % (beta_1, beta_2, epsilon, schedule_decay))
+        self._cache = {}        # device -> fp32 [1] momentum cache (Keras' _m_cache), beside the step counter
+        super().__init__(params, dict(learning_rate=float(learning_rate), beta_1=float(beta_1), beta_2=float(beta_2),
+                                      epsilon=float(epsilon), schedule_decay=float(schedule_decay)), process_group, force_exchange)
+
+    def _cache_word(self, dev):
+        c = self._cache.get(dev)
+        if c is None:
+            c = self._cache[dev] = torch.ones(1, dtype=torch.float32, device=dev)
+        return c
+
+    @property
+    def momentum_cache(self):
+        """The product of the completed steps' momenta (Keras' _m_cache), as a host float (synchronises)."""
+        return float(next(iter(self._cache.values()))[0]) if self._cache else 1.0
+
+    def _slot_init(self, group):
+        return 0.0, 0.0
+
+    def _sweeps(self, field_l2):
+        return True                     # m and v decay on every row
+
+    def _hyper(self, group, lr_dev=None, dev=None):
+        if isinstance(group["learning_rate"], schedules.LearningRateSchedule):
+            raise ValueError("The Nadam optimizer does not support tf.keras.optimizers.LearningRateSchedules as the learning rate.")
+        for k in ("beta_1", "schedule_decay"):
+            if group[k] != self.defaults[k]:
+                raise ValueError("optim.Nadam: a parameter group's %s=%r -- %s is optimizer-wide (%r): the momentum cache has one "
+                                 "recurrence" % (k, group[k], k, self.defaults[k]))
+        if dev is None and len(self._cache) == 1:
+            dev = next(iter(self._cache))
+        cache = self._cache_word(dev) if dev is not None and dev.type == "cuda" else None
+        return NadamHyper(group["learning_rate"], group["beta_1"], group["beta_2"], group["epsilon"], group["schedule_decay"], 0,
+                          ptr(cache)), None
+
+    def state_dict(self):
+        sd = super().state_dict()
+        sd["momentum_cache"] = self.momentum_cache
+        return sd
+
+    def load_state_dict(self, state_dict):
+        state_dict = dict(state_dict)
+        cache = float(state_dict.pop("momentum_cache", 1.0))
+        super().load_state_dict(state_dict)
+        for g in self.param_groups:
+            for p in g["params"]:
+                if p.device.type == "cuda":
+                    self._cache_word(p.device)
+        for c in self._cache.values():
+            c.fill_(cache)
+
+    def reset_(self):
+        super().reset_()
+        for c in self._cache.values():
+            c.fill_(1.0)
 
 
 def _rule_merged(entry, rule, ids, values, counts, W, cap, offsets, field_l2, table, slot0, slot1, stamp, step, hyper):
@@ -963,6 +1061,12 @@ def adaopt_merged(rule, ids, values, counts, W, cap, offsets, field_l2, table, s
     """fil_embed_adaopt_merged on W gathered lists (ids [W*cap], values [W*cap*K], counts [W]); table / slot0 / slot1 [V, K] in place;
     rule FIL_OPT_ADADELTA or FIL_OPT_ADAMAX, hyper an _lib.AdaoptHyper."""
     _rule_merged("fil_embed_adaopt_merged", rule, ids, values, counts, W, cap, offsets, field_l2, table, slot0, slot1, stamp, step, hyper)
+
+
+def nadam_merged(ids, values, counts, W, cap, offsets, field_l2, table, m, v, stamp, step, hyper):
+    """fil_embed_nadam_merged on W gathered lists (ids [W*cap], values [W*cap*K], counts [W]); table / m / v [V, K] in place; hyper
+    an _lib.NadamHyper (its m_cache the device address of the momentum cache word)."""
+    _rule_merged("fil_embed_nadam_merged", FIL_OPT_NADAM, ids, values, counts, W, cap, offsets, field_l2, table, m, v, stamp, step, hyper)
 
 
 def rowopt_merged(rule, ids, values, counts, W, cap, offsets, field_l2, table, accum, linear, stamp, step, hyper):
