@@ -87,6 +87,17 @@ static CinPath cin_path_of(const CinShape& s, int mode) {   // mode: the public 
   return CinPath{(mode & FIL_CIN_X_TRANSPOSED) != 0, (mode & FIL_CIN_GENERAL) != 0, tail_used(s, mode), qtail_used(s, mode, tune), qmerge_used(s, mode, tune),
                  qsplit_used(s, mode, tune), (mode & kCinPrecBf16) != 0 ? 1 : 3, tune, tail_geom(s)};
 }
+// Which form saved.R holds after a forward on the merged quadratic tail (exact mode).  True: the g-free gradient of x1,
+//   Ghat[m,:] = dw_L[k] R[m,:] + dw_p[k] S[m,:] + dw_1[k]     (dw_j[k] = dense_w[j K + k], k = m mod K, S = x wsum_p^T),
+// which the forward's epilogue holds in registers anyway; the backward's two GEMMs apply g[b] (G1 = g[b] Ghat) where they already apply a
+// per-row scale, and cin_last_bwd2_kernel's pass over R, x and G1 is gone.  False: R itself, G1 built by cin_last_bwd2_kernel.
+// It needs the Dense(1) head folded into the forward's epilogue (dense_w at hand there, dP_j = g dw_j) and the two-pass data-gradient
+// launch (its first pass scales its rows on load).  The forward and the backward both ask this function and nothing else.
+static bool cin_ghat_used(const CinShape& s, const CinPath& p, int output_dim) {
+  const bool headfold = output_dim == 1 && s.K <= 32 && (s.K & (s.K - 1)) == 0 && knobs().headfold != 0;
+  const bool dz2 = knobs().dz2 != 0 && s.HS(0) / 2 == 64;
+  return p.qmerge && p.fwdq(s) && !p.qsplit && headfold && dz2 && knobs().ghat != 0;
+}
 // precision code of the _p entry points -> the internal mode bit (FIL_OK), or FIL_ERR_ARG
 static int cin_precision_bits(const char* who, int mode, int precision, int* bits) {
   if (precision != FIL_CIN_PREC_DEFAULT && precision != FIL_CIN_PREC_BF16)
@@ -332,7 +343,7 @@ static int cin_fwd_merged_q(CinFwd& c) {
                              H[0], hf))
         return fail(FIL_ERR_UNSUPPORTED, "fil_cin_fwd: no split-bf16 forward kernel for JT=%d (F=%d)", JTs, F);
     } else if (!cin_launch_fwdq(st, JTs, ws.x2T, XL, ws.Wf, ws.WfT, c.bias[0], sv.wsnP, JT, sv.cvec, x1T, sv.R, HS0, ws.pool[0], ws.pool[p], ws.pool[lL], (int)M, F,
-                                H[0], hf))
+                                H[0], hf, cin_ghat_used(s, c.p, c.output_dim)))   // (true: the g-free G1 in R's place)
       return fail(FIL_ERR_UNSUPPORTED, "fil_cin_fwd: no merged forward kernel for JT=%d (F=%d)", JTs, F);
     c.pa.chunks[0] = c.pa.chunks[p] = c.pa.chunks[lL] = 1;
   }
@@ -606,7 +617,8 @@ static void cin_qtail_params_fill(const CinBwd& c) {
 
 // ---- quadratic tail with merged weight gradients (cin_qmerge.h): [dW1 | dT] = pairs(x)^T [G1 | dP_L x1] in ONE launch; the data
 // gradients are one two-pass launch of the pair-symmetric dZ kernel (G1 with W1, then the unscaled x1 with T, scaled by dP_L), or two
-// launches of it.  G1 = dP_p S + dP_1 + dP_L R and the shortcut's dX part come out of cin_last_bwd2_kernel.
+// launches of it.  G1 = dP_p S + dP_1 + dP_L R and the shortcut's dX part come out of cin_last_bwd2_kernel -- or, where the forward
+// saved the g-free G1 in R's place (cin_ghat_used), G1 = g Ghat is formed inside the two GEMMs and that kernel leaves the dX part alone.
 static int cin_bwd_top_merged_q(CinBwd& c) {
   const CinShape& s = c.s;
   const TailGeom& tg = c.p.tg;
@@ -629,11 +641,13 @@ static int cin_bwd_top_merged_q(CinBwd& c) {
   const int symD = F / 2 + 1, Cl = F * symD;
   const int JTs = cin_jt_sym(F);
   const int periods = cin_dz_periods(F, JTs), tiles0 = cin_slot_tiles(F, JTs);
-  const CinBwdWs::Scratch v = ws.scratch(s, true);   // xe [M][F+3]: x | 1 | dP_L | dP_p
-  float* G = ws.G[c.cur];
+  const bool ghat = cin_ghat_used(s, c.p, c.output_dim);   // saved.R holds the g-free G1: G1 = g[b] Ghat is applied by the GEMMs, ws.G stays untouched
+  const CinBwdWs::Scratch v = ws.scratch(s, true, ghat);   // xe [M][F+3]: x | 1 | dP_L | dP_p   (ghat: [M][F+4], | g)
+  const float* G = ghat ? sv.R : ws.G[c.cur];
+  const float* gsc = ghat ? c.g : nullptr;
   {
     ProfScope ps("cin_tail_a", st, (double)M * (2 * F + 3) * sizeof(float));
-    const size_t sh = (size_t)256 * (F + 3 + (c.output_dim == 1 ? L : 0)) * sizeof(float);
+    const size_t sh = (size_t)256 * (F + 3 + (c.output_dim == 1 ? L : 0) + (ghat ? 1 : 0)) * sizeof(float);
     allow_lds(cin_qtail_xe_kernel<3>, sh);
     allow_lds(cin_qtail_xe_kernel<1>, sh);
     const int np = (int)std::min<long>(((long)tiles0 * 32 * HS0 + 255) / 256, 1024);   // + W1 in the dZ kernel's slot order
@@ -642,16 +656,19 @@ static int cin_bwd_top_merged_q(CinBwd& c) {
     if (c.p.qnp == 1)
       hipLaunchKernelGGL(cin_qtail_xe_kernel<1>, dim3(c.ndc + np + nq2), dim3(kXeThreads), sh, st, xT, dPL, dPp, LK, K, v.xr, ws.dcpart, (int)M, F,
                          c.ndc, c.output_dim == 1 ? c.g : nullptr, c.dense_w, c.pooled, ws.dP, ws.hpart, LK, lL, p, c.W[0], ws.Wz, H[0], JTs, HS0, tiles0, np, sv.T,
-                         Hpp, ws.Wzb1, ws.Wzb2);
+                         Hpp, ws.Wzb1, ws.Wzb2, ghat ? 1 : 0);
     else
       hipLaunchKernelGGL(cin_qtail_xe_kernel<3>, dim3(c.ndc + np + nq2), dim3(kXeThreads), sh, st, xT, dPL, dPp, LK, K, v.xr, ws.dcpart, (int)M, F,
                          c.ndc, c.output_dim == 1 ? c.g : nullptr, c.dense_w, c.pooled, ws.dP, ws.hpart, LK, lL, p, c.W[0], ws.Wz, H[0], JTs, HS0, tiles0, np, sv.T,
-                         Hpp, ws.Wzb1, ws.Wzb2);
+                         Hpp, ws.Wzb1, ws.Wzb2, ghat ? 1 : 0);
   }
   FIL_CIN_BWD_LAUNCHED();
   {
     ProfScope ps("cin_last_bwd", st, 6.0 * (double)M * Hpp * F);
-    cin_launch_last_bwd2(st, JT, xT, xpT, xps, sv.wsumP, sv.wsnP, dPp, LK, dPprev, G, HS0, ws.dxT, (int)M, F, K, Hpp, sv.R, HS0, dPL, ws.small);
+    if (ghat)   // the shortcut's dX part alone: G1 = g Ghat needs no pass of its own
+      cin_launch_last_bwd2(st, JT, xT, xpT, xps, sv.wsumP, sv.wsnP, dPp, LK, nullptr, nullptr, HS0, ws.dxT, (int)M, F, K, Hpp);
+    else
+      cin_launch_last_bwd2(st, JT, xT, xpT, xps, sv.wsumP, sv.wsnP, dPp, LK, dPprev, ws.G[c.cur], HS0, ws.dxT, (int)M, F, K, Hpp, sv.R, HS0, dPL, ws.small);
   }
   FIL_CIN_BWD_LAUNCHED();
   int dw_parts = 0;   // partials [C][256] the weight-gradient launch leaves
@@ -663,24 +680,33 @@ static int cin_bwd_top_merged_q(CinBwd& c) {
       dw_parts = bp.splits;
     } else {
       const bool f4 = knobs().dwfold4 != 0;
-      const DwqPlan dp = f4 ? cin_dwq_plan4(M, Cl + F, cu_count()) : cin_dwq_plan(M, Cl + F, cu_count());
-      if (f4)
-        hipLaunchKernelGGL((cin_dwq_kernel<kDwqDepth, 4>), dim3((dp.wgs + 7) / 8 * 8), dim3(kDwqThreads), 0, st, G, xpT, HS0, v.xr, v.XS, ws.part, (int)M, F,
-                           symD, dp.rows_per_split, dp.splits, dp.ncol_full, dp.rem, dp.wgs_full, dp.wgs);
-      else
-        hipLaunchKernelGGL((cin_dwq_kernel<kDwqDepth, 2>), dim3((dp.wgs + 7) / 8 * 8), dim3(kDwqThreads), 0, st, G, xpT, HS0, v.xr, v.XS, ws.part, (int)M, F,
-                           symD, dp.rows_per_split, dp.splits, dp.ncol_full, dp.rem, dp.wgs_full, dp.wgs);
+      const int Cw = Cl + F + (ghat ? 1 : 0);   // (ghat: + the ones row whose first 128 columns are dbias_1 = sum_m g Ghat[m,:])
+      const DwqPlan dp = f4 ? cin_dwq_plan4(M, Cw, cu_count()) : cin_dwq_plan(M, Cw, cu_count());
+#define FIL_DWQ(FOLDV, GHV) \
+  hipLaunchKernelGGL((cin_dwq_kernel<kDwqDepth, FOLDV, GHV>), dim3((dp.wgs + 7) / 8 * 8), dim3(kDwqThreads), 0, st, G, xpT, HS0, v.xr, v.XS, ws.part, (int)M, F, \
+                     symD, dp.rows_per_split, dp.splits, dp.ncol_full, dp.rem, dp.wgs_full, dp.wgs)
+      if (ghat) {
+        if (f4) FIL_DWQ(4, true); else FIL_DWQ(2, true);
+      } else {
+        if (f4) FIL_DWQ(4, false); else FIL_DWQ(2, false);
+      }
+#undef FIL_DWQ
       dw_parts = dp.pairs;
     }
   }
   FIL_CIN_BWD_LAUNCHED();
   {
     // fixed-order sums of the partials -> dW1 (both rows of a pair), dT, v^T; + dbias1 from the column sums cin_last_bwd2_kernel left
+    // (ghat: from the ones row of the partials)
     ProfScope ps("cin_reduce_dw", st);
-    const int nb1 = cdiv(H[0], 64);
+    const int nb1 = ghat ? 0 : cdiv(H[0], 64);
     const int nh = c.output_dim == 1 ? cdiv(LK + 1, 64) : 0;   // + ddense_w | ddense_b from the head's block partials
-    hipLaunchKernelGGL(cin_reduce_expand_q_kernel, dim3((Cl + F + 3) / 4 + nb1 + nh), dim3(256), 0, st, ws.part, dw_parts, F, symD, H[0], Hpp, c.dW[0], ws.dT,
-                       ws.vlast, ws.small, c.ncol, c.dbias[0], nb1, ws.hpart, c.ndc, LK, c.ddense_w, c.ddense_b);
+    if (ghat)
+      hipLaunchKernelGGL(cin_reduce_expand_q_kernel<true>, dim3((Cl + F + 1 + 3) / 4 + nh), dim3(256), 0, st, ws.part, dw_parts, F, symD, H[0], Hpp, c.dW[0], ws.dT,
+                         ws.vlast, ws.small, c.ncol, c.dbias[0], nb1, ws.hpart, c.ndc, LK, c.ddense_w, c.ddense_b);
+    else
+      hipLaunchKernelGGL(cin_reduce_expand_q_kernel<false>, dim3((Cl + F + 3) / 4 + nb1 + nh), dim3(256), 0, st, ws.part, dw_parts, F, symD, H[0], Hpp, c.dW[0], ws.dT,
+                         ws.vlast, ws.small, c.ncol, c.dbias[0], nb1, ws.hpart, c.ndc, LK, c.ddense_w, c.ddense_b);
   }
   FIL_CIN_BWD_LAUNCHED();
   ready_next(c);   // the dense head
@@ -699,7 +725,7 @@ static int cin_bwd_top_merged_q(CinBwd& c) {
       split_done = cin_launch_dz2_b(st, c.p.qnp, JTs, G, xpT, HS0, dPL, LK, K, ws.Wzb1, ws.Wzb2, xT, ws.dxT, /*accumulate=*/1, (int)M, F, H[0], Hpp, periods, c.dx, sv.cvec);
     }
     if (!split_done &&
-        !cin_launch_dz2(st, JTs, G, xpT, HS0, dPL, LK, K, ws.Wz, sv.WzT, xT, ws.dxT, /*accumulate=*/1, (int)M, F, H[0], Hpp, periods, c.dx, sv.cvec))
+        !cin_launch_dz2(st, JTs, G, xpT, HS0, dPL, LK, K, ws.Wz, sv.WzT, xT, ws.dxT, /*accumulate=*/1, (int)M, F, H[0], Hpp, periods, c.dx, sv.cvec, gsc))
       return fail(FIL_ERR_UNSUPPORTED, "fil_cin_bwd: no two-pass data-gradient kernel for JT=%d (F=%d)", JTs, F);
     c.qm_joined = true;
   } else {

@@ -1507,6 +1507,9 @@ __global__ __launch_bounds__(256, 2) void cin_last_bwd2_kernel(const float* __re
   // Radd != nullptr (quadratic tail): G^{L-1}[m,n] += dPadd[m] * Radd[m,n] on the way out (one pass over G less)
   // colpart != nullptr: colpart[blockIdx][n < Hp] = sum over this workgroup's 128 rows of the G^{L-1} it writes (the partial
   // column sums of the next layer's dbias: cin_colsum3_kernel's output without its pass over G)
+  // GprevT == nullptr (merged quadratic tail whose forward saved the g-free G^{L-1}: cin_ghat_used): phase u alone -- no rows of x, no
+  // pass over G^{L-1}; Radd, dPprev and colpart are then not used
+  const bool do_t = GprevT != nullptr;
   __shared__ float colred[4][128];
   extern __shared__ __attribute__((aligned(16))) float smem[];  // wsum [Hp][F] | per wave: staging [kLast2Stage]
   for (int i = threadIdx.x; i < Hp * F; i += 256) smem[i] = wsum[i];
@@ -1521,7 +1524,7 @@ __global__ __launch_bounds__(256, 2) void cin_last_bwd2_kernel(const float* __re
   // The wave's 32 rows are contiguous in memory: they come in through LDS by coalesced 16-byte loads, the lanes read their rows there.
   float* stg = smem + ((Hp * F + 3) & ~3) + wave * kLast2Stage;
   const int nrow = min(32, M - wrow0);   // (<= 0: a wave past the end that only stays for the workgroup barriers)
-  if (nrow > 0) {
+  if (nrow > 0 && do_t) {
     const float4* src = reinterpret_cast<const float4*>(xT + (long)wrow0 * F);   // 32 rows x F floats = a multiple of 16 bytes from an aligned start
     const int n4 = nrow * F / 4, tail = nrow * F - 4 * n4;
     for (int i = lane; i < n4; i += 64) *reinterpret_cast<float4*>(stg + 4 * i) = src[i];
@@ -1534,7 +1537,7 @@ __global__ __launch_bounds__(256, 2) void cin_last_bwd2_kernel(const float* __re
 #pragma unroll
     for (int j = 0; j < JT; ++j) {
       const int f = 2 * j + half;
-      xr[j] = (f < F && nrow > 0) ? xrow[min(f, F - 1)] : 0.f;
+      xr[j] = (f < F && nrow > 0 && do_t) ? xrow[min(f, F - 1)] : 0.f;
     }
   }
   // the three pooled gradients of the wave's rows: lane r fetches row r's once, the store loops read them from LDS by row (48
@@ -1708,9 +1711,9 @@ __global__ __launch_bounds__(256, 2) void cin_last_bwd2_kernel(const float* __re
   // traffic around 4 JT MFMAs, u mostly its 128 MFMAs.  Every other group of eight workgroups (neighbours on an XCD, likely the two
   // resident on one CU) runs them in the other order, so the waves sharing a SIMD are not both in the MFMA-bound phase at once:
   // 38.8 -> 35.4 us (c4, one box).  The results do not depend on the order.
-  if ((blockIdx.x >> 3) & 1) {
+  if (!do_t || ((blockIdx.x >> 3) & 1)) {
     phase_u();
-    phase_t();
+    if (do_t) phase_t();
   } else {
     phase_t();
     phase_u();

@@ -61,14 +61,16 @@ static int env_int(const char* name, int dflt) {
 //   FIL_CIN_HEADFOLD=0    ... the pooled relayout + Dense(1) head as their own launch instead of the 256-column launch's epilogue
 //   FIL_CIN_PACKFOLD=0    ... T's two operand layouts by a pack launch instead of by the T workgroups themselves (exact mode)
 //   FIL_CIN_DWFOLD4=0     ... the merged weight-gradient launch folds PAIRS of row splits (4 tiles x 2 splits per workgroup) instead of quads
+//   FIL_CIN_GHAT=0        ... the forward saves R itself and cin_last_bwd2_kernel builds G1 from it, instead of the forward saving the
+//                         g-free G1 in R's place (cin_ghat_used, cin.hip)
 // Results are identical up to summation order whatever they say.  Per-call overrides for tests travel in `mode`
 // (FIL_CIN_MB2, FIL_CIN_NOSYM), not through the environment.
 struct Knobs {
-  int mb, sym, dw_mb, dw_splits, dz_mb, tail_splits, tail_settle, tail_dz_mode, ksplit, dzs_mb, qtail, qmerge, dz2, fwdq, headfold, packfold, dwfold4;
+  int mb, sym, dw_mb, dw_splits, dz_mb, tail_splits, tail_settle, tail_dz_mode, ksplit, dzs_mb, qtail, qmerge, dz2, fwdq, headfold, packfold, dwfold4, ghat;
 };
 static const Knobs& knobs() {
   static const Knobs k = {env_int("FIL_CIN_MB", 0), env_int("FIL_CIN_SYM", 1), env_int("FIL_CIN_DW_MB", 1), env_int("FIL_CIN_DW_SPLITS", 0),
-                          env_int("FIL_CIN_DZ_MB", 1), env_int("FIL_CIN_TAIL_SPLITS", 0), env_int("FIL_CIN_TAIL_SETTLE", 0), env_int("FIL_CIN_TAIL_DZ_MODE", 0), env_int("FIL_CIN_KSPLIT", -1), env_int("FIL_CIN_DZS_MB", 0), env_int("FIL_CIN_QTAIL", 1), env_int("FIL_CIN_QMERGE", 1), env_int("FIL_CIN_DZ2", 1), env_int("FIL_CIN_FWDQ", 1), env_int("FIL_CIN_HEADFOLD", 1), env_int("FIL_CIN_PACKFOLD", 1), env_int("FIL_CIN_DWFOLD4", 1)};
+                          env_int("FIL_CIN_DZ_MB", 1), env_int("FIL_CIN_TAIL_SPLITS", 0), env_int("FIL_CIN_TAIL_SETTLE", 0), env_int("FIL_CIN_TAIL_DZ_MODE", 0), env_int("FIL_CIN_KSPLIT", -1), env_int("FIL_CIN_DZS_MB", 0), env_int("FIL_CIN_QTAIL", 1), env_int("FIL_CIN_QMERGE", 1), env_int("FIL_CIN_DZ2", 1), env_int("FIL_CIN_FWDQ", 1), env_int("FIL_CIN_HEADFOLD", 1), env_int("FIL_CIN_PACKFOLD", 1), env_int("FIL_CIN_DWFOLD4", 1), env_int("FIL_CIN_GHAT", 1)};
   return k;
 }
 // per-call view of the knobs: the process defaults with the call's mode bits applied
@@ -227,7 +229,7 @@ static size_t dw_part_floats(const CinShape& s) {
   const int csym = s.F * (s.F / 2 + 1);
   pmax = std::max(pmax, (size_t)dw_plan(s.M(), csym, s.H[0]).splits * csym * s.H[0]);
   pmax = std::max(pmax, (size_t)dw_plan(s.M(), csym + s.F, s.H[0]).splits * (csym + s.F) * s.H[0]);   // quadratic tail: pairs + F single-field rows
-  if (s.L == 3) pmax = std::max(pmax, (size_t)cin_dwq_plan(s.M(), csym + s.F, cu_count()).pairs * (csym + s.F) * 256);   // ... merged: 256 columns
+  if (s.L == 3) pmax = std::max(pmax, (size_t)cin_dwq_plan(s.M(), csym + s.F + 1, cu_count()).pairs * (csym + s.F + 1) * 256);   // ... merged: 256 columns (+ the dbias_1 row)
   if (s.L == 3) pmax = std::max(pmax, (size_t)cin_dwqb_plan(s.M(), csym + s.F, cu_count()).splits * (csym + s.F) * 256);  // ... split-bf16: a partial per row split
   pmax = std::max(pmax, (size_t)dw_plan(s.M(), s.Hp(s.L - 1), s.F).splits * s.Hp(s.L - 1) * s.F);
   pmax = std::max(pmax, (size_t)dw_plan(s.M(), s.F, s.Hp(s.L - 1)).splits * s.Hp(s.L - 1) * s.F);   // (its swapped form)
@@ -351,13 +353,14 @@ struct CinBwdWs {
   static size_t ncol(const CinShape& s) { return ((size_t)s.M() + kColRows - 1) / kColRows; }        // ... of the column sums
   static size_t ndc(const CinShape& s) { return ((size_t)s.M() + 255) / 256; }                       // ... of the quadratic tail's 256-row blocks
   // the quadratic tail's views of G[1], free while no general layer runs: xr | gxR | dxR.  xr is [M][XS]: the merged path's xe
-  // (x | 1 | dP_L | dP_p, XS = F + 3), the two-launch path's xs (dP_L x | dP_p, XS = F + 1)
+  // (x | 1 | dP_L | dP_p, XS = F + 3; | g, XS = F + 4, where the forward saved the g-free G1: gxR and dxR are not used then), the
+  // two-launch path's xs (dP_L x | dP_p, XS = F + 1)
   struct Scratch {
     float *xr, *gxR, *dxR;
     int XS;
   };
-  Scratch scratch(const CinShape& s, bool qmerge) const {
-    const int XS = s.F + (qmerge ? 3 : 1);
+  Scratch scratch(const CinShape& s, bool qmerge, bool ghat = false) const {
+    const int XS = s.F + (qmerge ? (ghat ? 4 : 3) : 1);
     float* gxR = G[1] + (size_t)s.M() * XS;
     return Scratch{G[1], gxR, gxR + (size_t)s.M() * s.F, XS};
   }

@@ -30,6 +30,10 @@ namespace fil {
 // a split share its B rows through L1; the two waves of a tile fold their accumulators through LDS into ONE partial); the tiles left
 // over after the last full group of four (26 tiles at F = 39: 2) form workgroups of their own in which the spare waves take further
 // pairs, so every wave of the grid carries the same number of steps.
+// GHAT (cin_ghat_used, cin.hip): gT holds the g-free G1 and xe one more column, g[b] (XE = F+4): columns 0..127 take A g instead of A
+// -- one more gathered dword and multiply per step, from the same descriptor -- and ONE more channel row, c = Cp + F, with both factors
+// the ones column: its columns 0..127 are sum_m g Ghat[m,:] = dbias_1 (C = Cp + F + 1 rows in the partials; the row rides in the
+// spare rows of the last tile unless C - 1 is a multiple of 32).
 constexpr int kDwqDepth = 6;
 constexpr int kDwqThreads = 512;   // 8 waves: 4 channel tiles x 2 row splits
 struct DwqPlan {
@@ -83,7 +87,7 @@ inline DwqPlan cin_dwq_plan4(long M, int C, int cus) {
   return p;
 }
 
-template <int DEPTH = kDwqDepth, int FOLD = 2>
+template <int DEPTH = kDwqDepth, int FOLD = 2, bool GHAT = false>
 __global__ __launch_bounds__(kDwqThreads, 2) void cin_dwq_kernel(const float* __restrict__ gT, const float* __restrict__ x1T, int HS, const float* __restrict__ xe,
                                                                 int XE, float* __restrict__ part, int M, int F, int symD, int rows_per_split, int splits,
                                                                 int ncol_full, int rem, int wgs_full, int wgs) {
@@ -93,7 +97,7 @@ __global__ __launch_bounds__(kDwqThreads, 2) void cin_dwq_kernel(const float* __
   __shared__ float fold[4][128][64];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int r = lane & 31, half = lane >> 5;
-  const int Cp = F * symD, C = Cp + F;
+  const int Cp = F * symD, C = Cp + F + (GHAT ? 1 : 0);
   // XCD-aware work mapping (as cin_dw3_kernel): workgroup i of XCD i%8 takes item (i%8)*(grid/8) + i/8 of the split-major list
   const int item = (blockIdx.x & 7) * (gridDim.x >> 3) + (blockIdx.x >> 3);
   if (item >= wgs) return;   // (whole workgroup)
@@ -146,13 +150,17 @@ __global__ __launch_bounds__(kDwqThreads, 2) void cin_dwq_kernel(const float* __
     hh = cc / symD;
     ff = (hh + (cc - hh * symD)) % F;
     sel = 0;
-  } else {
+  } else if (!GHAT || cc < Cp + F) {
     hh = F;
     ff = cc - Cp;
+    sel = 1;
+  } else {   // the ones row: 1 * 1 (* g on columns 0..127)
+    hh = ff = F;
     sel = 1;
   }
   const int ho = (half * XE + hh) * 4, fo = (half * XE + ff) * 4, so = (half * XE + F + 1 + sel) * 4;
   const int go = (half * HS + 4 * r) * 4;
+  const int gso = (half * XE + F + 3) * 4;   // (GHAT) g of the row
   const int steps = work ? (m_hi - m_lo + 1) >> 1 : 0;
   const int groups = (steps + DEPTH - 1) / DEPTH;
 
@@ -162,7 +170,7 @@ __global__ __launch_bounds__(kDwqThreads, 2) void cin_dwq_kernel(const float* __
 #pragma unroll
     for (int i = 0; i < 16; ++i) acc[nb][i] = 0.f;
   f32x4s qg[DEPTH], q1[DEPTH];
-  float qh[DEPTH], qf[DEPTH], qs[DEPTH];
+  float qh[DEPTH], qf[DEPTH], qs[DEPTH], qgs[DEPTH];
   auto fetch = [&](int s, int d) {
     const int row = 2 * s;   // uniform, relative to the split's first row
     qg[d] = __builtin_bit_cast(f32x4s, __builtin_amdgcn_raw_buffer_load_b128(rg, go, row * HS * 4, 0));
@@ -170,11 +178,14 @@ __global__ __launch_bounds__(kDwqThreads, 2) void cin_dwq_kernel(const float* __
     qh[d] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rx, ho, row * XE * 4, 0));
     qf[d] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rx, fo, row * XE * 4, 0));
     qs[d] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rx, so, row * XE * 4, 0));
+    if constexpr (GHAT) qgs[d] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rx, gso, row * XE * 4, 0));
   };
 #pragma unroll
   for (int d = 0; d < DEPTH; ++d) fetch(d, d);
   // the generated operands of step s+1 are computed in front of step s's MFMAs and consumed a step later
   float ac = qh[0] * qf[0], ac2 = ac * qs[0], an, an2;
+  float ag = ac, ang;   // A operand of columns 0..127
+  if constexpr (GHAT) ag = ac * qgs[0];
 #pragma unroll 1
   for (int g = 0; g < groups; ++g) {
 #pragma unroll
@@ -182,17 +193,20 @@ __global__ __launch_bounds__(kDwqThreads, 2) void cin_dwq_kernel(const float* __
       const f32x4s g4 = qg[d], x4 = q1[d];
       an = qh[(d + 1) % DEPTH] * qf[(d + 1) % DEPTH];   // (slot 0 of the next group was refilled a group ago)
       an2 = an * qs[(d + 1) % DEPTH];
+      if constexpr (GHAT) ang = an * qgs[(d + 1) % DEPTH];
+      else ang = an;
       __builtin_amdgcn_sched_barrier(0);
-      acc[0] = mfma32(ac, g4[0], acc[0]);
-      acc[1] = mfma32(ac, g4[1], acc[1]);
-      acc[2] = mfma32(ac, g4[2], acc[2]);
-      acc[3] = mfma32(ac, g4[3], acc[3]);
+      acc[0] = mfma32(ag, g4[0], acc[0]);
+      acc[1] = mfma32(ag, g4[1], acc[1]);
+      acc[2] = mfma32(ag, g4[2], acc[2]);
+      acc[3] = mfma32(ag, g4[3], acc[3]);
       acc[4] = mfma32(ac2, x4[0], acc[4]);
       acc[5] = mfma32(ac2, x4[1], acc[5]);
       acc[6] = mfma32(ac2, x4[2], acc[6]);
       acc[7] = mfma32(ac2, x4[3], acc[7]);
       ac = an;
       ac2 = an2;
+      ag = ang;
       __builtin_amdgcn_sched_barrier(0);
       fetch(g * DEPTH + d + DEPTH, d);   // after the step's MFMAs: the refill may land in the registers it replaces
       __builtin_amdgcn_sched_barrier(0);
@@ -248,7 +262,7 @@ __global__ __launch_bounds__(kDwqThreads, 2) void cin_dwq_kernel(const float* __
     const int cr = c0 + mfma32_row(reg, half);
     if (cr < C) {
       float* dst = pout + (long)cr * 256 + 4 * r;
-      if (cr < Cp) *reinterpret_cast<float4*>(dst) = make_float4(acc[0][reg], acc[1][reg], acc[2][reg], acc[3][reg]);
+      if (cr < Cp || (GHAT && cr == C - 1)) *reinterpret_cast<float4*>(dst) = make_float4(acc[0][reg], acc[1][reg], acc[2][reg], acc[3][reg]);
       *reinterpret_cast<float4*>(dst + 128) = make_float4(acc[4][reg], acc[5][reg], acc[6][reg], acc[7][reg]);
     }
   }
@@ -260,12 +274,14 @@ __global__ __launch_bounds__(kDwqThreads, 2) void cin_dwq_kernel(const float* __
 //   pair row c, column 128 + n, n < H2:         dT[(h,f), n] / dT[(f,h), n] likewise  ([F*F][H2])
 //   single-field row c = Cp + f, column 128+n:  vT[f][n]                                                          ([F][H2])
 // Workgroups past those rows: the fixed-order sum of the nbp column-sum partials bpart [nbp][H1] -> dbias1 (cin_reduce_body).
+// GHAT (cin_dwq_kernel<.., GHAT>): one more row of the partials, c = Cp + F, whose columns n < H1 are dbias1 (nb1 = 0 then).
+template <bool GHAT = false>
 static __global__ __launch_bounds__(256) void cin_reduce_expand_q_kernel(const float* __restrict__ part, int parts, int F, int D, int H1, int H2,
                                                                           float* __restrict__ dW1, float* __restrict__ dT, float* __restrict__ vT,
                                                                           const float* __restrict__ bpart, int nbp, float* __restrict__ dbias1,
                                                                           int nb1, const float* __restrict__ hpart, int nhp, int LK,
                                                                           float* __restrict__ ddw, float* __restrict__ ddb) {
-  const int Cp = F * D, C = Cp + F;
+  const int Cp = F * D, C = Cp + F + (GHAT ? 1 : 0);
   const int nbw = (C + 3) / 4;   // a wave per row c (all 256 columns, four per lane), four rows per workgroup
   if ((int)blockIdx.x >= nbw + nb1) {   // the dense head's block partials (cin_qtail_xe_kernel) -> ddense_w | ddense_b
     cin_reduce_body(hpart, ddw, (long)LK + 1, nhp, ddb, (long)LK, (int)blockIdx.x - nbw - nb1);
@@ -294,6 +310,14 @@ static __global__ __launch_bounds__(256) void cin_reduce_expand_q_kernel(const f
   const int col = 4 * lane, n0 = col & 127;
   const bool second = col >= 128;
   const int H = second ? H2 : H1;
+  if (GHAT && c >= Cp + F) {   // the ones row
+    if (!second) {
+#pragma unroll
+      for (int e = 0; e < 4; ++e)
+        if (n0 + e < H1) dbias1[n0 + e] = v[e];
+    }
+    return;
+  }
   if (c >= Cp) {
     if (second) {
 #pragma unroll
@@ -325,6 +349,7 @@ static __global__ __launch_bounds__(256) void cin_reduce_expand_q_kernel(const f
 // dcpart[blk][f] = sum_m dP_L[m] x[m,f] (-> dc[f] = d pool_L / d c[f]), dcpart[blk][F] = sum_m dP_L[m], dcpart[blk][F+1] = sum_m dP_p[m]
 // (cf. cin_qtail_scale_kernel).  Further workgroups: [nscale, +nhead) the dense head's partial sums -> ddense_w | ddense_b; the
 // rest: the first layer's pair weights in the dZ kernel's slot order.   LDS: [256][F + 3 + L].  kXeThreads threads.
+// gcol = 1 (cin_ghat_used; g != nullptr): one more column behind them, g of the row's sample (XE = F+4; LDS: + [256]).
 constexpr int kXeThreads = 1024;
 template <int NP = 3>   // planes of the split-bf16 modes' weights
 static __global__ __launch_bounds__(kXeThreads) void cin_qtail_xe_kernel(const float* __restrict__ xT, const float* __restrict__ dPL,
@@ -335,7 +360,7 @@ static __global__ __launch_bounds__(kXeThreads) void cin_qtail_xe_kernel(const f
                                                                   int LK, int lL, int lp, const float* __restrict__ W0, float* __restrict__ Wz,
                                                                   int H0, int JTs, int HS0, int tiles0, int npz = -1,
                                                                   const float* __restrict__ Tq = nullptr, int HT = 0, u32x4* __restrict__ Wzb1 = nullptr,
-                                                                  u32x4* __restrict__ Wzb2 = nullptr) {
+                                                                  u32x4* __restrict__ Wzb2 = nullptr, int gcol = 0) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   if ((int)blockIdx.x >= nscale) {   // the first layer's weights in the dZ kernel's slot order (nothing else uses that buffer here)
     if (threadIdx.x >= 256) return;   // (the pack bodies are written for 256 threads)
@@ -355,7 +380,7 @@ static __global__ __launch_bounds__(kXeThreads) void cin_qtail_xe_kernel(const f
   // F + XE wave instructions with 64 lanes in 64 different lines each).  1024 threads: all of them fetch, then twelve waves write
   // the xe rows while the other four take the column sums and the head's partials.
   const int nl = g != nullptr ? LK / K : 0;
-  const int hl = nl + 1, XE = F + 3;
+  const int hl = nl + 1, XE = F + 3 + gcol;
   const int tid = threadIdx.x;
   const long m0 = (long)blockIdx.x * 256;
   const int nrows = (int)min((long)256, (long)M - m0);
@@ -363,6 +388,7 @@ static __global__ __launch_bounds__(kXeThreads) void cin_qtail_xe_kernel(const f
   float* dls = xs + 256 * F;
   float* dps = dls + 256;
   float* hd = dps + 256;
+  float* gs = hd + 256 * hl;   // (gcol)
   {
     const float* src = xT + m0 * F;
     const int n = nrows * F;
@@ -384,12 +410,13 @@ static __global__ __launch_bounds__(kXeThreads) void cin_qtail_xe_kernel(const f
   }
   if (tid < 256) {   // one row per thread: its pooled gradients (and the head's terms)
     const long m = m0 + tid;
-    float dl = 0.f, dp = 0.f;
+    float dl = 0.f, dp = 0.f, gr = 0.f;
     if (m < M) {
       const long b = m / K;
       const int k = (int)(m - b * K);
       if (g != nullptr) {   // the dense head's backward rides here: dP[b, j] = g[b] dense_w[j], and this row's terms of ddense_w | ddense_b
         const float gb = g[b];
+        gr = gb;
         for (int l = 0; l < nl; ++l) {
           const float d = gb * dense_w[l * K + k];
           dP[b * LK + l * K + k] = d;
@@ -407,6 +434,7 @@ static __global__ __launch_bounds__(kXeThreads) void cin_qtail_xe_kernel(const f
     }
     dls[tid] = dl;
     dps[tid] = dp;
+    if (gcol) gs[tid] = gr;
   }
   __syncthreads();
   __shared__ float cs[4][64];
@@ -422,7 +450,7 @@ static __global__ __launch_bounds__(kXeThreads) void cin_qtail_xe_kernel(const f
       float e[4];
 #pragma unroll
       for (int u = 0; u < 4; ++u) {
-        e[u] = c < F ? xs[rr * F + c] : c == F ? 1.f : c == F + 1 ? dls[rr] : dps[rr];
+        e[u] = c < F ? xs[rr * F + c] : c == F ? 1.f : c == F + 1 ? dls[rr] : c == F + 2 ? dps[rr] : gs[rr];
         if (++c == XE) {
           c = 0;
           ++rr;
@@ -432,7 +460,7 @@ static __global__ __launch_bounds__(kXeThreads) void cin_qtail_xe_kernel(const f
     }
     for (int i = 4 * n4 + tid; i < nrows * XE; i += NT) {
       const int rr = i / XE, c = i - rr * XE;
-      dst[i] = c < F ? xs[rr * F + c] : c == F ? 1.f : c == F + 1 ? dls[rr] : dps[rr];
+      dst[i] = c < F ? xs[rr * F + c] : c == F ? 1.f : c == F + 1 ? dls[rr] : c == F + 2 ? dps[rr] : gs[rr];
     }
   } else {
     const int t2 = tid - (kXeThreads - 256);
@@ -539,7 +567,9 @@ __global__ __launch_bounds__(256, 2) void cin_dz2_kernel(const float* __restrict
                                                          const float* __restrict__ dsc, int ldp, int K, const float* __restrict__ Wz1,
                                                          const float* __restrict__ Wz2, const float* __restrict__ xT, float* __restrict__ dxT,
                                                          int accumulate, int M, int F, int H1, int H2, int periods, int FR,
-                                                         float* __restrict__ dx, const float* __restrict__ cvec) {
+                                                         float* __restrict__ dx, const float* __restrict__ cvec,
+                                                         const float* __restrict__ gsc = nullptr) {
+  // gsc != nullptr (cin_ghat_used): g1T holds the g-free G1, pass 0 scales its rows by gsc[b] (g of the row's sample) on load
   extern __shared__ __attribute__((aligned(16))) float smem[];   // [FR][128 rows][2]
   constexpr int P = JT / gcd_c(16, JT);
   constexpr int HPP = 16 * P / JT;
@@ -574,10 +604,11 @@ __global__ __launch_bounds__(256, 2) void cin_dz2_kernel(const float* __restrict
       }
     }
   }
-  float dpl;
+  float dpl, g0;
   {
     const long bb = mq / K;
     dpl = dsc[bb * ldp + (mq - bb * K)];
+    g0 = gsc != nullptr ? gsc[bb] : 1.f;
   }
   __builtin_amdgcn_wave_barrier();  // the halves of a row read each other's x entries from here on
   const long wbytes = ((long)periods * P + 1) * 32 * 128 * 4;
@@ -594,7 +625,7 @@ __global__ __launch_bounds__(256, 2) void cin_dz2_kernel(const float* __restrict
         greg[4 * s4 + e] = __builtin_bit_cast(float, __builtin_bit_cast(int, gv) & keep) * sc;
       }
   };
-  to_greg(gq, H1, 1.f);
+  to_greg(gq, H1, g0);
 
 #pragma unroll 1
   for (int pass = 0; pass < 2; ++pass) {   // (running the passes in the other order in half of the workgroups, so that the two waves of a
@@ -739,7 +770,7 @@ __global__ __launch_bounds__(256, 2) void cin_dz2_kernel(const float* __restrict
 // dx != nullptr: the kernel finishes the job -- dx [B,F,K] = transpose(dxT (read only) + its image) + dP_L c -- instead of updating dxT
 bool cin_launch_dz2(hipStream_t st, int JT, const float* g1T, const float* g2T, int HS, const float* dsc, int ldp, int K, const float* Wz1,
                     const float* Wz2, const float* xT, float* dxT, int accumulate, int M, int F, int H1, int H2, int periods,
-                    float* dx = nullptr, const float* cvec = nullptr);
+                    float* dx = nullptr, const float* cvec = nullptr, const float* gsc = nullptr);
 
 // ------------------------------------------------------------------------------------------------------------------------------
 // Forward of the first layer and of the quadratic form in ONE launch: [x1 | R] = pairs(x) [W1s | Ts] (+ b1), 256 output columns.
@@ -757,12 +788,15 @@ struct CinHeadFold {
 // which differ only in how acc -- [x1 | R] of the wave's 32 rows, lane r owning columns 4r..4r+3 of each half -- was accumulated):
 // S = x wsum_p^T and <x, c> from the wrapped rows (exact fp32 MFMA), + b1, the stores of x1 and R, the three sum-pools and, with the
 // head folded in, pooled [B, L K] and the Dense(1) output.  NW = waves per workgroup (rows of the two small LDS arrays).
-template <int NW>
+// GHAT (cin_ghat_used, cin.hip; needs the head folded in with its Dense(1) output): what is stored in R's place is the g-free gradient of x1,
+//   Ghat[m,n] = dw_L[k] R[m,n] + dw_p[k] S[m,n] + dw_1[k]  (n < H, else 0),   dw_j[k] = dense_w[j K + k], k = m mod K,
+// formed after the pools have taken the true R; gw_s [NW][3][32] holds the three dense_w entries of the wave's rows.
+template <int NW, bool GHAT = false>
 __device__ __forceinline__ void cin_fwdq_epilogue(f32x16 (&acc)[8], const __amdgpu_buffer_rsrc_t& rx, int vhalf, int wo, int r, int half, int wave, int wrow0,
                                                   const float* __restrict__ bias1, const float* __restrict__ wsn, int JTG, const float* __restrict__ cvec,
                                                   float* __restrict__ x1T, float* __restrict__ RT, int HS, float* __restrict__ pool1,
                                                   float* __restrict__ pool_p, float* __restrict__ pool_L, int M, int F, int H, const CinHeadFold& hf,
-                                                  float (&lin_s)[NW][32], float (&pv_s)[NW][3][32]) {
+                                                  float (&lin_s)[NW][32], float (&pv_s)[NW][3][32], float (*gw_s)[3][32] = nullptr) {
   const int lane = half * 32 + r;
   // ---- S = x wsum_p^T and the linear term <x, c>: JTG steps of the general field order f = 2j + half (positions < F of the wrapped
   // rows; wsn rows f >= F are zero), four steps per group, the next group's operands in flight behind this group's MFMAs
@@ -815,6 +849,14 @@ __device__ __forceinline__ void cin_fwdq_epilogue(f32x16 (&acc)[8], const __amdg
   }
   lin = lane_halves_sum(lin);
   if (half == 0) lin_s[wave][r] = lin;
+  if constexpr (GHAT) {   // row r of the wave: its three dense_w entries, fetched once (first layer | p | L)
+    const int k = (wrow0 + r) & ((1 << hf.kshift) - 1);
+    if (half == 0) {
+      gw_s[wave][0][r] = hf.dense_w[k];
+      gw_s[wave][1][r] = hf.dense_w[hf.op + k];
+      gw_s[wave][2][r] = hf.dense_w[hf.oL + k];
+    }
+  }
   __builtin_amdgcn_wave_barrier();
 
   // ---- epilogue: + b1, store x1 and R ([M][HS]; lane r owns columns 4r..4r+3), the three sum-pools
@@ -830,7 +872,7 @@ __device__ __forceinline__ void cin_fwdq_epilogue(f32x16 (&acc)[8], const __amdg
     const float b0 = acc[4][reg], b1 = acc[5][reg], b2 = acc[6][reg], b3 = acc[7][reg];
     if (m < M) {
       *reinterpret_cast<float4*>(x1T + (long)m * HS + 4 * r) = make_float4(a0, a1, a2, a3);
-      *reinterpret_cast<float4*>(RT + (long)m * HS + 4 * r) = make_float4(b0, b1, b2, b3);
+      if constexpr (!GHAT) *reinterpret_cast<float4*>(RT + (long)m * HS + 4 * r) = make_float4(b0, b1, b2, b3);
     }
     float p1 = (a0 + a1) + (a2 + a3);
     float eL = a0 * b0, ep = a0 * t[0][reg];
@@ -840,6 +882,14 @@ __device__ __forceinline__ void cin_fwdq_epilogue(f32x16 (&acc)[8], const __amdg
     ep = fmaf(a1, t[1][reg], ep);
     ep = fmaf(a2, t[2][reg], ep);
     ep = fmaf(a3, t[3][reg], ep);
+    if constexpr (GHAT) {
+      const float w1 = gw_s[wave][0][row], wp = gw_s[wave][1][row], wL = gw_s[wave][2][row];
+      const float g0 = 4 * r + 0 < H ? fmaf(wL, b0, fmaf(wp, t[0][reg], w1)) : 0.f;
+      const float g1 = 4 * r + 1 < H ? fmaf(wL, b1, fmaf(wp, t[1][reg], w1)) : 0.f;
+      const float g2 = 4 * r + 2 < H ? fmaf(wL, b2, fmaf(wp, t[2][reg], w1)) : 0.f;
+      const float g3 = 4 * r + 3 < H ? fmaf(wL, b3, fmaf(wp, t[3][reg], w1)) : 0.f;
+      if (m < M) *reinterpret_cast<float4*>(RT + (long)m * HS + 4 * r) = make_float4(g0, g1, g2, g3);
+    }
     p1 = half_wave_sum_hi(p1);
     eL = half_wave_sum_hi(eL);
     ep = half_wave_sum_hi(ep);
@@ -889,7 +939,7 @@ __device__ __forceinline__ void cin_fwdq_epilogue(f32x16 (&acc)[8], const __amdg
 // i.e. cin_qtail_pool2_kernel's work without its pass over x1 and R.  x1 and R are still stored (the backward needs both).
 // Operand layouts: W1f / WTf as cin_pack_wf_sym_body packs them ([h][2 JT][128]); wsn = wsum_p in the forward operand layout
 // ([2 JTG][128], JTG = cin_jt_of(F) steps); cvec as cin_qtail_t_kernel leaves it.
-template <int JT>
+template <int JT, bool GHAT = false>
 __global__ __launch_bounds__(256, 2) void cin_fwdq_kernel(const float* __restrict__ x2T, int XL, const float* __restrict__ W1f, const float* __restrict__ WTf,
                                                           const float* __restrict__ bias1, const float* __restrict__ wsn, int JTG,
                                                           const float* __restrict__ cvec, float* __restrict__ x1T, float* __restrict__ RT, int HS,
@@ -899,6 +949,7 @@ __global__ __launch_bounds__(256, 2) void cin_fwdq_kernel(const float* __restric
   static_assert(JT % DEPTH == 0, "queue depth must divide the steps per h");
   __shared__ float lin_s[4][32];
   __shared__ float pv_s[4][3][32];   // (head folded in) the wave's pooled values, then their products with dense_w
+  __shared__ float gw_s[GHAT ? 4 : 1][3][32];   // (GHAT) the dense_w entries of the wave's rows
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int r = lane & 31, half = lane >> 5;
   const int wrow0 = (blockIdx.x * 4 + wave) * 32;
@@ -970,10 +1021,11 @@ __global__ __launch_bounds__(256, 2) void cin_fwdq_kernel(const float* __restric
   }
   if (h < F) run_h(h, xa, pa, xb, pb);
 
-  cin_fwdq_epilogue<4>(acc, rx, vhalf, wo, r, half, wave, wrow0, bias1, wsn, JTG, cvec, x1T, RT, HS, pool1, pool_p, pool_L, M, F, H, hf, lin_s, pv_s);
+  cin_fwdq_epilogue<4, GHAT>(acc, rx, vhalf, wo, r, half, wave, wrow0, bias1, wsn, JTG, cvec, x1T, RT, HS, pool1, pool_p, pool_L, M, F, H, hf, lin_s, pv_s, gw_s);
 }
 
 bool cin_launch_fwdq(hipStream_t st, int JT, const float* x2T, int XL, const float* W1f, const float* WTf, const float* bias1, const float* wsn, int JTG,
-                     const float* cvec, float* x1T, float* RT, int HS, float* pool1, float* pool_p, float* pool_L, int M, int F, int H, CinHeadFold hf);
+                     const float* cvec, float* x1T, float* RT, int HS, float* pool1, float* pool_p, float* pool_L, int M, int F, int H, CinHeadFold hf,
+                     bool ghat = false);   // ghat: the g-free G1 in R's place (cin_fwdq_epilogue<.., GHAT>)
 
 }  // namespace fil
