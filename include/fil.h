@@ -172,6 +172,11 @@ int fil_cin_bwd(const float* x, const float* const* W, const float* const* bias,
  *   DEFAULT, nothing runs), or a (negative) error code for arguments the _p entry points refuse. */
 enum fil_cin_precision { FIL_CIN_PREC_DEFAULT = 0, FIL_CIN_PREC_BF16 = 1 };
 int fil_cin_precision_used(int B, int F, int K, int L, const int* H, int mode, int precision);
+/* fil_cin_shortdx_used: 1 where a backward with these arguments computes the shortcut's data gradient with cin_shortcut_dx_kernel (merged
+ *   quadratic tail whose forward saved the g-free gradient of x1, exact kernels; FIL_CIN_SHORTDX=0 in the environment turns it off), 0 where
+ *   cin_last_bwd2_kernel or another path does (B = 0: 0, nothing runs), or a (negative) error code for arguments fil_cin_bwd_p refuses.
+ *   For tests and tools.  Entry point added only: the ABI version stays. */
+int fil_cin_shortdx_used(int B, int F, int K, int L, const int* H, int output_dim, int mode, int precision);
 int fil_cin_fwd_p(const float* x, const float* const* W, const float* const* bias, const float* dense_w,
                   const float* dense_b, float* out, float* pooled, float* saved, int B, int F, int K, int L,
                   const int* H, int output_dim, int mode, int precision, void* workspace, size_t workspace_bytes, void* stream);

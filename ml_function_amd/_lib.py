@@ -61,6 +61,7 @@ SIGNATURES = {
     "fil_cin_fwd": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _I, _I, _P, _Z, _P]),
     "fil_cin_bwd": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _I, _I, _P, _P, _Z, _P]),
     "fil_cin_precision_used": (_I, [_I, _I, _I, _I, _P, _I, _I]),
+    "fil_cin_shortdx_used": (_I, [_I, _I, _I, _I, _P, _I, _I, _I]),
     "fil_cin_fwd_p": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _I, _I, _I, _P, _Z, _P]),
     "fil_cin_bwd_p": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _I, _I, _I, _P, _P, _Z, _P]),
     "fil_attn_fwd_workspace_bytes": (_Z, [_I, _I, _I, _I, _I]),

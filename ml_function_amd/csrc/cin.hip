@@ -98,6 +98,11 @@ static bool cin_ghat_used(const CinShape& s, const CinPath& p, int output_dim) {
   const bool dz2 = knobs().dz2 != 0 && s.HS(0) / 2 == 64;
   return p.qmerge && p.fwdq(s) && !p.qsplit && headfold && dz2 && knobs().ghat != 0;
 }
+// Merged quadratic tail, backward: where the forward saved the g-free G1 (cin_ghat_used) the only work left for the cin_last_bwd launch is
+// the shortcut's data gradient, and cin_shortcut_dx_kernel (cin_shortdx.h) does it.  False: cin_last_bwd2_kernel, as everywhere else.
+// (ghat implies Hp = H[0] <= 128 and F <= 64, the kernel's limits; the split-bf16 and one-plane bf16 modes never have ghat where their
+// own kernels run -- they keep cin_last_bwd2_kernel -- and take this kernel where they fall back to the exact ones.)
+static bool cin_shortdx_used(const CinShape& s, const CinPath& p, int output_dim) { return cin_ghat_used(s, p, output_dim) && knobs().shortdx != 0; }
 // precision code of the _p entry points -> the internal mode bit (FIL_OK), or FIL_ERR_ARG
 static int cin_precision_bits(const char* who, int mode, int precision, int* bits) {
   if (precision != FIL_CIN_PREC_DEFAULT && precision != FIL_CIN_PREC_BF16)
@@ -189,6 +194,14 @@ extern "C" int fil_cin_grad_ready_points(int B, int F, int K, int L, const int* 
   const int n = cin_ready_order(L, cin_path_of(s, mode), slot, pt);
   for (int i = 0; i <= L; ++i) point[slot[i]] = pt[i];
   return n;
+}
+
+extern "C" int fil_cin_shortdx_used(int B, int F, int K, int L, const int* H, int output_dim, int mode, int precision) {
+  CinShape s;
+  if (int rc = check_shape("fil_cin_shortdx_used", B, F, K, L, H, s)) return rc;
+  CinPath p;
+  if (int rc = cin_path("fil_cin_shortdx_used", s, mode, precision, &p)) return rc;
+  return B > 0 && cin_shortdx_used(s, p, output_dim) ? 1 : 0;
 }
 
 extern "C" int fil_cin_precision_used(int B, int F, int K, int L, const int* H, int mode, int precision) {
@@ -618,7 +631,8 @@ static void cin_qtail_params_fill(const CinBwd& c) {
 // ---- quadratic tail with merged weight gradients (cin_qmerge.h): [dW1 | dT] = pairs(x)^T [G1 | dP_L x1] in ONE launch; the data
 // gradients are one two-pass launch of the pair-symmetric dZ kernel (G1 with W1, then the unscaled x1 with T, scaled by dP_L), or two
 // launches of it.  G1 = dP_p S + dP_1 + dP_L R and the shortcut's dX part come out of cin_last_bwd2_kernel -- or, where the forward
-// saved the g-free G1 in R's place (cin_ghat_used), G1 = g Ghat is formed inside the two GEMMs and that kernel leaves the dX part alone.
+// saved the g-free G1 in R's place (cin_ghat_used), G1 = g Ghat is formed inside the two GEMMs and only the dX part is left: for
+// cin_shortcut_dx_kernel (cin_shortdx_used), or for that kernel's second phase.
 static int cin_bwd_top_merged_q(CinBwd& c) {
   const CinShape& s = c.s;
   const TailGeom& tg = c.p.tg;
@@ -665,7 +679,9 @@ static int cin_bwd_top_merged_q(CinBwd& c) {
   FIL_CIN_BWD_LAUNCHED();
   {
     ProfScope ps("cin_last_bwd", st, 6.0 * (double)M * Hpp * F);
-    if (ghat)   // the shortcut's dX part alone: G1 = g Ghat needs no pass of its own
+    if (cin_shortdx_used(s, c.p, c.output_dim))   // the shortcut's dX part alone (G1 = g Ghat needs no pass of its own), by its own kernel
+      cin_launch_shortcut_dx(st, xpT, xps, sv.wsumP, dPp, LK, ws.dxT, (int)M, F, K, Hpp);
+    else if (ghat)
       cin_launch_last_bwd2(st, JT, xT, xpT, xps, sv.wsumP, sv.wsnP, dPp, LK, nullptr, nullptr, HS0, ws.dxT, (int)M, F, K, Hpp);
     else
       cin_launch_last_bwd2(st, JT, xT, xpT, xps, sv.wsumP, sv.wsnP, dPp, LK, dPprev, ws.G[c.cur], HS0, ws.dxT, (int)M, F, K, Hpp, sv.R, HS0, dPL, ws.small);

@@ -1,6 +1,7 @@
 // Instantiations + dispatch of cin_fwd3_kernel<MB, JT>.
 #include "cin_kernels.h"
 #include "cin_launch.h"
+#include "cin_shortdx.h"
 
 namespace fil {
 
@@ -68,6 +69,22 @@ void cin_launch_last_bwd2(hipStream_t st, int JT, const float* xT, const float* 
   case JTV: last_bwd2<JTV>(st, xT, xpT, xps, wsum, wsn, dP, ldp, dPprev, GprevT, HSp, dxT, M, F, K, Hp, Radd, HSr, dPadd, colpart); break;
   switch (JT) { FIL_LB(4) FIL_LB(8) FIL_LB(12) FIL_LB(16) FIL_LB(20) FIL_LB(24) FIL_LB(28) FIL_LB(32) }
 #undef FIL_LB
+}
+
+template <int NT>
+static void shortcut_dx(hipStream_t st, const float* xpT, int xps, const float* wsum, const float* dP, int ldp, float* dxT, int M, int F, int K, int Hp) {
+  const size_t sh = cin_shortdx_lds_bytes(NT);   // the operand image | four waves' staging areas
+  if (sh > 48 * 1024)
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(cin_shortcut_dx_kernel<NT>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh);
+  hipLaunchKernelGGL((cin_shortcut_dx_kernel<NT>), dim3((M + 127) / 128), dim3(kCinThreads), sh, st, xpT, xps, wsum, dP, ldp, dxT, M, F, K, Hp);
+}
+
+void cin_launch_shortcut_dx(hipStream_t st, const float* xpT, int xps, const float* wsum, const float* dP, int ldp, float* dxT, int M, int F, int K,
+                            int Hp) {
+#define FIL_SDX(NTV) \
+  case NTV: shortcut_dx<NTV>(st, xpT, xps, wsum, dP, ldp, dxT, M, F, K, Hp); break;
+  switch ((F + 15) / 16) { FIL_SDX(1) FIL_SDX(2) FIL_SDX(3) FIL_SDX(4) }
+#undef FIL_SDX
 }
 
 }  // namespace fil

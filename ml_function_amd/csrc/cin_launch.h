@@ -33,6 +33,10 @@ void cin_launch_last_bwd2(hipStream_t st, int JT, const float* xT, const float* 
                           const float* dP, int ldp, const float* dPprev, float* GprevT, int HSp, float* dxT, int M, int F, int K, int Hp,
                           const float* Radd = nullptr, int HSr = 0, const float* dPadd = nullptr, float* colpart = nullptr);
 
+// the shortcut's data gradient alone, dxT = dP * (x^{L-1} wsum), for Hp <= 128 <= xps and F <= 64: see cin_shortcut_dx_kernel (cin_shortdx.h)
+void cin_launch_shortcut_dx(hipStream_t st, const float* xpT, int xps, const float* wsum, const float* dP, int ldp, float* dxT, int M, int F, int K,
+                            int Hp);
+
 // symmetric first layer (x^{l-1} = x); FR = field rows of the LDS scratch (see cin_dz_sym_rows)
 void cin_launch_dz3_sym(hipStream_t st, int MB, int JT, int NHMAX, dim3 grid, const float* gT, int HS, const float* Wz, const float* xT,
                         float* gx0T, float* dxT, int accumulate, int M, int F, int H, int periods, int ks = 1);

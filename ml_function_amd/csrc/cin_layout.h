@@ -63,14 +63,16 @@ static int env_int(const char* name, int dflt) {
 //   FIL_CIN_DWFOLD4=0     ... the merged weight-gradient launch folds PAIRS of row splits (4 tiles x 2 splits per workgroup) instead of quads
 //   FIL_CIN_GHAT=0        ... the forward saves R itself and cin_last_bwd2_kernel builds G1 from it, instead of the forward saving the
 //                         g-free G1 in R's place (cin_ghat_used, cin.hip)
+//   FIL_CIN_SHORTDX=0     ... the shortcut's data gradient by cin_last_bwd2_kernel's phase u instead of cin_shortcut_dx_kernel (cin_shortdx_used,
+//                         cin.hip)
 // Results are identical up to summation order whatever they say.  Per-call overrides for tests travel in `mode`
 // (FIL_CIN_MB2, FIL_CIN_NOSYM), not through the environment.
 struct Knobs {
-  int mb, sym, dw_mb, dw_splits, dz_mb, tail_splits, tail_settle, tail_dz_mode, ksplit, dzs_mb, qtail, qmerge, dz2, fwdq, headfold, packfold, dwfold4, ghat;
+  int mb, sym, dw_mb, dw_splits, dz_mb, tail_splits, tail_settle, tail_dz_mode, ksplit, dzs_mb, qtail, qmerge, dz2, fwdq, headfold, packfold, dwfold4, ghat, shortdx;
 };
 static const Knobs& knobs() {
   static const Knobs k = {env_int("FIL_CIN_MB", 0), env_int("FIL_CIN_SYM", 1), env_int("FIL_CIN_DW_MB", 1), env_int("FIL_CIN_DW_SPLITS", 0),
-                          env_int("FIL_CIN_DZ_MB", 1), env_int("FIL_CIN_TAIL_SPLITS", 0), env_int("FIL_CIN_TAIL_SETTLE", 0), env_int("FIL_CIN_TAIL_DZ_MODE", 0), env_int("FIL_CIN_KSPLIT", -1), env_int("FIL_CIN_DZS_MB", 0), env_int("FIL_CIN_QTAIL", 1), env_int("FIL_CIN_QMERGE", 1), env_int("FIL_CIN_DZ2", 1), env_int("FIL_CIN_FWDQ", 1), env_int("FIL_CIN_HEADFOLD", 1), env_int("FIL_CIN_PACKFOLD", 1), env_int("FIL_CIN_DWFOLD4", 1), env_int("FIL_CIN_GHAT", 1)};
+                          env_int("FIL_CIN_DZ_MB", 1), env_int("FIL_CIN_TAIL_SPLITS", 0), env_int("FIL_CIN_TAIL_SETTLE", 0), env_int("FIL_CIN_TAIL_DZ_MODE", 0), env_int("FIL_CIN_KSPLIT", -1), env_int("FIL_CIN_DZS_MB", 0), env_int("FIL_CIN_QTAIL", 1), env_int("FIL_CIN_QMERGE", 1), env_int("FIL_CIN_DZ2", 1), env_int("FIL_CIN_FWDQ", 1), env_int("FIL_CIN_HEADFOLD", 1), env_int("FIL_CIN_PACKFOLD", 1), env_int("FIL_CIN_DWFOLD4", 1), env_int("FIL_CIN_GHAT", 1), env_int("FIL_CIN_SHORTDX", 1)};
   return k;
 }
 // per-call view of the knobs: the process defaults with the call's mode bits applied

@@ -212,6 +212,16 @@ def cin_precision_used(B, F, K, H, mode=0, precision="bf16"):
     return "bf16" if rc == CIN_PREC_BF16 else "f32"
 
 
+def cin_shortdx_used(B, F, K, H, output_dim=1, mode=0, precision="f32"):
+    """True where a CIN backward with this shape, head, mode and precision runs cin_shortcut_dx_kernel for the shortcut's data gradient
+    (fil_cin_shortdx_used)."""
+    lib = _lib.load()
+    rc = lib.fil_cin_shortdx_used(int(B), int(F), int(K), len(H), int_array(list(H)), int(output_dim), int(mode), _cin_precision_code(precision))
+    if rc < 0:
+        raise FilError("fil_cin_shortdx_used: %s" % lib.fil_last_error().decode())
+    return rc == 1
+
+
 def cin_grad_ready_points(B, F, K, H, mode=0):
     """Where in fil_cin_bwd each grad_ready slot is recorded (fil.h): list of L+1 ordinals, [l] for layer l and [L] for the dense
     head; slots with equal ordinals become final together, so a data-parallel caller reduces them with one collective."""
