@@ -92,6 +92,9 @@ def main():
                     help="with --optimizer keras: deferred Keras mode (optim.Adam(sweep_period=N)) -- the untouched table rows catch up "
                          "on read and in one rolling slice of 1/N of the table per step instead of a whole-table sweep per step; the "
                          "same bits as keras after a flush (state_dict).  8 is a good choice (DESIGN 6e); default: the per-step sweep")
+    ap.add_argument("--amsgrad", action="store_true",
+                    help="with --optimizer keras: Keras' Adam(amsgrad=True) (optim.Adam(amsgrad=True): a third slot vhat, the running "
+                         "maximum of v, in the denominator); not with --sweep-period")
     ap.add_argument("--ftrl-lr-power", type=float, default=-0.5, help="--optimizer keras-ftrl: learning_rate_power (<= 0)")
     ap.add_argument("--ftrl-l1", type=float, default=0.0, help="--optimizer keras-ftrl: l1_regularization_strength")
     ap.add_argument("--ftrl-l2", type=float, default=0.0, help="--optimizer keras-ftrl: l2_regularization_strength")
@@ -156,6 +159,8 @@ def main():
     lr = make_schedule(args)
     if args.sweep_period is not None and args.optimizer != "keras":
         ap.error("--sweep-period needs --optimizer keras")
+    if args.amsgrad and (args.optimizer != "keras" or args.sweep_period is not None):
+        ap.error("--amsgrad needs --optimizer keras and no --sweep-period")
     if args.sweep_period is not None and world > 1 and args.dp_tables != "runs":
         ap.error("--sweep-period needs --dp-tables runs when data parallel (dense table gradients are not deferred)")
     fi = models.FeatureInput(sparseInfo=info, useLinear=args.model != "DCN" and args.model != "AutoInt", useAddLinear=single,
@@ -198,7 +203,7 @@ def main():
                          l2_shrinkage_regularization_strength=args.ftrl_l2_shrinkage, decay=args.lr_decay)
     elif keras:     # Keras 'adam' (un_seq.py:61) with Keras' numerics; tables in "runs" mode get their l2 inside the update
         opt = optim.Adam(model.parameters(), learning_rate=lr, epsilon=1e-7, lazy_tables=args.optimizer == "keras-lazy",
-                         sweep_period=args.sweep_period, decay=args.lr_decay)
+                         sweep_period=args.sweep_period, decay=args.lr_decay, amsgrad=args.amsgrad)
     else:
         opt = torch.optim.Adam(model.parameters(), lr=args.lr, eps=1e-7, capturable=use_graph)      # Keras 'adam' (un_seq.py:61)
     keras_auc = metrics.AUC().build(device) if args.keras_auc else None      # the state exists before any capture

@@ -756,7 +756,63 @@ int fil_embed_nadam_merged(const int64_t* ids, const float* values, const int64_
                            const int64_t* step, int rule, const fil_nadam_hyper* hyper, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
- * M1  Keras' streaming AUC (TF 2.1 keras/metrics.py: AUC; keras/utils/metrics_utils.py: update_confusion_matrix_variables) --
+ * O7  Keras' Adam(amsgrad=True) (TF 2.1 keras/optimizer_v2/adam.py with amsgrad -> ApplyAdamWithAmsgrad; restated, parity with
+ *     TensorFlow unpinned), every tensor fp32.  Entry points added only: the ABI version stays.  O1's rule with a third slot `vhat`
+ *     (zeros to begin with), the running maximum of v, in the denominator:
+ *       t = *step + 1;  alpha = lr * sqrt(1 - b2^t) / (1 - b1^t)                    (as O1: powf on the device from the counter)
+ *       m += (g - m) * (1 - beta_1);  v += (g*g - v) * (1 - beta_2)
+ *       vhat = (vhat < v) ? v : vhat                                                (Eigen's cwiseMax order: a NaN v leaves vhat)
+ *       p -= (m * alpha) / (sqrt(vhat) + epsilon)
+ *   The rate: every entry point takes `lr` by value AND `const float* lr_dev`; lr_dev != NULL is the device word of
+ *     fil_lr_schedule_eval (O3), read by the launch, and lr is then ignored; lr_dev == NULL takes lr.  There are no _lrdev twins.
+ *     Requires lr (when used), epsilon >= 0 and betas in [0, 1) (FIL_ERR_ARG otherwise, a NaN included).  step: O1's counter; only
+ *     fil_amsgrad_multi(advance = 1) moves it, in a one-thread launch behind its update.
+ *   Which rows Keras updates: its sparse apply decays m and v over the WHOLE variable, takes the maximum over the whole variable and
+ *     moves every row (as O1's FIL_ADAM_KERAS): a touched row takes g = run sum + 2 field_l2[f] p, an untouched row g = 2 field_l2[f] p
+ *     (0 without l2: m and v decay, vhat keeps its bits, p still moves by m alpha / (sqrt(vhat) + epsilon)), a frozen field never
+ *     changes.  There is no lazy and no deferred mode.  The table kernels form m and v through the helpers of O1's table kernels, so
+ *     the table m and v are bit-identical to O1's on the same gradients.
+ *   fil_amsgrad_multi: fil_adam_multi's contract over fil_amsgrad_tensor descriptors (a DEVICE array of n entries): grad NULL = a
+ *     zero gradient; l2 != 0 adds 2 * l2 * p; 16-byte accesses where all FIVE arrays of a descriptor are 16-byte aligned, element-wise
+ *     otherwise and in the tail; n = 0 with advance = 1 only advances the counter.
+ *   fil_embed_amsgrad_runs: fil_embed_adam_runs in FIL_ADAM_KERAS mode with vhat [V, K]: the same run sums, every updated row stamped
+ *     (stamp [V] int32 is required).  R = 0 returns FIL_OK before any pointer is looked at; a NULL table, m, v, vhat, stamp or step is
+ *     FIL_ERR_ARG before any launch.  K <= 256.
+ *   fil_embed_amsgrad_sweep: every row not stamped with the current t, of every non-frozen field, takes the update with
+ *     g = 2 * field_l2[f] * p (field_l2 may be NULL; the sweep always runs: v decays on every row).  One read and one non-temporal
+ *     write of p, m, v, vhat and a read of stamp per row: 32 bytes per element; the write of vhat is skipped where it would store the
+ *     bits that were read (every untouched row of an unregularised field: 28 bytes per element).  16-byte accesses when K % 4 == 0
+ *     and the four arrays are 16-byte aligned, element-wise otherwise.  F <= 1024; V = 0 returns FIL_OK.
+ *   fil_embed_amsgrad_merged: fil_embed_adam_merged in FIL_ADAM_KERAS mode with vhat: every row of the union of the W gathered lists
+ *     of fil_embed_runs_compact updated once, by its owner, contributions summed in list order; W = 1 is bit-identical to
+ *     fil_embed_amsgrad_runs on the same record.  F <= 1024, K <= 256; cap = 0 or V = 0 returns FIL_OK.
+ *   Nothing allocates, synchronises or sizes a launch by data: the step captures.
+ */
+typedef struct {
+  float* param;
+  const float* grad;   /* NULL = zero gradient */
+  float* m;
+  float* v;
+  float* vhat;
+  int64_t numel;
+  float l2;            /* g += 2 * l2 * param; 0 = none */
+  int32_t reserved;    /* 0 */
+} fil_amsgrad_tensor;  /* 56 bytes */
+int fil_amsgrad_multi(const fil_amsgrad_tensor* tensors, int n, int64_t total_numel, int64_t* step, float lr, const float* lr_dev,
+                      float beta_1, float beta_2, float epsilon, int advance, void* stream);
+int fil_embed_amsgrad_runs(const void* g, const int64_t* perm, const int64_t* sorted_ids, long R, int K, int g_dtype, int F,
+                           const float* field_l2, float* table, float* m, float* v, float* vhat, int32_t* stamp, const int64_t* step,
+                           float lr, const float* lr_dev, float beta_1, float beta_2, float epsilon, void* stream);
+int fil_embed_amsgrad_sweep(float* table, float* m, float* v, float* vhat, const int32_t* stamp, int64_t V, int K, const int64_t* offsets,
+                            const float* field_l2, const unsigned char* frozen, int F, const int64_t* step, float lr, const float* lr_dev,
+                            float beta_1, float beta_2, float epsilon, void* stream);
+int fil_embed_amsgrad_merged(const int64_t* ids, const float* values, const int64_t* counts, int W, long cap, int K,
+                             const int64_t* offsets, const float* field_l2, int F, float* table, float* m, float* v, float* vhat,
+                             int32_t* stamp, int64_t V, const int64_t* step, float lr, const float* lr_dev, float beta_1, float beta_2,
+                             float epsilon, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * M1 Keras' streaming AUC (TF 2.1 keras/metrics.py: AUC; keras/utils/metrics_utils.py: update_confusion_matrix_variables) --
  *     replaces metrics=[tf.keras.metrics.AUC()] of example/ctr_example/un_seq.py:61.  Entry points added only: the ABI version stays.
  *   State: cm [4][T] fp32 = TP | FP | TN | FN per threshold, as Keras keeps them, and one int64 `invalid`.
  *   fil_confusion_update: p, y [n] fp32 (y != 0 is a positive label); thr [T] fp32 ascending (duplicates allowed); for every i

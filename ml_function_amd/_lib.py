@@ -145,6 +145,12 @@ SIGNATURES = {
     "fil_embed_nadam_runs": (_I, [_P, _P, _P, _c.c_long, _I, _I, _I, _P, _P, _P, _P, _P, _P, _I, _P, _P]),
     "fil_embed_nadam_sweep": (_I, [_P, _P, _P, _P, _c.c_int64, _I, _P, _P, _P, _I, _P, _I, _P, _P]),
     "fil_embed_nadam_merged": (_I, [_P, _P, _P, _I, _c.c_long, _I, _P, _P, _I, _P, _P, _P, _P, _c.c_int64, _P, _I, _P, _P]),
+    # O7: Adam with amsgrad -- O1's Keras-mode argument lists with vhat behind v and (lr, lr_dev) in place of lr; no _lrdev twins
+    "fil_amsgrad_multi": (_I, [_P, _I, _c.c_int64, _P, _F, _P, _F, _F, _F, _I, _P]),
+    "fil_embed_amsgrad_runs": (_I, [_P, _P, _P, _c.c_long, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _F, _P, _F, _F, _F, _P]),
+    "fil_embed_amsgrad_sweep": (_I, [_P, _P, _P, _P, _P, _c.c_int64, _I, _P, _P, _P, _I, _P, _F, _P, _F, _F, _F, _P]),
+    "fil_embed_amsgrad_merged": (_I, [_P, _P, _P, _I, _c.c_long, _I, _P, _P, _I, _P, _P, _P, _P, _P, _c.c_int64, _P, _F, _P, _F, _F, _F,
+                                      _P]),
     "fil_confusion_workspace_bytes": (_Z, [_I, _I]),
     "fil_confusion_update": (_I, [_P, _P, _I, _P, _I, _P, _P, _P, _Z, _P]),
     "fil_auc_result": (_I, [_P, _I, _I, _I, _P, _P]),
@@ -179,6 +185,15 @@ class NadamHyper(_c.Structure):
 
 
 assert _c.sizeof(NadamHyper) == 32
+
+
+class AmsgradTensor(_c.Structure):
+    """fil_amsgrad_tensor (include/fil.h O7)"""
+    _fields_ = [("param", _P), ("grad", _P), ("m", _P), ("v", _P), ("vhat", _P), ("numel", _c.c_int64), ("l2", _F),
+                ("reserved", _c.c_int32)]
+
+
+assert _c.sizeof(AmsgradTensor) == 56
 
 FIL_LR_CONSTANT, FIL_LR_EXPONENTIAL, FIL_LR_INVERSE_TIME, FIL_LR_POLYNOMIAL, FIL_LR_PIECEWISE = 0, 1, 2, 3, 4
 FIL_LR_MAX_BOUNDARIES = 32

@@ -12,65 +12,23 @@
 // of fil_embed_run_sum (embed_runs.h): the same order, so a row's gradient is bit-identical to what the dense path materialises.
 // Data parallel: fil_embed_adam_merged applies the W gathered lists of fil_embed_runs_compact (runs_compact.hip) -- every row once,
 // by its lowest rank, summed in rank order -- before the sweep, so every replica computes the same bits.
-// This file is Adam only.  Its kernels sit on a few shared pieces: the field table of a sweep (FieldTab), four elements of a row in
-// and out (row_load4, row_store4), a touched element (adam_touched_at) and one replayed step (replay_step); what the launchers
-// compute the same way as the row-rule optimizers' (grids, the step tag, sweep_vec, the shape check) comes from optim_rows.h and
-// embed_runs.h.
+// This file is Adam only.  Its kernels sit on a few shared pieces: the field table of a sweep (FieldTab, optim_adam.h), four elements
+// of a row in and out (row_load4, row_store4), a touched element (adam_touched_at) and one replayed step (replay_step); what the
+// launchers compute the same way as the row-rule optimizers' (grids, the step tag, sweep_vec, the shape check) comes from
+// optim_rows.h and embed_runs.h.  The coefficients and the two table-element updates live in optim_adam.h, which optim_amsgrad.hip
+// (O7, Adam with amsgrad) shares.
 #include "common.h"
 #include "embed_runs.h"
 #include "optim_rows.h"
+#include "optim_adam.h"
 #include <hip/hip_bf16.h>
 
 namespace fil {
 
 static_assert(sizeof(fil_adam_tensor) == 48, "fil_adam_tensor is 48 bytes (fil.h)");
 
-struct AdamCoef {
-  float alpha, omb1, omb2, eps;
-};
-
-__device__ __forceinline__ AdamCoef adam_coef(const int64_t* step, float lr, float b1, float b2, float eps) {
-  const float t = (float)(*step + 1);                 // Keras: local_step = cast(iterations + 1, float32)
-  const float b1p = powf(b1, t), b2p = powf(b2, t);
-  AdamCoef c;
-  c.alpha = lr * sqrtf(1.f - b2p) / (1.f - b1p);
-  c.omb1 = 1.f - b1;
-  c.omb2 = 1.f - b2;
-  c.eps = eps;
-  return c;
-}
-
-// the step's rate: the by-value one, or the word fil_lr_schedule_eval left on the device (the *_lrdev entry points).  A
-// wave-uniform load, once per kernel.
-__device__ __forceinline__ float rate_of(float lr, const float* __restrict__ lr_dev) { return lr_dev ? *lr_dev : lr; }
-
-// The embedding-table kernels, Keras mode and deferred mode alike, update a row through the two helpers below and nothing else: one
-// definition of each update's rounding, written with contraction off and explicit fmas, so the deferred replays give the Keras-mode
-// bits by construction, whatever the compiler makes of each kernel's context.
-//
-// the untouched-row update of the sweep (g = 2 l2[f] p); fused_m: its 16-byte path (K % 4 == 0, 16-byte aligned arrays) rounds
-// m += (g - m)(1 - b1) as one fma, its element path rounds the product first
-template <bool fused_m>
-__device__ __forceinline__ void adam_untouched(float& p, float& m, float& v, float l2x2, const AdamCoef& c) {
-#pragma clang fp contract(off)
-  const float g = l2x2 * p;
-  const float d = __builtin_fmaf(l2x2, p, -m);
-  const float gg = __builtin_fmaf(g, g, -v);
-  m = fused_m ? __builtin_fmaf(c.omb1, d, m) : m + c.omb1 * d;
-  v = __builtin_fmaf(c.omb2, gg, v);
-  p = p - (m * c.alpha) / (sqrtf(v) + c.eps);
-}
-
-// the touched-row update of the runs and merged kernels: g = (run sum) + 2 l2 p
-__device__ __forceinline__ void adam_touched(float& p, float& m, float& v, float acc, float l2x2, const AdamCoef& c) {
-#pragma clang fp contract(off)
-  const float g = __builtin_fmaf(l2x2, p, acc);
-  const float d = g - m;
-  const float gg = __builtin_fmaf(g, g, -v);
-  m = m + c.omb1 * d;
-  v = __builtin_fmaf(c.omb2, gg, v);
-  p = p - (m * c.alpha) / (sqrtf(v) + c.eps);
-}
+// (the step's coefficients, adam_touched / adam_untouched -- the one definition of a table element's rounding, DESIGN 6e -- the
+// sweep's field table and the hyper-parameter check: optim_adam.h, shared with optim_amsgrad.hip)
 
 // one element of ApplyAdam (Eigen's order of operations), left to the compiler's contraction: fil_adam_multi only, whose dense
 // tensors nothing replays
@@ -78,25 +36,6 @@ __device__ __forceinline__ void adam_elem(float& p, float& m, float& v, float g,
   m += (g - m) * c.omb1;
   v += (g * g - v) * c.omb2;
   p -= (m * c.alpha) / (sqrtf(v) + c.eps);
-}
-
-// the sweep's view of the fields, in LDS: a row's field is the last f with off[f] <= row; l2x2 = 2 l2[f], NaN for a frozen field
-struct FieldTab {
-  int64_t off[kSweepMaxF];
-  float l2x2[kSweepMaxF];
-};
-
-__device__ __forceinline__ void load_field_tab(FieldTab* s, const int64_t* __restrict__ offsets, const float* __restrict__ field_l2,
-                                               const unsigned char* __restrict__ frozen, int F) {
-  for (int f = threadIdx.x; f < F; f += blockDim.x) {
-    s->off[f] = offsets[f];
-    s->l2x2[f] = (frozen && frozen[f]) ? __builtin_nanf("") : (field_l2 ? 2.f * field_l2[f] : 0.f);
-  }
-}
-
-__device__ __forceinline__ float field_l2x2(const FieldTab* s, int F, int64_t row) {
-  const int f = sweep_field(s->off, F, row);
-  return f >= 0 ? s->l2x2[f] : 0.f;
 }
 
 // four elements of a row in and out: lane kq of the row's lane group holds elements kq * 4 ... kq * 4 + 3, those below K (the others
@@ -535,13 +474,6 @@ static int check_mode(const char* who, int mode, const int32_t* stamp) {
   if (mode != FIL_ADAM_KERAS && mode != FIL_ADAM_LAZY) return fail(FIL_ERR_ARG, "%s: mode %d (FIL_ADAM_KERAS or FIL_ADAM_LAZY)", who, mode);
   if (mode == FIL_ADAM_KERAS && stamp == nullptr)
     return fail(FIL_ERR_ARG, "%s: FIL_ADAM_KERAS needs the row stamps (fil_embed_adam_sweep skips the rows stamped here)", who);
-  return FIL_OK;
-}
-
-static int check_hyper(const char* who, float lr, float b1, float b2, float eps) {
-  if (!(lr >= 0.f) || !(b1 >= 0.f && b1 < 1.f) || !(b2 >= 0.f && b2 < 1.f) || !(eps >= 0.f))
-    return fail(FIL_ERR_ARG, "%s: hyper-parameters lr=%g beta_1=%g beta_2=%g epsilon=%g (lr, epsilon >= 0; betas in [0, 1))", who,
-                (double)lr, (double)b1, (double)b2, (double)eps);
   return FIL_OK;
 }
 

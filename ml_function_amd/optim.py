@@ -1,4 +1,4 @@
-"""Keras' Adam, Adagrad, Ftrl, SGD, RMSprop, Adadelta, Adamax and Nadam on the HIP path (include/fil.h O1, O2, O4, O5, O6): the optimizer the reference compiles (optimizer='adam', example/ctr_example/
+"""Keras' Adam, Adagrad, Ftrl, SGD, RMSprop, Adadelta, Adamax and Nadam on the HIP path (include/fil.h O1, O2, O4, O5, O6, O7): the optimizer the reference compiles (optimizer='adam', example/ctr_example/
 un_seq.py:61; TF 2.1), with Keras' names, defaults and numerics.
 
     opt = optim.Adam(model.parameters())                    # learning_rate 1e-3, beta_1 0.9, beta_2 0.999, epsilon 1e-7
@@ -71,6 +71,19 @@ advances the counter, so a captured step moves both on every replay.  The step's
 words; its powers are the device's powf, so it is Keras-exact within Adam's bars, bit-exact in m and v.  Keras' Nadam takes neither a
 schedule nor decay=, and neither does this one.
 
+Adam(amsgrad=True) (Keras' Adam with amsgrad, TF 2.1 ApplyAdamWithAmsgrad; O7) keeps a third slot `vhat` (Keras' name, zeros): vhat =
+(vhat < v) ? v : vhat after m and v, and p -= alpha m / (sqrt(vhat) + epsilon).  Same contract as Adam's Keras mode -- one dense launch
+per (group, device) over a five-array descriptor (fil_amsgrad_multi), runs tables in place (fil_embed_amsgrad_runs, or with an exchange
+fil_embed_amsgrad_merged, then fil_embed_amsgrad_sweep over every other row of every non-frozen field), schedules and decay=, capture,
+the data-parallel route.  Whole-variable semantics: an untouched row's m and v decay, its vhat holds, and it keeps moving on the old,
+larger denominator.  The table m and v are formed by Adam's own helpers: bit-equal to an optim.Adam run on the same gradients.  Not
+with sweep_period (the deferred ring and replays carry no third slot) and not with lazy_tables (ValueError); state_dict() carries vhat
+and a top-level "amsgrad": True only when it is on, and loading across the flag raises.  An Adam built without amsgrad makes exactly the
+calls it made before.  The sweep writes a lane's vhat only where its bits change (never on an untouched row of an unregularised
+field: 28 bytes per element there, 32 elsewhere, against Adam's 24).  Measured (profiles/r21_optim_amsgrad_bench.txt, 33.8 M rows x
+K=16, replayed): 3.45 ms with no field regularised and 3.90 ms with every one, against Adam's 3.13 ms in the same run -- 1.10 and 1.24
+of Adam's step for 1.17 and 1.33 of its bytes, 0.70 / 0.71 of 6.3 TB/s against Adam's 0.67.
+
 Only fp32 parameters on a GPU are supported: anything else raises (there is no CPU / eager fallback).
 """
 import ctypes
@@ -83,7 +96,7 @@ from torch.utils.weak import WeakIdKeyDictionary
 from . import _lib, schedules
 from ._lib import (FIL_ADAM_KERAS, FIL_ADAM_LAZY, FIL_ADAM_ROLL_FLUSH, FIL_ADAM_ROLL_SKIP, FIL_ADAM_ROLL_STEP, FIL_MOMOPT_NESTEROV,
                    FIL_OPT_ADADELTA, FIL_OPT_ADAGRAD, FIL_OPT_ADAMAX, FIL_OPT_FTRL, FIL_OPT_NADAM, FIL_OPT_RMSPROP, FIL_OPT_SGD, AdaoptHyper,
-                   FilError, MomoptHyper, NadamHyper, RowoptHyper, check, ptr, stream_ptr)
+                   AmsgradTensor, FilError, MomoptHyper, NadamHyper, RowoptHyper, check, ptr, stream_ptr)
 
 
 class _Desc(ctypes.Structure):
@@ -101,6 +114,13 @@ def _rated(lib, name, lr):
     if isinstance(lr, torch.Tensor):
         return getattr(lib, name + "_lrdev"), lr.data_ptr(), name + "_lrdev"
     return getattr(lib, name), lr, name
+
+
+def _rate_pair(lr):
+    """The (lr, lr_dev) of an entry point that takes both (include/fil.h O7): a float by value, or a device tensor's address."""
+    if isinstance(lr, torch.Tensor):
+        return 0.0, lr.data_ptr()
+    return lr, None
 
 
 def _check_rate(who, learning_rate, decay):
@@ -212,7 +232,7 @@ class _RunsOptimizer(torch.optim.Optimizer):
     """What the fused optimizers of this module share: the device step counter (Keras' iterations), the staged descriptor arrays of
     the one dense launch per (group, device), the pending runs records, the row stamps, the data-parallel exchange of the runs
     tables, the step loop and the state.  A subclass sets _NAME (its name in messages) and _SLOTS (the state keys of its per-element
-    slots: up to two, none for a rule without state; an instance may set its own) and supplies _slot_init (their initial values), _hyper, _launch_dense and _apply_runs; Adam's deferred mode hooks in
+    slots: up to three, none for a rule without state; an instance may set its own) and supplies _slot_init (their initial values), _hyper, _launch_dense and _apply_runs; Adam's deferred mode hooks in
     through _skip and _admit."""
     _NAME = None
     _SLOTS = ()
@@ -344,14 +364,16 @@ class _RunsOptimizer(torch.optim.Optimizer):
 
     # -- state ---------------------------------------------------------------------------------------------------
     def _slots(self, p, group):
-        """The parameter's two slot tensors, made on first use (None for a slot the rule does not have)."""
+        """The parameter's slot tensors, made on first use: two of them (None for a slot the rule does not have), three for a rule
+        with a third."""
         if not self._SLOTS:
             return None, None
         st = self.state[p]
         if self._SLOTS[0] not in st:
             for k, x in zip(self._SLOTS, self._slot_init(group)):
                 st[k] = torch.full_like(p, x, memory_format=torch.contiguous_format)
-        return st[self._SLOTS[0]], (st[self._SLOTS[1]] if len(self._SLOTS) > 1 else None)
+        slots = tuple(st[k] for k in self._SLOTS)
+        return slots if len(slots) > 1 else slots + (None,)
 
     def state_dict(self):
         sd = super().state_dict()
@@ -418,13 +440,13 @@ class _RunsOptimizer(torch.optim.Optimizer):
                 if p.device.type != "cuda" or p.dtype != torch.float32 or not p.is_contiguous():
                     raise FilError("%s: parameter %s %s on %s -- contiguous fp32 GPU tensors only" % (self._NAME, tuple(p.shape), p.dtype,
                                                                                                    p.device))
-                s0, s1 = self._slots(p, group)
+                slots = self._slots(p, group)
                 t = self._counter(p.device)
                 if pend is not None:
                     if p.grad is not None:
                         raise FilError("%s: table %s has both a .grad and a pending runs record (a gradient reached the table "
                                        "outside its gather -- e.g. a regulariser not detached)" % (self._NAME, tuple(p.shape)))
-                    self._apply_runs(lib, p, pend, s0, s1, t, hyper)
+                    self._apply_runs(lib, p, pend, *slots, t, hyper)
                     p._fil_pending_runs = None
                     continue
                 g = p.grad
@@ -433,7 +455,7 @@ class _RunsOptimizer(torch.optim.Optimizer):
                                                                                                                     tuple(p.shape)))
                 if g.dtype != torch.float32 or not g.is_contiguous() or g.shape != p.shape:
                     raise FilError("%s: gradient of %s must be a dense contiguous fp32 tensor of its shape" % (self._NAME, tuple(p.shape)))
-                per_dev.setdefault(p.device, []).append((p.data_ptr(), g.data_ptr(), ptr(s0), ptr(s1), p.numel(), 0.0))
+                per_dev.setdefault(p.device, []).append((p.data_ptr(), g.data_ptr(), *[ptr(x) for x in slots], p.numel(), 0.0))
             for dev, entries in per_dev.items():
                 calls.append((dev, hypers[dev], entries))
         # the last launch on every device advances its counter -- one with no tensors where nothing dense had a gradient
@@ -452,7 +474,7 @@ class _RunsOptimizer(torch.optim.Optimizer):
         for i, (dev, hyper, entries) in enumerate(calls):
             with torch.cuda.device(dev):
                 desc = self._desc_array(dev, entries) if entries else None
-                self._launch_dense(lib, desc, len(entries), sum(e[4] for e in entries), self._counter(dev), hyper,
+                self._launch_dense(lib, desc, len(entries), sum(e[-2] for e in entries), self._counter(dev), hyper,
                                    1 if last[dev] == i else 0)
         return loss
 
@@ -461,7 +483,9 @@ class _RunsOptimizer(torch.optim.Optimizer):
         hit = self._descs.get(key)
         if hit is not None:
             return hit[0]
-        host = (_Desc * len(entries))(*[_Desc(p, g, m, v, n, l2, 0) for p, g, m, v, n, l2 in entries])
+        # an entry: (param, grad, the slots, numel, l2) -- fil_adam_tensor, or with a third slot fil_amsgrad_tensor
+        cls = _Desc if len(entries[0]) == 6 else AmsgradTensor
+        host = (cls * len(entries))(*[cls(*e, 0) for e in entries])
         size = ctypes.sizeof(host)
         capturing = torch.cuda.is_current_stream_capturing()
         if capturing:
@@ -547,7 +571,9 @@ class Adam(_RunsOptimizer):
     _SLOTS = ("m", "v")
 
     def __init__(self, params, learning_rate=1e-3, beta_1=0.9, beta_2=0.999, epsilon=1e-7, lazy_tables=False, process_group=None,
-                 force_exchange=False, sweep_period=None, decay=0.0):
+                 force_exchange=False, sweep_period=None, decay=0.0, amsgrad=False):
+        if not isinstance(amsgrad, bool):
+            raise TypeError("Adam: amsgrad must be a bool, not %r" % (amsgrad,))
         learning_rate, decay = _check_rate("Adam", learning_rate, decay)
         if not 0.0 <= beta_1 < 1.0 or not 0.0 <= beta_2 < 1.0 or not epsilon >= 0.0:
             raise ValueError("Adam: learning_rate=%r beta_1=%r beta_2=%r epsilon=%r (rate, epsilon >= 0; betas in [0, 1))"
@@ -559,6 +585,14 @@ class Adam(_RunsOptimizer):
                 raise ValueError("Adam: sweep_period %d (1 ... %d)" % (sweep_period, MAX_SWEEP_PERIOD))
             if lazy_tables:
                 raise ValueError("Adam: sweep_period (deferred Keras mode) and lazy_tables exclude each other")
+        if amsgrad and sweep_period is not None:
+            raise ValueError("Adam: amsgrad and sweep_period exclude each other (the deferred ring and replays carry no third slot)")
+        if amsgrad and lazy_tables:
+            raise ValueError("Adam: amsgrad and lazy_tables exclude each other (the lazy mode is a labelled deviation with nothing to "
+                             "pin an AMSGrad form against)")
+        self.amsgrad = amsgrad
+        if amsgrad:
+            self._SLOTS = ("m", "v", "vhat")        # Keras' slot name; zeros
         # (set before the base class adds the parameter groups: add_param_group attaches their runs tables)
         self.sweep_period = sweep_period
         self.lazy_tables = bool(lazy_tables)
@@ -578,20 +612,35 @@ class Adam(_RunsOptimizer):
                     self._attach(p)
 
     def _slot_init(self, group):
-        return 0.0, 0.0
+        return (0.0,) * len(self._SLOTS)
 
     def _hyper(self, group, lr_dev=None, dev=None):
         return group["learning_rate"] if lr_dev is None else lr_dev, group["beta_1"], group["beta_2"], group["epsilon"]
 
     def _launch_dense(self, lib, desc, n, numel, t, hyper, advance):
+        if self.amsgrad:
+            check(lib.fil_amsgrad_multi(ptr(desc), n, numel, ptr(t), *_rate_pair(hyper[0]), *hyper[1:], advance, stream_ptr()),
+                  "fil_amsgrad_multi")
+            return
         fn, lr, name = _rated(lib, "fil_adam_multi", hyper[0])
         check(fn(ptr(desc), n, numel, ptr(t), lr, *hyper[1:], advance, stream_ptr()), name)
 
     def state_dict(self):
         self.flush()
-        return super().state_dict()
+        sd = super().state_dict()
+        if self.amsgrad:
+            sd["amsgrad"] = True
+        return sd
 
     def load_state_dict(self, state_dict):
+        state_dict = dict(state_dict)
+        flag = bool(state_dict.pop("amsgrad", False))
+        if flag != self.amsgrad:
+            raise FilError("optim.Adam: the checkpoint was taken with amsgrad=%r, this optimizer has amsgrad=%r" % (flag, self.amsgrad))
+        if self.amsgrad:
+            for k, st in state_dict.get("state", {}).items():
+                if "m" in st and "vhat" not in st:
+                    raise FilError("optim.Adam: parameter %r of the checkpoint has m but no vhat (amsgrad=True)" % (k,))
         super().load_state_dict(state_dict)
         it = int(state_dict.get("iterations", 0))
         for p, d in self._defer.items():        # deferred: a checkpoint is taken flushed -- every row is current through `it`
@@ -609,6 +658,9 @@ class Adam(_RunsOptimizer):
             self._defer[p].roll(p, hyper, FIL_ADAM_ROLL_SKIP)
 
     def _admit(self, p, pend):
+        if self.amsgrad and deferred_state(p) is not None:
+            raise FilError("optim.Adam: table %s is in another optim.Adam's deferred mode (sweep_period) -- drop that optimizer first"
+                           % (tuple(p.shape),))
         if pend is not None and self.sweep_period is not None and p not in self._defer:
             # a runs table that was not one when it joined (swept every step so far, so current): deferred from now on
             self._attach(p)
@@ -616,10 +668,36 @@ class Adam(_RunsOptimizer):
             raise FilError("optim.Adam: deferred table %s has a .grad -- with sweep_period its gradient must arrive as runs "
                            "(SparseEmbed(grad_mode='runs'))" % (tuple(p.shape),))
 
-    def _apply_runs(self, lib, p, pend, m, v, t, hyper):
+    def _apply_runs_amsgrad(self, lib, p, pend, m, v, vhat, t, hyper):
+        """amsgrad=True: fil_embed_amsgrad_runs, or with an exchange fil_embed_amsgrad_merged of the gathered lists; then
+        fil_embed_amsgrad_sweep over every row the update did not stamp (include/fil.h O7)."""
+        r, b1, b2, eps = hyper
+        lr, lr_dev = _rate_pair(r)
+        V, K = p.shape
+        stamp = self._stamp(p)
+        with torch.cuda.device(p.device):
+            st = stream_ptr()
+            world = self._exchange_world()
+            if world:
+                ids, values, counts, cap = self._compact_and_exchange(lib, p, pend, world, st)
+                check(lib.fil_embed_amsgrad_merged(ptr(ids), ptr(values), ptr(counts), world, cap, K, ptr(pend["offsets"]),
+                                                   ptr(pend["field_l2"]), pend["F"], ptr(p), ptr(m), ptr(v), ptr(vhat), ptr(stamp), V,
+                                                   ptr(t), lr, lr_dev, b1, b2, eps, st), "fil_embed_amsgrad_merged")
+            else:
+                check(lib.fil_embed_amsgrad_runs(ptr(pend["g"]), ptr(pend["perm"]), ptr(pend["sorted_ids"]), pend["R"], K,
+                                                 pend["g_dtype"], pend["F"], ptr(pend["field_l2"]), ptr(p), ptr(m), ptr(v), ptr(vhat),
+                                                 ptr(stamp), ptr(t), lr, lr_dev, b1, b2, eps, st), "fil_embed_amsgrad_runs")
+            check(lib.fil_embed_amsgrad_sweep(ptr(p), ptr(m), ptr(v), ptr(vhat), ptr(stamp), V, K, ptr(pend["offsets"]),
+                                              ptr(pend["field_l2"]), ptr(pend["frozen"]), pend["F"], ptr(t), lr, lr_dev, b1, b2, eps, st),
+                  "fil_embed_amsgrad_sweep")
+
+    def _apply_runs(self, lib, p, pend, m, v, *rest):
         """One table's step from its runs record.  The update: fil_embed_adam_runs, or with an exchange (data parallel,
         force_exchange) fil_embed_adam_merged of the gathered lists; either in its _deferred form for a deferred table.  Then the rows
         the batch did not touch: a deferred table's roll, Keras mode's sweep, nothing in lazy mode."""
+        if self.amsgrad:
+            return self._apply_runs_amsgrad(lib, p, pend, m, v, *rest)
+        t, hyper = rest
         lr, b1, b2, eps = hyper
         V, K = p.shape
         d = self._defer.get(p)
@@ -1086,6 +1164,16 @@ def runs_compact(rec, K, ids, values, count, cap, workspace):
     check(_lib.load().fil_embed_runs_compact(ptr(rec["g"]), ptr(rec["perm"]), ptr(rec["sorted_ids"]), int(rec["R"]), int(K),
                                              int(rec["g_dtype"]), ptr(ids), ptr(values), ptr(count), int(cap), ptr(workspace),
                                              workspace.numel() * workspace.element_size(), stream_ptr()), "fil_embed_runs_compact")
+
+
+def amsgrad_merged(ids, values, counts, W, cap, offsets, field_l2, table, m, v, vhat, stamp, step, lr=1e-3, beta_1=0.9, beta_2=0.999,
+                   epsilon=1e-7):
+    """fil_embed_amsgrad_merged on W gathered lists (ids [W*cap], values [W*cap*K], counts [W]); table / m / v / vhat [V, K] in
+    place; stamp [V] int32 is required."""
+    V, K = table.shape
+    check(_lib.load().fil_embed_amsgrad_merged(ptr(ids), ptr(values), ptr(counts), int(W), int(cap), K, ptr(offsets), ptr(field_l2),
+                                               offsets.numel(), ptr(table), ptr(m), ptr(v), ptr(vhat), ptr(stamp), V, ptr(step),
+                                               *_rate_pair(lr), beta_1, beta_2, epsilon, stream_ptr()), "fil_embed_amsgrad_merged")
 
 
 def adam_merged(ids, values, counts, W, cap, offsets, field_l2, table, m, v, stamp, step, lr=1e-3, beta_1=0.9, beta_2=0.999,
