@@ -125,6 +125,11 @@ def main():
                     help="also keep the reference's compiled metric, tf.keras.metrics.AUC() (metrics.AUC: 200 thresholds, stateful), "
                          "updated inside the training step -- so inside the captured graph -- over every batch; the log line then "
                          "prints the running Keras AUC beside the logged batch's exact one (data parallel: the whole group's)")
+    ap.add_argument("--keras-metrics", action="store_true",
+                    help="also keep what Keras reports for a compiled model at every batch: the running loss (metrics.Mean over the "
+                         "batch loss, the progress bar's `loss`), metrics.BinaryCrossentropy (the LogLoss of the CTR papers) and "
+                         "metrics.BinaryAccuracy, updated inside the training step -- so inside the captured graph -- and read at the "
+                         "logging steps without a launch (data parallel: the whole group's)")
     ap.add_argument("--no-graph", action="store_true",
                     help="run every step eagerly (default on one GPU: the whole step -- forward, backward, Adam -- is captured once "
                          "into a HIP graph and replayed; the C ABI neither allocates nor synchronises, so it is capture-safe)")
@@ -207,6 +212,9 @@ def main():
     else:
         opt = torch.optim.Adam(model.parameters(), lr=args.lr, eps=1e-7, capturable=use_graph)      # Keras 'adam' (un_seq.py:61)
     keras_auc = metrics.AUC().build(device) if args.keras_auc else None      # the state exists before any capture
+    # (the same for Keras' running loss, LogLoss and accuracy)
+    keras_metrics = ([metrics.Mean(name="loss").build(device), metrics.BinaryCrossentropy().build(device),
+                      metrics.BinaryAccuracy().build(device)] if args.keras_metrics else None)
     pipe = data.data_pipeline(table, batch_size=args.batch, shuffle_buffer=2048, repeat=2, prefetch=2, seed=rank, device=device)
 
     def train_step(dense, idx, y):
@@ -233,6 +241,11 @@ def main():
         opt.step()
         if keras_auc is not None:
             keras_auc.update_state(y, p)            # one launch, no host synchronisation
+        if keras_metrics is not None:               # one launch each, likewise; the launch also leaves the result
+            pc = p.detach().contiguous()            # (a column of the softmax head is a strided view: one copy for both readers)
+            keras_metrics[0].update_state(bce)
+            keras_metrics[1].update_state(y, pc)
+            keras_metrics[2].update_state(y, pc)
         return bce.detach(), p.detach()
 
     graph, static = None, None
@@ -263,6 +276,8 @@ def main():
                                 v.zero_()
                 if keras_auc is not None:
                     keras_auc.reset_states()        # the warm-up batches do not count (in place: the capture keeps the state)
+                for m in keras_metrics or ():
+                    m.reset_states()
                 graph = torch.cuda.CUDAGraph()
                 opt.zero_grad(set_to_none=True)
                 with torch.cuda.graph(graph):
@@ -277,6 +292,9 @@ def main():
             # (every rank takes part in the group read; result_value() is also where scores outside [0, 1] would raise)
             running = "" if keras_auc is None else "  keras auc (running) %.4f" % keras_auc.result_value(
                 process_group=dist.group.WORLD if world > 1 else None)
+            if keras_metrics is not None:
+                group = dist.group.WORLD if world > 1 else None
+                running += "  keras " + "  ".join("%s %.4f" % (m.name, float(m.result(process_group=group))) for m in keras_metrics)
             # (the rate of the NEXT step: the counter has advanced; computed on the device, read here)
             rate = float(opt.current_learning_rate()) if keras else args.lr
             if rank == 0:

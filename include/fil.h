@@ -837,6 +837,37 @@ int fil_confusion_update(const float* p, const float* y, int n, const float* thr
                          void* workspace, size_t workspace_bytes, void* stream);
 int fil_auc_result(const float* cm, int T, int curve, int summation, float* out, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * M2 Keras' Mean and the metrics that are a Mean of a per-sample value (TF 2.1 keras/metrics.py: Reduce / Mean / MeanMetricWrapper;
+ *     BinaryCrossentropy, BinaryAccuracy) -- the rest of what model.compile(loss=binary_crossentropy, metrics=[...]) reports per batch.
+ *     Entry points added only: the ABI version stays.  (Precision and Recall are fil_confusion_update with their own thresholds.)
+ *   State: state [3] fp32 = total | count | result.
+ *   fil_mean_update: a [n] fp32 and, except for FIL_MEAN_VALUES, y [n] fp32.  With v[i] as the kind defines it below,
+ *     state[0] += sum_i v[i] and state[1] += (float)n, each ONE fp32 addition (Keras' assign_add: the count is integer-exact below
+ *     2^24 and rounds past it), and state[2] = div_no_nan(state[0], state[1]) (the correctly rounded quotient, 0 for a zero count) is
+ *     written by the same launch: reading the result costs nothing.
+ *       FIL_MEAN_VALUES      v[i] = a[i]                                         (y may be NULL; c0, c1 unused)
+ *       FIL_MEAN_BCE         ys = c1 != 0 ? y[i] (1 - c1) + 0.5 c1 : y[i],  pc = clip(a[i], c0, 1 - c0),
+ *                            v[i] = -(ys log(pc + c0) + (1 - ys) log(1 - pc + c0))    c0 = epsilon (Keras: 1e-7), c1 = label_smoothing;
+ *                            every operation fp32, in this order, none fused (fil_bce_mean_fwd's per-sample expression)
+ *       FIL_MEAN_BINARY_ACC  v[i] = (y[i] == (a[i] > c0 ? 1.f : 0.f)) ? 1 : 0      c0 = threshold; a strict >, and a label that is
+ *                            neither 0 nor 1 never matches; counted in integers, converted once
+ *     NaN and infinity are not filtered: a NaN value makes total and result NaN, and they stay NaN (Keras asserts no range here).
+ *     The sum's order is fixed by n and the addresses' alignment alone -- per-thread sums, a fixed fold inside each wave, the waves in
+ *     wave order, the workgroups' partials by the same fold; no floating-point atomics -- so repeats from the same state on the same
+ *     inputs are bit-identical.  n <= FIL_MEAN_ONE_LAUNCH_N is one kernel launch and needs no workspace (workspace may be NULL);
+ *     larger n is a partial launch of at most 256 workgroups and a one-workgroup finishing launch, with one 4-byte partial per
+ *     workgroup in the workspace, which needs no initialisation.  1 <= n <= 2^24 (larger inputs are the caller's loop).  a, y and
+ *     state need 4-byte alignment only (16-byte loads where the addresses allow).
+ */
+#define FIL_MEAN_VALUES 0
+#define FIL_MEAN_BCE 1
+#define FIL_MEAN_BINARY_ACC 2
+#define FIL_MEAN_ONE_LAUNCH_N 16384
+size_t fil_mean_workspace_bytes(int n);
+int fil_mean_update(int kind, const float* a, const float* y, int n, float c0, float c1, float* state, void* workspace,
+                    size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -34,6 +34,8 @@ FIL_MOMOPT_NESTEROV = 1
 FIL_OPT_ADADELTA, FIL_OPT_ADAMAX = 5, 6
 FIL_OPT_NADAM = 7
 FIL_CONFUSION_MAX_T, FIL_CONFUSION_ONE_LAUNCH_N = 2048, 16384
+FIL_MEAN_VALUES, FIL_MEAN_BCE, FIL_MEAN_BINARY_ACC = 0, 1, 2
+FIL_MEAN_ONE_LAUNCH_N = 16384
 
 _c = ctypes
 _P = _c.c_void_p
@@ -154,6 +156,8 @@ SIGNATURES = {
     "fil_confusion_workspace_bytes": (_Z, [_I, _I]),
     "fil_confusion_update": (_I, [_P, _P, _I, _P, _I, _P, _P, _P, _Z, _P]),
     "fil_auc_result": (_I, [_P, _I, _I, _I, _P, _P]),
+    "fil_mean_workspace_bytes": (_Z, [_I]),
+    "fil_mean_update": (_I, [_I, _P, _P, _I, _F, _F, _P, _P, _Z, _P]),
 }
 
 

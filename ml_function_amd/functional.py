@@ -820,6 +820,42 @@ def auc_result(cm, curve="ROC", summation="interpolation", out=None):
     return out.reshape(())
 
 
+# --------------------------------------------------------------------------------------------- M2  Keras' Mean metrics
+MEAN_KINDS = {"values": _lib.FIL_MEAN_VALUES, "binary_crossentropy": _lib.FIL_MEAN_BCE, "binary_accuracy": _lib.FIL_MEAN_BINARY_ACC}
+
+
+def mean_update(kind, a, y, state, c0=0.0, c1=0.0, workspace=None):
+    """One update of a Keras Mean state (fil_mean_update): a [n] fp32 (n <= 2^24) and, except for kind "values", y [n] fp32; state
+    [3] fp32 = total | count | result updated IN PLACE: total += sum v, count += n (one fp32 addition each) and result =
+    div_no_nan(total, count), all by the same launch.  kind "values": v = a; "binary_crossentropy": Keras' per-sample loss, c0 =
+    epsilon, c1 = label_smoothing; "binary_accuracy": v = (y == (a > c0)), c0 = threshold.  No host synchronisation: capturable.
+    workspace: a uint8 tensor of fil_mean_workspace_bytes(n) bytes (none is needed up to _lib.FIL_MEAN_ONE_LAUNCH_N samples);
+    allocated here when missing."""
+    if kind not in MEAN_KINDS:
+        raise FilError("mean_update: kind %r (%s)" % (kind, ", ".join(MEAN_KINDS)))
+    _require_cuda(a, y, state)
+    if kind == "values":
+        y = None
+    elif y is None:
+        raise FilError("mean_update: kind %r needs y" % kind)
+    if a.dim() != 1 or (y is not None and a.shape != y.shape):
+        raise FilError("mean_update: a is %s, y is %s (vectors of one length)" % (tuple(a.shape), None if y is None else tuple(y.shape)))
+    a, y = _f32c(a), _f32c(y)
+    if state.dtype != torch.float32 or tuple(state.shape) != (3,) or not state.is_contiguous():
+        raise FilError("mean_update: state must be a contiguous float32 [3] tensor, got %s %s" % (state.dtype, tuple(state.shape)))
+    n = a.numel()
+    if n == 0:
+        return state
+    lib = _lib.load()
+    need = lib.fil_mean_workspace_bytes(n)
+    if need and workspace is None:
+        workspace = _scratch(need, a.device, "mean")
+    check(lib.fil_mean_update(MEAN_KINDS[kind], ptr(a), ptr(y), n, float(c0), float(c1), ptr(state), ptr(workspace),
+                              0 if workspace is None else workspace.numel() * workspace.element_size(), stream_ptr()),
+          "fil_mean_update")
+    return state
+
+
 _DISJOINT_CACHE = {}
 
 
