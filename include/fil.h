@@ -295,6 +295,44 @@ int fil_embed_run_sum_dt(const void* g, const int64_t* perm, const int64_t* sort
                          void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * N3  Pooled multi-valued sparse fields -- tf.feature_column.embedding_column(combiner=...) / tf.nn.safe_embedding_lookup_sparse
+ *     without weights, or Embedding(mask_zero=True) + a masked average (the reference's sparseFea.mask_zero / input_length,
+ *     InputFeature.seq_info / seq_inputs).  Entry points added only: the ABI version stays.
+ *   table, offsets, sizes: as N1.  idx [B,F,T] int64: T slots per sample and field.  A slot is PADDING iff id == pad_id
+ *   (FIL_BAG_NO_PAD: no id is padding; 0 = Keras' mask_zero, row 0 of every field is then never read), OUT OF RANGE iff it is not
+ *   padding and id < 0 or id >= sizes[f] (sizes NULL = ids are trusted): it contributes nothing and is counted in *oob_count (device
+ *   int, may be NULL; the caller zeroes it; padding is not counted).  Every other slot is LIVE; n(b,f) = their number (an id repeated
+ *   in a bag counts once per occurrence; padding may sit anywhere in the row).
+ *   fil_embed_bag_fwd: out[b,f,:] = (sum over the live t, ascending, of table[offsets[f] + idx[b,f,t], :]) / d, fp32 additions in that
+ *     order, then ONE correctly rounded division: FIL_BAG_SUM none, FIL_BAG_MEAN d = (float)n, FIL_BAG_SQRTN d = sqrtf((float)n);
+ *     n = 0 gives a zero row.  No reciprocal, no fused multiply-add: bit-equal to the sequential fp32 restatement.  count [B,F]
+ *     (int32) receives n.  A padding or out-of-range slot issues no table read.  One launch; ceil(K/4) lanes per bag, 16-byte row
+ *     accesses when K % 4 == 0, at most FIL_BAG_MAX_BLOCKS workgroups of 256 threads walking the bags in a grid-stride loop.
+ *   Gradient (deterministic, no atomics, no data-dependent sizes):
+ *     fil_embed_bag_row_ids   row_ids[(b F + f) T + t] = offsets[f] + idx[b,f,t], or -1 for a padding / out-of-range slot and for
+ *                             a frozen field (frozen [F] bytes, may be NULL);
+ *     (the caller sorts row_ids stably -> sorted_ids [R], slot_perm [R], R = B F T)
+ *     fil_embed_bag_bwd_prep  gs[b,f,:] = g[b,f,:] / d with the forward's d (count = the forward's; n = 0: zeros) and
+ *                             perm[j] = slot_perm[j] / T = the bag b F + f of sorted slot j (perm may be slot_perm itself), in one
+ *                             launch.  FIL_BAG_SUM: gs must be NULL (g and count are not read): the incoming rows are used as they are.
+ *     (g = gs [B F][K] fp32, perm, sorted_ids, R, F) is then a record of exactly the form fil_embed_run_sum_dt,
+ *     fil_embed_segment_sum, fil_embed_runs_compact and every fil_embed_*_runs / _merged optimizer entry point take: they read the
+ *     gradient row as g[perm[j]] and the field as perm[j] % F, and b F + f satisfies both.
+ *   B == 0 returns FIL_OK before any pointer is looked at; K <= 256 (the run sums' limit) and B F T < 2^31 (FIL_ERR_UNSUPPORTED).
+ */
+#define FIL_BAG_SUM 0
+#define FIL_BAG_MEAN 1
+#define FIL_BAG_SQRTN 2
+#define FIL_BAG_NO_PAD INT64_MIN
+#define FIL_BAG_MAX_BLOCKS 2048
+int fil_embed_bag_fwd(const float* table, const int64_t* offsets, const int64_t* sizes, const int64_t* idx, int64_t pad_id, float* out,
+                      int* count, int* oob_count, int B, int F, int T, int K, int combiner, void* stream);
+int fil_embed_bag_row_ids(const int64_t* offsets, const int64_t* sizes, const unsigned char* frozen, const int64_t* idx,
+                          int64_t pad_id, int64_t* row_ids, int B, int F, int T, void* stream);
+int fil_embed_bag_bwd_prep(const float* g, const int* count, const int64_t* slot_perm, float* gs, int64_t* perm, int B, int F, int T,
+                           int K, int combiner, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * N2  The score head and the loss behind the interaction layers (all tensors fp32, n = batch rows).
  *   ScoreLayer(use_add=True).call (kon/model/ctr_model/layer/core_layer/core_layer.py:58-84): keras Add over the [B,1] parts,
  *   then sigmoid.  fil_score_add_sigmoid_fwd: out[i] = sigmoid(((a[i] + b[i]) + c[i]) + d[i]) -- left to right like the
@@ -382,7 +420,8 @@ int fil_merge_softmax_bwd(const void* const* parts, const int* widths, const int
  *     fp32 = each run's sum in fil_embed_run_sum's order (bit-identical to the dense gradient's row), *count_out (device int64) = the
  *     number of ids; slots [count, cap) get ids INT64_MAX (a binary search over all cap entries stays valid; their values are left
  *     as they were).  cap >= R; R < 2^31.  Workspace: fil_embed_runs_compact_workspace_bytes(R).  Three launches, none sized by data
- *     (capturable); the compaction scan is integer, hence deterministic.
+ *     (capturable); the compaction scan is integer, hence deterministic.  perm may name a position more than once (a pooled
+ *     field's record, N3: every slot of a bag names the bag); sorted_ids must then ascend over the whole record.
  *   fil_embed_adam_merged: W such lists gathered back to back -- ids [W][cap], values [W][cap][K], counts [W] (device) -- applied to
  *     table / m / v [V, K] in place: every row of the union is updated once, by its owner (the lowest list holding it), with
  *     g = the row's sums added in list order 0 .. W-1 + 2 * field_l2[f] * p (f = the last field with offsets[f] <= row, as in the

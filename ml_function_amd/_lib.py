@@ -36,6 +36,9 @@ FIL_OPT_NADAM = 7
 FIL_CONFUSION_MAX_T, FIL_CONFUSION_ONE_LAUNCH_N = 2048, 16384
 FIL_MEAN_VALUES, FIL_MEAN_BCE, FIL_MEAN_BINARY_ACC = 0, 1, 2
 FIL_MEAN_ONE_LAUNCH_N = 16384
+FIL_BAG_SUM, FIL_BAG_MEAN, FIL_BAG_SQRTN = 0, 1, 2
+FIL_BAG_NO_PAD = -(1 << 63)      # INT64_MIN: no id is padding
+FIL_BAG_MAX_BLOCKS = 2048        # fil_embed_bag_fwd's grid cap (workgroups of 256 threads)
 
 _c = ctypes
 _P = _c.c_void_p
@@ -81,6 +84,10 @@ SIGNATURES = {
     "fil_embed_segment_sum": (_I, [_P, _P, _P, _P, _P, _P, _c.c_long, _I, _P]),
     "fil_embed_run_sum": (_I, [_P, _P, _P, _P, _c.c_long, _I, _P]),
     "fil_embed_run_sum_dt": (_I, [_P, _P, _P, _P, _c.c_long, _I, _I, _P]),
+    # N3: pooled multi-valued fields
+    "fil_embed_bag_fwd": (_I, [_P, _P, _P, _P, _c.c_int64, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
+    "fil_embed_bag_row_ids": (_I, [_P, _P, _P, _P, _c.c_int64, _P, _I, _I, _I, _P]),
+    "fil_embed_bag_bwd_prep": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
     "fil_score_add_sigmoid_fwd": (_I, [_P, _P, _P, _P, _P, _I, _P]),
     "fil_score_add_sigmoid_bwd": (_I, [_P, _P, _P, _I, _P]),
     "fil_bce_mean_fwd": (_I, [_P, _P, _F, _P, _P, _I, _P]),

@@ -12,7 +12,10 @@ namespace fil {
 //   write  every workgroup sums the counts of the tiles before it (and of all tiles: the total), scans its own starts in position
 //          order and writes ids_out[u] = id and slot[perm of the start] = u; the slots [count, cap) get INT64_MAX, count_out the total;
 //   sums   embed_run_sums with an epilogue that stores the row into values_out[slot[perm of the run's first element]].
-// perm holds each position b*F + f exactly once (< R), so the slot map needs R entries.  Integer scans: deterministic.
+// A one-id record's perm holds each position b*F + f exactly once (< R), so the slot map needs R entries and no two runs share one.
+// A pooled field's record (embed_bag.hip) names the BAG in perm, once per slot: two runs that start with slots of one bag then write
+// the same map entry.  The epilogue therefore checks ids_out[slot] against the run's row and, where another run's slot sits there,
+// looks the row up in ids_out (ascending, padded with INT64_MAX: a binary search over all cap entries).  Integer scans: deterministic.
 constexpr int kCompactPer = 8;
 constexpr int kCompactTile = 256 * kCompactPer;
 
@@ -72,11 +75,21 @@ __global__ __launch_bounds__(256) void runs_write_kernel(const int64_t* __restri
 template <typename GT>
 __global__ __launch_bounds__(256) void runs_compact_sums_kernel(const GT* __restrict__ g, const int64_t* __restrict__ perm,
                                                                 const int64_t* __restrict__ sorted_ids, long R, int K,
-                                                                const int32_t* __restrict__ slot, long cap, float* __restrict__ values_out) {
-  embed_run_sums(g, perm, sorted_ids, R, K, [=](int64_t, int kq, const float (&acc)[4], int64_t first) {
+                                                                const int32_t* __restrict__ slot, long cap,
+                                                                const int64_t* __restrict__ ids_out, float* __restrict__ values_out) {
+  embed_run_sums(g, perm, sorted_ids, R, K, [=](int64_t row, int kq, const float (&acc)[4], int64_t first) {
     if ((uint64_t)first >= (uint64_t)R) return;
-    const long u = slot[first];
+    long u = slot[first];
     if (u < 0 || u >= cap) return;
+    if (ids_out[u] != row) {       // (a perm entry shared by several runs: the map holds another run's slot)
+      long lo = 0, hi = cap;
+      while (lo < hi) {
+        const long mid = lo + (hi - lo) / 2;
+        if (ids_out[mid] < row) lo = mid + 1; else hi = mid;
+      }
+      if (lo >= cap || ids_out[lo] != row) return;
+      u = lo;
+    }
 #pragma unroll
     for (int i = 0; i < 4; ++i)
       if (kq * 4 + i < K) values_out[u * K + kq * 4 + i] = acc[i];
@@ -125,10 +138,10 @@ extern "C" int fil_embed_runs_compact(const void* g, const int64_t* perm, const 
   const dim3 grid = run_sums_grid(R, K);
   if (g_dtype == FIL_F32)
     hipLaunchKernelGGL(runs_compact_sums_kernel<float>, grid, dim3(256), 0, st, static_cast<const float*>(g), perm, sorted_ids, R, K, slot,
-                       cap, values_out);
+                       cap, ids_out, values_out);
   else
     hipLaunchKernelGGL(runs_compact_sums_kernel<__hip_bfloat16>, grid, dim3(256), 0, st, static_cast<const __hip_bfloat16*>(g), perm,
-                       sorted_ids, R, K, slot, cap, values_out);
+                       sorted_ids, R, K, slot, cap, ids_out, values_out);
   FIL_CHECK_LAUNCH();
   return FIL_OK;
 }

@@ -1050,3 +1050,107 @@ def embed_gather(table, offsets, idx, sizes=None, frozen=None, sparse_grad=False
     out._fil_xt = xt
     out._fil_xt_version = out._version      # a consumer ignores xt once the block has been modified in place
     return out
+
+
+# --------------------------------------------------------------------------------------------- N3  pooled multi-valued fields
+BAG_COMBINERS = {"sum": _lib.FIL_BAG_SUM, "mean": _lib.FIL_BAG_MEAN, "sqrtn": _lib.FIL_BAG_SQRTN}
+
+
+def _bag_combiner(combiner):
+    if combiner not in BAG_COMBINERS:
+        raise ValueError("embed_bag: combiner %r (%s)" % (combiner, ", ".join(BAG_COMBINERS)))
+    return BAG_COMBINERS[combiner]
+
+
+class _EmbedBagFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, table, offsets, sizes, idx, combiner, pad_id, frozen, sparse_grad, oob_count, runs_grad):
+        _require_cuda(table, offsets, idx, sizes, frozen, oob_count)
+        if idx.dim() != 3:
+            raise FilError("embed_bag: idx must be [B, F, T], got %s" % (tuple(idx.shape),))
+        if deferred_state(table) is not None:
+            raise FilError("embed_bag: the table is in deferred Keras mode (optim.Adam(sweep_period=N)); a pooled field's rows are not "
+                           "brought current by its forward -- deferred Adam on bag tables is not supported")
+        if runs_grad is not None and sparse_grad:
+            raise FilError("embed_bag: grad_mode='runs' excludes sparse_grad")
+        ctx.runs_grad = runs_grad
+        ctx.table_param = table if runs_grad is not None else None
+        table = _f32c(table)
+        idx = idx.to(torch.int64).contiguous()
+        offsets = offsets.to(torch.int64).contiguous()
+        B, F, T = idx.shape
+        K = table.shape[1]
+        if offsets.numel() != F:
+            raise FilError("embed_bag: idx has %d fields, offsets %d" % (F, offsets.numel()))
+        out = torch.empty((B, F, K), dtype=torch.float32, device=table.device)
+        count = torch.empty((B, F), dtype=torch.int32, device=table.device)
+        check(_lib.load().fil_embed_bag_fwd(ptr(table), ptr(offsets), ptr(sizes), ptr(idx), pad_id, ptr(out), ptr(count), ptr(oob_count),
+                                            B, F, T, K, combiner, stream_ptr()), "fil_embed_bag_fwd")
+        ctx.save_for_backward(offsets, idx, count, *[t for t in (sizes, frozen) if t is not None])
+        ctx.cfg = (tuple(table.shape), sizes is not None, frozen is not None, bool(sparse_grad), combiner, pad_id)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        table_shape, has_sizes, has_frozen, sparse_grad, combiner, pad_id = ctx.cfg
+        sv = list(ctx.saved_tensors)
+        offsets, idx, count = sv[:3]
+        rest = sv[3:]
+        sizes = rest.pop(0) if has_sizes else None
+        frozen = rest.pop(0) if has_frozen else None
+        B, F, T = idx.shape
+        K = table_shape[1]
+        R = B * F * T
+        lib = _lib.load()
+        g = _f32c(g)
+        table = ctx.table_param
+        if table is not None and getattr(table, "_fil_pending_runs", None) is not None:
+            raise FilError("embed_bag(grad_mode='runs'): the table already holds a pending gradient record -- one backward per "
+                           "table per optimizer step (call optimizer.step() or zero_grad() in between)")
+        # the slots' global row ids, their stable sort (plumbing: torch's; 32-bit keys when the row ids fit, as the one-id gradient's
+        # global sort), then one launch: the rows divided by the forward's divisor and every sorted slot mapped back to its bag
+        row_ids = torch.empty(R, dtype=torch.int64, device=g.device)
+        check(lib.fil_embed_bag_row_ids(ptr(offsets), ptr(sizes), ptr(frozen), ptr(idx), pad_id, ptr(row_ids), B, F, T, stream_ptr()),
+              "fil_embed_bag_row_ids")
+        if has_sizes and table_shape[0] < 2 ** 31 and R > 0:
+            s32, perm = torch.sort(row_ids.to(torch.int32), stable=True)
+            sorted_ids = s32.to(torch.int64)
+        else:
+            sorted_ids, perm = torch.sort(row_ids, stable=True)
+        gs = g if combiner == _lib.FIL_BAG_SUM else torch.empty_like(g)
+        check(lib.fil_embed_bag_bwd_prep(ptr(g), ptr(count), ptr(perm), None if gs is g else ptr(gs), ptr(perm), B, F, T, K, combiner,
+                                         stream_ptr()), "fil_embed_bag_bwd_prep")
+        if table is not None:     # the optimizer applies the runs in place: a record of the form embed_gather's backward leaves
+            table._fil_pending_runs = dict(g=gs, perm=perm, sorted_ids=sorted_ids, R=R, K=K, F=F, g_dtype=FIL_F32, **ctx.runs_grad)
+            dtable = None
+        elif sparse_grad:         # the touched rows only: the record compacted by the dense gradient's own walk (the same bits)
+            cap = max(R, 1)
+            rows = torch.empty(cap, dtype=torch.int64, device=g.device)
+            values = torch.empty((cap, K), dtype=torch.float32, device=g.device)
+            n_rows = torch.zeros(1, dtype=torch.int64, device=g.device)
+            if R > 0:
+                ws = _scratch(lib.fil_embed_runs_compact_workspace_bytes(R), g.device, "embed_bag_compact")
+                check(lib.fil_embed_runs_compact(ptr(gs), ptr(perm), ptr(sorted_ids), R, K, FIL_F32, ptr(rows), ptr(values), ptr(n_rows), cap,
+                                                 ptr(ws), ws.numel(), stream_ptr()), "fil_embed_runs_compact")
+            u = int(n_rows)       # (a sparse tensor has a data-dependent shape: this path synchronises, as embed_gather's does)
+            dtable = torch.sparse_coo_tensor(rows[:u].unsqueeze(0), values[:u], table_shape)
+        else:                     # dense table, deterministic, no data-dependent shapes (HIP-graph capturable)
+            dtable = torch.zeros(table_shape, dtype=torch.float32, device=g.device)
+            check(lib.fil_embed_run_sum_dt(ptr(gs), ptr(perm), ptr(sorted_ids), ptr(dtable), R, K, FIL_F32, stream_ptr()),
+                  "fil_embed_run_sum_dt")
+        return dtable, None, None, None, None, None, None, None, None, None
+
+
+def embed_bag(table, offsets, idx, sizes=None, combiner="mean", padding_id=0, frozen=None, sparse_grad=False, oob_count=None,
+              runs_grad=None):
+    """Pooled multi-valued fields (tf.nn.safe_embedding_lookup_sparse without weights): table [sum V_f, K], offsets [F], idx [B,F,T]
+    (T padded slots per sample and field) -> [B,F,K] = combiner over each bag's live rows, in one launch (fil_embed_bag_fwd).
+    A slot is padding iff its id == padding_id (default 0, Keras' mask_zero: row 0 of a field is never read or updated; None: no
+    id is padding).  With sizes [F] int64, a non-padding id outside [0, V_f) contributes nothing, is counted in oob_count (an int32
+    device scalar) and gets no gradient.  combiner: "sum"; "mean" = the sum divided by the number n of live slots; "sqrtn" = divided
+    by sqrt(n); n = 0 gives a zero row.  fp32 additions in slot order and one division: bit-equal to the sequential restatement.
+    The gradient is deterministic (the slots' sorted run sums, no atomics): a dense table by default, a sparse COO tensor over the
+    touched rows with sparse_grad=True; runs_grad (embed_gather's dict) leaves the record on the table as `_fil_pending_runs` for
+    the fused optimizers of ml_function_amd.optim instead.  frozen [F] uint8: fields whose rows get no gradient."""
+    pad = _lib.FIL_BAG_NO_PAD if padding_id is None else int(padding_id)
+    return _EmbedBagFn.apply(table, offsets, sizes, idx, _bag_combiner(combiner), pad, frozen, sparse_grad, oob_count, runs_grad)

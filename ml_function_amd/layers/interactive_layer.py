@@ -506,3 +506,55 @@ class SparseEmbed(Layer):
             masks = [(idx[:, f:f + 1] != 0) for f in range(idx.shape[1])]
             return embed_list, masks
         return embed_list
+
+
+class BagEmbed(SparseEmbed):
+    """Pooled multi-valued sparse fields (extension): what TF 2.1 builds with tf.feature_column.embedding_column(combiner=...) --
+    tf.nn.safe_embedding_lookup_sparse -- or with Embedding(mask_zero=True) and a masked average: a movie's genres, an ad's tags,
+    the last T items a user clicked, pooled to ONE [B,1,K] tensor per field, so every zoo body consumes it like a one-id field.
+
+    sparse_info: as SparseEmbed's (make_seq_info sets mask_zero / input_length the way the reference's descriptors carry them);
+    build() is SparseEmbed's, unchanged: one concatenated table, offsets, sizes, frozen fields, emb_reg, the runs-table mark.
+    call(idx [B,F,T] integer tensor, or a list of F [B,T]) -> list of F tensors [B,1,K] (views of the packed block; [B,K] with
+    use_flatten; the block itself with packed=True).  combiner "sum" | "mean" | "sqrtn" over a bag's live slots; a slot whose id
+    == padding_id (default 0 = Keras' mask_zero: row 0 of each field's table is never read or updated; None: no padding id) is
+    padding, wherever it sits in the row; a bag without live slots gives a zero row.  Ids outside [0, word_size) contribute nothing
+    (check_ids=True raises, as SparseEmbed).  Gather and reduction are one launch (Fn.embed_bag); sparse_grad and grad_mode="runs"
+    as SparseEmbed's -- every ml_function_amd.optim class updates a bag table in place, except Adam(sweep_period=N) (the call raises
+    FilError)."""
+
+    def __init__(self, sparse_info: list, combiner="mean", padding_id=0, is_linear=False, use_flatten=False, seed=2020, packed=False,
+                 check_ids=None, sparse_grad=False, grad_mode="dense"):
+        super().__init__(sparse_info, is_linear=is_linear, use_flatten=use_flatten, seed=seed, packed=packed, check_ids=check_ids,
+                         sparse_grad=sparse_grad, grad_mode=grad_mode)
+        if combiner not in Fn.BAG_COMBINERS:
+            raise ValueError("BagEmbed: combiner %r (%s)" % (combiner, ", ".join(Fn.BAG_COMBINERS)))
+        if padding_id is not None and (isinstance(padding_id, bool) or not isinstance(padding_id, int)):
+            raise ValueError("BagEmbed: padding_id %r (an int, or None for no padding id)" % (padding_id,))
+        self.combiner = combiner
+        self.padding_id = padding_id
+
+    def call(self, inputs, **kwargs):
+        idx = torch.stack([t.reshape(t.shape[0], -1) for t in inputs], dim=1) if isinstance(inputs, (list, tuple)) else inputs
+        if idx.dim() != 3 or idx.shape[1] != len(self.sparse_info):
+            raise ValueError("BagEmbed: ids must be [B, %d, T] (or a list of %d [B, T] tensors), got %s"
+                             % (len(self.sparse_info), len(self.sparse_info), tuple(idx.shape)))
+        idx = idx.to(torch.int64)
+        oob = torch.zeros((), dtype=torch.int32, device=idx.device) if self.check_ids else None
+        block = Fn.embed_bag(self.embeddings, self.offsets, idx, sizes=self.sizes, combiner=self.combiner, padding_id=self.padding_id,
+                             frozen=self.frozen, sparse_grad=self.sparse_grad, oob_count=oob,
+                             runs_grad=(dict(offsets=self.offsets, frozen=self.frozen, field_l2=self.field_l2)
+                                        if self.grad_mode == "runs" else None))  # [B,F,K]
+        if oob is not None and int(oob) > 0:
+            bad = (idx < 0) | (idx >= self.sizes.view(1, -1, 1))
+            if self.padding_id is not None:
+                bad &= idx != self.padding_id
+            b, f, t = bad.nonzero()[0].tolist()
+            raise IndexError("BagEmbed: %d ids outside their vocabulary, first at sample %d, field %s, slot %d (id %d, word_size %d)"
+                             % (int(oob), b, self.sparse_info[f].fea_name, t, int(idx[b, f, t]), int(self.sizes[f])))
+        if self.packed:
+            return block
+        embed_list = list(block.split(1, dim=1))  # F x [B,1,K]
+        if self.use_flatten:
+            embed_list = [e.reshape(e.shape[0], -1) for e in embed_list]
+        return embed_list

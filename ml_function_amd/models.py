@@ -9,7 +9,7 @@ from collections import namedtuple
 
 import torch
 
-from .layers import (CIN, AttentionBaseLayer, CrossLayer, DnnLayer, FmLayer, InnerLayer, IPnnLayer, MergeScoreLayer,
+from .layers import (CIN, AttentionBaseLayer, BagEmbed, CrossLayer, DnnLayer, FmLayer, InnerLayer, IPnnLayer, MergeScoreLayer,
                      MultHeadAttentionLayer, OPnnLayer, ScoreLayer, SparseEmbed, StackLayer)
 from .layers.base import Layer
 from .layers.interactive_layer import pack_fields
@@ -26,6 +26,14 @@ def make_sparse_info(word_sizes, embed_dim=8, linear_dim=1, names=None, batch_si
     return [sparseFea(fea_name=n, word_size=int(v), input_dim=None, cross_unit=embed_dim, linear_unit=linear_dim, pre_weight=None,
                       mask_zero=False, is_trainable=True, input_length=1, sample_num=None, batch_size=batch_size, emb_reg=1e-8)
             for n, v in zip(names, word_sizes)]
+
+
+def make_seq_info(word_sizes, input_length, embed_dim=8, linear_dim=1, names=None, batch_size=None):
+    """sparseFea descriptors of multi-valued (pooled) fields: make_sparse_info's, with mask_zero=True (id 0 is padding) and
+    input_length = the number T of slots per sample, the way the reference's descriptors carry them (data_prepare.py:59)."""
+    names = names or ["S%d" % (i + 1) for i in range(len(word_sizes))]
+    return [i._replace(mask_zero=True, input_length=int(input_length))
+            for i in make_sparse_info(word_sizes, embed_dim=embed_dim, linear_dim=linear_dim, names=names, batch_size=batch_size)]
 
 
 class InputFeature(object):
@@ -46,30 +54,56 @@ class InputFeature(object):
 
 class FeatureInput(Layer):
     """data_prepare.FeatureInput (data_prepare.py:65-76): embeds the sparse ids (cross embeddings [B,1,K] per field,
-    optional linear embeddings) and passes the dense columns through as F_d tensors [B,1]."""
+    optional linear embeddings) and passes the dense columns through as F_d tensors [B,1].  With seqInfo (multi-valued fields,
+    make_seq_info) the call takes (dense, sparse_idx, seq_idx [B, F_seq, T]) and appends one pooled embedding per such field."""
 
     def __init__(self, sparseInfo=None, denseInfo=None, useLinear=False, useAddLinear=False, useFlattenLinear=False,
-                 useFlattenSparse=False, emitXT=False, embedDtype=None, tableGrad="dense"):
+                 useFlattenSparse=False, emitXT=False, embedDtype=None, tableGrad="dense", seqInfo=None, seqCombiner="mean"):
         super().__init__()
         self.sparse_info = sparseInfo or []
         self.dense_info = denseInfo or []
+        self.seq_info = seqInfo or []
         self.use_linear = useLinear
+        self.use_add_linear = useAddLinear
         # emitXT (extension): the embedding gather also writes the block in the layout the CIN kernels read (XDeepFM)
         # embedDtype (extension): torch.bfloat16 = the cross embeddings leave the gather as bf16 (a bf16 model's cast of the block, fused)
         # tableGrad (extension): "runs" = the tables' gradients go to ml_function_amd.optim.Adam, .Adagrad or .Ftrl as the batch's
         # sorted runs and are applied in place (SparseEmbed(grad_mode="runs")); "dense" (default) = a [V,K] gradient tensor per table
+        # seqInfo / seqCombiner (extension): multi-valued fields (make_seq_info), pooled to one embedding per field by
+        # layers.BagEmbed and appended to the one-id fields' embeddings (and linear terms); their tables follow tableGrad too
+        if self.seq_info and emitXT:
+            raise ValueError("FeatureInput: seqInfo and emitXT exclude each other (the transposed block holds the one-id fields only)")
         self.sparse_embed = (SparseEmbed(self.sparse_info, use_flatten=useFlattenSparse, emit_xt=emitXT, out_dtype=embedDtype,
                                          grad_mode=tableGrad) if self.sparse_info else None)
         self.linear_embed = (SparseEmbed(self.sparse_info, use_flatten=useFlattenLinear, is_linear=True, use_add=useAddLinear,
                                          grad_mode=tableGrad) if (useLinear and self.sparse_info) else None)
+        self.seq_embed = (BagEmbed(self.seq_info, combiner=seqCombiner, use_flatten=useFlattenSparse, grad_mode=tableGrad)
+                          if self.seq_info else None)
+        self.seq_linear_embed = (BagEmbed(self.seq_info, combiner=seqCombiner, use_flatten=useFlattenLinear, is_linear=True,
+                                          grad_mode=tableGrad) if (useLinear and self.seq_info) else None)
 
     def call(self, inputs, **kwargs):
-        dense, sparse_idx = inputs
+        dense, sparse_idx, seq_idx = inputs if len(inputs) == 3 else (*inputs, None)
+        if (seq_idx is not None) != bool(self.seq_info):
+            raise ValueError("FeatureInput: seqInfo describes %d multi-valued fields but the call %s"
+                             % (len(self.seq_info), "has no seq_idx" if seq_idx is None else "passes seq_idx"))
         dense_inputs = [] if dense is None else [dense[:, i:i + 1] for i in range(dense.shape[1])]
         sparse_inputs = [] if sparse_idx is None else [sparse_idx[:, i:i + 1] for i in range(sparse_idx.shape[1])]
         linear = self.linear_embed(sparse_idx) if self.linear_embed is not None else None
         embed = self.sparse_embed(sparse_idx) if self.sparse_embed is not None else None
-        return InputFeature(self.dense_info, self.sparse_info, None, dense_inputs, sparse_inputs, [], linear, embed, [None, None])
+        if seq_idx is None:
+            return InputFeature(self.dense_info, self.sparse_info, None, dense_inputs, sparse_inputs, [], linear, embed, [None, None])
+        seq_inputs = [seq_idx[:, i] for i in range(seq_idx.shape[1])]
+        embed = list(embed or []) + self.seq_embed(seq_idx)
+        if self.seq_linear_embed is not None:
+            seq_linear = self.seq_linear_embed(seq_idx)
+            if self.use_add_linear:      # one summed linear term (Keras Add): the pooled fields' terms join the sum
+                pooled = torch.stack(seq_linear, 0).sum(0)
+                linear = pooled if linear is None else linear + pooled
+            else:
+                linear = list(linear or []) + seq_linear
+        return InputFeature(self.dense_info, self.sparse_info, self.seq_info, dense_inputs, sparse_inputs, seq_inputs, linear, embed,
+                            [None, None])
 
 
 class FM(torch.nn.Module):
@@ -236,12 +270,15 @@ class AutoInt(torch.nn.Module):
 
 
 class CTRModel(torch.nn.Module):
-    """FeatureInput + zoo body on raw batch tensors: model(dense [B, n_dense] or None, sparse_ids [B, F])."""
+    """FeatureInput + zoo body on raw batch tensors: model(dense [B, n_dense] or None, sparse_ids [B, F]), and with multi-valued
+    fields (FeatureInput(seqInfo=...)) model(dense, sparse_ids, seq_ids [B, F_seq, T])."""
 
     def __init__(self, feature_input, body):
         super().__init__()
         self.feature_input = feature_input
         self.body = body
 
-    def forward(self, dense, sparse_idx):
-        return self.body(self.feature_input((dense, sparse_idx)))
+    def forward(self, dense, sparse_idx, seq_idx=None):
+        if seq_idx is None:
+            return self.body(self.feature_input((dense, sparse_idx)))
+        return self.body(self.feature_input((dense, sparse_idx, seq_idx)))
