@@ -213,11 +213,22 @@ int fil_cin_bwd_p(const float* x, const float* const* W, const float* const* bia
  *       scores, weighted sums and their gradients) are rounded to fp16 and multiplied on v_mfma_f32_16x16x16_f16 with
  *       fp32 accumulation; sigmoid, LayerNorm, residual, ReLU, all tensors in memory and all reductions stay fp32.
  *       Parity of that mode is ~1e-3 (tests state 5e-3 / 2e-2); values beyond the fp16 range (65504) overflow.
- *   Limits: K <= 64, A <= 16, H <= 8, F <= 512 (and the LDS footprint <= 160 KiB).
+ *   Limits: K <= 64, A <= 16, H <= 8, F <= 512, AND the kernel's dynamic LDS footprint <= 163,328 bytes (the CU's 160 KiB less the
+ *       kernels' static arrays, rounded to the allocation granule).  The footprint grows with H and F (f16: also with K), and the
+ *       backward's is the larger one: in FIL_PREC_F32 with H = 8 the forward runs up to F = 240 and the backward up to F = 128; with
+ *       H = 4 up to F = 496 / 384.  FIL_PREC_F16_MFMA, K = 64: the backward runs up to F = 208 at H = 8 and F = 480 at H = 4.  A shape
+ *       past the limit returns FIL_ERR_UNSUPPORTED before anything is launched or written.
+ *   fil_attn_plan: which instantiation fil_attn_fwd / fil_attn_bwd launch for a shape, from the same host function the launchers
+ *       use (no GPU call, no allocation; the environment knobs FIL_ATTN_KREG / FIL_ATTN_WPH / FIL_ATTN_DX_LDS apply as they do to the
+ *       launch).  plan[10] = {fwd_ok, fwd_kreg (k fragments in registers), fwd_a16 (A == 16 form), fwd_lds_bytes,
+ *       bwd_ok, bwd_nb (key-block menu entry 4 / 8 / 13 / 32), bwd_wph (waves per head), bwd_dx_lds (dx image in LDS),
+ *       bwd_a16, bwd_lds_bytes}; *_ok = 0 where the LDS footprint (then of the smallest configuration) exceeds the limit.  Returns
+ *       FIL_OK, or the argument / menu error the launch would give.  Entry point added only: the ABI version stays.
  */
 enum fil_cin_mode_bits { FIL_CIN_GENERAL = 1, FIL_CIN_BF16X3 = 2, FIL_CIN_MB2 = 4, FIL_CIN_NOSYM = 8, FIL_CIN_X_TRANSPOSED = 16,
                          FIL_CIN_NOTAIL = 32, FIL_CIN_TAIL_ALWAYS = 64, FIL_CIN_NOKSPLIT = 128, FIL_CIN_NOQTAIL = 256, FIL_CIN_NOQMERGE = 512 };
 enum fil_precision { FIL_PREC_F32 = 0, FIL_PREC_F16_MFMA = 1 };
+int fil_attn_plan(int F, int K, int H, int A, int precision, int* plan /* [10] */);
 size_t fil_attn_fwd_workspace_bytes(int B, int F, int K, int H, int A);
 size_t fil_attn_bwd_workspace_bytes(int B, int F, int K, int H, int A, int have_saved);
 int fil_attn_fwd(const float* x, const float* Wq, const float* Wk, const float* Wr, const float* gamma,

@@ -69,6 +69,7 @@ SIGNATURES = {
     "fil_cin_shortdx_used": (_I, [_I, _I, _I, _I, _P, _I, _I, _I]),
     "fil_cin_fwd_p": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _I, _I, _I, _P, _Z, _P]),
     "fil_cin_bwd_p": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _I, _I, _I, _P, _P, _Z, _P]),
+    "fil_attn_plan": (_I, [_I, _I, _I, _I, _I, _P]),
     "fil_attn_fwd_workspace_bytes": (_Z, [_I, _I, _I, _I, _I]),
     "fil_attn_bwd_workspace_bytes": (_Z, [_I, _I, _I, _I, _I, _I]),
     "fil_attn_fwd": (_I, [_P] * 10 + [_I, _I, _I, _I, _I, _F, _F, _I, _I, _I, _P, _Z, _P]),

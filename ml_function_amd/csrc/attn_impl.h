@@ -926,7 +926,11 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(FIL_ATTN_BW
         for (int s = 0; s < 4; ++s) {
           dgam[s] = fmaf(dz[s], xh[s], dgam[s]);
           dbet[s] += dz[s];
-          dxh[s] = dz[s] * gam[s];
+          // the product is rounded ONCE, behind an empty asm: contracted into s1 and into dxh - m1 below, the two would see different
+          // products, and a row of one element (A = 1: dxh == m1, a zero gradient) would leave rstd = 31.6 x the rounding error
+          float dzg = dz[s] * gam[s];
+          asm("" : "+v"(dzg));
+          dxh[s] = dzg;
           s1 += dxh[s];
           s2 = fmaf(dxh[s], xh[s], s2);
         }
@@ -974,7 +978,10 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(FIL_ATTN_BW
         for (int r = 0; r < 4; ++r) {
           const float e = __builtin_amdgcn_exp2f(sc[r]);        // exp(-score)
           sg[r] = __builtin_amdgcn_rcpf(1.0f + e);
-          dp[r] = ds[r] * (e * sg[r] * sg[r]);                  // dS S (1-S), 1-S = e S; the 1/sqrt(A) factor rides on qc and dq
+          // dS S (1-S) with S (1-S) = S - S^2; the 1/sqrt(A) factor rides on qc and dq.  (Not e S^2: a score below -88.7 overflows e
+          // to inf with S = 0, and inf * 0 is NaN -- one saturated score poisoned the sample's whole dx.  One packed fma for two
+          // packed multiplies; the absolute error of S (1-S) stays below an ulp of S, 6e-8.)
+          dp[r] = ds[r] * fmaf(-sg[r], sg[r], sg[r]);
         }
         const Op dp_o = to_op<F16>(dp), sg_o = to_op<F16>(sg);
         sc_n = mma<F16>(qn, kB_n, f32x4{0.f, 0.f, 0.f, 0.f});
@@ -1419,7 +1426,7 @@ struct AttnBwdLaunch {
   float scale, eps;
   int fuse_relu;
   long long* stamps;
-  int wph, dx_lds;
+  int nb, wph, dx_lds, a16;   // the instantiation plan_bwd chose: key-block menu entry, waves per head, dx image in LDS, A == 16 form
   size_t sh;
   hipStream_t st;
 };
@@ -1439,7 +1446,7 @@ int attn_launch_bwd_f32(const AttnBwdLaunch& a, int* G_out) {
   float *dx = a.dx, *wpart = a.wpart, *gb_part = a.gb_part;
   const AttnDims& d = a.d;
   const float scale = a.scale, eps = a.eps;
-  const int fuse_relu = a.fuse_relu, wph = a.wph, dx_lds = a.dx_lds, H = a.d.H;
+  const int fuse_relu = a.fuse_relu, nb = a.nb, wph = a.wph, dx_lds = a.dx_lds, a16 = a.a16, H = a.d.H;
   long long* g_attn_stamps = a.stamps;
   const size_t sh = a.sh;
   hipStream_t st = a.st;
@@ -1475,18 +1482,18 @@ int attn_launch_bwd_f32(const AttnBwdLaunch& a, int* G_out) {
 // (the attention_dim == 16 form -- one 16-byte access per row piece, no column masks -- exists for the large-F instantiations, where
 // the per-block prologue is a measurable part of the kernel; small shapes take the general form)
 #define CALL_BWD_NBD(N, P, NBV, WV, DX) \
-  if (NBV >= 13 && d.A == 16) { CALL_BWD_NBDA(N, P, NBV, WV, DX, (NBV >= 13)); } else { CALL_BWD_NBDA(N, P, NBV, WV, DX, false); }
+  if (NBV >= 13 && a16) { CALL_BWD_NBDA(N, P, NBV, WV, DX, (NBV >= 13)); } else { CALL_BWD_NBDA(N, P, NBV, WV, DX, false); }
 #define CALL_BWD_NB(N, P, NBV, WV) \
   if (dx_lds) { CALL_BWD_NBD(N, P, NBV, WV, true); } else { CALL_BWD_NBD(N, P, NBV, WV, false); }
   // (the two-waves-per-head form exists for the large-F instantiations only: smaller shapes fit two workgroups per CU)
 #ifdef FIL_ATTN_DEV
 #define CALL_BWD(N, P) \
-  if (d.nblk > 8 && d.nblk <= 13 && dx_lds) { if (wph == 2) { CALL_BWD_NBD(N, P, 13, 2, true); } else { CALL_BWD_NBD(N, P, 13, 1, true); } }
+  if (nb == 13 && dx_lds) { if (wph == 2) { CALL_BWD_NBD(N, P, 13, 2, true); } else { CALL_BWD_NBD(N, P, 13, 1, true); } }
 #else
 #define CALL_BWD(N, P)                                                                     \
-  if (d.nblk <= 4) { CALL_BWD_NB(N, P, 4, 1); }                                            \
-  else if (d.nblk <= 8) { CALL_BWD_NB(N, P, 8, 1); }                                       \
-  else if (d.nblk <= 13) { if (wph == 2) { CALL_BWD_NB(N, P, 13, 2); } else { CALL_BWD_NB(N, P, 13, 1); } } \
+  if (nb == 4) { CALL_BWD_NB(N, P, 4, 1); }                                                \
+  else if (nb == 8) { CALL_BWD_NB(N, P, 8, 1); }                                           \
+  else if (nb == 13) { if (wph == 2) { CALL_BWD_NB(N, P, 13, 2); } else { CALL_BWD_NB(N, P, 13, 1); } } \
   else { if (wph == 2) { CALL_BWD_NB(N, P, 32, 2); } else { CALL_BWD_NB(N, P, 32, 1); } }
 #endif
     FIL_ATTN_NC_P(d.NC, CALL_BWD)
@@ -1509,17 +1516,85 @@ namespace fil {
 // diagnostic builds (-DFIL_ATTN_STAMPS): device buffer the backward writes its per-phase clocks to (fil_attn_debug_stamps)
 static long long* g_attn_stamps = nullptr;
 
-static int launch_fwd(const float* x, const float* Wq, const float* Wk, const float* Wr, const float* gamma, const float* beta,
-                      float* y, float* res_out, float* av_out, float* rstd_out, const AttnDims& d, float scale, float eps,
-                      int fuse_relu, bool f16, hipStream_t st) {
+// ---- which instantiation a shape takes: decided here, once, for the launchers, fil_attn_plan and (through it) the layer and the tests.
+// Pure host arithmetic: no GPU call, no allocation, no occupancy query (the grid size is the launcher's).
+struct AttnFwdPlan {
+  bool ok, kreg, a16;   // ok: the dynamic LDS fits; kreg: k fragments in registers (f16, up to 13 key tiles); a16: the A == 16 form
+  size_t sh;            // dynamic LDS bytes (what the launch would need when !ok)
+};
+struct AttnBwdPlan {
+  bool ok;
+  int nb, wph, dx_lds, a16;   // key-block menu entry 4 / 8 / 13 / 32, waves per head, dx image in LDS, A == 16 form (NB >= 13 only)
+  size_t sh;                  // dynamic LDS bytes (!ok: of the smallest configuration, one wave per head without the dx image)
+};
+
+static AttnFwdPlan plan_fwd(const AttnDims& d, bool f16) {
   // f16 mode, up to 13 key tiles: the k fragments live in registers (no k image in LDS; FIL_ATTN_KREG=0 keeps the image)
   static const int kreg_knob = [] {
     const char* e = getenv("FIL_ATTN_KREG");
     return e != nullptr ? atoi(e) : 1;
   }();
-  const bool kreg = f16 && d.nblk <= 13 && kreg_knob != 0;
-  const size_t sh = kreg ? (size_t)d.NC * d.FP * 16 * sizeof(_Float16) : fwd_lds(d, f16);
-  if (sh > kLdsCap) return fail(FIL_ERR_UNSUPPORTED, "fil_attn_fwd: F=%d K=%d H=%d needs %zu bytes of LDS (> 160 KiB)", d.F, d.K, d.H, sh);
+  AttnFwdPlan p;
+  p.kreg = f16 && d.nblk <= 13 && kreg_knob != 0;
+  p.a16 = d.A == 16;
+  p.sh = p.kreg ? (size_t)d.NC * d.FP * 16 * sizeof(_Float16) : fwd_lds(d, f16);
+  p.ok = p.sh <= kLdsCap;
+  return p;
+}
+
+static AttnBwdPlan plan_bwd(const AttnDims& d, bool f16) {
+  AttnBwdPlan p;
+  p.nb = d.nblk <= 4 ? 4 : d.nblk <= 8 ? 8 : d.nblk <= 13 ? 13 : 32;
+  p.a16 = p.nb >= 13 && d.A == 16;
+  p.wph = 1;
+  p.dx_lds = 0;
+  size_t sh = bwd_lds(d, f16);
+  p.sh = sh;
+  p.ok = sh <= kLdsCap;
+  if (!p.ok) return p;
+  // two waves per head when the footprint lets only ONE one-wave-per-head workgroup onto a CU (and the doubled workgroup fits)
+  static const int wph_knob = [] {   // 0 = automatic, 1 / 2 = forced (tests, sweeps); read once
+    const char* e = getenv("FIL_ATTN_WPH");
+    return e != nullptr ? atoi(e) : 0;
+  }();
+  int wph = (2 * sh > kLdsCap && d.nblk > 8) ? 2 : 1;
+  // ... and also where two one-wave-per-head workgroups do fit but only WITHOUT the LDS dx image, while one two-waves-per-head
+  // workgroup fits with it: the image is worth more than the second workgroup (K = 64, F = 160, f16: 0.435 ms against 0.462 --
+  // tools/attn_occ_probe.py; the dx part through global memory is a read-modify-write of 2 x |dx| per launch)
+  if (wph == 1 && d.nblk > 8 && d.H <= 4) {
+    const size_t sh1d = bwd_lds(d, f16, 1, true), sh2d = bwd_lds(d, f16, 2, true);
+    const bool dx_with_1 = sh1d <= kLdsCap && kLdsCap / sh1d >= std::min<size_t>(kLdsCap / sh, 2);
+    if (!dx_with_1 && sh2d <= kLdsCap) wph = 2;
+  }
+  if (wph_knob == 1 || wph_knob == 2) wph = d.nblk > 8 ? wph_knob : 1;
+  if (wph == 2 && (d.H > 4 || bwd_lds(d, f16, 2) > kLdsCap || d.nblk < 2)) wph = 1;
+  sh = bwd_lds(d, f16, wph);
+  // dx image in LDS when it fits without costing a resident workgroup (FIL_ATTN_DX_LDS=0 keeps the global second visit)
+  static const int dxl_knob = [] {
+    const char* e = getenv("FIL_ATTN_DX_LDS");
+    return e != nullptr ? atoi(e) : 1;
+  }();
+  if (dxl_knob != 0) {
+    const size_t sh2 = bwd_lds(d, f16, wph, true);
+    if (sh2 <= kLdsCap && kLdsCap / sh2 >= std::min<size_t>(kLdsCap / sh, 2)) {   // (at most two workgroups per CU run anyway: registers)
+      p.dx_lds = 1;
+      sh = sh2;
+    }
+  }
+  p.wph = wph;
+  p.sh = sh;
+  return p;
+}
+
+static int launch_fwd(const float* x, const float* Wq, const float* Wk, const float* Wr, const float* gamma, const float* beta,
+                      float* y, float* res_out, float* av_out, float* rstd_out, const AttnDims& d, float scale, float eps,
+                      int fuse_relu, bool f16, hipStream_t st) {
+  const AttnFwdPlan pl = plan_fwd(d, f16);
+  const bool kreg = pl.kreg;
+  const size_t sh = pl.sh;
+  if (!pl.ok)
+    return fail(FIL_ERR_UNSUPPORTED, "fil_attn_fwd: F=%d K=%d H=%d A=%d needs %zu bytes of LDS (> %zu available)%s", d.F, d.K, d.H, d.A, sh,
+                kLdsCap, f16 ? "" : "; the f16-MFMA precision needs less");
   const dim3 grid(d.B), block(64 * d.H);
   int rc = FIL_OK;
 #define CALL_FWD_K(...)                                                                                                       \
@@ -1530,7 +1605,7 @@ static int launch_fwd(const float* x, const float* Wq, const float* Wk, const fl
 #define CALL_FWD_A(N, P, AV) \
   if (kreg) { CALL_FWD_K(N, P, AV, (P ? 13 : 0)); } else { CALL_FWD_K(N, P, AV, 0); }
 #define CALL_FWD(N, P) \
-  if (d.A == 16) { CALL_FWD_A(N, P, true); } else { CALL_FWD_A(N, P, false); }
+  if (pl.a16) { CALL_FWD_A(N, P, true); } else { CALL_FWD_A(N, P, false); }
   FIL_ATTN_NC(d.NC, CALL_FWD)
 #undef CALL_FWD
 #undef CALL_FWD_A
@@ -1554,6 +1629,20 @@ extern "C" size_t fil_attn_bwd_workspace_bytes(int B, int F, int K, int H, int A
   AttnDims d;
   if (make_dims("fil_attn_bwd_workspace_bytes", B, F, K, H, A, 0, d) != FIL_OK || B == 0) return 0;
   return attn_bwd_ws(d, have_saved != 0);
+}
+
+extern "C" int fil_attn_plan(int F, int K, int H, int A, int precision, int* plan) {
+  AttnDims d;
+  int rc = make_dims("fil_attn_plan", 0, F, K, H, A, 0, d);
+  if (rc != FIL_OK) return rc;
+  if (precision != FIL_PREC_F32 && precision != FIL_PREC_F16_MFMA) return fail(FIL_ERR_ARG, "fil_attn_plan: precision=%d", precision);
+  FIL_CHECK_ARG(plan != nullptr);
+  const bool f16 = precision == FIL_PREC_F16_MFMA;
+  const AttnFwdPlan f = plan_fwd(d, f16);
+  const AttnBwdPlan b = plan_bwd(d, f16);
+  const int out[10] = {f.ok, f.kreg, f.a16, (int)f.sh, b.ok, b.nb, b.wph, b.dx_lds, b.a16, (int)b.sh};
+  for (int i = 0; i < 10; ++i) plan[i] = out[i];
+  return FIL_OK;
 }
 
 extern "C" int fil_attn_fwd(const float* x, const float* Wq, const float* Wk, const float* Wr, const float* gamma,
@@ -1610,40 +1699,12 @@ extern "C" int fil_attn_bwd(const float* x, const float* Wq, const float* Wk, co
   // unfused mode: the residual branch's gradient arrives separately (dres_in)
   const bool has_res = Wr != nullptr;
   if (!fuse_relu && has_res && dres_in == nullptr) return fail(FIL_ERR_ARG, "fil_attn_bwd: dres is required when fuse_relu == 0 and Wr != NULL");
-  size_t sh = bwd_lds(d, f16);
-  if (sh > kLdsCap)
-    return fail(FIL_ERR_UNSUPPORTED, "fil_attn_bwd: F=%d K=%d H=%d needs %zu bytes of LDS (> 160 KiB)%s", F, K, H, sh,
-                f16 ? "" : "; the f16-MFMA precision needs less than half of that");
-  // two waves per head when the footprint lets only ONE one-wave-per-head workgroup onto a CU (and the doubled workgroup fits)
-  static const int wph_knob = [] {   // 0 = automatic, 1 / 2 = forced (tests, sweeps); read once
-    const char* e = getenv("FIL_ATTN_WPH");
-    return e != nullptr ? atoi(e) : 0;
-  }();
-  int wph = (2 * sh > kLdsCap && d.nblk > 8) ? 2 : 1;
-  // ... and also where two one-wave-per-head workgroups do fit but only WITHOUT the LDS dx image, while one two-waves-per-head
-  // workgroup fits with it: the image is worth more than the second workgroup (K = 64, F = 160, f16: 0.435 ms against 0.462 --
-  // tools/attn_occ_probe.py; the dx part through global memory is a read-modify-write of 2 x |dx| per launch)
-  if (wph == 1 && d.nblk > 8 && H <= 4) {
-    const size_t sh1d = bwd_lds(d, f16, 1, true), sh2d = bwd_lds(d, f16, 2, true);
-    const bool dx_with_1 = sh1d <= kLdsCap && kLdsCap / sh1d >= std::min<size_t>(kLdsCap / sh, 2);
-    if (!dx_with_1 && sh2d <= kLdsCap) wph = 2;
-  }
-  if (wph_knob == 1 || wph_knob == 2) wph = d.nblk > 8 ? wph_knob : 1;
-  if (wph == 2 && (H > 4 || bwd_lds(d, f16, 2) > kLdsCap || d.nblk < 2)) wph = 1;
-  sh = bwd_lds(d, f16, wph);
-  // dx image in LDS when it fits without costing a resident workgroup (FIL_ATTN_DX_LDS=0 keeps the global second visit)
-  static const int dxl_knob = [] {
-    const char* e = getenv("FIL_ATTN_DX_LDS");
-    return e != nullptr ? atoi(e) : 1;
-  }();
-  int dx_lds = 0;
-  if (dxl_knob != 0) {
-    const size_t sh2 = bwd_lds(d, f16, wph, true);
-    if (sh2 <= kLdsCap && kLdsCap / sh2 >= std::min<size_t>(kLdsCap / sh, 2)) {   // (at most two workgroups per CU run anyway: registers)
-      dx_lds = 1;
-      sh = sh2;
-    }
-  }
+  const AttnBwdPlan pl = plan_bwd(d, f16);
+  if (!pl.ok)
+    return fail(FIL_ERR_UNSUPPORTED, "fil_attn_bwd: F=%d K=%d H=%d A=%d needs %zu bytes of LDS (> %zu available)%s", F, K, H, A, pl.sh,
+                kLdsCap, f16 ? "" : "; the f16-MFMA precision needs less than half of that");
+  const int wph = pl.wph;
+  const size_t sh = pl.sh;
   const long Gws = std::min<long>(kMaxBwdGrid, 2L * B);
   Carver ws(workspace);
   float* wpart = ws.take<float>((size_t)Gws * 3 * K * H * A);
@@ -1669,7 +1730,7 @@ extern "C" int fil_attn_bwd(const float* x, const float* Wq, const float* Wk, co
     ProfScope ps("attn_bwd", st, (double)B * H * (10.0 * F * (double)F * A + 2.0 * F * K * A * (has_res ? 9 : 7)));
     int lrc = FIL_OK;
     const AttnBwdLaunch la{x, Wq, Wk, Wr, gamma, dy, dres_in, y_saved, av_saved, rstd_saved, dx, wpart, gb_part, d, scale, eps, fuse_relu, g_attn_stamps,
-                           wph, dx_lds, sh, st};
+                           pl.nb, pl.wph, pl.dx_lds, pl.a16, sh, st};
     lrc = f16 ? attn_launch_bwd_f16(la, &G) : attn_launch_bwd_f32(la, &G);
     if (lrc != FIL_OK) return fail(lrc, "fil_attn_bwd: cannot reserve %zu bytes of LDS", sh);
     FIL_CHECK_LAUNCH();

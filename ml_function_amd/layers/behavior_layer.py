@@ -2,11 +2,17 @@
 MultHeadAttentionLayer (:313-380) of the reference.  Reference quirks are kept on purpose: the "softmax" is a
 sigmoid (:286,308), V is projected with key_w (:360; value_w exists but never receives a gradient), LayerNorm
 epsilon is Keras' default 1e-3, the output is head-major [H,B,F,A]."""
+import ctypes
+
 import torch
 
+from .. import _lib
 from .. import functional as Fn
 from .._lib import FilError
 from .base import Layer
+
+_FIL_ERR_UNSUPPORTED = -4      # include/fil.h
+_PLAN_FITS = {}                # (F, K, H, A, precision) -> fil_attn_plan's answer (the plan is fixed for the life of the process)
 
 
 class ProductAttentionLayer(Layer):
@@ -66,10 +72,22 @@ class MultHeadAttentionLayer(Layer):
                 self.ln_gamma if self.use_ln else None, self.ln_beta if self.use_ln else None)
 
     def fits_fused_kernel(self, inputs):
-        """The fused kernel's menu (include/fil.h): K <= 64, A <= 16, H <= 8, F <= 512.  A reference-legal layer outside it
-        (e.g. attention_dim = 32) takes the composed path below instead of raising."""
-        return (inputs.dim() == 3 and inputs.shape[2] <= 64 and self.attention_dim <= 16 and self.attention_head_dim <= 8
-                and inputs.shape[1] <= 512)
+        """The fused kernel's menu (include/fil.h): K <= 64, A <= 16, H <= 8, F <= 512, and the dynamic LDS footprint of BOTH the
+        forward and the backward within the launchers' limit (163,328 bytes) in this layer's precision -- fil_attn_plan answers from
+        the launchers' own arithmetic.  The backward's footprint is the larger one: in "f32" with 8 heads it ends the menu at F = 128
+        (4 heads: F = 384), in "f16_mfma" with K = 64 at F = 208 (4 heads: F = 480).  A reference-legal layer outside the menu
+        (e.g. attention_dim = 32, or 8 heads over 129 fields in f32) takes the composed path below instead of raising."""
+        if inputs.dim() != 3:
+            return False
+        key = (int(inputs.shape[1]), int(inputs.shape[2]), int(self.attention_head_dim), int(self.attention_dim), Fn._precision(self.precision))
+        fits = _PLAN_FITS.get(key)
+        if fits is None:
+            plan = (ctypes.c_int * 10)()
+            rc = _lib.load().fil_attn_plan(*key, plan)
+            if rc != _FIL_ERR_UNSUPPORTED:
+                _lib.check(rc, "fil_attn_plan")
+            fits = _PLAN_FITS[key] = rc == 0 and bool(plan[0]) and bool(plan[4])      # fwd_ok and bwd_ok
+        return fits
 
     def _composed(self, inputs, mask):
         """The reference's op order (:358-369) with the attention core on the stand-alone kernel (fil_pattn_*: A <= 64, any mask) --

@@ -1,5 +1,5 @@
 """Poisoned inputs and guarded outputs for tests that call the C ABI directly on flat tensors (tests/test_fm_edges_gpu.py,
-tests/test_dcn_edges_gpu.py, tests/test_head_edges_gpu.py, tests/test_pattn_edges_gpu.py).  Every payload starts 16-byte aligned: an input at
+tests/test_dcn_edges_gpu.py, tests/test_head_edges_gpu.py, tests/test_pattn_edges_gpu.py, tests/test_attn_edges_gpu.py).  Every payload starts 16-byte aligned: an input at
 the start of its allocation with TAIL words of the payload NaN behind it (a read past the end turns up in the results), an output GUARD_BYTES into a sentinel-filled allocation whose words in front
 of and behind the payload must hold the sentinel's bits after the call.  Words are uint32 (fp32) or uint16 (bf16)."""
 import numpy as np

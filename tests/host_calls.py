@@ -78,6 +78,22 @@ def run(lib):
     expect(lib.fil_attn_fwd(*nul9, 4, 200, 16, 9, 16, 0.25, 1e-3, 1, 0, 0, None, 0, None), -4)
     expect(lib.fil_attn_fwd(*nul9, 4, 600, 16, 4, 16, 0.25, 1e-3, 1, 0, 0, None, 0, None), -4, b"512")
     expect(lib.fil_attn_bwd(*([None] * 17), 4, 200, 16, 4, 16, 0.25, 1e-3, 1, 0, 0, None, 0, None), -1)
+    # fil_attn_plan: pure host; the menu's errors, the LDS limit in both directions, a NULL plan
+    plan = (ctypes.c_int * 10)()
+    expect(lib.fil_attn_plan(200, 16, 4, 16, 0, plan), 0)
+    assert plan[0] == 1 and plan[4] == 1 and plan[5] == 13 and plan[8] == 1 and 0 < plan[9] <= 160 * 1024 - 512, list(plan)
+    expect(lib.fil_attn_plan(129, 16, 8, 16, 0, plan), 0)
+    assert plan[0] == 1 and plan[4] == 0 and plan[9] > 160 * 1024 - 512, list(plan)        # f32, 8 heads: the backward ends at F = 128
+    expect(lib.fil_attn_plan(512, 64, 4, 16, 0, plan), 0)
+    assert plan[0] == 0 and plan[4] == 0, list(plan)
+    expect(lib.fil_attn_plan(512, 64, 8, 16, 1, plan), 0)
+    expect(lib.fil_attn_plan(200, 16, 4, 16, 0, None), -1)
+    expect(lib.fil_attn_plan(200, 16, 4, 16, 2, plan), -1, b"precision")
+    expect(lib.fil_attn_plan(0, 16, 4, 16, 0, plan), -1)
+    expect(lib.fil_attn_plan(513, 16, 4, 16, 0, plan), -4, b"512")
+    expect(lib.fil_attn_plan(200, 65, 4, 16, 0, plan), -4)
+    expect(lib.fil_attn_plan(200, 16, 9, 16, 0, plan), -4)
+    expect(lib.fil_attn_plan(200, 16, 4, 17, 0, plan), -4)
     expect(lib.fil_score_add_sigmoid_fwd(None, None, None, None, None, 4, None), -1, b"bad argument")
     expect(lib.fil_score_add_sigmoid_fwd(None, None, None, None, None, 0, None), 0)
     expect(lib.fil_score_add_sigmoid_bwd(None, None, None, 4, None), -1)

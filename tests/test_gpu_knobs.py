@@ -54,6 +54,22 @@ def test_attn_two_waves_per_head_forced_on_fewer_heads():
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("knob,value", [("FIL_ATTN_WPH", "2"), ("FIL_ATTN_DX_LDS", "0"), ("FIL_ATTN_KREG", "0")])
+def test_attn_edges_with_one_knob(knob, value):
+    """The constructed shape cases of tests/test_attn_edges_gpu.py with F >= 129 (the `big` ids: NB = 13 and 32, where the knobs act) in a fresh
+    child per knob: FIL_ATTN_WPH=2 = two waves per head wherever it fits, FIL_ATTN_DX_LDS=0 = the dx part through global memory everywhere,
+    FIL_ATTN_KREG=0 = the f16 forward's k image in LDS up to 13 key tiles.  Every case asserts fil_attn_plan == the restatement of
+    tests/attn_edge_cases.py inside the child, and both read the knob, so the instantiation asserted follows it; the refused pairs stay refused."""
+    env = dict(os.environ)
+    env[knob] = value
+    r = subprocess.run([sys.executable, "-m", "pytest", "tests/test_attn_edges_gpu.py", "-x", "-q", "-m", "gpu", "-k",
+                        "(shape_edges or refuses) and big", "-p", "no:cacheprovider"], cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
+    tail = "\n".join((r.stdout + r.stderr).strip().splitlines()[-15:])
+    assert r.returncode == 0, "%s=%s:\n%s" % (knob, value, tail)
+    assert "25 passed" in r.stdout and "no tests ran" not in r.stdout, tail
+
+
+@pytest.mark.gpu
 def test_gemm_edges_with_one_wave_per_tile():
     """FIL_GEMM_KW=1 (read once per process) launches the dense GEMM with ONE wave per output tile -- the eight
     gemm_f32_kernel<*, *, *, 1> instantiations, no join of k halves through LDS.  A fresh child runs the constructed-edge cases of

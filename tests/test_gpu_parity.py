@@ -1298,6 +1298,50 @@ def test_autoint_layer_outside_the_kernel_menu_takes_the_composed_path():
     check("composed autoint dWk", lay.key_w.grad, o["Wk"].grad.numpy(), tol=2e-5)
 
 
+@pytest.mark.parametrize("F,fused", [(129, False), (128, True)])
+def test_autoint_layer_past_the_lds_limit_takes_the_composed_path(F, fused):
+    """MultHeadAttentionLayer(16, 8) in f32: K <= 64, A <= 16, H <= 8, F <= 512 all hold, but from F = 129 on the backward kernel's LDS footprint
+    exceeds the launcher's limit (fil_attn_plan: bwd_ok = 0 while fwd_ok = 1) -- the forward would succeed and backward() raise.  The layer asks
+    the plan: F = 129 takes the composed path (no fil_attn_* launch), F = 128 the fused kernels (no fil_pattn_* launch); both match the oracle
+    graph, forward and backward."""
+    from ml_function_amd import _lib
+    from ml_function_amd.layers import MultHeadAttentionLayer
+    from oracle import graph
+    B, K, H, A = 2, 16, 8, 16
+    c = synth.attn_case(B, F, K, H, A, dist="normal")
+    lay = MultHeadAttentionLayer(A, H)
+    x = dev(c["x"]).requires_grad_()
+    assert lay.fits_fused_kernel(x) == fused
+    lay(x)
+    with torch.no_grad():
+        lay.query_w.copy_(dev(c["Wq"])); lay.key_w.copy_(dev(c["Wk"])); lay.res_w.copy_(dev(c["Wr"]))
+        lay.ln_gamma.copy_(dev(c["gamma"])); lay.ln_beta.copy_(dev(c["beta"]))
+    T64 = lambda a: torch.tensor(np.asarray(a), dtype=torch.float64, requires_grad=True)
+    o = {n: T64(c[n]) for n in ["x", "Wq", "Wk", "Wr", "gamma", "beta"]}
+    _lib.profile_begin(None)
+    try:
+        av, res = lay(x)
+        av_o, res_o = graph.mult_head_attention(o["x"], o["Wq"], o["Wk"], o["Wr"], o["gamma"], o["beta"])
+        check("lds-limit mha atten_v", av, av_o.detach().numpy())
+        check("lds-limit mha res", res, res_o.detach().numpy())
+        y = lay.fused_relu(x)
+        y_o = graph.autoint_interacting(o["x"], o["Wq"], o["Wk"], o["Wr"], o["gamma"], o["beta"])
+        check("lds-limit autoint y", y, y_o.detach().numpy())
+        y.backward(dev(c["dy"]))
+        torch.cuda.synchronize()
+    finally:
+        scopes = set(_lib.profile_end())
+    assert ({"attn_fwd", "attn_bwd"} <= scopes) == fused and ({"pattn_fwd", "pattn_bwd"} <= scopes) == (not fused), scopes
+    assert bool({"attn_fwd", "attn_bwd"} & scopes) == fused and bool({"pattn_fwd", "pattn_bwd"} & scopes) == (not fused), scopes
+    y_o.backward(torch.tensor(c["dy"], dtype=torch.float64))
+    check("lds-limit autoint dx", x.grad, o["x"].grad.numpy(), tol=2e-5)
+    check("lds-limit autoint dWq", lay.query_w.grad, o["Wq"].grad.numpy(), tol=2e-5)
+    check("lds-limit autoint dWk", lay.key_w.grad, o["Wk"].grad.numpy(), tol=2e-5)
+    check("lds-limit autoint dWr", lay.res_w.grad, o["Wr"].grad.numpy(), tol=2e-5)
+    check("lds-limit autoint dgamma", lay.ln_gamma.grad, o["gamma"].grad.numpy(), tol=2e-5)
+    check("lds-limit autoint dbeta", lay.ln_beta.grad, o["beta"].grad.numpy(), tol=2e-5)
+
+
 def test_cin_step_is_hipgraph_capturable():
     """The C ABI enqueues on the caller's stream without allocating or synchronising, so a whole forward+backward can be
     captured into a HIP graph (torch.cuda.CUDAGraph) and replayed: results equal the eager run bit for bit."""

@@ -109,6 +109,52 @@ def test_workspace_sizes(lib):
     assert lib.fil_cin_bwd_workspace_bytes(0, F, K, 3, H) >= 0
 
 
+def test_attn_plan_equals_its_restatement_over_the_whole_menu(lib):
+    """fil_attn_plan -- the host function fil_attn_fwd / fil_attn_bwd launch from -- against the plain-Python restatement of
+    tests/attn_edge_cases.py at every F of the menu x the K at every chunk edge x every H x A in {1, 7, 16} x both precisions: all ten words.
+    Then the tables tests/test_attn_edges_gpu.py runs: every case sits on the instantiation it was built for, the refused pairs are refused,
+    the limits that include/fil.h and the layer's docstring quote are the first refused F, and the cases cover the backward menu."""
+    import ctypes
+    import itertools
+    from tests import attn_edge_cases as ac
+    assert not ac.knobs_set(), ac.knobs_set()
+    out = (ctypes.c_int * 10)()
+    n = 0
+    for prec in (ac.F32, ac.F16):
+        for K, H, A in itertools.product(ac.SWEEP_K, ac.SWEEP_H, ac.SWEEP_A):
+            for F in ac.SWEEP_F:
+                assert lib.fil_attn_plan(F, K, H, A, prec, out) == 0
+                assert tuple(out) == tuple(ac.plan(F, K, H, A, prec)), (F, K, H, A, prec, list(out))
+                n += 1
+    assert n == 2 * 8 * 8 * 3 * 512
+    for args in [(0, 16, 4, 16, 0), (513, 16, 4, 16, 0), (200, 65, 4, 16, 1), (200, 16, 9, 16, 0), (200, 16, 4, 17, 1), (200, 16, 4, 16, 2),
+                 (200, 0, 4, 16, 0), (200, 16, 0, 16, 0), (200, 16, 4, 0, 0)]:
+        assert lib.fil_attn_plan(*args, out) == ac.plan_rc(*args), args
+
+    seen_nb_nc, seen_wph_dx = set(), set()
+    for shape, prec in ac.shape_case_list():
+        p = ac.plan(*shape, ac.PRECISIONS[prec])
+        assert p.fwd_ok and p.bwd_ok, (shape, prec, p)
+        want = ac.expected_tuple(shape, prec)
+        assert want is None or want == (p.bwd_nb, p.bwd_wph, p.bwd_dx_lds), (shape, prec, p)
+        seen_nb_nc.add((p.bwd_nb, ac.cdiv(shape[1], 16), prec))
+        if p.bwd_nb >= 13:
+            seen_wph_dx.add((p.bwd_wph, p.bwd_dx_lds))
+    assert seen_nb_nc == set(itertools.product((4, 8, 13, 32), (1, 2, 3, 4), ac.PRECISIONS)), sorted(seen_nb_nc)
+    assert seen_wph_dx == set(itertools.product((1, 2), (0, 1)))
+    for (shape, prec), nbytes in ac.BWD_LDS_BYTES.items():
+        assert ac.plan(*shape, prec).bwd_lds == nbytes
+    for (shape, prec), (fwd_refused, bwd_refused) in ac.REFUSED.items():
+        p = ac.plan(*shape, prec)
+        assert (not p.fwd_ok, not p.bwd_ok) == (fwd_refused, bwd_refused), (shape, prec, p)
+    for (K, H, prec, which), first in ac.FIRST_REFUSED_F.items():
+        ok = [getattr(ac.plan(F, K, H, 16, prec), which + "_ok") for F in range(1, 513)]
+        assert all(ok[:first - 1]) and not any(ok[first - 1:]), (K, H, prec, which)
+    for shape, nb in ac.MULTI_CASES.items():
+        assert {ac.plan(*shape, prec).bwd_nb for prec in (ac.F32, ac.F16)} == {nb}, shape
+    assert sorted(ac.MULTI_CASES.values()) == [4, 4, 8, 13, 32]
+
+
 def test_dcn_workspace_size_follows_the_predicted_backward_path(lib):
     """fil_dcn_bwd_workspace_bytes at every (B, D, L) of tests/dcn_edge_cases.py equals the formula of the backward path that dcn_paths
     predicts -- the register path's one partial per workgroup, or the generic path's ds + chunk partials -- and the tables' own path
