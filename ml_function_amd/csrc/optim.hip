@@ -12,11 +12,13 @@
 // of fil_embed_run_sum (embed_runs.h): the same order, so a row's gradient is bit-identical to what the dense path materialises.
 // Data parallel: fil_embed_adam_merged applies the W gathered lists of fil_embed_runs_compact (runs_compact.hip) -- every row once,
 // by its lowest rank, summed in rank order -- before the sweep, so every replica computes the same bits.
-// This file is Adam only.  Its kernels sit on a few shared pieces: the field table of a sweep (FieldTab, optim_adam.h), four elements
-// of a row in and out (row_load4, row_store4), a touched element (adam_touched_at) and one replayed step (replay_step); what the
-// launchers compute the same way as the row-rule optimizers' (grids, the step tag, sweep_vec, the shape check) comes from
-// optim_rows.h and embed_runs.h.  The coefficients and the two table-element updates live in optim_adam.h, which optim_amsgrad.hip
-// (O7, Adam with amsgrad) shares.
+// This file holds Adam's dense kernel, the deferred mode and the O1 entry points.  The Keras-mode table kernels (runs, sweep, merged)
+// and the launcher bodies of the dense, runs, sweep and merged launches are defined once in optim_adam.h, templated on whether the
+// amsgrad slot travels along; the entry points here instantiate them without it, optim_amsgrad.hip (O7) with it.  The deferred
+// kernels sit on a few pieces of their own: four elements of a row in and out (row_load4, row_store4) and one replayed step
+// (replay_step); the field table of a sweep (FieldTab), the coefficients and the two table-element updates come from optim_adam.h,
+// and what the launchers compute the same way as the row-rule optimizers' (grids, the step tag, sweep_vec, the shape check) from
+// optim_rows.h and embed_runs.h.
 #include "common.h"
 #include "embed_runs.h"
 #include "optim_rows.h"
@@ -28,7 +30,8 @@ namespace fil {
 static_assert(sizeof(fil_adam_tensor) == 48, "fil_adam_tensor is 48 bytes (fil.h)");
 
 // (the step's coefficients, adam_touched / adam_untouched -- the one definition of a table element's rounding, DESIGN 6e -- the
-// sweep's field table and the hyper-parameter check: optim_adam.h, shared with optim_amsgrad.hip)
+// sweep's field table, the hyper-parameter check and the Keras-mode runs, sweep and merged kernels: optim_adam.h, shared with
+// optim_amsgrad.hip)
 
 // one element of ApplyAdam (Eigen's order of operations), left to the compiler's contraction: fil_adam_multi only, whose dense
 // tensors nothing replays
@@ -73,16 +76,6 @@ __device__ __forceinline__ void row_store4(float* __restrict__ table, float* __r
   }
 }
 
-// one element of a touched row in place
-__device__ __forceinline__ void adam_touched_at(float* __restrict__ table, float* __restrict__ m, float* __restrict__ v, int64_t e,
-                                                float acc, float l2x2, const AdamCoef& c) {
-  float p = table[e], mm = m[e], vv = v[e];
-  adam_touched(p, mm, vv, acc, l2x2, c);
-  table[e] = p;
-  m[e] = mm;
-  v[e] = vv;
-}
-
 // one replayed step on NE elements in registers.  vec: the sweep would take its 16-byte path on this table -- the only place that
 // picks the rounding of a replay, which deferred mode's bit-identity to Keras mode rests on
 template <int NE>
@@ -111,101 +104,6 @@ __global__ __launch_bounds__(256) void adam_multi_kernel(const fil_adam_tensor* 
   });
 }
 
-// ---- fil_embed_adam_runs: the run sums of embed_runs.h with an Adam epilogue.  Row `row` of field f = perm % F takes
-// g = run sum + 2 l2[f] p; Keras mode stamps the row with the step it was updated at (the sweep skips stamped rows).
-template <typename GT>
-__global__ __launch_bounds__(256) void embed_adam_runs_kernel(const GT* __restrict__ g, const int64_t* __restrict__ perm,
-                                                              const int64_t* __restrict__ sorted_ids, long R, int K, int F,
-                                                              const float* __restrict__ field_l2, float* __restrict__ table,
-                                                              float* __restrict__ m, float* __restrict__ v, int32_t* __restrict__ stamp,
-                                                              const int64_t* __restrict__ step, float lr, float b1, float b2, float eps,
-                                                              const float* __restrict__ lr_dev) {
-  const AdamCoef c = adam_coef(step, rate_of(lr, lr_dev), b1, b2, eps);
-  const int32_t tag = step_tag(step);
-  embed_run_sums(g, perm, sorted_ids, R, K, [=](int64_t row, int kq, const float (&acc)[4], int64_t first) {
-    const float l2x2 = field_l2 ? 2.f * field_l2[first % F] : 0.f;
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-      if (kq * 4 + i < K) adam_touched_at(table, m, v, row * K + kq * 4 + i, acc[i], l2x2, c);
-    if (stamp && kq == 0) stamp[row] = tag;
-  });
-}
-
-// ---- fil_embed_adam_sweep: every row the run pass did not stamp at this step takes g = 2 l2[f] p (or 0); frozen fields are
-// left alone.  The field of a row comes from a binary search of the offsets held in LDS (FieldTab).
-__global__ __launch_bounds__(256) void embed_adam_sweep_kernel(float* __restrict__ table, float* __restrict__ m, float* __restrict__ v,
-                                                               const int32_t* __restrict__ stamp, int64_t V, int K,
-                                                               const int64_t* __restrict__ offsets, const float* __restrict__ field_l2,
-                                                               const unsigned char* __restrict__ frozen, int F,
-                                                               const int64_t* __restrict__ step, float lr, float b1, float b2, float eps,
-                                                               int vec, const float* __restrict__ lr_dev) {
-  __shared__ FieldTab s;
-  load_field_tab(&s, offsets, field_l2, frozen, F);
-  __syncthreads();
-  const AdamCoef c = adam_coef(step, rate_of(lr, lr_dev), b1, b2, eps);
-  const int32_t tag = step_tag(step);
-  const int64_t n = V * K;
-  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  if (vec) {                                  // K % 4 == 0 and 16-byte aligned arrays: a lane moves 4 elements of one row
-    const int64_t nq = n / 4;
-    for (int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; q < nq; q += stride) {
-      const int64_t row = q * 4 / K;
-      if (stamp[row] == tag) continue;
-      const float l2x2 = field_l2x2(&s, F, row);
-      if (l2x2 != l2x2) continue;             // frozen
-      f32x4 p = reinterpret_cast<const f32x4*>(table)[q];
-      f32x4 mm = reinterpret_cast<const f32x4*>(m)[q];
-      f32x4 vv = reinterpret_cast<const f32x4*>(v)[q];
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        float pi = p[i], mi = mm[i], vi = vv[i];
-        adam_untouched<true>(pi, mi, vi, l2x2, c);
-        p[i] = pi;
-        mm[i] = mi;
-        vv[i] = vi;
-      }
-      __builtin_nontemporal_store(p, reinterpret_cast<f32x4*>(table) + q);
-      __builtin_nontemporal_store(mm, reinterpret_cast<f32x4*>(m) + q);
-      __builtin_nontemporal_store(vv, reinterpret_cast<f32x4*>(v) + q);
-    }
-    return;
-  }
-  for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += stride) {
-    const int64_t row = e / K;
-    if (stamp[row] == tag) continue;
-    const float l2x2 = field_l2x2(&s, F, row);
-    if (l2x2 != l2x2) continue;
-    float p = table[e], mm = m[e], vv = v[e];
-    adam_untouched<false>(p, mm, vv, l2x2, c);
-    __builtin_nontemporal_store(p, table + e);
-    __builtin_nontemporal_store(mm, m + e);
-    __builtin_nontemporal_store(vv, v + e);
-  }
-}
-
-// ---- fil_embed_adam_merged: the merged walk of the gathered lists (merged_row_sums, optim_rows.h); the owner of a row adds the
-// field's l2 term and updates the row exactly as embed_adam_runs_kernel does.
-__global__ __launch_bounds__(256) void embed_adam_merged_kernel(const int64_t* __restrict__ ids, const float* __restrict__ values,
-                                                                const int64_t* __restrict__ counts, int W, long cap, int K,
-                                                                const int64_t* __restrict__ offsets, const float* __restrict__ field_l2,
-                                                                int F, float* __restrict__ table, float* __restrict__ m,
-                                                                float* __restrict__ v, int32_t* __restrict__ stamp, int64_t V,
-                                                                const int64_t* __restrict__ step, float lr, float b1, float b2, float eps,
-                                                                const float* __restrict__ lr_dev) {
-  __shared__ int64_t s_off[kSweepMaxF];
-  for (int f = threadIdx.x; f < F; f += blockDim.x) s_off[f] = offsets[f];
-  __syncthreads();
-  const AdamCoef c = adam_coef(step, rate_of(lr, lr_dev), b1, b2, eps);
-  const int32_t tag = step_tag(step);
-  const auto epi = [=](int64_t row, int f, float l2x2, int k0, const float (&acc)[kMergeChunk]) {
-#pragma unroll
-    for (int e = 0; e < kMergeChunk; ++e)
-      if (k0 + e < K) adam_touched_at(table, m, v, row * K + k0 + e, acc[e], l2x2, c);
-  };
-  merged_row_sums((long)blockIdx.x * blockDim.x + threadIdx.x, (long)gridDim.x * blockDim.x, ids, values, counts, W, cap, K, V, s_off,
-                  field_l2, F, epi, [=](int64_t row) { if (stamp) stamp[row] = tag; });
-}
-
 // ==== Deferred mode (optim.Adam(sweep_period=N)).  A row the batch did not touch takes g = 2 l2 p: an update that depends
 // on the row's own (p, m, v), its field's l2 and the step's coefficients only.  So the steps a row misses can be applied later, with
 // the same fp32 operations in the same order, and give the sweep's bits.  Persistent state per table:
@@ -216,7 +114,7 @@ __global__ __launch_bounds__(256) void embed_adam_merged_kernel(const int64_t* _
 // behind: every replay reads at most the N newest entries, and D >= N + 1 keeps the entry being written out of their way.
 constexpr int kRingMax = 1024;                 // D <= 1024 (the roll keeps the ring in LDS): sweep_period <= 1023
 
-// The replays go through adam_untouched, the sweep's own update (above): a replayed step rounds as the sweep would have rounded it.
+// The replays go through adam_untouched, the sweep's own update (optim_adam.h): a replayed step rounds as the sweep would have rounded it.
 __device__ __forceinline__ bool coef_is_skip(const AdamCoef& c) { return c.omb1 != c.omb1; }   // (1 - beta_1 is never NaN)
 
 __device__ __forceinline__ AdamCoef coef_skip() {
@@ -469,152 +367,61 @@ static int check_deferred(const char* who, int K, int F, int N, const float* rin
   return FIL_OK;
 }
 
-// the Keras / lazy mode of the runs and merged updates
-static int check_mode(const char* who, int mode, const int32_t* stamp) {
-  if (mode != FIL_ADAM_KERAS && mode != FIL_ADAM_LAZY) return fail(FIL_ERR_ARG, "%s: mode %d (FIL_ADAM_KERAS or FIL_ADAM_LAZY)", who, mode);
-  if (mode == FIL_ADAM_KERAS && stamp == nullptr)
-    return fail(FIL_ERR_ARG, "%s: FIL_ADAM_KERAS needs the row stamps (fil_embed_adam_sweep skips the rows stamped here)", who);
-  return FIL_OK;
-}
-
 }  // namespace fil
 
 using namespace fil;
 
-static int adam_multi_impl(const char* who, const fil_adam_tensor* tensors, int n, int64_t total_numel, int64_t* step, float lr,
-                           float beta_1, float beta_2, float epsilon, int advance, void* stream, const float* lr_dev) {
-  FIL_CHECK_ARG_W(who, n >= 0 && total_numel >= 0);
-  FIL_CHECK_ARG_W(who, step != nullptr);
-  FIL_CHECK_ARG_W(who, n == 0 || tensors != nullptr);
-  if (int rc = check_hyper(who, lr, beta_1, beta_2, epsilon)) return rc;
-  if (advance != 0 && advance != 1) return fail(FIL_ERR_ARG, "%s: advance %d (0 or 1)", who, advance);
-  hipStream_t st = (hipStream_t)stream;
-  if (n > 0) {
-    ProfScope ps("adam_multi", st, 28.0 * (double)total_numel);
-    const long chunks = std::max<long>(1, (long)((total_numel + kMultiChunk - 1) / kMultiChunk));
-    const dim3 grid((int)std::min<long>(chunks, 256 * 8));
-    hipLaunchKernelGGL(adam_multi_kernel, grid, dim3(256), 0, st, tensors, n, step, lr, beta_1, beta_2, epsilon, lr_dev);
-    FIL_CHECK_LAUNCH_W(who);
-  }
-  if (advance) {
-    launch_step_advance(step, st);
-    FIL_CHECK_LAUNCH_W(who);
-  }
-  return FIL_OK;
-}
-
+// ---- the dense launch and the Keras / lazy mode table updates: the launchers of optim_adam.h without the amsgrad slot.  A _lrdev
+// twin passes lr = 0 and its device rate.
 extern "C" int fil_adam_multi(const fil_adam_tensor* tensors, int n, int64_t total_numel, int64_t* step, float lr, float beta_1,
                               float beta_2, float epsilon, int advance, void* stream) {
-  return adam_multi_impl("fil_adam_multi", tensors, n, total_numel, step, lr, beta_1, beta_2, epsilon, advance, stream, nullptr);
+  return adam_multi_launch("fil_adam_multi", "adam_multi", 28.0, adam_multi_kernel, tensors, n, total_numel, step, lr, nullptr, beta_1,
+                           beta_2, epsilon, advance, stream);
 }
 
 extern "C" int fil_adam_multi_lrdev(const fil_adam_tensor* tensors, int n, int64_t total_numel, int64_t* step, const float* lr_dev, float beta_1,
                               float beta_2, float epsilon, int advance, void* stream) {
   if (lr_dev == nullptr) return fail(FIL_ERR_ARG, "fil_adam_multi_lrdev: no device rate (lr_dev is NULL)");
-  return adam_multi_impl("fil_adam_multi_lrdev", tensors, n, total_numel, step, 0.f, beta_1, beta_2, epsilon, advance, stream, lr_dev);
-}
-
-static int embed_adam_runs_impl(const char* who, const void* g, const int64_t* perm, const int64_t* sorted_ids, long R, int K, int g_dtype,
-                                int F, const float* field_l2, float* table, float* m, float* v, int32_t* stamp, const int64_t* step,
-                                float lr, float beta_1, float beta_2, float epsilon, int mode, void* stream, const float* lr_dev) {
-  FIL_CHECK_ARG_W(who, R >= 0 && K >= 1 && F >= 1);
-  if (g_dtype != FIL_F32 && g_dtype != FIL_BF16) return fail(FIL_ERR_ARG, "%s: g_dtype %d (f32 or bf16)", who, g_dtype);
-  if (int rc = check_mode(who, mode, stamp)) return rc;
-  if (int rc = check_table_shape(who, K, 0)) return rc;
-  if (int rc = check_hyper(who, lr, beta_1, beta_2, epsilon)) return rc;
-  if (R == 0) return FIL_OK;
-  FIL_CHECK_ARG_W(who, g && perm && sorted_ids && table && m && v && step);
-  hipStream_t st = (hipStream_t)stream;
-  ProfScope ps("embed_adam_runs", st, (double)R * K * (g_dtype == FIL_F32 ? 4 : 2) + 24.0 * R * K);
-  const dim3 grid = run_sums_grid(R, K);
-  if (g_dtype == FIL_F32)
-    hipLaunchKernelGGL(embed_adam_runs_kernel<float>, grid, dim3(256), 0, st, static_cast<const float*>(g), perm, sorted_ids, R, K, F,
-                       field_l2, table, m, v, mode == FIL_ADAM_KERAS ? stamp : nullptr, step, lr, beta_1, beta_2, epsilon, lr_dev);
-  else
-    hipLaunchKernelGGL(embed_adam_runs_kernel<__hip_bfloat16>, grid, dim3(256), 0, st, static_cast<const __hip_bfloat16*>(g), perm,
-                       sorted_ids, R, K, F, field_l2, table, m, v, mode == FIL_ADAM_KERAS ? stamp : nullptr, step, lr, beta_1, beta_2,
-                       epsilon, lr_dev);
-  FIL_CHECK_LAUNCH_W(who);
-  return FIL_OK;
+  return adam_multi_launch("fil_adam_multi_lrdev", "adam_multi", 28.0, adam_multi_kernel, tensors, n, total_numel, step, 0.f, lr_dev,
+                           beta_1, beta_2, epsilon, advance, stream);
 }
 
 extern "C" int fil_embed_adam_runs(const void* g, const int64_t* perm, const int64_t* sorted_ids, long R, int K, int g_dtype, int F,
                                    const float* field_l2, float* table, float* m, float* v, int32_t* stamp, const int64_t* step,
                                    float lr, float beta_1, float beta_2, float epsilon, int mode, void* stream) {
-  return embed_adam_runs_impl("fil_embed_adam_runs", g, perm, sorted_ids, R, K, g_dtype, F, field_l2, table, m, v, stamp, step, lr, beta_1,
-                              beta_2, epsilon, mode, stream, nullptr);
+  return embed_adam_runs_launch<false>("fil_embed_adam_runs", g, perm, sorted_ids, R, K, g_dtype, F, field_l2, table, m, v, nullptr, stamp,
+                                       step, lr, nullptr, beta_1, beta_2, epsilon, mode, stream);
 }
 
 extern "C" int fil_embed_adam_runs_lrdev(const void* g, const int64_t* perm, const int64_t* sorted_ids, long R, int K, int g_dtype, int F,
                                    const float* field_l2, float* table, float* m, float* v, int32_t* stamp, const int64_t* step,
                                    const float* lr_dev, float beta_1, float beta_2, float epsilon, int mode, void* stream) {
   if (lr_dev == nullptr) return fail(FIL_ERR_ARG, "fil_embed_adam_runs_lrdev: no device rate (lr_dev is NULL)");
-  return embed_adam_runs_impl("fil_embed_adam_runs_lrdev", g, perm, sorted_ids, R, K, g_dtype, F, field_l2, table, m, v, stamp, step, 0.f,
-                              beta_1, beta_2, epsilon, mode, stream, lr_dev);
-}
-
-static int embed_adam_sweep_impl(const char* who, float* table, float* m, float* v, const int32_t* stamp, int64_t V, int K,
-                                 const int64_t* offsets, const float* field_l2, const unsigned char* frozen, int F, const int64_t* step,
-                                 float lr, float beta_1, float beta_2, float epsilon, void* stream, const float* lr_dev) {
-  FIL_CHECK_ARG_W(who, V >= 0 && K >= 1 && F >= 1);
-  if (int rc = check_table_shape(who, 0, F)) return rc;
-  if (int rc = check_hyper(who, lr, beta_1, beta_2, epsilon)) return rc;
-  if (V == 0) return FIL_OK;
-  FIL_CHECK_ARG_W(who, table && m && v && stamp && offsets && step);
-  hipStream_t st = (hipStream_t)stream;
-  const int64_t n = V * K;
-  const int vec = sweep_vec(K, table, m, v);
-  const int64_t work = vec ? n / 4 : n;
-  ProfScope ps("embed_adam_sweep", st, 24.0 * (double)n + 4.0 * (double)V);
-  const dim3 grid = stride_grid(work);
-  hipLaunchKernelGGL(embed_adam_sweep_kernel, grid, dim3(256), 0, st, table, m, v, stamp, V, K, offsets, field_l2, frozen, F, step, lr,
-                     beta_1, beta_2, epsilon, vec, lr_dev);
-  FIL_CHECK_LAUNCH_W(who);
-  return FIL_OK;
+  return embed_adam_runs_launch<false>("fil_embed_adam_runs_lrdev", g, perm, sorted_ids, R, K, g_dtype, F, field_l2, table, m, v, nullptr,
+                                       stamp, step, 0.f, lr_dev, beta_1, beta_2, epsilon, mode, stream);
 }
 
 extern "C" int fil_embed_adam_sweep(float* table, float* m, float* v, const int32_t* stamp, int64_t V, int K, const int64_t* offsets,
                                     const float* field_l2, const unsigned char* frozen, int F, const int64_t* step, float lr,
                                     float beta_1, float beta_2, float epsilon, void* stream) {
-  return embed_adam_sweep_impl("fil_embed_adam_sweep", table, m, v, stamp, V, K, offsets, field_l2, frozen, F, step, lr, beta_1, beta_2,
-                               epsilon, stream, nullptr);
+  return embed_adam_sweep_launch<false>("fil_embed_adam_sweep", table, m, v, nullptr, stamp, V, K, offsets, field_l2, frozen, F, step, lr,
+                                        nullptr, beta_1, beta_2, epsilon, stream);
 }
 
 extern "C" int fil_embed_adam_sweep_lrdev(float* table, float* m, float* v, const int32_t* stamp, int64_t V, int K, const int64_t* offsets,
                                     const float* field_l2, const unsigned char* frozen, int F, const int64_t* step, const float* lr_dev,
                                     float beta_1, float beta_2, float epsilon, void* stream) {
   if (lr_dev == nullptr) return fail(FIL_ERR_ARG, "fil_embed_adam_sweep_lrdev: no device rate (lr_dev is NULL)");
-  return embed_adam_sweep_impl("fil_embed_adam_sweep_lrdev", table, m, v, stamp, V, K, offsets, field_l2, frozen, F, step, 0.f, beta_1,
-                               beta_2, epsilon, stream, lr_dev);
-}
-
-
-static int embed_adam_merged_impl(const char* who, const int64_t* ids, const float* values, const int64_t* counts, int W, long cap, int K,
-                                  const int64_t* offsets, const float* field_l2, int F, float* table, float* m, float* v, int32_t* stamp,
-                                  int64_t V, const int64_t* step, float lr, float beta_1, float beta_2, float epsilon, int mode,
-                                  void* stream, const float* lr_dev) {
-  FIL_CHECK_ARG_W(who, W >= 1 && cap >= 0 && K >= 1 && F >= 1 && V >= 0);
-  if (int rc = check_mode(who, mode, stamp)) return rc;
-  if (int rc = check_table_shape(who, K, F)) return rc;
-  if (int rc = check_hyper(who, lr, beta_1, beta_2, epsilon)) return rc;
-  if (cap == 0 || V == 0) return FIL_OK;
-  FIL_CHECK_ARG_W(who, ids && values && counts && offsets && table && m && v && step);
-  hipStream_t st = (hipStream_t)stream;
-  const long n = (long)W * cap;
-  ProfScope ps("embed_adam_merged", st, 8.0 * n + 4.0 * (double)n * K + 24.0 * (double)cap * K);
-  const dim3 grid = stride_grid(n);
-  hipLaunchKernelGGL(embed_adam_merged_kernel, grid, dim3(256), 0, st, ids, values, counts, W, cap, K, offsets, field_l2, F, table, m, v,
-                     mode == FIL_ADAM_KERAS ? stamp : nullptr, V, step, lr, beta_1, beta_2, epsilon, lr_dev);
-  FIL_CHECK_LAUNCH_W(who);
-  return FIL_OK;
+  return embed_adam_sweep_launch<false>("fil_embed_adam_sweep_lrdev", table, m, v, nullptr, stamp, V, K, offsets, field_l2, frozen, F, step,
+                                        0.f, lr_dev, beta_1, beta_2, epsilon, stream);
 }
 
 extern "C" int fil_embed_adam_merged(const int64_t* ids, const float* values, const int64_t* counts, int W, long cap, int K,
                                      const int64_t* offsets, const float* field_l2, int F, float* table, float* m, float* v, int32_t* stamp,
                                      int64_t V, const int64_t* step, float lr, float beta_1, float beta_2, float epsilon, int mode,
                                      void* stream) {
-  return embed_adam_merged_impl("fil_embed_adam_merged", ids, values, counts, W, cap, K, offsets, field_l2, F, table, m, v, stamp, V, step,
-                                lr, beta_1, beta_2, epsilon, mode, stream, nullptr);
+  return embed_adam_merged_launch<false>("fil_embed_adam_merged", ids, values, counts, W, cap, K, offsets, field_l2, F, table, m, v, nullptr,
+                                         stamp, V, step, lr, nullptr, beta_1, beta_2, epsilon, mode, stream);
 }
 
 extern "C" int fil_embed_adam_merged_lrdev(const int64_t* ids, const float* values, const int64_t* counts, int W, long cap, int K,
@@ -622,8 +429,8 @@ extern "C" int fil_embed_adam_merged_lrdev(const int64_t* ids, const float* valu
                                      int64_t V, const int64_t* step, const float* lr_dev, float beta_1, float beta_2, float epsilon, int mode,
                                      void* stream) {
   if (lr_dev == nullptr) return fail(FIL_ERR_ARG, "fil_embed_adam_merged_lrdev: no device rate (lr_dev is NULL)");
-  return embed_adam_merged_impl("fil_embed_adam_merged_lrdev", ids, values, counts, W, cap, K, offsets, field_l2, F, table, m, v, stamp, V,
-                                step, 0.f, beta_1, beta_2, epsilon, mode, stream, lr_dev);
+  return embed_adam_merged_launch<false>("fil_embed_adam_merged_lrdev", ids, values, counts, W, cap, K, offsets, field_l2, F, table, m, v,
+                                         nullptr, stamp, V, step, 0.f, lr_dev, beta_1, beta_2, epsilon, mode, stream);
 }
 
 extern "C" int fil_embed_adam_ring_len(int sweep_period) { return ring_len(sweep_period); }

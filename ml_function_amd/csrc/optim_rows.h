@@ -1,9 +1,11 @@
-// What the fused optimizers of optim.hip (Adam), optim_rowwise.hip (Adagrad, Ftrl) and optim_momentum.hip (SGD, RMSprop) share: the
-// walk of the dense descriptors (fil_adam_multi, fil_rowopt_multi, fil_momopt_multi), the field of a row, the walk of the gathered
+// What the fused optimizers of optim.hip (Adam), optim_amsgrad.hip (Adam with amsgrad), optim_rowwise.hip (Adagrad, Ftrl) and
+// optim_momentum.hip (SGD, RMSprop) share: the one walk of the dense descriptors, two-slot or with amsgrad's third slot (fil_adam_multi,
+// fil_amsgrad_multi, fil_rowopt_multi, fil_momopt_multi), the field of a row, the walk of the gathered
 // compact lists of fil_embed_runs_compact (runs_compact.hip; the merged updates), the regulariser's gradient, the sweeps' compacted
 // field table, the workgroup sum and scan, and what every launcher computes the same way: the row tag of a step, the sweep's 16-byte
 // predicate, the grid-stride grid and the table-shape check.
-// optim.hip builds its own kernels on them (its coefficients depend on the step; lazy and deferred modes); the row-rule families get
+// Adam and its amsgrad form build their kernels on them in optim_adam.h and optim.hip (their coefficients depend on the step; lazy
+// and deferred modes); the row-rule families get
 // theirs, and their host launchers, from optim_rule.h, which sits on this header: there a rule supplies only its per-element update.
 #pragma once
 #include "common.h"
@@ -67,13 +69,15 @@ __device__ __forceinline__ long find_in_list(const int64_t* __restrict__ ids, co
 
 // ---- the dense launch: the descriptors' elements form one index space of kMultiChunk-element chunks (a workgroup's 256 lanes x 4),
 // dealt round robin over the grid; a workgroup walks the descriptor list once and takes its chunks of each (grid-stride, balanced
-// over tensors of any size).  16-byte accesses where the descriptor's arrays allow it (`m` and `v` only count when the rule has them:
-// kM, kV -- a slot the rule does not have is neither read nor written and may be NULL), element-wise otherwise and in the tail.  elem(p, m, v, g, l2x2) updates one element: g the gradient (0 without one), l2x2 = 2 l2
-// of the descriptor.
+// over tensors of any size).  16-byte accesses where the descriptor's arrays allow it (a slot only counts when the rule has it: kM,
+// kV, kH -- a slot the rule does not have is neither read nor written and may be NULL), element-wise otherwise and in the tail.
+// The one walk, multi_tensor_walk_desc, is over any descriptor type T with fil_adam_tensor's members; kH: T also has a third slot
+// `vhat` (fil_amsgrad_tensor).  elem(p, m, v, h, g, l2x2) updates one element: g the gradient (0 without one), l2x2 = 2 l2 of the
+// descriptor.
 constexpr int kMultiChunk = 1024;
 
-template <bool kM, bool kV, typename Elem>
-__device__ __forceinline__ void multi_tensor_walk_slots(const fil_adam_tensor* __restrict__ ts, int n, const Elem& elem) {
+template <typename T, bool kM, bool kV, bool kH, typename Elem>
+__device__ __forceinline__ void multi_tensor_walk_desc(const T* __restrict__ ts, int n, const Elem& elem) {
   const long G = gridDim.x;
   long base = 0;
   for (int d = 0; d < n; ++d) {
@@ -81,10 +85,13 @@ __device__ __forceinline__ void multi_tensor_walk_slots(const fil_adam_tensor* _
     const float* __restrict__ Gr = ts[d].grad;
     float* __restrict__ M = ts[d].m;
     float* __restrict__ V = ts[d].v;
+    float* __restrict__ H = nullptr;
+    if constexpr (kH) H = ts[d].vhat;
     const long numel = ts[d].numel;
     const float l2x2 = 2.f * ts[d].l2;
     const long nc = (numel + kMultiChunk - 1) / kMultiChunk;
-    const bool vec = ((((uintptr_t)P | (uintptr_t)Gr | (kM ? (uintptr_t)M : 0) | (kV ? (uintptr_t)V : 0)) & 15) == 0);
+    const uintptr_t slots = (kM ? (uintptr_t)M : 0) | (kV ? (uintptr_t)V : 0) | (kH ? (uintptr_t)H : 0);
+    const bool vec = ((((uintptr_t)P | (uintptr_t)Gr | slots) & 15) == 0);
     long r = ((long)blockIdx.x - base) % G;
     if (r < 0) r += G;
     for (long ch = r; ch < nc; ch += G) {
@@ -94,25 +101,35 @@ __device__ __forceinline__ void multi_tensor_walk_slots(const fil_adam_tensor* _
         float4 g = Gr ? *reinterpret_cast<const float4*>(Gr + e) : make_float4(0.f, 0.f, 0.f, 0.f);
         float4 m = kM ? *reinterpret_cast<const float4*>(M + e) : make_float4(0.f, 0.f, 0.f, 0.f);
         float4 v = kV ? *reinterpret_cast<const float4*>(V + e) : make_float4(0.f, 0.f, 0.f, 0.f);
-        elem(p.x, m.x, v.x, g.x, l2x2);
-        elem(p.y, m.y, v.y, g.y, l2x2);
-        elem(p.z, m.z, v.z, g.z, l2x2);
-        elem(p.w, m.w, v.w, g.w, l2x2);
+        float4 h = kH ? *reinterpret_cast<const float4*>(H + e) : make_float4(0.f, 0.f, 0.f, 0.f);
+        elem(p.x, m.x, v.x, h.x, g.x, l2x2);
+        elem(p.y, m.y, v.y, h.y, g.y, l2x2);
+        elem(p.z, m.z, v.z, h.z, g.z, l2x2);
+        elem(p.w, m.w, v.w, h.w, g.w, l2x2);
         *reinterpret_cast<float4*>(P + e) = p;
         if (kM) *reinterpret_cast<float4*>(M + e) = m;
         if (kV) *reinterpret_cast<float4*>(V + e) = v;
+        if (kH) *reinterpret_cast<float4*>(H + e) = h;
       } else {
         for (long i = e; i < e + 4 && i < numel; ++i) {
-          float p = P[i], m = kM ? M[i] : 0.f, v = kV ? V[i] : 0.f;
-          elem(p, m, v, Gr ? Gr[i] : 0.f, l2x2);
+          float p = P[i], m = kM ? M[i] : 0.f, v = kV ? V[i] : 0.f, h = kH ? H[i] : 0.f;
+          elem(p, m, v, h, Gr ? Gr[i] : 0.f, l2x2);
           P[i] = p;
           if (kM) M[i] = m;
           if (kV) V[i] = v;
+          if (kH) H[i] = h;
         }
       }
     }
     base += nc;
   }
+}
+
+// the walk of the two-slot descriptor: elem(p, m, v, g, l2x2)
+template <bool kM, bool kV, typename Elem>
+__device__ __forceinline__ void multi_tensor_walk_slots(const fil_adam_tensor* __restrict__ ts, int n, const Elem& elem) {
+  multi_tensor_walk_desc<fil_adam_tensor, kM, kV, false>(
+      ts, n, [&](float& p, float& m, float& v, float&, float g, float l2x2) { elem(p, m, v, g, l2x2); });
 }
 
 // the walk of a rule that always has its first slot (Adam, Adagrad, Ftrl)
