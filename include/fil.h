@@ -344,6 +344,40 @@ int fil_embed_bag_bwd_prep(const float* g, const int* count, const int64_t* slot
                            int K, int combiner, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * N3  AFM pair-attention pooling with the softmax over the PAIRS (extension: the reference's AttentionBaseLayer,
+ *     interactive_layer.py:357-364, normalises over a size-1 axis, so all of its weights are 1; that stays the layers' default and is
+ *     not computed here).  All tensors fp32.  Entry points added only: the ABI version stays.
+ *   emb [B,F,K]; W [K,A], b [A], h [A] (single_score_w, single_score_b, single_mlp_kernel [A,1]).  Pairs p = (i, j), i < j, in
+ *   itertools.combinations order, P = F(F-1)/2; x_p = e_i * e_j, u_p = x_p W + b;
+ *     flags bit 0 clear (reference op order): s_p = relu(u_p . h);   set (FIL_AFM_HIDDEN_RELU, the paper's form): s_p = relu(u_p) . h;
+ *     a = softmax_p(s) with the maximum subtracted;  pooled[b,:] = sum_p a_p x_p   [B,K].
+ *   fil_afm_fwd: pooled, and stats [B,2] = (maximum score, softmax denominator) for the backward (opaque to the caller).
+ *   fil_afm_bwd: g = d pooled [B,K] -> demb [B,F,K], dW [K,A], db [A], dh [A]; the scores are recomputed (same code, same bits).
+ *     ds_p = a_p (g.x_p - g.pooled); du_p through the ReLU of the chosen form (derivative 0 at 0); dW = sum x_p^T du_p, db = sum du_p,
+ *     dh = sum dt_p u_p (reference form) or sum ds_p relu(u_p) (paper form); dx_p = a_p g + W du_p; de_i += dx_p * e_j, de_j += dx_p * e_i.
+ *     demb may be NULL, and dW / db / dh may each be NULL (all three NULL: no parameter pass, no workspace; everything NULL: FIL_ERR_ARG).
+ *     The parameter gradients leave the main launch as one partial per workgroup in `workspace` (fil_afm_bwd_workspace_bytes; every
+ *     byte that is read was written by that launch) and a second small launch adds the partials in a fixed order.
+ *   Nothing of size B P touches global memory in either direction.  No atomics; every sum has a fixed order for a given shape: the
+ *   same inputs give the same bits on every call.  A wave owns whole samples out of an LDS-resident [F,K] slab; W, b, h and the pair
+ *   table are staged once per workgroup.  F = 2 (one pair): pooled == e_0 * e_1 and demb == g * e_other bit for bit, dW = db = dh = 0.
+ *   Menu: 2 <= F <= 64, K % 4 == 0, K <= 64, A <= 16 (FIL_ERR_UNSUPPORTED otherwise, the limit in the message); the dynamic LDS stays
+ *   within 163,328 bytes over the whole menu (the workgroup shrinks from 4 waves to 1 as the footprint grows).
+ *   B == 0 returns FIL_OK before any pointer is looked at.  A workspace smaller than needed: FIL_ERR_ARG, the needed size in the message.
+ *   fil_afm_plan: the launchers' own arithmetic (no GPU call): plan[8] = {fwd_ok, bwd_ok, samples per workgroup tile (= waves per
+ *     workgroup), grid, grid cap, parameter-gradient partials (= grid), forward LDS bytes, backward LDS bytes}.  Returns FIL_OK, or
+ *     the argument / menu error the launch would give.
+ */
+#define FIL_AFM_HIDDEN_RELU 1
+int fil_afm_plan(int B, int F, int K, int A, int* plan /* [8] */);
+int fil_afm_fwd(const float* emb, const float* W, const float* b, const float* h, float* pooled, float* stats, int B, int F, int K,
+                int A, int flags, void* stream);
+size_t fil_afm_bwd_workspace_bytes(int B, int F, int K, int A);
+int fil_afm_bwd(const float* emb, const float* W, const float* b, const float* h, const float* pooled, const float* stats,
+                const float* g, float* demb, float* dW, float* db, float* dh, void* workspace, size_t workspace_bytes, int B, int F,
+                int K, int A, int flags, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * N2  The score head and the loss behind the interaction layers (all tensors fp32, n = batch rows).
  *   ScoreLayer(use_add=True).call (kon/model/ctr_model/layer/core_layer/core_layer.py:58-84): keras Add over the [B,1] parts,
  *   then sigmoid.  fil_score_add_sigmoid_fwd: out[i] = sigmoid(((a[i] + b[i]) + c[i]) + d[i]) -- left to right like the

@@ -39,6 +39,8 @@ FIL_MEAN_ONE_LAUNCH_N = 16384
 FIL_BAG_SUM, FIL_BAG_MEAN, FIL_BAG_SQRTN = 0, 1, 2
 FIL_BAG_NO_PAD = -(1 << 63)      # INT64_MIN: no id is padding
 FIL_BAG_MAX_BLOCKS = 2048        # fil_embed_bag_fwd's grid cap (workgroups of 256 threads)
+FIL_AFM_HIDDEN_RELU = 1          # fil_afm_*'s flag bit 0: s_p = relu(u_p) . h (the paper's form)
+FIL_ERR_UNSUPPORTED = -4
 
 _c = ctypes
 _P = _c.c_void_p
@@ -89,6 +91,11 @@ SIGNATURES = {
     "fil_embed_bag_fwd": (_I, [_P, _P, _P, _P, _c.c_int64, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
     "fil_embed_bag_row_ids": (_I, [_P, _P, _P, _P, _c.c_int64, _P, _I, _I, _I, _P]),
     "fil_embed_bag_bwd_prep": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
+    # N3: AFM pair-attention pooling (softmax over the pairs)
+    "fil_afm_plan": (_I, [_I, _I, _I, _I, _P]),
+    "fil_afm_fwd": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
+    "fil_afm_bwd_workspace_bytes": (_Z, [_I, _I, _I, _I]),
+    "fil_afm_bwd": (_I, [_P] * 12 + [_Z, _I, _I, _I, _I, _I, _P]),
     "fil_score_add_sigmoid_fwd": (_I, [_P, _P, _P, _P, _P, _I, _P]),
     "fil_score_add_sigmoid_bwd": (_I, [_P, _P, _P, _I, _P]),
     "fil_bce_mean_fwd": (_I, [_P, _P, _F, _P, _P, _I, _P]),

@@ -148,6 +148,70 @@ def fm_pairs(emb):
     return _FmPairsFn.apply(emb)
 
 
+class _AfmPoolFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, emb, w, b, h, hidden_relu):
+        _require_cuda(emb, w, b, h)
+        emb, w, b, h = _f32c(emb), _f32c(w), _f32c(b), _f32c(h)
+        if emb.dim() != 3 or w.dim() != 2 or w.shape[0] != emb.shape[2]:
+            raise FilError("afm_pool: emb must be [B,F,K] and w [K,A], got %s and %s" % (tuple(emb.shape), tuple(w.shape)))
+        B, F, K = emb.shape
+        A = w.shape[1]
+        if b.numel() != A or h.numel() != A:
+            raise FilError("afm_pool: b must be [A] and h [A,1] with A = %d, got %s and %s" % (A, tuple(b.shape), tuple(h.shape)))
+        flags = _lib.FIL_AFM_HIDDEN_RELU if hidden_relu else 0
+        pooled = torch.empty((B, K), dtype=torch.float32, device=emb.device)
+        stats = torch.empty((B, 2), dtype=torch.float32, device=emb.device)
+        check(_lib.load().fil_afm_fwd(ptr(emb), ptr(w), ptr(b), ptr(h), ptr(pooled), ptr(stats), B, F, K, A, flags, stream_ptr()),
+              "fil_afm_fwd")
+        ctx.save_for_backward(emb, w, b, h, pooled, stats)
+        ctx.flags = flags
+        ctx.shapes = (tuple(b.shape), tuple(h.shape))
+        return pooled
+
+    @staticmethod
+    def backward(ctx, g):
+        emb, w, b, h, pooled, stats = ctx.saved_tensors
+        B, F, K = emb.shape
+        A = w.shape[1]
+        need = ctx.needs_input_grad
+        if not any(need[:4]):
+            return None, None, None, None, None
+        lib = _lib.load()
+        demb = torch.empty_like(emb) if need[0] else None
+        dw = torch.empty_like(w) if need[1] else None
+        db = torch.empty(ctx.shapes[0], dtype=torch.float32, device=emb.device) if need[2] else None
+        dh = torch.empty(ctx.shapes[1], dtype=torch.float32, device=emb.device) if need[3] else None
+        ws, nws = None, 0
+        if need[1] or need[2] or need[3]:
+            nws = lib.fil_afm_bwd_workspace_bytes(B, F, K, A)
+            ws = _scratch(nws, emb.device, "afm_bwd")
+        check(lib.fil_afm_bwd(ptr(emb), ptr(w), ptr(b), ptr(h), ptr(pooled), ptr(stats), ptr(_f32c(g)), ptr(demb), ptr(dw), ptr(db),
+                              ptr(dh), ptr(ws), nws, B, F, K, A, ctx.flags, stream_ptr()), "fil_afm_bwd")
+        return demb, dw, db, dh, None
+
+
+def afm_pool(emb, w, b, h, hidden_relu=False):
+    """AFM's attention pooling with the softmax over the PAIRS (extension; include/fil.h fil_afm_*): emb [B,F,K], w [K,A], b [A],
+    h [A,1] (or [A]) -> [B,K] = sum_p softmax_p(s)_p e_i * e_j over the pairs p = (i, j), i < j, with s_p = relu((x_p w + b) . h)
+    (the reference's op order) or, hidden_relu=True, relu(x_p w + b) . h (the paper's form).  One launch per direction (plus the small
+    fixed-order sum of the parameter-gradient partials); no [B,P,K] tensor exists.  Shapes outside the kernel menu raise FilError
+    (layers.AFMLayer takes its composed path there)."""
+    return _AfmPoolFn.apply(emb, w, b, h, bool(hidden_relu))
+
+
+def afm_plan(B, F, K, A):
+    """fil_afm_plan's answer as a dict (fits, tile, grid, cap, partials, lds_fwd, lds_bwd); fits=False (and nothing else) for a shape
+    outside the kernel menu."""
+    plan = (ctypes.c_int * 8)()
+    rc = _lib.load().fil_afm_plan(int(B), int(F), int(K), int(A), plan)
+    if rc == _lib.FIL_ERR_UNSUPPORTED:
+        return dict(fits=False)
+    check(rc, "fil_afm_plan")
+    return dict(fits=bool(plan[0]) and bool(plan[1]), tile=plan[2], grid=plan[3], cap=plan[4], partials=plan[5], lds_fwd=plan[6],
+                lds_bwd=plan[7])
+
+
 # --------------------------------------------------------------------------------------------- A2  DCN
 class _DcnFn(torch.autograd.Function):
     @staticmethod

@@ -3,10 +3,10 @@ from .base import Layer
 from .behavior_layer import MultHeadAttentionLayer, ProductAttentionLayer
 from .core_layer import (AlignLayer, Dense, DnnLayer, HiddenLayer, IntraViewPoolingLayer, MergeScoreLayer, ResActivateLayer, ScoreLayer,
                          StackLayer)
-from .interactive_layer import (CIN, AttentionBaseLayer, BagEmbed, CrossLayer, ExtractLayer, FmLayer, InnerLayer, IPnnLayer, LinearLayer,
+from .interactive_layer import (CIN, AFMLayer, AttentionBaseLayer, BagEmbed, CrossLayer, ExtractLayer, FmLayer, InnerLayer, IPnnLayer, LinearLayer,
                                 OPnnLayer, SparseEmbed)
 
 __all__ = ["capture_step", "Layer", "InnerLayer", "FmLayer", "CrossLayer", "CIN", "SparseEmbed", "ProductAttentionLayer",
            "MultHeadAttentionLayer", "StackLayer", "ScoreLayer", "MergeScoreLayer", "HiddenLayer", "ResActivateLayer",
            "DnnLayer", "Dense", "IPnnLayer", "OPnnLayer", "LinearLayer", "AttentionBaseLayer", "ExtractLayer",
-           "IntraViewPoolingLayer", "AlignLayer", "BagEmbed"]
+           "IntraViewPoolingLayer", "AlignLayer", "BagEmbed", "AFMLayer"]

@@ -156,28 +156,86 @@ class AttentionBaseLayer(Layer):
     x = concat(pairs, axis=1) [B,P,K]; score = Dense(1, relu, no bias)(x . single_score_w + single_score_b) [B,P,1];
     ``Activation('softmax')`` normalises over the LAST axis, which has size 1 here, so every weight is exactly 1 and
     the layer returns Dense(output_dim)(sum_p x_p): the reference's quirk is kept (the score weights get zero gradient).
-    The pair tensor comes from the HIP pair kernel (InnerLayer); the small dense algebra runs in torch."""
+    The pair tensor comes from the HIP pair kernel (InnerLayer); the small dense algebra runs in torch.
+    softmax_axis=1 (extension; default -1 = the quirk above): the softmax runs over the PAIRS, the paper's layer, in torch on the pair
+    list it is given -- the composed form of AFMLayer below, and the form for a caller who already holds the pairs.
+    hidden_relu=True (extension): score = relu(x . w + b) . single_mlp_kernel, the paper's op order, instead of the reference's
+    relu((x . w + b) . single_mlp_kernel)."""
 
-    def __init__(self, attention_dim=4, seed=2020, output_dim=1):
+    def __init__(self, attention_dim=4, seed=2020, output_dim=1, softmax_axis=-1, hidden_relu=False):
         super().__init__()
         from .core_layer import Dense
+        if softmax_axis not in (-1, 1):
+            raise ValueError("AttentionBaseLayer: softmax_axis %r (-1 = the reference's size-1 axis, 1 = over the pairs)" % (softmax_axis,))
         self.atten_dim = attention_dim
         self.seed = seed
+        self.softmax_axis = softmax_axis
+        self.hidden_relu = bool(hidden_relu)
         self.output_layer = Dense(output_dim)
 
     def build(self, input_shape):
-        k = input_shape[0][-1]
+        k = input_shape[0][-1] if isinstance(input_shape, list) else input_shape[-1]
         self.kernel_w = self.add_weight("single_score_w", [k, self.atten_dim], "glorot_uniform", seed=self.seed)
         self.kernel_b = self.add_weight("single_score_b", [self.atten_dim], "glorot_uniform", seed=self.seed)
         self.single_mlp_kernel = self.add_weight("single_mlp_kernel", [self.atten_dim, 1], "glorot_uniform", seed=self.seed)
         super().build(input_shape)
 
+    def _pool(self, x, softmax_axis):
+        """x [B,P,K] pair products -> [B,K]: the scores, their softmax over `softmax_axis`, the weighted sum over the pairs."""
+        u = torch.matmul(x, self.kernel_w) + self.kernel_b
+        if self.hidden_relu:
+            score = torch.matmul(torch.relu(u), self.single_mlp_kernel)
+        else:
+            score = torch.relu(torch.matmul(u, self.single_mlp_kernel))
+        score_w = torch.softmax(score, dim=softmax_axis)
+        return (score_w * x).sum(dim=1)
+
     def call(self, inputs, **kwargs):
-        x = pack_fields(inputs)
-        score = torch.relu(torch.matmul(torch.matmul(x, self.kernel_w) + self.kernel_b, self.single_mlp_kernel))
-        score_w = torch.softmax(score, dim=-1)
-        atten_inputs = (score_w * x).sum(dim=1)
-        return self.output_layer(atten_inputs)
+        return self.output_layer(self._pool(pack_fields(inputs), self.softmax_axis))
+
+
+_AFM_FITS = {}                 # (F, K, A) -> fil_afm_plan's answer (the menu is fixed for the life of the process)
+
+
+class AFMLayer(AttentionBaseLayer):
+    """AFM's attention pooling with the softmax over the PAIRS (extension: the paper's layer; AttentionBaseLayer above is the
+    reference's, whose softmax over a size-1 axis leaves every weight at 1 and the score weights without gradient).
+
+    call(list of F field embeddings [B,1,K], or a packed [B,F,K]) -> [B, output_dim] =
+    Dense(output_dim)(sum_p softmax_p(score)_p e_i * e_j).  It takes the FIELD embeddings, not the pair list: pair products, scores,
+    softmax and the weighted sum run in one HIP kernel per direction (Fn.afm_pool, include/fil.h fil_afm_*) and no [B,P,K] tensor
+    exists.  Weights: AttentionBaseLayer's (single_score_w [K,attention_dim], single_score_b, single_mlp_kernel [attention_dim,1],
+    output_layer; same names, initialisers and seed), so a state dict moves between the two layers.  hidden_relu: as
+    AttentionBaseLayer's.  Outside the kernel menu (fits_kernel_menu) or for a non-fp32 input the layer takes the composed path
+    instead of raising: the HIP pair kernel plus AttentionBaseLayer(softmax_axis=1)'s torch graph, computed in fp32."""
+
+    def __init__(self, attention_dim=4, seed=2020, output_dim=1, hidden_relu=False):
+        super().__init__(attention_dim=attention_dim, seed=seed, output_dim=output_dim, softmax_axis=1, hidden_relu=hidden_relu)
+
+    def fits_kernel_menu(self, inputs):
+        """fil_afm_*'s menu (include/fil.h): 2 <= F <= 64, K % 4 == 0, K <= 64, attention_dim <= 16 -- fil_afm_plan answers from the
+        launchers' own arithmetic; the answer is cached per shape."""
+        if inputs.dim() != 3:
+            return False
+        key = (int(inputs.shape[1]), int(inputs.shape[2]), int(self.atten_dim))
+        fits = _AFM_FITS.get(key)
+        if fits is None:
+            fits = _AFM_FITS[key] = Fn.afm_plan(1, *key)["fits"]
+        return fits
+
+    def _composed(self, emb):
+        """Fn.fm_pairs (HIP) + the torch graph of AttentionBaseLayer(softmax_axis=1), in fp32: six passes over [B,P,K] per direction
+        where the fused kernel makes none -- it exists so that a shape outside the kernel menu never raises."""
+        Fn._require_cuda(emb)        # (torch ops would run on a CPU tensor: there is no CPU path in this package)
+        return self._pool(Fn.fm_pairs(emb.to(torch.float32)), 1)
+
+    def call(self, inputs, **kwargs):
+        emb = pack_fields(inputs)
+        if emb.dtype == torch.float32 and self.fits_kernel_menu(emb):
+            pooled = Fn.afm_pool(emb, self.kernel_w, self.kernel_b, self.single_mlp_kernel, hidden_relu=self.hidden_relu)
+        else:
+            pooled = self._composed(emb)
+        return self.output_layer(pooled)
 
 
 class FmLayer(Layer):

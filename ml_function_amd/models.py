@@ -9,7 +9,7 @@ from collections import namedtuple
 
 import torch
 
-from .layers import (CIN, AttentionBaseLayer, BagEmbed, CrossLayer, DnnLayer, FmLayer, InnerLayer, IPnnLayer, MergeScoreLayer,
+from .layers import (CIN, AFMLayer, AttentionBaseLayer, BagEmbed, CrossLayer, DnnLayer, FmLayer, InnerLayer, IPnnLayer, MergeScoreLayer,
                      MultHeadAttentionLayer, OPnnLayer, ScoreLayer, SparseEmbed, StackLayer)
 from .layers.base import Layer
 from .layers.interactive_layer import pack_fields
@@ -189,16 +189,25 @@ class NFM(torch.nn.Module):
 
 
 class AFM(torch.nn.Module):
-    """models.AFM (:141-147)."""
+    """models.AFM (:141-147).  The defaults are the reference's model, whose attention softmax runs over a size-1 axis (every weight 1).
+    pair_softmax=True (extension): the paper's model -- the softmax over the pairs, through layers.AFMLayer on the field embeddings
+    (one fused kernel per direction; no InnerLayer, no pair tensor).  hidden_relu / attention_dim: the attention layer's."""
 
-    def __init__(self):
+    def __init__(self, pair_softmax=False, hidden_relu=False, attention_dim=4):
         super().__init__()
-        self.inner = InnerLayer()
-        self.atten = AttentionBaseLayer()
+        self.pair_softmax = bool(pair_softmax)
+        if self.pair_softmax:
+            self.atten = AFMLayer(attention_dim=attention_dim, hidden_relu=hidden_relu)
+        else:
+            self.inner = InnerLayer()
+            self.atten = AttentionBaseLayer(attention_dim=attention_dim, hidden_relu=hidden_relu)
         self.score = ScoreLayer(use_add=True)
 
     def forward(self, inputFea):
-        atten_output = self.atten(self.inner(inputFea.sparse_embed))
+        if self.pair_softmax:
+            atten_output = self.atten(inputFea.sparse_embed)
+        else:
+            atten_output = self.atten(self.inner(inputFea.sparse_embed))
         return self.score(list(inputFea.linear_embed) + [atten_output])
 
 
