@@ -378,6 +378,50 @@ int fil_afm_bwd(const float* emb, const float* W, const float* b, const float* h
                 int K, int A, int flags, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * N3  DIN attention pooling over a behaviour sequence (extension: the Deep Interest Network paper's activation unit; the
+ *     reference's AttentionUnitLayer / ActivationUnitLayer are not restated -- their source was not available).  All tensors fp32
+ *     except mask.  Entry points added only: the ABI version stays.
+ *   q [B,K] the candidate; keys [B,T,K] the history; mask [B,T] uint8, non-zero = live, NULL = all live (live slots may sit anywhere);
+ *   W1 [4K,H1], b1 [H1], alpha1 [H1], W2 [H1,H2], b2 [H2], alpha2 [H2], w3 [H2], b3 [1].
+ *     x_t = [q, k_t, q - k_t, q * k_t];  h1 = act(x_t W1 + b1);  h2 = act(h1 W2 + b2);  s_t = h2 . w3 + b3  (not scaled by sqrt(K));
+ *     flags bit 0 clear (raw, the paper): a_t = s_t for live t, 0 for masked t;  set (FIL_DIN_SOFTMAX): a = softmax of s over the LIVE t;
+ *     out[b,:] = sum_t a_t k_t  [B,K]  (a sample with no live slot: the zero row).
+ *     act = PReLU, u > 0 ? u : alpha u, a slope per unit (derivative at 0: alpha); flags bit 1 (FIL_DIN_SIGMOID): the logistic
+ *     sigmoid, alpha1 / alpha2 are then ignored and may be NULL.  ReLU = PReLU with alpha = 0 and no gradient asked for alpha.
+ *   fil_din_fwd: out, and stats [B, T+2] = (the T scores, maximum live score, softmax denominator) for the backward (opaque to the
+ *     caller).
+ *   fil_din_bwd: g = d out [B,K] -> dq [B,K], dkeys [B,T,K], dW1, db1, dalpha1, dW2, db2, dalpha2, dw3, db3; the hidden layers are
+ *     recomputed (same code, same bits).  ds_t = a_t (g.k_t - g.out) (softmax) or g.k_t (raw), 0 at masked t, with g.out summed as
+ *     sum_t a_t (g.k_t) from the saved scores (`out` itself is not read); dkeys is exactly 0 at masked slots.
+ *     Each of the ten outputs may be NULL and is then not computed (all eight parameter gradients NULL: no parameter pass, no
+ *     workspace; everything NULL: FIL_ERR_ARG).  With FIL_DIN_SIGMOID dalpha1 / dalpha2 receive zeros.  The parameter gradients leave
+ *     the main launch as one partial per workgroup in `workspace` (fil_din_bwd_workspace_bytes; every byte that is read was written
+ *     by that launch) and a second small launch adds the partials in a fixed order.
+ *   Nothing of size B T n, n >= K, other than keys and dkeys touches global memory.  No atomics; every sum has a fixed order for a
+ *   given shape: the same inputs give the same bits on every call.  A masked slot's key is never read.  Softmax with ONE live slot:
+ *   its weight is exactly 1, out is that key bit for bit, ds is exactly 0 (g.out is then that slot's g.k_t, the same bits).
+ *   Menu: K % 4 == 0, K <= 64, T <= 256, H1 <= 128, H2 <= 64, 4 K H1 + H1 H2 <= 16384 (FIL_ERR_UNSUPPORTED otherwise, the limit in
+ *   the message); the dynamic LDS stays within 163,328 bytes over the whole menu (a workgroup holds 4 samples down to 1 as the
+ *   footprint grows; a shape that still did not fit would return FIL_ERR_UNSUPPORTED with the byte count).
+ *   B == 0 returns FIL_OK before any pointer is looked at.  A workspace smaller than needed: FIL_ERR_ARG, the needed size in the message.
+ *   fil_din_plan: the launchers' own arithmetic (no GPU call): plan[8] = {fwd_ok, bwd_ok, samples per workgroup tile, grid, grid cap,
+ *     parameter-gradient partials (= grid), forward LDS bytes, backward LDS bytes}.  Returns FIL_OK, or the argument / menu error the
+ *     launch would give.
+ */
+#define FIL_DIN_SOFTMAX 1
+#define FIL_DIN_SIGMOID 2
+int fil_din_plan(int B, int T, int K, int H1, int H2, int* plan /* [8] */);
+int fil_din_fwd(const float* q, const float* keys, const unsigned char* mask, const float* W1, const float* b1, const float* alpha1,
+                const float* W2, const float* b2, const float* alpha2, const float* w3, const float* b3, float* out, float* stats, int B,
+                int T, int K, int H1, int H2, int flags, void* stream);
+size_t fil_din_bwd_workspace_bytes(int B, int T, int K, int H1, int H2);
+int fil_din_bwd(const float* q, const float* keys, const unsigned char* mask, const float* W1, const float* b1, const float* alpha1,
+                const float* W2, const float* b2, const float* alpha2, const float* w3, const float* b3, const float* out,
+                const float* stats, const float* g, float* dq, float* dkeys, float* dW1, float* db1, float* dalpha1, float* dW2,
+                float* db2, float* dalpha2, float* dw3, float* db3, void* workspace, size_t workspace_bytes, int B, int T, int K, int H1,
+                int H2, int flags, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * N2  The score head and the loss behind the interaction layers (all tensors fp32, n = batch rows).
  *   ScoreLayer(use_add=True).call (kon/model/ctr_model/layer/core_layer/core_layer.py:58-84): keras Add over the [B,1] parts,
  *   then sigmoid.  fil_score_add_sigmoid_fwd: out[i] = sigmoid(((a[i] + b[i]) + c[i]) + d[i]) -- left to right like the

@@ -40,6 +40,7 @@ FIL_BAG_SUM, FIL_BAG_MEAN, FIL_BAG_SQRTN = 0, 1, 2
 FIL_BAG_NO_PAD = -(1 << 63)      # INT64_MIN: no id is padding
 FIL_BAG_MAX_BLOCKS = 2048        # fil_embed_bag_fwd's grid cap (workgroups of 256 threads)
 FIL_AFM_HIDDEN_RELU = 1          # fil_afm_*'s flag bit 0: s_p = relu(u_p) . h (the paper's form)
+FIL_DIN_SOFTMAX, FIL_DIN_SIGMOID = 1, 2   # fil_din_*'s flag bits: softmax over the live slots; sigmoid instead of PReLU
 FIL_ERR_UNSUPPORTED = -4
 
 _c = ctypes
@@ -96,6 +97,11 @@ SIGNATURES = {
     "fil_afm_fwd": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
     "fil_afm_bwd_workspace_bytes": (_Z, [_I, _I, _I, _I]),
     "fil_afm_bwd": (_I, [_P] * 12 + [_Z, _I, _I, _I, _I, _I, _P]),
+    # N3: DIN attention pooling over a behaviour sequence
+    "fil_din_plan": (_I, [_I, _I, _I, _I, _I, _P]),
+    "fil_din_fwd": (_I, [_P] * 13 + [_I] * 6 + [_P]),
+    "fil_din_bwd_workspace_bytes": (_Z, [_I, _I, _I, _I, _I]),
+    "fil_din_bwd": (_I, [_P] * 25 + [_Z] + [_I] * 6 + [_P]),
     "fil_score_add_sigmoid_fwd": (_I, [_P, _P, _P, _P, _P, _I, _P]),
     "fil_score_add_sigmoid_bwd": (_I, [_P, _P, _P, _I, _P]),
     "fil_bce_mean_fwd": (_I, [_P, _P, _F, _P, _P, _I, _P]),

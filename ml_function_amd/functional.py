@@ -212,6 +212,113 @@ def afm_plan(B, F, K, A):
                 lds_bwd=plan[7])
 
 
+DIN_ACTIVATIONS = ("prelu", "sigmoid")
+
+
+def _din_flags(softmax, activation):
+    if activation not in DIN_ACTIVATIONS:
+        raise ValueError("din_attention: activation %r (%s)" % (activation, ", ".join(DIN_ACTIVATIONS)))
+    return (_lib.FIL_DIN_SOFTMAX if softmax else 0) | (_lib.FIL_DIN_SIGMOID if activation == "sigmoid" else 0)
+
+
+class _DinAttentionFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, q, keys, mask, w1, b1, alpha1, w2, b2, alpha2, w3, b3, flags):
+        _require_cuda(q, keys, mask, w1, b1, alpha1, w2, b2, alpha2, w3, b3)
+        q, keys, w1, b1, alpha1, w2, b2, alpha2, w3, b3 = (_f32c(t) for t in (q, keys, w1, b1, alpha1, w2, b2, alpha2, w3, b3))
+        if q.dim() != 2 or keys.dim() != 3 or keys.shape[0] != q.shape[0] or keys.shape[2] != q.shape[1]:
+            raise FilError("din_attention: q must be [B,K] and keys [B,T,K], got %s and %s" % (tuple(q.shape), tuple(keys.shape)))
+        B, T, K = keys.shape
+        if w1.dim() != 2 or w1.shape[0] != 4 * K or w2.dim() != 2 or w2.shape[0] != w1.shape[1]:
+            raise FilError("din_attention: w1 must be [4K,H1] and w2 [H1,H2] with K = %d, got %s and %s" % (K, tuple(w1.shape), tuple(w2.shape)))
+        H1, H2 = w1.shape[1], w2.shape[1]
+        sig = bool(flags & _lib.FIL_DIN_SIGMOID)
+        for name, t, n in (("b1", b1, H1), ("alpha1", alpha1, H1), ("b2", b2, H2), ("alpha2", alpha2, H2), ("w3", w3, H2), ("b3", b3, 1)):
+            if t is None:
+                if not (sig and name.startswith("alpha")):
+                    raise FilError("din_attention: %s is None (only alpha1 / alpha2 may be, with the sigmoid)" % name)
+            elif t.numel() != n:
+                raise FilError("din_attention: %s must hold %d values, got %s" % (name, n, tuple(t.shape)))
+        if mask is not None:
+            if tuple(mask.shape) != (B, T) or mask.dtype not in (torch.bool, torch.uint8):
+                raise FilError("din_attention: mask must be a [B,T] bool or uint8 tensor, got %s %s" % (tuple(mask.shape), mask.dtype))
+            mask = (mask.to(torch.uint8) if mask.dtype == torch.bool else mask).contiguous()
+        out = torch.empty((B, K), dtype=torch.float32, device=q.device)
+        stats = torch.empty((B, T + 2), dtype=torch.float32, device=q.device)
+        check(_lib.load().fil_din_fwd(ptr(q), ptr(keys), ptr(mask), ptr(w1), ptr(b1), ptr(alpha1), ptr(w2), ptr(b2), ptr(alpha2), ptr(w3),
+                                      ptr(b3), ptr(out), ptr(stats), B, T, K, H1, H2, flags, stream_ptr()), "fil_din_fwd")
+        ctx.has = (mask is not None, alpha1 is not None, alpha2 is not None)
+        ctx.save_for_backward(*[t for t in (q, keys, mask, w1, b1, alpha1, w2, b2, alpha2, w3, b3, out, stats) if t is not None])
+        ctx.flags = flags
+        ctx.shapes = {n: tuple(t.shape) for n, t in (("b1", b1), ("alpha1", alpha1), ("b2", b2), ("alpha2", alpha2), ("w3", w3), ("b3", b3))
+                      if t is not None}
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        sv = list(ctx.saved_tensors)
+        has_mask, has_a1, has_a2 = ctx.has
+        q, keys = sv.pop(0), sv.pop(0)
+        mask = sv.pop(0) if has_mask else None
+        w1, b1 = sv.pop(0), sv.pop(0)
+        alpha1 = sv.pop(0) if has_a1 else None
+        w2, b2 = sv.pop(0), sv.pop(0)
+        alpha2 = sv.pop(0) if has_a2 else None
+        w3, b3, out, stats = sv
+        B, T, K = keys.shape
+        H1, H2 = w1.shape[1], w2.shape[1]
+        need = ctx.needs_input_grad
+        none = (None,) * 12
+        if not any(need):
+            return none
+        dev = q.device
+        new = lambda shape: torch.empty(shape, dtype=torch.float32, device=dev)
+        dq = new(q.shape) if need[0] else None
+        dkeys = new(keys.shape) if need[1] else None
+        dw1 = new(w1.shape) if need[3] else None
+        db1 = new(ctx.shapes["b1"]) if need[4] else None
+        da1 = new(ctx.shapes["alpha1"]) if (need[5] and has_a1) else None
+        dw2 = new(w2.shape) if need[6] else None
+        db2 = new(ctx.shapes["b2"]) if need[7] else None
+        da2 = new(ctx.shapes["alpha2"]) if (need[8] and has_a2) else None
+        dw3 = new(ctx.shapes["w3"]) if need[9] else None
+        db3 = new(ctx.shapes["b3"]) if need[10] else None
+        lib = _lib.load()
+        ws, nws = None, 0
+        if any(t is not None for t in (dw1, db1, da1, dw2, db2, da2, dw3, db3)):
+            nws = lib.fil_din_bwd_workspace_bytes(B, T, K, H1, H2)
+            ws = _scratch(nws, dev, "din_bwd")
+        check(lib.fil_din_bwd(ptr(q), ptr(keys), ptr(mask), ptr(w1), ptr(b1), ptr(alpha1), ptr(w2), ptr(b2), ptr(alpha2), ptr(w3), ptr(b3),
+                              ptr(out), ptr(stats), ptr(_f32c(g)), ptr(dq), ptr(dkeys), ptr(dw1), ptr(db1), ptr(da1), ptr(dw2), ptr(db2),
+                              ptr(da2), ptr(dw3), ptr(db3), ptr(ws), nws, B, T, K, H1, H2, ctx.flags, stream_ptr()), "fil_din_bwd")
+        return dq, dkeys, None, dw1, db1, da1, dw2, db2, da2, dw3, db3, None
+
+
+def din_attention(q, keys, mask, W1, b1, alpha1, W2, b2, alpha2, w3, b3, softmax=False, activation="prelu"):
+    """The Deep Interest Network's attention pooling of a behaviour sequence (extension: the paper's activation unit; the reference's
+    AttentionUnitLayer / ActivationUnitLayer are not restated, their source was not available; include/fil.h fil_din_*):
+    q [B,K] the candidate, keys [B,T,K] the history, mask [B,T] bool / uint8 (non-zero = live; None = all live), W1 [4K,H1], b1, alpha1
+    [H1], W2 [H1,H2], b2, alpha2 [H2], w3 [H2] (or [H2,1]), b3 [1] -> [B,K] = sum_t a_t k_t with s_t = act(act([q, k_t, q - k_t, q * k_t]
+    W1 + b1) W2 + b2) . w3 + b3 and a_t = s_t on the live slots (the paper) or, softmax=True, the softmax of s over the live slots.
+    activation "prelu" (a slope per unit; alpha = 0 without a gradient is ReLU) or "sigmoid" (alpha1 / alpha2 are ignored and may be
+    None).  One launch per direction (plus the small fixed-order sum of the parameter-gradient partials); no [B,T,4K] or [B,T,H1]
+    tensor exists; only the gradients that are asked for are computed.  GPU only; shapes outside the kernel menu raise FilError
+    (layers.DinAttentionLayer takes its composed path there)."""
+    return _DinAttentionFn.apply(q, keys, mask, W1, b1, alpha1, W2, b2, alpha2, w3, b3, _din_flags(softmax, activation))
+
+
+def din_plan(B, T, K, H1, H2):
+    """fil_din_plan's answer as a dict (fits, tile, grid, cap, partials, lds_fwd, lds_bwd); fits=False (and nothing else) for a shape
+    outside the kernel menu."""
+    plan = (ctypes.c_int * 8)()
+    rc = _lib.load().fil_din_plan(int(B), int(T), int(K), int(H1), int(H2), plan)
+    if rc == _lib.FIL_ERR_UNSUPPORTED:
+        return dict(fits=False)
+    check(rc, "fil_din_plan")
+    return dict(fits=bool(plan[0]) and bool(plan[1]), tile=plan[2], grid=plan[3], cap=plan[4], partials=plan[5], lds_fwd=plan[6],
+                lds_bwd=plan[7])
+
+
 # --------------------------------------------------------------------------------------------- A2  DCN
 class _DcnFn(torch.autograd.Function):
     @staticmethod

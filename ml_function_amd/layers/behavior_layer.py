@@ -1,7 +1,8 @@
 """AutoInt's interacting layer: the MI355X re-host of ProductAttentionLayer (behavior_layer.py:272-311) and
 MultHeadAttentionLayer (:313-380) of the reference.  Reference quirks are kept on purpose: the "softmax" is a
 sigmoid (:286,308), V is projected with key_w (:360; value_w exists but never receives a gradient), LayerNorm
-epsilon is Keras' default 1e-3, the output is head-major [H,B,F,A]."""
+epsilon is Keras' default 1e-3, the output is head-major [H,B,F,A].
+DinAttentionLayer (extension): the Deep Interest Network's attention pooling of a behaviour sequence, one fused kernel per direction."""
 import ctypes
 
 import torch
@@ -125,3 +126,117 @@ class MultHeadAttentionLayer(Layer):
         if self.attention_head_dim == 1:
             return atten_v.squeeze(0)
         return [atten_v, res]
+
+
+_DIN_FITS = {}                 # (T, K, H1, H2) -> fil_din_plan's answer
+_DIN_ACTIVATIONS = ("prelu", "relu", "sigmoid")
+
+
+def din_attention_graph(q, keys, mask, w1, b1, alpha1, w2, b2, alpha2, w3, b3, softmax=False, activation="prelu"):
+    """Fn.din_attention's math as torch ops on the tensors given (their dtype and device; autograd for the backward): the composed
+    path of DinAttentionLayer and the comparator of its benchmark.  It materialises [B,T,4K] and [B,T,H1].  mask: [B,T] bool or None.
+    A masked key is replaced by zero before anything reads it."""
+    B, T, K = keys.shape
+    live = torch.ones((B, T), dtype=torch.bool, device=keys.device) if mask is None else mask.to(torch.bool)
+    keys = torch.where(live.unsqueeze(-1), keys, torch.zeros((), dtype=keys.dtype, device=keys.device))
+    qe = q.unsqueeze(1).expand(B, T, K)
+    x = torch.cat([qe, keys, qe - keys, qe * keys], dim=-1)
+    if activation == "sigmoid":
+        act = lambda u, a: torch.sigmoid(u)
+    else:
+        act = lambda u, a: torch.where(u > 0, u, a * u)
+    h1 = act(torch.matmul(x, w1) + b1, alpha1)
+    h2 = act(torch.matmul(h1, w2) + b2, alpha2)
+    s = torch.matmul(h2, w3.reshape(-1, 1)).squeeze(-1) + b3.reshape(())
+    if softmax:
+        sm = s.masked_fill(~live, float("-inf"))
+        mx = sm.max(dim=1, keepdim=True).values
+        mx = torch.where(torch.isfinite(mx), mx, torch.zeros_like(mx))
+        w = torch.exp(sm - mx)
+        a = w / w.sum(dim=1, keepdim=True).clamp_min(torch.finfo(w.dtype).tiny)      # no live slot: 0 / tiny = 0
+    else:
+        a = s * live.to(s.dtype)
+    return (a.unsqueeze(-1) * keys).sum(dim=1)
+
+
+class DinAttentionLayer(Layer):
+    """The Deep Interest Network's attention pooling of a behaviour sequence (extension: the paper's activation unit; the
+    reference's AttentionUnitLayer / ActivationUnitLayer are not restated here, their source was not available).
+
+    call([query [B,1,K] or [B,K], keys [B,T,K]], mask=None) -> [B,1,K] = sum_t a_t k_t: the candidate scores every item of the
+    history through Dense(H1) -> act -> Dense(H2) -> act -> Dense(1) on [q, k, q - k, q * k]; a_t is the score itself on the live
+    slots (the paper; softmax=False) or the softmax of the scores over the live slots (softmax=True); scores are not scaled by
+    sqrt(K).  mask: a [B,T] bool or uint8 tensor, non-zero = live (models.DINInput builds it as id != padding_id); None = all live.
+    activation: "prelu" (Keras PReLU, a slope per unit, zeros-initialised), "relu" (the slopes frozen at 0) or "sigmoid" (no slopes).
+    Dice is not offered (it needs batch statistics).  Weights: att_w1 [4K,H1], att_b1, att_alpha1, att_w2 [H1,H2], att_b2,
+    att_alpha2, att_w3 [H2,1], att_b3 [1] -- glorot_uniform(seed), zeros, zeros: Keras' Dense and PReLU defaults.
+    The MLP, the (masked) softmax and the weighted sum run in ONE HIP kernel per direction (Fn.din_attention, include/fil.h
+    fil_din_*): no [B,T,4K] or [B,T,H1] tensor exists.  Outside the kernel menu (fits_kernel_menu) or for a non-fp32 input the
+    layer takes the composed path -- the same graph in torch ops on the GPU, computed in fp32 -- instead of raising."""
+
+    def __init__(self, hidden_units=(80, 40), activation="prelu", softmax=False, padding_id=0, seed=2020):
+        super().__init__()
+        hidden_units = tuple(int(h) for h in hidden_units)
+        if len(hidden_units) != 2 or min(hidden_units) < 1:
+            raise ValueError("DinAttentionLayer: hidden_units must be two positive widths, got %r" % (hidden_units,))
+        if activation not in _DIN_ACTIVATIONS:
+            raise ValueError("DinAttentionLayer: activation %r (%s)" % (activation, ", ".join(_DIN_ACTIVATIONS)))
+        self.hidden_units = hidden_units
+        self.activation = activation
+        self.softmax = bool(softmax)
+        self.padding_id = padding_id      # the id models.DINInput masks; the layer itself only sees the mask
+        self.seed = seed
+
+    def build(self, input_shape):
+        k = int(input_shape[1][-1])
+        h1, h2 = self.hidden_units
+        self.att_w1 = self.add_weight("att_w1", [4 * k, h1], "glorot_uniform", seed=self.seed)
+        self.att_b1 = self.add_weight("att_b1", [h1], "zeros")
+        if self.activation != "sigmoid":
+            self.att_alpha1 = self.add_weight("att_alpha1", [h1], "zeros", trainable=self.activation == "prelu")
+        self.att_w2 = self.add_weight("att_w2", [h1, h2], "glorot_uniform", seed=self.seed)
+        self.att_b2 = self.add_weight("att_b2", [h2], "zeros")
+        if self.activation != "sigmoid":
+            self.att_alpha2 = self.add_weight("att_alpha2", [h2], "zeros", trainable=self.activation == "prelu")
+        self.att_w3 = self.add_weight("att_w3", [h2, 1], "glorot_uniform", seed=self.seed)
+        self.att_b3 = self.add_weight("att_b3", [1], "zeros")
+        super().build(input_shape)
+
+    def _weights(self):
+        sig = self.activation == "sigmoid"
+        return (self.att_w1, self.att_b1, None if sig else self.att_alpha1, self.att_w2, self.att_b2, None if sig else self.att_alpha2,
+                self.att_w3, self.att_b3)
+
+    def fits_kernel_menu(self, query, keys):
+        """fil_din_*'s menu (include/fil.h): K % 4 == 0, K <= 64, T <= 256, H1 <= 128, H2 <= 64, 4 K H1 + H1 H2 <= 16384 --
+        fil_din_plan answers from the launchers' own arithmetic; the answer is cached per shape."""
+        if keys.dim() != 3:
+            return False
+        key = (int(keys.shape[1]), int(keys.shape[2]), *self.hidden_units)
+        fits = _DIN_FITS.get(key)
+        if fits is None:
+            fits = _DIN_FITS[key] = Fn.din_plan(1, *key)["fits"]
+        return fits
+
+    def _composed(self, q, keys, mask):
+        """din_attention_graph on the GPU in fp32: a dozen launches and two [B,T,n] blocks per direction where the fused kernel makes
+        none -- it exists so that a shape outside the kernel menu never raises."""
+        Fn._require_cuda(q, keys, mask)      # (torch ops would run on a CPU tensor: there is no CPU path in this package)
+        kernel_act = "sigmoid" if self.activation == "sigmoid" else "prelu"
+        return din_attention_graph(q.to(torch.float32), keys.to(torch.float32), mask, *self._weights(), softmax=self.softmax,
+                                   activation=kernel_act)
+
+    def call(self, inputs, mask=None, **kwargs):
+        query, keys = inputs
+        if keys.dim() != 3 or query.dim() not in (2, 3) or query.numel() != keys.shape[0] * keys.shape[2]:
+            raise ValueError("DinAttentionLayer: query must be [B,1,K] or [B,K] and keys [B,T,K], got %s and %s"
+                             % (tuple(query.shape), tuple(keys.shape)))
+        q = query.reshape(keys.shape[0], keys.shape[2])
+        if mask is not None and (tuple(mask.shape) != tuple(keys.shape[:2]) or mask.dtype not in (torch.bool, torch.uint8)):
+            raise ValueError("DinAttentionLayer: mask must be a [B,T] bool or uint8 tensor, got %s %s" % (tuple(mask.shape), mask.dtype))
+        if q.dtype == torch.float32 and keys.dtype == torch.float32 and self.fits_kernel_menu(q, keys):
+            pooled = Fn.din_attention(q, keys, mask, *self._weights(), softmax=self.softmax,
+                                      activation="sigmoid" if self.activation == "sigmoid" else "prelu")
+        else:
+            pooled = self._composed(q, keys, mask)
+        return pooled.unsqueeze(1)

@@ -3,13 +3,15 @@
 the feature-input plumbing it relies on (kon/utils/data_prepare.py: InputFeature :39-54, sparseFea/denseFea :59-60,
 FeatureInput :65-76).  The reference builds symbolic Keras models; here every zoo entry is a Layer whose call takes
 the concrete InputFeature of one batch, and ``CTRModel`` chains FeatureInput -> zoo body on raw (dense, sparse-id)
-tensors.  Hyper-parameter names and defaults are the reference's.  Sequence models are out of scope.
+tensors.  Hyper-parameter names and defaults are the reference's.  Sequence models are out of scope,
+except DINInput / DIN (extension): the Deep Interest Network's attention pooling of behaviour histories (layers.DinAttentionLayer).
 """
 from collections import namedtuple
 
 import torch
 
-from .layers import (CIN, AFMLayer, AttentionBaseLayer, BagEmbed, CrossLayer, DnnLayer, FmLayer, InnerLayer, IPnnLayer, MergeScoreLayer,
+from . import functional as Fn
+from .layers import (CIN, AFMLayer, AttentionBaseLayer, BagEmbed, CrossLayer, DinAttentionLayer, DnnLayer, FmLayer, InnerLayer, IPnnLayer, MergeScoreLayer,
                      MultHeadAttentionLayer, OPnnLayer, ScoreLayer, SparseEmbed, StackLayer)
 from .layers.base import Layer
 from .layers.interactive_layer import pack_fields
@@ -276,6 +278,88 @@ class AutoInt(torch.nn.Module):
         atten_vec = self.dnn(cross_embed)
         final_input = self.stack_flat([h.squeeze(0) for h in torch.split(atten_vec, 1, dim=0)])
         return self.score(final_input)
+
+
+class DINInput(Layer):
+    """Feature input of a Deep Interest Network (extension): FeatureInput's one-id fields plus, per behaviour, the history of a
+    candidate field -- the last T items of the kind that field names -- embedded from the candidate field's OWN rows (a shared table).
+
+    behavior: [(candidate_fea_name, T), ...].  call((dense [B, n_dense] or None, sparse_idx [B,F], hist_idx [B,N,T])) -> InputFeature
+    with sparse_embed = the F one-id embeddings [B,1,K] and seq_embed_list = [keys list (N x [B,T,K]), mask list (N x [B,T] bool,
+    id != padding_id)].  The F + N T ids go through ONE Fn.embed_gather, with the candidate's offset and size repeated for its
+    history slots; such overlapping fields take the global sort of the table gradient, so ONE gradient reaches the table.
+    tableGrad="runs" is not offered for the shared table."""
+
+    def __init__(self, sparseInfo, behavior, denseInfo=None, padding_id=0, tableGrad="dense"):
+        super().__init__()
+        if tableGrad != "dense":
+            raise ValueError("DINInput: tableGrad %r -- the shared table takes the dense gradient only ('runs' is out of scope)" % (tableGrad,))
+        self.sparse_info = sparseInfo or []
+        self.dense_info = denseInfo or []
+        names = [i.fea_name for i in self.sparse_info]
+        self.behavior = []
+        for name, T in behavior:
+            if name not in names or int(T) < 1:
+                raise ValueError("DINInput: behaviour (%r, %r): the candidate must be one of %s and T >= 1" % (name, T, names))
+            self.behavior.append((names.index(name), int(T)))
+        if len({T for _, T in self.behavior}) > 1:
+            raise ValueError("DINInput: one history length T for all behaviours (hist_idx is [B,N,T])")
+        self.padding_id = padding_id
+        self.sparse_embed = SparseEmbed(self.sparse_info, use_flatten=False, packed=True)
+
+    def build(self, input_shape):
+        emb = self.sparse_embed
+        emb._build_device = self._build_device
+        emb.build(None)
+        emb.built = True
+        fields = list(range(len(self.sparse_info))) + [f for f, T in self.behavior for _ in range(T)]
+        sel = torch.tensor(fields, dtype=torch.int64, device=self._build_device)
+        self.register_buffer("gather_offsets", emb.offsets[sel].contiguous())
+        self.register_buffer("gather_sizes", emb.sizes[sel].contiguous())
+        super().build(input_shape)
+
+    def call(self, inputs, **kwargs):
+        dense, sparse_idx, hist_idx = inputs
+        Fn._require_cuda(sparse_idx, hist_idx, dense)
+        F, N = len(self.sparse_info), len(self.behavior)
+        if sparse_idx.dim() != 2 or sparse_idx.shape[1] != F or hist_idx.dim() != 3 or hist_idx.shape[1] != N or \
+                hist_idx.shape[2] != self.behavior[0][1]:
+            raise ValueError("DINInput: sparse_idx must be [B,%d] and hist_idx [B,%d,%d], got %s and %s"
+                             % (F, N, self.behavior[0][1], tuple(sparse_idx.shape), tuple(hist_idx.shape)))
+        B, T = sparse_idx.shape[0], hist_idx.shape[2]
+        hist_idx = hist_idx.to(torch.int64)
+        idx = torch.cat([sparse_idx.to(torch.int64), hist_idx.reshape(B, N * T)], dim=1)
+        block = Fn.embed_gather(self.sparse_embed.embeddings, self.gather_offsets, idx, sizes=self.gather_sizes)   # [B, F + N T, K]
+        embed = list(block[:, :F].split(1, dim=1))
+        keys = [block[:, F + n * T:F + (n + 1) * T] for n in range(N)]
+        masks = [hist_idx[:, n] != self.padding_id for n in range(N)]
+        dense_inputs = [] if dense is None else [dense[:, i:i + 1] for i in range(dense.shape[1])]
+        sparse_inputs = [sparse_idx[:, i:i + 1] for i in range(F)]
+        return InputFeature(self.dense_info, self.sparse_info, self.behavior, dense_inputs, sparse_inputs,
+                            [hist_idx[:, n] for n in range(N)], None, embed, [keys, masks])
+
+
+class DIN(torch.nn.Module):
+    """Deep Interest Network (extension; the paper's model on DINInput's features): one DinAttentionLayer per behaviour pools the
+    history with the candidate's embedding as the query, then StackLayer over dense + field embeddings + pooled histories ->
+    DnnLayer -> MergeScoreLayer(use_merge=False)."""
+
+    def __init__(self, att_hidden_units=(80, 40), att_activation="prelu", att_softmax=False, hidden_units=None):
+        super().__init__()
+        self.att_args = dict(hidden_units=tuple(att_hidden_units), activation=att_activation, softmax=att_softmax)
+        self.atten = torch.nn.ModuleList()
+        self.stack = StackLayer()
+        self.dnn = DnnLayer(hidden_units=hidden_units or [200, 80])
+        self.score = MergeScoreLayer(use_merge=False)
+
+    def forward(self, inputFea):
+        keys, masks = inputFea.seq_embed_list
+        while len(self.atten) < len(keys):
+            self.atten.append(DinAttentionLayer(**self.att_args))
+        pooled = []
+        for n, (cand, _) in enumerate(inputFea.seq_info):
+            pooled.append(self.atten[n]([inputFea.sparse_embed[cand], keys[n]], mask=masks[n]))
+        return self.score(self.dnn(self.stack(list(inputFea.dense_inputs) + list(inputFea.sparse_embed) + pooled)))
 
 
 class CTRModel(torch.nn.Module):
