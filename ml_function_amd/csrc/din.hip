@@ -17,7 +17,8 @@
 //             group): the weighted sum of the keys, group partials added in group order, ONE division by the softmax denominator.
 //             NS <= 4 samples per workgroup (64 NS threads).
 //   backward  always 256 threads; waves 0 .. NS-1 own the samples of a tile, ALL threads own the parameter gradients.  Per 64 slots:
-//             0  softmax: g.out = sum_t a_t (g.k_t) from the saved scores, one pass over the keys.
+//             0  softmax: g.out = sum_t a_t (g.k_t) from the saved scores, one pass over the keys; both relative to g.k of the slot
+//                with the largest score, so that a weight of nearly 1 costs ds no digits.
 //             A  lane = slot: the score again (same code, same bits), a_t, ds_t = a_t (g.k_t - g.out) [softmax] or g.k_t [raw],
 //                u1 (PReLU) or h1 (sigmoid) -> LDS, du2 -> LDS and registers; db2, dalpha2, dw3, db3 by a butterfly over the lanes.
 //             P2 (barrier) every thread: its 4 x 16 tile(s) of dW2 += h1^T du2 over the tile's samples, in registers.
@@ -494,7 +495,7 @@ __global__ __launch_bounds__(kDinBwdThreads) void din_bwd_kernel(const float* __
     const int nvalid = left < L.NS ? (int)left : L.NS;
     const float* keys_b = keys + (have ? b : 0) * T * K;
     const unsigned char* mask_b = (mask != nullptr && have) ? mask + b * T : nullptr;
-    float mx = 0.f, den = 1.f, gp = 0.f;
+    float mx = 0.f, den = 1.f, gp = 0.f, gc = 0.f;
     if (have) {
       if (lane < K) {
         qS[lane] = q[b * K + lane];
@@ -507,7 +508,19 @@ __global__ __launch_bounds__(kDinBwdThreads) void din_bwd_kernel(const float* __
       if (softmax) {
         // g . out as sum_t a_t (g . k_t) over the very a_t and g . k_t that ds_t = a_t (g . k_t - g . out) is made of (a_t from the
         // saved scores): the sum of ds over a sample then cancels to rounding, and with one live slot (a = 1) g . out IS that
-        // slot's g . k and ds is exactly 0
+        // slot's g . k and ds is exactly 0.  Where the slot with the largest score (the first one whose saved score is mx) holds
+        // more than half of the weight (its weight is 1 / den), every g . k_t is taken relative to gc = its g . k (same chain, same
+        // bits, so its own difference is exactly 0): with a weight of 1 - eps, g . k - g . out of that slot is eps-small, and formed
+        // from the absolute values it carries their rounding, 2^-24 |g . k|, against a true value of eps |g . k| -- a relative
+        // error of 2^-24 / eps in ds of every slot of the sample.  At or below one half nothing is lost and gc stays 0 (x - 0 = x).
+        if (den < 2.f) {
+          int tm = T;
+          for (int t = lane; t < T; t += 64)
+            if ((mask_b == nullptr || mask_b[t] != 0) && stats[b * (T + 2) + t] == mx) tm = min(tm, t);
+#pragma unroll
+          for (int o = 32; o >= 1; o >>= 1) tm = min(tm, __shfl_xor(tm, o));
+          if (tm < T) gc = din_dot(gS, keys_b + (long)tm * K, KQ);
+        }
         float part = 0.f;
         for (int c0 = 0; c0 < T; c0 += 64) {
           din_load_keys(kS, keys_b, mask_b, L, c0, lane);
@@ -515,7 +528,7 @@ __global__ __launch_bounds__(kDinBwdThreads) void din_bwd_kernel(const float* __
           const int t = c0 + lane;
           const bool live = t < T && (mask_b == nullptr || mask_b[t] != 0);
           const float a = live ? expf(stats[b * (T + 2) + t] - mx) / den : 0.f;
-          part = fmaf(a, din_dot(gS, kS + lane * L.KP, KQ), part);
+          part = fmaf(a, din_dot(gS, kS + lane * L.KP, KQ) - gc, part);
           din_wave_sync();
         }
         gp = wave_sum(part);
@@ -539,7 +552,7 @@ __global__ __launch_bounds__(kDinBwdThreads) void din_bwd_kernel(const float* __
         float ds;
         if (softmax) {
           a_t = live ? expf(stats[b * (T + 2) + t] - mx) / den : 0.f;      // (the saved score: the bits of s)
-          ds = a_t * (gk - gp);
+          ds = a_t * ((gk - gc) - gp);
         } else {
           a_t = live ? s : 0.f;
           ds = live ? gk : 0.f;
