@@ -422,6 +422,50 @@ int fil_din_bwd(const float* q, const float* keys, const unsigned char* mask, co
                 int H2, int flags, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * N3  GRU / AUGRU / AGRU over a behaviour sequence (extension: the interest extraction and interest evolution layers of the Deep
+ *     Interest Evolution Network paper; the GRU is TF 2 Keras' GRU with its defaults -- reset_after=True, sigmoid / tanh -- and the
+ *     attention-gated variants are the paper's eq. 15-16; the reference's rnn_demo.py is not restated, its source was not
+ *     available).  All tensors fp32 except mask.  Entry points added only: the ABI version stays.
+ *   x [B,T,K] the sequence; a [B,T] the attention scores (NULL in FIL_GRU_GRU mode, required otherwise); mask [B,T] uint8, non-zero =
+ *   live, NULL = all live (live slots may sit anywhere); W [K,3H] and U [H,3H] in Keras' column order z | r | h; b [2,3H]: row 0 the
+ *   input bias, row 1 the recurrent bias; hs [B,T,H] the output.  One live step, h = the previous state, h_0 = 0:
+ *     xp = x_t W + b[0];  hp = h U + b[1];  z = sigmoid(xp_z + hp_z);  r = sigmoid(xp_r + hp_r);  c = tanh(xp_h + r * hp_h);
+ *     u = 1 - z  (z is Keras' keep gate, u the paper's update gate);
+ *     u' = u (FIL_GRU_GRU) | a_t * u (FIL_GRU_AUGRU) | a_t for every unit (FIL_GRU_AGRU: z is unused and gets no gradient);
+ *     h_new = fma(u', c, (1 - u') * h) -- one expression for the three modes: GRU and AUGRU with a = 1 return the same bits, and
+ *     a_t = 0 repeats the state.
+ *   A masked step carries the state: hs[b,t] = h bit for bit (zeros before the first live step); its x_t and a_t are never read.
+ *   fil_gru_fwd: hs, and `saved` [B,T,4,H] = (z, r, c, hp_h) of the live steps for the backward (fil_gru_saved_bytes; opaque to the
+ *     caller; masked steps are left unwritten; NULL: nothing is saved, for inference).  x_t W is fused into the step: nothing else of
+ *     size B T n touches global memory.
+ *   fil_gru_bwd: g_hs [B,T,H] and / or g_last [B,H] (the gradient of hs[:,T-1], for return_sequences=False; either may be NULL, not
+ *     both) -> dx [B,T,K], da [B,T] (not in FIL_GRU_GRU mode), dW, dU, db [2,3H].  No product is recomputed: the gates come from
+ *     `saved`, the previous state from hs.  Each output may be NULL and is then not computed (dW, dU, db all NULL: no parameter pass,
+ *     no workspace; everything NULL: FIL_ERR_ARG).  dx and da are exactly 0 at masked steps.  The parameter gradients leave the main
+ *     launch as one partial per workgroup in `workspace` (fil_gru_bwd_workspace_bytes; every byte that is read was written by that
+ *     launch) and a second small launch adds the partials in a fixed order.
+ *   One launch per direction (plus the partial sum).  No atomics; every sum has a fixed order for a given shape: the same inputs give
+ *   the same bits on every call.
+ *   Menu: any T >= 1; K % 4 == 0, H % 4 == 0, K <= 64, H <= 64 in both directions (FIL_ERR_UNSUPPORTED otherwise, the limit in the
+ *   message); the dynamic LDS stays within 163,328 bytes over the whole menu (161,024 in the backward at K = H = 64).
+ *   B == 0 returns FIL_OK before any pointer is looked at.  A workspace smaller than needed: FIL_ERR_ARG, the needed size in the message.
+ *   fil_gru_plan: the launchers' own arithmetic (no GPU call): plan[8] = {fwd_ok, bwd_ok, samples per workgroup tile, grid, grid cap,
+ *     parameter-gradient partials (= grid), forward LDS bytes, backward LDS bytes}.  The tile grows with B (small batches take small
+ *     tiles and more workgroups).  Returns FIL_OK, or the argument / menu error the launch would give.
+ */
+#define FIL_GRU_GRU 0
+#define FIL_GRU_AUGRU 1
+#define FIL_GRU_AGRU 2
+int fil_gru_plan(int B, int T, int K, int H, int mode, int* plan /* [8] */);
+size_t fil_gru_saved_bytes(int B, int T, int K, int H);
+int fil_gru_fwd(const float* x, const float* a, const unsigned char* mask, const float* W, const float* U, const float* b, float* hs,
+                float* saved, int B, int T, int K, int H, int mode, void* stream);
+size_t fil_gru_bwd_workspace_bytes(int B, int T, int K, int H);
+int fil_gru_bwd(const float* x, const float* a, const unsigned char* mask, const float* W, const float* U, const float* hs,
+                const float* saved, const float* g_hs, const float* g_last, float* dx, float* da, float* dW, float* dU, float* db,
+                void* workspace, size_t workspace_bytes, int B, int T, int K, int H, int mode, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * N2  The score head and the loss behind the interaction layers (all tensors fp32, n = batch rows).
  *   ScoreLayer(use_add=True).call (kon/model/ctr_model/layer/core_layer/core_layer.py:58-84): keras Add over the [B,1] parts,
  *   then sigmoid.  fil_score_add_sigmoid_fwd: out[i] = sigmoid(((a[i] + b[i]) + c[i]) + d[i]) -- left to right like the

@@ -41,6 +41,7 @@ FIL_BAG_NO_PAD = -(1 << 63)      # INT64_MIN: no id is padding
 FIL_BAG_MAX_BLOCKS = 2048        # fil_embed_bag_fwd's grid cap (workgroups of 256 threads)
 FIL_AFM_HIDDEN_RELU = 1          # fil_afm_*'s flag bit 0: s_p = relu(u_p) . h (the paper's form)
 FIL_DIN_SOFTMAX, FIL_DIN_SIGMOID = 1, 2   # fil_din_*'s flag bits: softmax over the live slots; sigmoid instead of PReLU
+FIL_GRU_GRU, FIL_GRU_AUGRU, FIL_GRU_AGRU = 0, 1, 2   # fil_gru_*'s mode
 FIL_ERR_UNSUPPORTED = -4
 
 _c = ctypes
@@ -102,6 +103,12 @@ SIGNATURES = {
     "fil_din_fwd": (_I, [_P] * 13 + [_I] * 6 + [_P]),
     "fil_din_bwd_workspace_bytes": (_Z, [_I, _I, _I, _I, _I]),
     "fil_din_bwd": (_I, [_P] * 25 + [_Z] + [_I] * 6 + [_P]),
+    # N3: GRU / AUGRU / AGRU over a behaviour sequence
+    "fil_gru_plan": (_I, [_I, _I, _I, _I, _I, _P]),
+    "fil_gru_saved_bytes": (_Z, [_I, _I, _I, _I]),
+    "fil_gru_fwd": (_I, [_P] * 8 + [_I] * 5 + [_P]),
+    "fil_gru_bwd_workspace_bytes": (_Z, [_I, _I, _I, _I]),
+    "fil_gru_bwd": (_I, [_P] * 15 + [_Z] + [_I] * 5 + [_P]),
     "fil_score_add_sigmoid_fwd": (_I, [_P, _P, _P, _P, _P, _I, _P]),
     "fil_score_add_sigmoid_bwd": (_I, [_P, _P, _P, _I, _P]),
     "fil_bce_mean_fwd": (_I, [_P, _P, _F, _P, _P, _I, _P]),

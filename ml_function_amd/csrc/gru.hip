@@ -1,0 +1,600 @@
+// N3  GRU / AUGRU / AGRU over a behaviour sequence for gfx950, forward and backward, fp32 (extension: the interest extraction and
+// interest evolution layers of the Deep Interest Evolution Network; the GRU is TF 2 Keras' GRU with its defaults, reset_after=True).
+//
+//     xp = x_t W + b[0];  hp = h U + b[1]                        (columns z | r | h)
+//     z = sigmoid(xp_z + hp_z);  r = sigmoid(xp_r + hp_r);  c = tanh(xp_h + r hp_h);  u = 1 - z
+//     u' = u (GRU) | a_t u (AUGRU) | a_t (AGRU);   h_new = (1 - u') h + u' c;   a masked step carries h.
+//
+// Structure (both directions).  A workgroup owns a tile of NS = 4 G samples for all T steps; a thread owns ONE hidden unit j of FOUR
+// samples (g = its sample quad), so that every weight read from LDS feeds four samples.  The weights are staged once per workgroup
+// (forward: W, U as given, lanes = consecutive columns; backward: their transposes, and nothing else -- the backward recomputes no
+// product, it reads z, r, c and hp_h from `saved`).  x_t and the hidden state sit in LDS TRANSPOSED ([feature][sample], row stride
+// NS + 4) so that one 16-byte read gives a feature of the thread's four samples; they are double buffered and the global loads of
+// the next step are in flight during the arithmetic of this one (the step is a dependent chain: nothing else hides the load).
+//   forward   per step: 3 (K + H) weight reads + (K + H) state reads for 12 (K + H) FMAs per thread; the gates; hs, saved -> global;
+//             the new state -> LDS.  One barrier.
+//   backward  t = T-1 .. 0, dh (the gradient of the state) in registers.  Per step:
+//             1  the gate gradients of the thread's unit and samples from `saved` -> LDS, both [column][sample] and [sample][column];
+//                the da terms -> LDS.                                                                               (barrier)
+//             2  dh_prev = dh (1 - u') + d_hp U^T, dx_t = d_xp W^T (transposed weights, lanes = consecutive outputs);
+//                da[b,t] = the units' terms added in unit order;
+//                dW / dU: the thread's three columns (the gates of its unit) of the rows g, g + G, ... of [x_t ; h_prev]^T [d_xp | d_hp],
+//                summed over the tile's samples in sample order, in registers over all steps and tiles (NR x 3 accumulators, NR <= 32). (barrier)
+//             One partial per workgroup; gru_param_reduce_kernel adds the partials in a fixed order.
+// No atomics; every sum has a fixed order for a given shape: repeats are bit-identical.
+#include "common.h"
+#include <algorithm>
+#include <math.h>
+
+namespace fil {
+
+constexpr int kGruMaxK = 64, kGruMaxH = 64;
+constexpr int kGruGridCap = 1024;      // workgroups per launch
+constexpr int kGruLdsLimit = 163328;   // the launchers' dynamic LDS limit (include/fil.h)
+constexpr int kGruThreads = 256;       // the most a workgroup has
+constexpr int kGruXV = 4;              // 16-byte pieces of x_t a thread stages per step, at most
+
+// all LDS offsets in floats (multiples of 4)
+struct GruLayout {
+  int T, K, H, H3, G, NS, NSP, threads, NR;
+  int f_U, f_b, f_x, f_h, f_live, f_a, lds_fwd;              // forward:  W | U | b [2][3H] | xT [2][K][NSP] | hT [2][H][NSP] | live [2][NS] | a [2][NS]
+  int b_UT, b_in, b_dT, b_dS, b_da, b_live, b_a, lds_bwd;    // backward: WT [3H][K] | UT [3H][H] | inT [2][K+H][NSP] | dT [4H][NSP] | dS [NS][4H] |
+                                                             //           da terms [H][NSP] | live [2][NS] | a [2][NS]
+  int n_out;                                                 // one partial: dW [K][3H] | dU [H][3H] | db [2][3H]
+};
+
+static GruLayout gru_layout(int B, int T, int K, int H) {
+  GruLayout L;
+  L.T = T; L.K = K; L.H = H; L.H3 = 3 * H;
+  const int P = std::max(H, K / 4);                         // threads per sample quad: a unit each, and enough to stage x_t in kGruXV pieces
+  const int Gmax = kGruThreads / P;                         // >= 4
+  const int Gmin = std::min(Gmax, cdiv(64, P));             // a full wave where the shape allows
+  const int Glow = std::max(Gmin, cdiv(K + H, 32));         // at most 32 rows of [dW ; dU] per thread
+  const long want = ((long)B + 4L * kGruGridCap - 1) / (4L * kGruGridCap);      // small batches: small tiles, more workgroups
+  L.G = (int)std::min((long)Gmax, std::max((long)Glow, want));
+  L.NS = 4 * L.G;
+  L.NSP = L.NS + 4;
+  L.threads = (L.G * P + 63) / 64 * 64;
+  const int nr = cdiv(K + H, L.G);
+  L.NR = nr <= 8 ? 8 : (nr <= 16 ? 16 : 32);
+  L.f_U = K * L.H3;
+  L.f_b = L.f_U + H * L.H3;
+  L.f_x = L.f_b + 2 * L.H3;
+  L.f_h = L.f_x + 2 * K * L.NSP;
+  L.f_live = L.f_h + 2 * H * L.NSP;
+  L.f_a = L.f_live + 2 * L.NS;
+  L.lds_fwd = 4 * (L.f_a + 2 * L.NS);
+  L.b_UT = K * L.H3;
+  L.b_in = L.b_UT + H * L.H3;
+  L.b_dT = L.b_in + 2 * (K + H) * L.NSP;
+  L.b_dS = L.b_dT + 4 * H * L.NSP;
+  L.b_da = L.b_dS + L.NS * 4 * H;
+  L.b_live = L.b_da + H * L.NSP;
+  L.b_a = L.b_live + 2 * L.NS;
+  L.lds_bwd = 4 * (L.b_a + 2 * L.NS);
+  L.n_out = (K + H + 2) * L.H3;
+  return L;
+}
+
+static inline int gru_grid(int B, int NS) { return B <= 0 ? 0 : std::min(cdiv(B, NS), kGruGridCap); }
+
+__device__ __forceinline__ float gru_sigmoid(float v) { return 1.f / (1.f + expf(-v)); }
+
+// 16-byte pieces of x_t of the tile's samples -> registers; a masked step's (and a sample past B's) row is never read: zeros
+__device__ __forceinline__ void gru_load_x(float4 (&xr)[kGruXV], const float* __restrict__ x, const unsigned char* __restrict__ mask, long b0,
+                                           int B, int t, const GruLayout& L) {
+  const int KQ = L.K / 4, n = L.NS * KQ;
+#pragma unroll
+  for (int i = 0; i < kGruXV; ++i) {
+    const int idx = threadIdx.x + i * blockDim.x;
+    xr[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (idx < n) {
+      const int s = idx / KQ, kq = idx - s * KQ;
+      const long bb = b0 + s;
+      if (bb < B && (mask == nullptr || mask[bb * L.T + t] != 0))
+        xr[i] = *reinterpret_cast<const float4*>(x + (bb * L.T + t) * L.K + kq * 4);
+    }
+  }
+}
+
+// ... -> the transposed LDS image xT [K][NSP]
+__device__ __forceinline__ void gru_store_x(const float4 (&xr)[kGruXV], float* xT, const GruLayout& L) {
+  const int KQ = L.K / 4, n = L.NS * KQ;
+#pragma unroll
+  for (int i = 0; i < kGruXV; ++i) {
+    const int idx = threadIdx.x + i * blockDim.x;
+    if (idx < n) {
+      const int s = idx / KQ, kq = idx - s * KQ;
+      float* d = xT + (kq * 4) * L.NSP + s;
+      d[0] = xr[i].x; d[L.NSP] = xr[i].y; d[2 * L.NSP] = xr[i].z; d[3 * L.NSP] = xr[i].w;
+    }
+  }
+}
+
+// live flag (1 / 0) and score of sample b0 + threadIdx.x at step t (threads below NS)
+__device__ __forceinline__ void gru_load_step(float& lv, float& av, const float* __restrict__ a, const unsigned char* __restrict__ mask, long b0,
+                                              int B, int t, const GruLayout& L) {
+  lv = 0.f; av = 0.f;
+  if ((int)threadIdx.x < L.NS) {
+    const long bb = b0 + threadIdx.x;
+    if (bb < B && (mask == nullptr || mask[bb * L.T + t] != 0)) {
+      lv = 1.f;
+      av = a != nullptr ? a[bb * L.T + t] : 1.f;
+    }
+  }
+}
+
+__global__ __launch_bounds__(kGruThreads) void gru_fwd_kernel(const float* __restrict__ x, const float* __restrict__ a,
+                                                             const unsigned char* __restrict__ mask, const float* __restrict__ W,
+                                                             const float* __restrict__ U, const float* __restrict__ bias, float* __restrict__ hs,
+                                                             float* __restrict__ saved, int B, int mode, GruLayout L) {
+  extern __shared__ __attribute__((aligned(16))) float gru_smem[];
+  const int tid = threadIdx.x, nthr = blockDim.x;
+  const int T = L.T, K = L.K, H = L.H, H3 = L.H3, NS = L.NS, NSP = L.NSP;
+  for (int i = tid; i < K * H3; i += nthr) gru_smem[i] = W[i];
+  for (int i = tid; i < H * H3; i += nthr) gru_smem[L.f_U + i] = U[i];
+  for (int i = tid; i < 2 * H3; i += nthr) gru_smem[L.f_b + i] = bias[i];
+  const float* Ws = gru_smem;
+  const float* Us = gru_smem + L.f_U;
+  const float* bs = gru_smem + L.f_b;
+  const bool active = tid < L.G * H;
+  const int g = tid / H, j = tid - g * H;
+  const long n_tiles = ((long)B + NS - 1) / NS;
+  for (long tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
+    const long b0 = tile * NS;
+    float h[4] = {0.f, 0.f, 0.f, 0.f};
+    float4 xr[kGruXV];
+    float lvn, avn;
+    __syncthreads();      // the weights are staged; the previous tile's images are free
+    gru_load_x(xr, x, mask, b0, B, 0, L);
+    gru_load_step(lvn, avn, a, mask, b0, B, 0, L);
+    gru_store_x(xr, gru_smem + L.f_x, L);
+    if (tid < NS) { gru_smem[L.f_live + tid] = lvn; gru_smem[L.f_a + tid] = avn; }
+    if (active) *reinterpret_cast<float4*>(gru_smem + L.f_h + j * NSP + 4 * g) = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (T > 1) {
+      gru_load_x(xr, x, mask, b0, B, 1, L);
+      gru_load_step(lvn, avn, a, mask, b0, B, 1, L);
+    }
+    __syncthreads();
+    // Order within a step: the arithmetic; the registers loaded a step ago -> LDS (the wait for them also covers the stores of the
+    // step before, long under way); this step's stores; the loads of the step after next.  A wait right behind fresh stores would
+    // put their latency on the chain.
+    for (int t = 0; t < T; ++t) {
+      const int cur = t & 1, nxt = cur ^ 1;
+      float zv[4], rv[4], cv[4], pv[4];
+      bool lv[4] = {false, false, false, false};
+      if (active) {
+        float ax[3][4], ah[3][4];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+          const float bx = bs[c * H + j], bh = bs[H3 + c * H + j];
+#pragma unroll
+          for (int e = 0; e < 4; ++e) { ax[c][e] = bx; ah[c][e] = bh; }
+        }
+        const float* xc = gru_smem + L.f_x + cur * K * NSP + 4 * g;
+        const float* hc = gru_smem + L.f_h + cur * H * NSP + 4 * g;
+#pragma unroll 4
+        for (int k = 0; k < K; ++k) {
+          const float4 v = *reinterpret_cast<const float4*>(xc + k * NSP);
+          const float ve[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+          for (int c = 0; c < 3; ++c) {
+            const float w = Ws[k * H3 + c * H + j];
+#pragma unroll
+            for (int e = 0; e < 4; ++e) ax[c][e] = fmaf(ve[e], w, ax[c][e]);
+          }
+        }
+#pragma unroll 4
+        for (int k = 0; k < H; ++k) {
+          const float4 v = *reinterpret_cast<const float4*>(hc + k * NSP);
+          const float ve[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+          for (int c = 0; c < 3; ++c) {
+            const float w = Us[k * H3 + c * H + j];
+#pragma unroll
+            for (int e = 0; e < 4; ++e) ah[c][e] = fmaf(ve[e], w, ah[c][e]);
+          }
+        }
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          const int s = 4 * g + e;
+          lv[e] = gru_smem[L.f_live + cur * NS + s] != 0.f;
+          const float at = gru_smem[L.f_a + cur * NS + s];
+          const float z = gru_sigmoid(ax[0][e] + ah[0][e]);
+          const float r = gru_sigmoid(ax[1][e] + ah[1][e]);
+          const float c = tanhf(ax[2][e] + r * ah[2][e]);
+          const float u = 1.f - z;
+          const float up = mode == FIL_GRU_AGRU ? at : (mode == FIL_GRU_AUGRU ? at * u : u);
+          const float hn = fmaf(up, c, (1.f - up) * h[e]);
+          if (lv[e]) h[e] = hn;
+          zv[e] = z; rv[e] = r; cv[e] = c; pv[e] = ah[2][e];
+        }
+        *reinterpret_cast<float4*>(gru_smem + L.f_h + nxt * H * NSP + j * NSP + 4 * g) = make_float4(h[0], h[1], h[2], h[3]);
+      }
+      if (t + 1 < T) {
+        gru_store_x(xr, gru_smem + L.f_x + nxt * K * NSP, L);
+        if (tid < NS) { gru_smem[L.f_live + nxt * NS + tid] = lvn; gru_smem[L.f_a + nxt * NS + tid] = avn; }
+      }
+      if (active) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          const long bb = b0 + 4 * g + e;
+          if (lv[e] && saved != nullptr) {
+            float* sv = saved + ((bb * T + t) * 4) * H + j;
+            sv[0] = zv[e]; sv[H] = rv[e]; sv[2 * H] = cv[e]; sv[3 * H] = pv[e];
+          }
+          if (bb < B) hs[(bb * T + t) * H + j] = h[e];
+        }
+      }
+      if (t + 2 < T) {
+        gru_load_x(xr, x, mask, b0, B, t + 2, L);
+        gru_load_step(lvn, avn, a, mask, b0, B, t + 2, L);
+      }
+      __syncthreads();
+    }
+  }
+}
+
+template <int NR>
+__global__ __launch_bounds__(kGruThreads) void gru_bwd_kernel(const float* __restrict__ x, const float* __restrict__ a,
+                                                             const unsigned char* __restrict__ mask, const float* __restrict__ W,
+                                                             const float* __restrict__ U, const float* __restrict__ hs,
+                                                             const float* __restrict__ saved, const float* __restrict__ g_hs,
+                                                             const float* __restrict__ g_last, float* __restrict__ dx, float* __restrict__ da,
+                                                             float* __restrict__ partials, int B, int mode, GruLayout L) {
+  extern __shared__ __attribute__((aligned(16))) float gru_smem[];
+  const int tid = threadIdx.x, nthr = blockDim.x;
+  const int T = L.T, K = L.K, H = L.H, H3 = L.H3, NS = L.NS, NSP = L.NSP, G = L.G, KH = L.K + L.H;
+  for (int i = tid; i < K * H3; i += nthr) {       // WT [m][k] = W [k][m]
+    const int k = i / H3, m = i - k * H3;
+    gru_smem[m * K + k] = W[i];
+  }
+  for (int i = tid; i < H * H3; i += nthr) {
+    const int k = i / H3, m = i - k * H3;
+    gru_smem[L.b_UT + m * H + k] = U[i];
+  }
+  const float* WT = gru_smem;
+  const float* UT = gru_smem + L.b_UT;
+  float* dT = gru_smem + L.b_dT;
+  float* dS = gru_smem + L.b_dS;
+  float* daS = gru_smem + L.b_da;
+  const bool active = tid < G * H;
+  const int g = tid / H, j = tid - g * H;
+  const bool want_params = partials != nullptr;
+  float acc[NR][3];
+#pragma unroll
+  for (int r = 0; r < NR; ++r) acc[r][0] = acc[r][1] = acc[r][2] = 0.f;
+  float dbs[4] = {0.f, 0.f, 0.f, 0.f};      // the thread's samples' dz, dr, dc (input side), dc r (recurrent side)
+  const long n_tiles = ((long)B + NS - 1) / NS;
+  for (long tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
+    const long b0 = tile * NS;
+    float dh[4] = {0.f, 0.f, 0.f, 0.f};
+    float svn[4][4], hpn[4], ghn[4], lvn, avn;
+    float4 xr[kGruXV];
+    // what step tt needs, of the thread's unit and samples -> registers
+    auto prefetch = [&](int tt) {
+      if (want_params) gru_load_x(xr, x, mask, b0, B, tt, L);
+      gru_load_step(lvn, avn, a, mask, b0, B, tt, L);
+      if (active) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          const long bb = b0 + 4 * g + e;
+          const bool valid = bb < B;
+          const bool live = valid && (mask == nullptr || mask[bb * T + tt] != 0);
+          const float* sv = saved + ((bb * T + tt) * 4) * H + j;
+#pragma unroll
+          for (int c = 0; c < 4; ++c) svn[e][c] = live ? sv[c * H] : 0.f;
+          hpn[e] = (live && tt > 0) ? hs[(bb * T + tt - 1) * H + j] : 0.f;
+          ghn[e] = (valid && g_hs != nullptr) ? g_hs[(bb * T + tt) * H + j] : 0.f;
+        }
+      }
+    };
+    float sv[4][4], hp[4], gh[4];
+    // ... -> the LDS images of buffer `buf` and the registers of the current step
+    auto commit = [&](int buf) {
+      float* inT = gru_smem + L.b_in + buf * KH * NSP;
+      if (want_params) {
+        gru_store_x(xr, inT, L);
+        if (active) *reinterpret_cast<float4*>(inT + (K + j) * NSP + 4 * g) = make_float4(hpn[0], hpn[1], hpn[2], hpn[3]);
+      }
+      if (tid < NS) { gru_smem[L.b_live + buf * NS + tid] = lvn; gru_smem[L.b_a + buf * NS + tid] = avn; }
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+#pragma unroll
+        for (int c = 0; c < 4; ++c) sv[e][c] = svn[e][c];
+        hp[e] = hpn[e];
+        gh[e] = ghn[e];
+      }
+    };
+    if (active && g_last != nullptr) {
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const long bb = b0 + 4 * g + e;
+        if (bb < B) dh[e] = g_last[bb * H + j];
+      }
+    }
+    __syncthreads();      // the weights are staged; the previous tile's images are free
+    prefetch(T - 1);
+    commit((T - 1) & 1);
+    __syncthreads();
+    for (int t = T - 1; t >= 0; --t) {
+      const int cur = t & 1;
+      if (t > 0) prefetch(t - 1);
+      float keep[4] = {0.f, 0.f, 0.f, 0.f};
+      if (active) {
+        // phase 1: the gate gradients of (unit j, the quad's samples)
+        float dz[4], dr[4], dcx[4], dch[4], dat[4];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          const int s = 4 * g + e;
+          const bool live = gru_smem[L.b_live + cur * NS + s] != 0.f;
+          const float at = gru_smem[L.b_a + cur * NS + s];
+          if (g_hs != nullptr) dh[e] += gh[e];
+          const float z = sv[e][0], r = sv[e][1], c = sv[e][2], hph = sv[e][3];
+          const float u = 1.f - z;
+          const float up = mode == FIL_GRU_AGRU ? at : (mode == FIL_GRU_AUGRU ? at * u : u);
+          const float dup = dh[e] * (c - hp[e]);
+          const float du = mode == FIL_GRU_AGRU ? 0.f : (mode == FIL_GRU_AUGRU ? at * dup : dup);
+          const float dcp = (dh[e] * up) * (1.f - c * c);
+          dz[e] = live ? -du * (z * (1.f - z)) : 0.f;
+          dr[e] = live ? (dcp * hph) * (r * (1.f - r)) : 0.f;
+          dcx[e] = live ? dcp : 0.f;
+          dch[e] = live ? dcp * r : 0.f;
+          dat[e] = live ? (mode == FIL_GRU_AGRU ? dup : dup * u) : 0.f;
+          keep[e] = live ? dh[e] * (1.f - up) : dh[e];
+          dS[s * 4 * H + j] = dz[e];
+          dS[s * 4 * H + H + j] = dr[e];
+          dS[s * 4 * H + 2 * H + j] = dcx[e];
+          dS[s * 4 * H + 3 * H + j] = dch[e];
+          dbs[0] += dz[e]; dbs[1] += dr[e]; dbs[2] += dcx[e]; dbs[3] += dch[e];
+        }
+        *reinterpret_cast<float4*>(dT + j * NSP + 4 * g) = make_float4(dz[0], dz[1], dz[2], dz[3]);
+        *reinterpret_cast<float4*>(dT + (H + j) * NSP + 4 * g) = make_float4(dr[0], dr[1], dr[2], dr[3]);
+        *reinterpret_cast<float4*>(dT + (2 * H + j) * NSP + 4 * g) = make_float4(dcx[0], dcx[1], dcx[2], dcx[3]);
+        *reinterpret_cast<float4*>(dT + (3 * H + j) * NSP + 4 * g) = make_float4(dch[0], dch[1], dch[2], dch[3]);
+        if (da != nullptr) *reinterpret_cast<float4*>(daS + j * NSP + 4 * g) = make_float4(dat[0], dat[1], dat[2], dat[3]);
+      }
+      __syncthreads();
+      // phase 2
+      if (active) {
+        // dh_prev = dh (1 - u') + d_hp U^T: rows z, r of dT, then the recurrent side's dc r
+        float nh[4] = {0.f, 0.f, 0.f, 0.f};
+        if (t > 0) {
+#pragma unroll 4
+          for (int m = 0; m < H3; ++m) {
+            const float4 d = *reinterpret_cast<const float4*>(dT + (m < 2 * H ? m : m + H) * NSP + 4 * g);
+            const float w = UT[m * H + j];
+            nh[0] = fmaf(d.x, w, nh[0]); nh[1] = fmaf(d.y, w, nh[1]); nh[2] = fmaf(d.z, w, nh[2]); nh[3] = fmaf(d.w, w, nh[3]);
+          }
+        }
+#pragma unroll
+        for (int e = 0; e < 4; ++e) dh[e] = keep[e] + nh[e];
+        if (want_params) {
+          const float* inT = gru_smem + L.b_in + cur * KH * NSP;
+          for (int s4 = 0; s4 < NS; s4 += 4) {
+            float ez[4], er[4], ex[4], eh[4];
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+              const float* d = dS + (s4 + e) * 4 * H + j;
+              ez[e] = d[0]; er[e] = d[H]; ex[e] = d[2 * H]; eh[e] = d[3 * H];
+            }
+#pragma unroll
+            for (int r = 0; r < NR; ++r) {
+              const int i = g + r * G;
+              if (i < KH) {
+                const float4 v = *reinterpret_cast<const float4*>(inT + i * NSP + s4);
+                const float ve[4] = {v.x, v.y, v.z, v.w};
+                const bool xrow = i < K;
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                  acc[r][0] = fmaf(ve[e], ez[e], acc[r][0]);
+                  acc[r][1] = fmaf(ve[e], er[e], acc[r][1]);
+                  acc[r][2] = fmaf(ve[e], xrow ? ex[e] : eh[e], acc[r][2]);
+                }
+              }
+            }
+          }
+        }
+      }
+      // the registers loaded at the top of the step -> LDS BEFORE this step's stores are issued: the wait for those loads would
+      // otherwise also sit out the fresh stores, on the chain
+      if (t > 0) commit((t - 1) & 1);
+      if (da != nullptr && tid < NS) {
+        const long bb = b0 + tid;
+        if (bb < B) {
+          float sum = 0.f;
+          for (int jj = 0; jj < H; ++jj) sum += daS[jj * NSP + tid];
+          da[bb * T + t] = sum;
+        }
+      }
+      if (active) {
+        if (dx != nullptr) {
+          for (int k = j; k < K; k += H) {
+            float v[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll 4
+            for (int m = 0; m < H3; ++m) {
+              const float4 d = *reinterpret_cast<const float4*>(dT + m * NSP + 4 * g);
+              const float w = WT[m * K + k];
+              v[0] = fmaf(d.x, w, v[0]); v[1] = fmaf(d.y, w, v[1]); v[2] = fmaf(d.z, w, v[2]); v[3] = fmaf(d.w, w, v[3]);
+            }
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+              const long bb = b0 + 4 * g + e;
+              const bool live = gru_smem[L.b_live + cur * NS + 4 * g + e] != 0.f;
+              if (bb < B) dx[(bb * T + t) * K + k] = live ? v[e] : 0.f;
+            }
+          }
+        }
+      }
+      __syncthreads();
+    }
+  }
+  if (!want_params) return;
+  // the workgroup's partial: the accumulators as they stand; db = the quads' sums in quad order
+  float* part = partials + (long)blockIdx.x * L.n_out;
+  if (active) {
+#pragma unroll
+    for (int r = 0; r < NR; ++r) {
+      const int i = g + r * G;
+      if (i < KH) {
+        part[i * H3 + j] = acc[r][0];
+        part[i * H3 + H + j] = acc[r][1];
+        part[i * H3 + 2 * H + j] = acc[r][2];
+      }
+    }
+    // (the last barrier of the step loop has passed: dS is free)
+#pragma unroll
+    for (int c = 0; c < 4; ++c) dS[(g * 4 + c) * H + j] = dbs[c];
+  }
+  __syncthreads();
+  for (int o = tid; o < 4 * H; o += nthr) {
+    const int c = o / H, jj = o - c * H;
+    float sum = 0.f;
+    for (int gg = 0; gg < G; ++gg) sum += dS[(gg * 4 + c) * H + jj];
+    float* db = part + KH * H3;
+    if (c < 2) { db[c * H + jj] = sum; db[H3 + c * H + jj] = sum; }
+    else if (c == 2) db[2 * H + jj] = sum;
+    else db[H3 + 2 * H + jj] = sum;
+  }
+}
+
+struct GruGradPtrs {
+  float* p[3];      // dW, dU, db
+  int off[4];       // their offsets in a partial; off[3] = n_out
+};
+
+// out[o] = sum over the partials in a fixed order: 16 slices of every 16th partial, then the slices in order
+__global__ __launch_bounds__(256) void gru_param_reduce_kernel(const float* __restrict__ partials, int nparts, GruGradPtrs Gp) {
+  __shared__ float red[16][17];
+  const int ol = threadIdx.x & 15, sl = threadIdx.x >> 4;
+  const int n_out = Gp.off[3];
+  const int o = blockIdx.x * 16 + ol;
+  float t = 0.f;
+  if (o < n_out)
+    for (int pq = sl; pq < nparts; pq += 16) t += partials[(long)pq * n_out + o];
+  red[sl][ol] = t;
+  __syncthreads();
+  if (sl == 0 && o < n_out) {
+    float s = 0.f;
+    for (int pq = 0; pq < 16; ++pq) s += red[pq][ol];
+    int w = 0;
+    while (o >= Gp.off[w + 1]) ++w;
+    if (Gp.p[w] != nullptr) Gp.p[w][o - Gp.off[w]] = s;
+  }
+}
+
+// argument and menu checks shared by the entry points
+static int gru_dims(const char* who, int B, int T, int K, int H, int mode, GruLayout* L) {
+  FIL_CHECK_ARG_W(who, B >= 0 && T >= 1 && K >= 1 && H >= 1);
+  FIL_CHECK_ARG_W(who, mode == FIL_GRU_GRU || mode == FIL_GRU_AUGRU || mode == FIL_GRU_AGRU);
+  if (K % 4 != 0 || K > kGruMaxK) return fail(FIL_ERR_UNSUPPORTED, "%s: K=%d needs K %% 4 == 0 and K <= %d", who, K, kGruMaxK);
+  if (H % 4 != 0 || H > kGruMaxH) return fail(FIL_ERR_UNSUPPORTED, "%s: H=%d needs H %% 4 == 0 and H <= %d", who, H, kGruMaxH);
+  *L = gru_layout(B, T, K, H);
+  if (L->lds_fwd > kGruLdsLimit || L->lds_bwd > kGruLdsLimit)
+    return fail(FIL_ERR_UNSUPPORTED, "%s: K=%d H=%d needs %d bytes of LDS (limit %d)", who, K, H, std::max(L->lds_fwd, L->lds_bwd), kGruLdsLimit);
+  return FIL_OK;
+}
+
+template <typename KernelT>
+static int gru_allow_lds(const char* who, KernelT kernel, int bytes) {
+  if (bytes > 48 * 1024) {
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+    if (e != hipSuccess) return fail(FIL_ERR_HIP, "%s: %d bytes of dynamic LDS refused: %s", who, bytes, hipGetErrorString(e));
+  }
+  return FIL_OK;
+}
+
+struct GruBwdArgs {
+  const float *x, *a;
+  const unsigned char* mask;
+  const float *W, *U, *hs, *saved, *g_hs, *g_last;
+  float *dx, *da, *partials;
+};
+
+template <int NR>
+static int gru_launch_bwd(const char* who, const GruBwdArgs& p, int B, int mode, const GruLayout& L, hipStream_t st) {
+  if (int rc = gru_allow_lds(who, gru_bwd_kernel<NR>, L.lds_bwd)) return rc;
+  hipLaunchKernelGGL((gru_bwd_kernel<NR>), dim3(gru_grid(B, L.NS)), dim3(L.threads), L.lds_bwd, st, p.x, p.a, p.mask, p.W, p.U, p.hs, p.saved,
+                     p.g_hs, p.g_last, p.dx, p.da, p.partials, B, mode, L);
+  return FIL_OK;
+}
+
+}  // namespace fil
+
+using namespace fil;
+
+extern "C" int fil_gru_plan(int B, int T, int K, int H, int mode, int* plan) {
+  GruLayout L;
+  if (int rc = gru_dims(__func__, B, T, K, H, mode, &L)) return rc;
+  FIL_CHECK_ARG(plan != nullptr);
+  const int grid = gru_grid(B, L.NS);
+  plan[0] = 1;            // forward fits
+  plan[1] = 1;            // backward fits
+  plan[2] = L.NS;         // samples per workgroup tile
+  plan[3] = grid;
+  plan[4] = kGruGridCap;
+  plan[5] = grid;         // parameter-gradient partials: one per workgroup
+  plan[6] = L.lds_fwd;
+  plan[7] = L.lds_bwd;
+  return FIL_OK;
+}
+
+extern "C" size_t fil_gru_saved_bytes(int B, int T, int K, int H) {
+  GruLayout L;
+  if (gru_dims(__func__, B, T, K, H, FIL_GRU_GRU, &L) != FIL_OK) return 0;
+  return align_up((size_t)B * (size_t)T * 4 * (size_t)H * sizeof(float), 256);
+}
+
+extern "C" int fil_gru_fwd(const float* x, const float* a, const unsigned char* mask, const float* W, const float* U, const float* b,
+                           float* hs, float* saved, int B, int T, int K, int H, int mode, void* stream) {
+  GruLayout L;
+  if (int rc = gru_dims(__func__, B, T, K, H, mode, &L)) return rc;
+  if (B == 0) return FIL_OK;
+  FIL_CHECK_ARG(x != nullptr && W != nullptr && U != nullptr && b != nullptr && hs != nullptr);
+  FIL_CHECK_ARG((mode == FIL_GRU_GRU) == (a == nullptr));
+  hipStream_t st = (hipStream_t)stream;
+  ProfScope ps("gru_fwd", st, 4.0 * (double)B * T * (K + H + (saved != nullptr ? 4.0 * H : 0.0)));
+  if (int rc = gru_allow_lds(__func__, gru_fwd_kernel, L.lds_fwd)) return rc;
+  hipLaunchKernelGGL(gru_fwd_kernel, dim3(gru_grid(B, L.NS)), dim3(L.threads), L.lds_fwd, st, x, a, mask, W, U, b, hs, saved, B, mode, L);
+  FIL_CHECK_LAUNCH();
+  return FIL_OK;
+}
+
+extern "C" size_t fil_gru_bwd_workspace_bytes(int B, int T, int K, int H) {
+  GruLayout L;
+  if (gru_dims(__func__, B, T, K, H, FIL_GRU_GRU, &L) != FIL_OK) return 0;
+  return align_up((size_t)gru_grid(B, L.NS) * (size_t)L.n_out * sizeof(float), 256);
+}
+
+extern "C" int fil_gru_bwd(const float* x, const float* a, const unsigned char* mask, const float* W, const float* U, const float* hs,
+                           const float* saved, const float* g_hs, const float* g_last, float* dx, float* da, float* dW, float* dU, float* db,
+                           void* workspace, size_t workspace_bytes, int B, int T, int K, int H, int mode, void* stream) {
+  GruLayout L;
+  if (int rc = gru_dims(__func__, B, T, K, H, mode, &L)) return rc;
+  if (B == 0) return FIL_OK;
+  FIL_CHECK_ARG(x != nullptr && W != nullptr && U != nullptr && hs != nullptr && saved != nullptr);
+  FIL_CHECK_ARG((mode == FIL_GRU_GRU) == (a == nullptr));
+  FIL_CHECK_ARG(g_hs != nullptr || g_last != nullptr);
+  FIL_CHECK_ARG(da == nullptr || mode != FIL_GRU_GRU);
+  const bool want_params = dW != nullptr || dU != nullptr || db != nullptr;
+  FIL_CHECK_ARG(dx != nullptr || da != nullptr || want_params);
+  const int nparts = gru_grid(B, L.NS);
+  const size_t need = align_up((size_t)nparts * (size_t)L.n_out * sizeof(float), 256);
+  if (want_params && (workspace == nullptr || workspace_bytes < need))
+    return fail(FIL_ERR_ARG, "fil_gru_bwd: workspace of %zu bytes, %zu needed (fil_gru_bwd_workspace_bytes)", workspace_bytes, need);
+  hipStream_t st = (hipStream_t)stream;
+  ProfScope ps("gru_bwd", st, 4.0 * (double)B * T * (2.0 * K + 6.0 * H));
+  const GruBwdArgs p = {x, a, mask, W, U, hs, saved, g_hs, g_last, dx, da, want_params ? static_cast<float*>(workspace) : nullptr};
+  if (int rc = L.NR == 8 ? gru_launch_bwd<8>(__func__, p, B, mode, L, st)
+                         : (L.NR == 16 ? gru_launch_bwd<16>(__func__, p, B, mode, L, st) : gru_launch_bwd<32>(__func__, p, B, mode, L, st)))
+    return rc;
+  FIL_CHECK_LAUNCH();
+  if (want_params) {
+    GruGradPtrs Gp;
+    Gp.p[0] = dW; Gp.p[1] = dU; Gp.p[2] = db;
+    Gp.off[0] = 0; Gp.off[1] = K * L.H3; Gp.off[2] = (K + H) * L.H3; Gp.off[3] = L.n_out;
+    hipLaunchKernelGGL(gru_param_reduce_kernel, dim3(cdiv(L.n_out, 16)), dim3(256), 0, st, static_cast<const float*>(workspace), nparts, Gp);
+    FIL_CHECK_LAUNCH();
+  }
+  return FIL_OK;
+}

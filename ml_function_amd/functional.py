@@ -319,6 +319,103 @@ def din_plan(B, T, K, H1, H2):
                 lds_bwd=plan[7])
 
 
+GRU_MODES = {"gru": _lib.FIL_GRU_GRU, "augru": _lib.FIL_GRU_AUGRU, "agru": _lib.FIL_GRU_AGRU}
+
+
+class _GruFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, a, mask, w, u, b, mode, return_sequences):
+        _require_cuda(x, a, mask, w, u, b)
+        x, a, w, u, b = (_f32c(t) for t in (x, a, w, u, b))
+        if x.dim() != 3 or w.dim() != 2 or u.dim() != 2 or w.shape[0] != x.shape[2] or u.shape[1] != 3 * u.shape[0] or w.shape[1] != u.shape[1]:
+            raise FilError("gru: x must be [B,T,K], W [K,3H] and U [H,3H], got %s, %s and %s" % (tuple(x.shape), tuple(w.shape), tuple(u.shape)))
+        B, T, K = x.shape
+        H = u.shape[0]
+        if tuple(b.shape) != (2, 3 * H):
+            raise FilError("gru: b must be [2,3H] with H = %d (input bias, recurrent bias), got %s" % (H, tuple(b.shape)))
+        if (mode == _lib.FIL_GRU_GRU) != (a is None):
+            raise FilError("gru: the scores a are given in the modes 'augru' and 'agru' and only there")
+        if a is not None and tuple(a.shape) != (B, T):
+            raise FilError("gru: a must be [B,T], got %s" % (tuple(a.shape),))
+        if mask is not None:
+            if tuple(mask.shape) != (B, T) or mask.dtype not in (torch.bool, torch.uint8):
+                raise FilError("gru: mask must be a [B,T] bool or uint8 tensor, got %s %s" % (tuple(mask.shape), mask.dtype))
+            mask = (mask.to(torch.uint8) if mask.dtype == torch.bool else mask).contiguous()
+        lib = _lib.load()
+        hs = torch.empty((B, T, H), dtype=torch.float32, device=x.device)
+        need = ctx.needs_input_grad
+        saved = None
+        if any(need[i] for i in (0, 1, 3, 4, 5)):
+            saved = torch.empty(max(int(lib.fil_gru_saved_bytes(B, T, K, H)), 256) // 4, dtype=torch.float32, device=x.device)
+        check(lib.fil_gru_fwd(ptr(x), ptr(a), ptr(mask), ptr(w), ptr(u), ptr(b), ptr(hs), ptr(saved), B, T, K, H, mode, stream_ptr()),
+              "fil_gru_fwd")
+        ctx.has = (a is not None, mask is not None)
+        ctx.save_for_backward(*[t for t in (x, a, mask, w, u, hs, saved) if t is not None])
+        ctx.mode, ctx.return_sequences = mode, return_sequences
+        if return_sequences:
+            return hs
+        return hs[:, T - 1].clone() if B > 0 else hs.new_zeros((0, H))
+
+    @staticmethod
+    def backward(ctx, g):
+        sv = list(ctx.saved_tensors)
+        has_a, has_mask = ctx.has
+        x = sv.pop(0)
+        a = sv.pop(0) if has_a else None
+        mask = sv.pop(0) if has_mask else None
+        w, u, hs, saved = sv
+        B, T, K = x.shape
+        H = u.shape[0]
+        need = ctx.needs_input_grad
+        none = (None,) * 8
+        want_da = need[1] and has_a
+        if not (need[0] or want_da or need[3] or need[4] or need[5]):
+            return none
+        dev = x.device
+        new = lambda shape: torch.empty(shape, dtype=torch.float32, device=dev)
+        dx = new(x.shape) if need[0] else None
+        da = new(a.shape) if want_da else None
+        dw = new(w.shape) if need[3] else None
+        du = new(u.shape) if need[4] else None
+        db = new((2, 3 * H)) if need[5] else None
+        g = _f32c(g)
+        g_hs, g_last = (g, None) if ctx.return_sequences else (None, g)
+        lib = _lib.load()
+        ws, nws = None, 0
+        if dw is not None or du is not None or db is not None:
+            nws = lib.fil_gru_bwd_workspace_bytes(B, T, K, H)
+            ws = _scratch(nws, dev, "gru_bwd")
+        check(lib.fil_gru_bwd(ptr(x), ptr(a), ptr(mask), ptr(w), ptr(u), ptr(hs), ptr(saved), ptr(g_hs), ptr(g_last), ptr(dx), ptr(da),
+                              ptr(dw), ptr(du), ptr(db), ptr(ws), nws, B, T, K, H, ctx.mode, stream_ptr()), "fil_gru_bwd")
+        return dx, da, None, dw, du, db, None, None
+
+
+def gru(x, a, mask, W, U, b, mode="gru", return_sequences=True):
+    """A GRU over a behaviour sequence, or the Deep Interest Evolution Network's attention-gated variants (extension; include/fil.h
+    fil_gru_*): x [B,T,K], a [B,T] attention scores (None with mode "gru"), mask [B,T] bool / uint8 (non-zero = live; None = all
+    live), W [K,3H], U [H,3H] (Keras' column order z | r | h), b [2,3H] (input bias, recurrent bias: Keras' reset_after=True) ->
+    hs [B,T,H], or hs[:, -1] [B,H] with return_sequences=False (its gradient then enters the backward as [B,H]: no zero [B,T,H] block
+    is made).  mode "gru": Keras' GRU; "augru": the score scales the update gate, u' = a_t (1 - z); "agru": the score replaces it.
+    A masked step repeats the state (Keras' masking).  One launch per direction (plus the small fixed-order sum of the
+    parameter-gradient partials); only the gradients that are asked for are computed.  GPU only; shapes outside the kernel menu raise
+    FilError (layers.GRULayer takes its composed path there)."""
+    if mode not in GRU_MODES:
+        raise ValueError("gru: mode %r (%s)" % (mode, ", ".join(GRU_MODES)))
+    return _GruFn.apply(x, a, mask, W, U, b, GRU_MODES[mode], bool(return_sequences))
+
+
+def gru_plan(B, T, K, H, mode="gru"):
+    """fil_gru_plan's answer as a dict (fits, tile, grid, cap, partials, lds_fwd, lds_bwd); fits=False (and nothing else) for a shape
+    outside the kernel menu."""
+    plan = (ctypes.c_int * 8)()
+    rc = _lib.load().fil_gru_plan(int(B), int(T), int(K), int(H), GRU_MODES[mode], plan)
+    if rc == _lib.FIL_ERR_UNSUPPORTED:
+        return dict(fits=False)
+    check(rc, "fil_gru_plan")
+    return dict(fits=bool(plan[0]) and bool(plan[1]), tile=plan[2], grid=plan[3], cap=plan[4], partials=plan[5], lds_fwd=plan[6],
+                lds_bwd=plan[7])
+
+
 # --------------------------------------------------------------------------------------------- A2  DCN
 class _DcnFn(torch.autograd.Function):
     @staticmethod

@@ -97,6 +97,28 @@ def glorot_uniform_(tensor, seed=None):
     return tensor
 
 
+def orthogonal_(tensor, seed=None):
+    """Keras Orthogonal (gain 1) on a matrix: QR of a seeded N(0, 1) draw of the larger-by-smaller shape, Q multiplied by the sign of
+    R's diagonal (a unique, uniformly distributed factor), transposed back when there are fewer rows than columns -- applied to the
+    whole matrix, as Keras applies it to a GRU's [H,3H] recurrent kernel: the ROWS are then orthonormal."""
+    shape = tuple(tensor.shape)
+    if len(shape) != 2:
+        raise ValueError("orthogonal initializer: a matrix is needed, got shape %s" % (shape,))
+    rows, cols = shape
+    gen = None
+    if seed is not None:
+        gen = torch.Generator(device="cpu")
+        gen.manual_seed(int(seed))
+    a = torch.randn((max(rows, cols), min(rows, cols)), generator=gen, dtype=torch.float64)
+    q, r = torch.linalg.qr(a)
+    q = q * torch.sign(torch.diagonal(r)).unsqueeze(0)
+    if rows < cols:
+        q = q.t()
+    with torch.no_grad():
+        tensor.copy_(q.to(torch.float32).to(tensor.device))
+    return tensor
+
+
 class Layer(torch.nn.Module):
     """tf.keras.layers.Layer lifecycle: lazy build() on first __call__, weights via add_weight()."""
 
@@ -126,6 +148,8 @@ class Layer(torch.nn.Module):
             torch.nn.init.ones_(p)
         elif initializer == "glorot_uniform":
             glorot_uniform_(p, seed=seed)
+        elif initializer == "orthogonal":
+            orthogonal_(p, seed=seed)
         elif initializer == "random_normal":
             torch.nn.init.normal_(p, mean=0.0, std=0.05)  # Keras RandomNormal default stddev
         else:

@@ -240,3 +240,109 @@ class DinAttentionLayer(Layer):
         else:
             pooled = self._composed(q, keys, mask)
         return pooled.unsqueeze(1)
+
+
+_GRU_FITS = {}                 # (K, H, mode) -> fil_gru_plan's answer
+_GRU_MODES = ("gru", "augru", "agru")
+
+
+def gru_graph(x, a, mask, w, u, b, mode="gru", return_sequences=True):
+    """Fn.gru's math as torch ops on the tensors given (their dtype and device; autograd for the backward), one step at a time: the
+    composed path of GRULayer and the comparator of its benchmark -- about a dozen launches per step.  mask: [B,T] bool or None.
+    x_t and a_t of a masked step are replaced by zero before anything reads them."""
+    B, T, K = x.shape
+    H = u.shape[0]
+    zero = torch.zeros((), dtype=x.dtype, device=x.device)
+    live = None if mask is None else mask.to(torch.bool)
+    if live is not None:
+        x = torch.where(live.unsqueeze(-1), x, zero)
+        if a is not None:
+            a = torch.where(live, a, zero)
+    h = torch.zeros((B, H), dtype=x.dtype, device=x.device)
+    out = []
+    for t in range(T):
+        xp = torch.matmul(x[:, t], w) + b[0]
+        hp = torch.matmul(h, u) + b[1]
+        z = torch.sigmoid(xp[:, :H] + hp[:, :H])
+        r = torch.sigmoid(xp[:, H:2 * H] + hp[:, H:2 * H])
+        c = torch.tanh(xp[:, 2 * H:] + r * hp[:, 2 * H:])
+        up = 1 - z
+        if mode == "augru":
+            up = a[:, t:t + 1] * up
+        elif mode == "agru":
+            up = a[:, t:t + 1].expand(B, H)
+        hn = (1 - up) * h + up * c
+        h = hn if live is None else torch.where(live[:, t:t + 1], hn, h)
+        if return_sequences:
+            out.append(h)
+    return torch.stack(out, dim=1) if return_sequences else h
+
+
+class GRULayer(Layer):
+    """A GRU over a behaviour sequence, and the Deep Interest Evolution Network's attention-gated variants (extension: TF 2 Keras' GRU
+    with its defaults -- reset_after=True, sigmoid / tanh, no dropout -- and the paper's AUGRU / AGRU, eq. 15-16).
+
+    call(x [B,T,K], mask=None) with mode "gru"; call([x, scores [B,T]], mask=None) with "augru" (u' = a_t (1 - z)) or "agru"
+    (u' = a_t) -> hs [B,T,units], or the last state [B,units] with return_sequences=False.  mask: a [B,T] bool or uint8 tensor,
+    non-zero = live; a masked step repeats the state, zeros before the first live step (Keras' masking).  Weights carry Keras' names
+    and defaults: kernel [K,3 units] glorot_uniform(seed), recurrent_kernel [units,3 units] orthogonal(seed), bias [2,3 units] zeros;
+    the column order is z | r | h.  The whole recurrence runs in ONE HIP kernel per direction (Fn.gru, include/fil.h fil_gru_*).
+    Outside the kernel menu (fits_kernel_menu) or for a non-fp32 input the layer takes the composed path -- gru_graph on the GPU,
+    computed in fp32 -- instead of raising."""
+
+    def __init__(self, units, mode="gru", return_sequences=True, seed=2020):
+        super().__init__()
+        if int(units) < 1:
+            raise ValueError("GRULayer: units must be positive, got %r" % (units,))
+        if mode not in _GRU_MODES:
+            raise ValueError("GRULayer: mode %r (%s)" % (mode, ", ".join(_GRU_MODES)))
+        self.units = int(units)
+        self.mode = mode
+        self.return_sequences = bool(return_sequences)
+        self.seed = seed
+
+    def build(self, input_shape):
+        shape = input_shape[0] if isinstance(input_shape, list) else input_shape
+        k, h = int(shape[-1]), self.units
+        self.kernel = self.add_weight("kernel", [k, 3 * h], "glorot_uniform", seed=self.seed)
+        self.recurrent_kernel = self.add_weight("recurrent_kernel", [h, 3 * h], "orthogonal", seed=self.seed)
+        self.bias = self.add_weight("bias", [2, 3 * h], "zeros")
+        super().build(input_shape)
+
+    def fits_kernel_menu(self, x):
+        """fil_gru_*'s menu (include/fil.h): K % 4 == 0, H % 4 == 0, K <= 64, H <= 64 -- fil_gru_plan answers from the launchers' own
+        arithmetic; the answer is cached per shape."""
+        if x.dim() != 3:
+            return False
+        key = (int(x.shape[2]), self.units, self.mode)
+        fits = _GRU_FITS.get(key)
+        if fits is None:
+            fits = _GRU_FITS[key] = Fn.gru_plan(1, 1, key[0], key[1], key[2])["fits"]
+        return fits
+
+    def _composed(self, x, scores, mask):
+        """gru_graph on the GPU in fp32: about a dozen launches per step where the fused kernel makes one per direction -- it exists so
+        that a shape outside the kernel menu never raises."""
+        Fn._require_cuda(x, scores, mask)      # (torch ops would run on a CPU tensor: there is no CPU path in this package)
+        return gru_graph(x.to(torch.float32), None if scores is None else scores.to(torch.float32), mask, self.kernel,
+                         self.recurrent_kernel, self.bias, mode=self.mode, return_sequences=self.return_sequences)
+
+    def call(self, inputs, mask=None, **kwargs):
+        if self.mode == "gru":
+            x, scores = (inputs[0] if isinstance(inputs, (list, tuple)) and len(inputs) == 1 else inputs), None
+            if isinstance(x, (list, tuple)):
+                raise ValueError("GRULayer: mode 'gru' takes x alone, got %d inputs" % len(x))
+        else:
+            if not isinstance(inputs, (list, tuple)) or len(inputs) != 2:
+                raise ValueError("GRULayer: mode %r takes [x, scores]" % self.mode)
+            x, scores = inputs
+        if x.dim() != 3:
+            raise ValueError("GRULayer: x must be [B,T,K], got %s" % (tuple(x.shape),))
+        if scores is not None and tuple(scores.shape) != tuple(x.shape[:2]):
+            raise ValueError("GRULayer: scores must be [B,T] = %s, got %s" % (tuple(x.shape[:2]), tuple(scores.shape)))
+        if mask is not None and (tuple(mask.shape) != tuple(x.shape[:2]) or mask.dtype not in (torch.bool, torch.uint8)):
+            raise ValueError("GRULayer: mask must be a [B,T] bool or uint8 tensor, got %s %s" % (tuple(mask.shape), mask.dtype))
+        if x.dtype == torch.float32 and (scores is None or scores.dtype == torch.float32) and self.fits_kernel_menu(x):
+            return Fn.gru(x, scores, mask, self.kernel, self.recurrent_kernel, self.bias, mode=self.mode,
+                          return_sequences=self.return_sequences)
+        return self._composed(x, scores, mask)

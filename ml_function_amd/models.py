@@ -4,14 +4,15 @@ the feature-input plumbing it relies on (kon/utils/data_prepare.py: InputFeature
 FeatureInput :65-76).  The reference builds symbolic Keras models; here every zoo entry is a Layer whose call takes
 the concrete InputFeature of one batch, and ``CTRModel`` chains FeatureInput -> zoo body on raw (dense, sparse-id)
 tensors.  Hyper-parameter names and defaults are the reference's.  Sequence models are out of scope,
-except DINInput / DIN (extension): the Deep Interest Network's attention pooling of behaviour histories (layers.DinAttentionLayer).
+except DINInput / DIN (extension): the Deep Interest Network's attention pooling of behaviour histories (layers.DinAttentionLayer),
+and DIEN (extension): the Deep Interest Evolution Network's GRU + AUGRU over the same histories (layers.GRULayer).
 """
 from collections import namedtuple
 
 import torch
 
 from . import functional as Fn
-from .layers import (CIN, AFMLayer, AttentionBaseLayer, BagEmbed, CrossLayer, DinAttentionLayer, DnnLayer, FmLayer, InnerLayer, IPnnLayer, MergeScoreLayer,
+from .layers import (CIN, AFMLayer, AttentionBaseLayer, BagEmbed, CrossLayer, DinAttentionLayer, DnnLayer, FmLayer, GRULayer, InnerLayer, IPnnLayer, MergeScoreLayer,
                      MultHeadAttentionLayer, OPnnLayer, ScoreLayer, SparseEmbed, StackLayer)
 from .layers.base import Layer
 from .layers.interactive_layer import pack_fields
@@ -360,6 +361,64 @@ class DIN(torch.nn.Module):
         for n, (cand, _) in enumerate(inputFea.seq_info):
             pooled.append(self.atten[n]([inputFea.sparse_embed[cand], keys[n]], mask=masks[n]))
         return self.score(self.dnn(self.stack(list(inputFea.dense_inputs) + list(inputFea.sparse_embed) + pooled)))
+
+
+class _DienBehavior(Layer):
+    """One behaviour of DIEN: interest extraction, the candidate's scores against every interest state, interest evolution."""
+
+    def __init__(self, gru_type, seed=2020):
+        super().__init__()
+        self.gru_type = gru_type
+        self.seed = seed
+
+    def build(self, input_shape):
+        k = int(input_shape[1][-1])
+        self.extract = GRULayer(k, mode="gru", return_sequences=True, seed=self.seed)
+        self.evolve = GRULayer(k, mode=self.gru_type, return_sequences=False, seed=self.seed + 1)
+        self.att_w = self.add_weight("att_w", [k, k], "glorot_uniform", seed=self.seed)      # A [H,K], H = K
+        super().build(input_shape)
+
+    def call(self, inputs, mask=None, **kwargs):
+        query, keys = inputs
+        q = query.reshape(keys.shape[0], keys.shape[2])
+        interests = self.extract(keys, mask=mask)                                # [B,T,H]
+        s = torch.matmul(interests, torch.matmul(q, self.att_w.t()).unsqueeze(-1)).squeeze(-1)      # s_t = h_t . (A q)
+        if mask is not None:
+            s = s.masked_fill(~mask.to(torch.bool), float("-inf"))
+        mx = s.max(dim=1, keepdim=True).values
+        mx = torch.where(torch.isfinite(mx), mx, torch.zeros_like(mx))
+        w = torch.exp(s - mx)
+        scores = w / w.sum(dim=1, keepdim=True).clamp_min(torch.finfo(w.dtype).tiny)      # no live slot: 0 / tiny = 0
+        return self.evolve([interests, scores], mask=mask).unsqueeze(1)          # [B,1,H]
+
+
+class DIEN(torch.nn.Module):
+    """Deep Interest Evolution Network (extension; the paper's model on DINInput's features, without the auxiliary loss).  Per
+    behaviour: a GRU over the history keys extracts the interest states (GRULayer(K), Keras' masking), the candidate scores every
+    state, s_t = h_t . (A q) with a trainable att_w = A [H,K], softmax over the live slots (the paper's eq. 14), and a second
+    GRULayer(K, mode=gru_type, return_sequences=False) evolves the interests under those scores ("augru", the paper's choice,
+    "agru", or "gru", which ignores them).  Then, as DIN: StackLayer over dense + field embeddings + evolved interests -> DnnLayer ->
+    MergeScoreLayer(use_merge=False)."""
+
+    def __init__(self, gru_type="augru", hidden_units=None, seed=2020):
+        super().__init__()
+        if gru_type not in ("gru", "augru", "agru"):
+            raise ValueError("DIEN: gru_type %r (gru, augru, agru)" % (gru_type,))
+        self.gru_type = gru_type
+        self.seed = seed
+        self.behaviors = torch.nn.ModuleList()
+        self.stack = StackLayer()
+        self.dnn = DnnLayer(hidden_units=hidden_units or [200, 80])
+        self.score = MergeScoreLayer(use_merge=False)
+
+    def forward(self, inputFea):
+        keys, masks = inputFea.seq_embed_list
+        while len(self.behaviors) < len(keys):
+            self.behaviors.append(_DienBehavior(self.gru_type, seed=self.seed + 2 * len(self.behaviors)))
+        evolved = []
+        for n, (cand, _) in enumerate(inputFea.seq_info):
+            evolved.append(self.behaviors[n]([inputFea.sparse_embed[cand], keys[n]], mask=masks[n]))
+        return self.score(self.dnn(self.stack(list(inputFea.dense_inputs) + list(inputFea.sparse_embed) + evolved)))
 
 
 class CTRModel(torch.nn.Module):
