@@ -466,6 +466,48 @@ int fil_gru_bwd(const float* x, const float* a, const unsigned char* mask, const
                 void* workspace, size_t workspace_bytes, int B, int T, int K, int H, int mode, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * N3  Masked multi-head self-attention over a behaviour sequence (extension: the scaled dot-product layer of "Attention is all you
+ *     need" as the Behaviour Sequence Transformer applies it to a history; NOT the reference's MultHeadAttentionLayer, which
+ *     fil_attn_* / fil_pattn_* restate and which stays as it is).  All tensors fp32 except mask.  Entry points added only: the ABI
+ *     version stays.
+ *   x [B,T,K] the sequence; mask [B,T] uint8, non-zero = live, NULL = all live (live slots may sit anywhere); Wq, Wk, Wv [K, H*D],
+ *   H heads of width D; out [B,T,H*D], position-major, heads concatenated.  With q = x Wq, k = x Wk, v = x Wv, per sample and head h
+ *   (columns hD .. hD+D-1):
+ *     s_ij = q_i . k_j (* 1/sqrt(D) when use_scale != 0);  p_ij = softmax of s_ij over the LIVE j (max-subtracted);
+ *     out_i = sum_j p_ij v_j for a live i;  out_i = 0 for a masked i (a sample with no live slot: zeros).
+ *   No biases, no output projection, no dropout, no causal mask.  A masked position's x row is never read.
+ *   fil_seqattn_fwd: out, and `saved` [B,T,3,H*D] = (q, k, v) of the live positions for the backward (fil_seqattn_saved_bytes; opaque
+ *     to the caller; masked positions are left unwritten; NULL: nothing is saved, for inference).
+ *   fil_seqattn_bwd: g [B,T,H*D] -> dx [B,T,K], dWq, dWk, dWv [K, H*D].  A masked position's g row is never read; dx is exactly 0
+ *     there.  The scores and probabilities are recomputed from `saved`; the softmax gradient is taken relative to the row's top key
+ *     (a row with one live key gives exactly 0, a peaked row keeps its digits).  Each output may be NULL and is then not
+ *     written, the others keep the bits of the full call (dWq, dWk, dWv all NULL: no parameter pass, no workspace; all four NULL:
+ *     FIL_ERR_ARG).  The parameter gradients leave the main launch as one partial per workgroup in `workspace`
+ *     (fil_seqattn_bwd_workspace_bytes; every byte that is read was written by that launch) and a second small launch adds the
+ *     partials in a fixed order.  `out` is the forward's output (kept in the signature for a caller-side check; not read).
+ *   One launch per direction (plus the partial sum).  Nothing of size [T,T] or [B,T,3HD] beyond `saved` touches global memory.  No
+ *   atomics; every sum has a fixed order: the same inputs give the same bits on every call, and a sample's out / dx rows do not
+ *   depend on the rest of the batch.
+ *   Menu: K % 4 == 0, D % 4 == 0, K <= 64, H <= 8, H*D <= 64, 1 <= T <= 256, and a one-sample tile within 163,328 bytes of dynamic
+ *   LDS in both directions: 4 (T (K + 5 H D + 5 H + 25) + 8) bytes in the backward, the larger (every menu shape at T <= 64 fits,
+ *   and T <= 256 at K, H*D <= 16).  FIL_ERR_UNSUPPORTED otherwise, the limit in the message.
+ *   B == 0 returns FIL_OK before any pointer is looked at.  A workspace smaller than needed: FIL_ERR_ARG, the needed size in the message.
+ *   fil_seqattn_plan: the launchers' own arithmetic (no GPU call): plan[8] = {fwd_ok, bwd_ok, samples per workgroup tile, grid, grid
+ *     cap, parameter-gradient partials (= grid), forward LDS bytes, backward LDS bytes}.  The tile is the most samples that give each of a
+ *     workgroup's 256 threads at most one (head, row) pair, floor(256 / (H T)), at least 1 and at most what LDS holds; it does not
+ *     grow with B (a small LDS image keeps several workgroups on a CU): past grid cap tiles a workgroup walks several.  Returns
+ *     FIL_OK, or the argument / menu error the launch would give.
+ */
+int fil_seqattn_plan(int B, int T, int K, int H, int D, int* plan /* [8] */);
+size_t fil_seqattn_saved_bytes(int B, int T, int K, int H, int D);
+int fil_seqattn_fwd(const float* x, const unsigned char* mask, const float* Wq, const float* Wk, const float* Wv, float* out,
+                    float* saved, int B, int T, int K, int H, int D, int use_scale, void* stream);
+size_t fil_seqattn_bwd_workspace_bytes(int B, int T, int K, int H, int D);
+int fil_seqattn_bwd(const float* x, const unsigned char* mask, const float* Wq, const float* Wk, const float* Wv, const float* out,
+                    const float* saved, const float* g, float* dx, float* dWq, float* dWk, float* dWv, void* workspace,
+                    size_t workspace_bytes, int B, int T, int K, int H, int D, int use_scale, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * N2  The score head and the loss behind the interaction layers (all tensors fp32, n = batch rows).
  *   ScoreLayer(use_add=True).call (kon/model/ctr_model/layer/core_layer/core_layer.py:58-84): keras Add over the [B,1] parts,
  *   then sigmoid.  fil_score_add_sigmoid_fwd: out[i] = sigmoid(((a[i] + b[i]) + c[i]) + d[i]) -- left to right like the

@@ -109,6 +109,12 @@ SIGNATURES = {
     "fil_gru_fwd": (_I, [_P] * 8 + [_I] * 5 + [_P]),
     "fil_gru_bwd_workspace_bytes": (_Z, [_I, _I, _I, _I]),
     "fil_gru_bwd": (_I, [_P] * 15 + [_Z] + [_I] * 5 + [_P]),
+    # N3: masked multi-head self-attention over a behaviour sequence
+    "fil_seqattn_plan": (_I, [_I, _I, _I, _I, _I, _P]),
+    "fil_seqattn_saved_bytes": (_Z, [_I, _I, _I, _I, _I]),
+    "fil_seqattn_fwd": (_I, [_P] * 7 + [_I] * 6 + [_P]),
+    "fil_seqattn_bwd_workspace_bytes": (_Z, [_I, _I, _I, _I, _I]),
+    "fil_seqattn_bwd": (_I, [_P] * 13 + [_Z] + [_I] * 6 + [_P]),
     "fil_score_add_sigmoid_fwd": (_I, [_P, _P, _P, _P, _P, _I, _P]),
     "fil_score_add_sigmoid_bwd": (_I, [_P, _P, _P, _I, _P]),
     "fil_bce_mean_fwd": (_I, [_P, _P, _F, _P, _P, _I, _P]),

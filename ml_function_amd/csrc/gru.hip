@@ -23,6 +23,7 @@
 //             One partial per workgroup; gru_param_reduce_kernel adds the partials in a fixed order.
 // No atomics; every sum has a fixed order for a given shape: repeats are bit-identical.
 #include "common.h"
+#include "param_reduce.h"
 #include <algorithm>
 #include <math.h>
 
@@ -483,6 +484,13 @@ __global__ __launch_bounds__(256) void gru_param_reduce_kernel(const float* __re
   }
 }
 
+void param_reduce_launch(const float* partials, int nparts, float* const outs[3], const int off[4], hipStream_t st) {
+  GruGradPtrs Gp;
+  for (int w = 0; w < 3; ++w) Gp.p[w] = outs[w];
+  for (int w = 0; w < 4; ++w) Gp.off[w] = off[w];
+  hipLaunchKernelGGL(gru_param_reduce_kernel, dim3(cdiv(off[3], 16)), dim3(256), 0, st, partials, nparts, Gp);
+}
+
 // argument and menu checks shared by the entry points
 static int gru_dims(const char* who, int B, int T, int K, int H, int mode, GruLayout* L) {
   FIL_CHECK_ARG_W(who, B >= 0 && T >= 1 && K >= 1 && H >= 1);
@@ -590,10 +598,9 @@ extern "C" int fil_gru_bwd(const float* x, const float* a, const unsigned char* 
     return rc;
   FIL_CHECK_LAUNCH();
   if (want_params) {
-    GruGradPtrs Gp;
-    Gp.p[0] = dW; Gp.p[1] = dU; Gp.p[2] = db;
-    Gp.off[0] = 0; Gp.off[1] = K * L.H3; Gp.off[2] = (K + H) * L.H3; Gp.off[3] = L.n_out;
-    hipLaunchKernelGGL(gru_param_reduce_kernel, dim3(cdiv(L.n_out, 16)), dim3(256), 0, st, static_cast<const float*>(workspace), nparts, Gp);
+    float* const outs[3] = {dW, dU, db};
+    const int off[4] = {0, K * L.H3, (K + H) * L.H3, L.n_out};
+    param_reduce_launch(static_cast<const float*>(workspace), nparts, outs, off, st);
     FIL_CHECK_LAUNCH();
   }
   return FIL_OK;

@@ -416,6 +416,87 @@ def gru_plan(B, T, K, H, mode="gru"):
                 lds_bwd=plan[7])
 
 
+class _SeqAttnFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, mask, wq, wk, wv, heads, use_scale):
+        _require_cuda(x, mask, wq, wk, wv)
+        x, wq, wk, wv = (_f32c(t) for t in (x, wq, wk, wv))
+        if (x.dim() != 3 or wq.dim() != 2 or wq.shape[0] != x.shape[2] or tuple(wk.shape) != tuple(wq.shape)
+                or tuple(wv.shape) != tuple(wq.shape)):
+            raise FilError("seq_self_attention: x must be [B,T,K] and Wq, Wk, Wv [K,H*D], got %s, %s, %s and %s"
+                           % (tuple(x.shape), tuple(wq.shape), tuple(wk.shape), tuple(wv.shape)))
+        B, T, K = x.shape
+        HD = wq.shape[1]
+        if heads < 1 or HD % heads != 0:
+            raise FilError("seq_self_attention: %d heads do not divide the %d projection columns" % (heads, HD))
+        H, D = heads, HD // heads
+        if mask is not None:
+            if tuple(mask.shape) != (B, T) or mask.dtype not in (torch.bool, torch.uint8):
+                raise FilError("seq_self_attention: mask must be a [B,T] bool or uint8 tensor, got %s %s" % (tuple(mask.shape), mask.dtype))
+            mask = (mask.to(torch.uint8) if mask.dtype == torch.bool else mask).contiguous()
+        lib = _lib.load()
+        out = torch.empty((B, T, HD), dtype=torch.float32, device=x.device)
+        need = ctx.needs_input_grad
+        saved = None
+        if any(need[i] for i in (0, 2, 3, 4)):
+            saved = torch.empty(max(int(lib.fil_seqattn_saved_bytes(B, T, K, H, D)), 256) // 4, dtype=torch.float32, device=x.device)
+        check(lib.fil_seqattn_fwd(ptr(x), ptr(mask), ptr(wq), ptr(wk), ptr(wv), ptr(out), ptr(saved), B, T, K, H, D, int(use_scale),
+                                  stream_ptr()), "fil_seqattn_fwd")
+        ctx.has_mask = mask is not None
+        ctx.save_for_backward(*[t for t in (x, mask, wq, wk, wv, out, saved) if t is not None])
+        ctx.dims = (H, D, int(use_scale))
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        sv = list(ctx.saved_tensors)
+        x = sv.pop(0)
+        mask = sv.pop(0) if ctx.has_mask else None
+        need = ctx.needs_input_grad
+        if not (need[0] or need[2] or need[3] or need[4]):
+            return (None,) * 7
+        wq, wk, wv, out, saved = sv
+        B, T, K = x.shape
+        H, D, use_scale = ctx.dims
+        dev = x.device
+        new = lambda shape: torch.empty(shape, dtype=torch.float32, device=dev)
+        dx = new(x.shape) if need[0] else None
+        dwq = new(wq.shape) if need[2] else None
+        dwk = new(wk.shape) if need[3] else None
+        dwv = new(wv.shape) if need[4] else None
+        g = _f32c(g)
+        lib = _lib.load()
+        ws, nws = None, 0
+        if dwq is not None or dwk is not None or dwv is not None:
+            nws = lib.fil_seqattn_bwd_workspace_bytes(B, T, K, H, D)
+            ws = _scratch(nws, dev, "seqattn_bwd")
+        check(lib.fil_seqattn_bwd(ptr(x), ptr(mask), ptr(wq), ptr(wk), ptr(wv), ptr(out), ptr(saved), ptr(g), ptr(dx), ptr(dwq), ptr(dwk),
+                                  ptr(dwv), ptr(ws), nws, B, T, K, H, D, use_scale, stream_ptr()), "fil_seqattn_bwd")
+        return dx, None, dwq, dwk, dwv, None, None
+
+
+def seq_self_attention(x, mask, Wq, Wk, Wv, heads, use_scale=True):
+    """Masked multi-head scaled dot-product self-attention over a behaviour sequence (extension; include/fil.h fil_seqattn_*):
+    x [B,T,K], mask [B,T] bool / uint8 (non-zero = live; None = all live), Wq, Wk, Wv [K,H*D] with H = heads -> [B,T,H*D], heads
+    concatenated.  The softmax runs over the live keys; a masked position's row is 0 and its x row is never read.  No biases, no
+    output projection, no dropout, no causal mask.  One launch per direction (plus the small fixed-order sum of the
+    parameter-gradient partials); only the gradients that are asked for are written.  GPU only; shapes outside the kernel menu raise
+    FilError (layers.SeqSelfAttentionLayer takes its composed path there)."""
+    return _SeqAttnFn.apply(x, mask, Wq, Wk, Wv, int(heads), bool(use_scale))
+
+
+def seq_attn_plan(B, T, K, H, D):
+    """fil_seqattn_plan's answer as a dict (fits, tile, grid, cap, partials, lds_fwd, lds_bwd); fits=False (and nothing else) for a
+    shape outside the kernel menu."""
+    plan = (ctypes.c_int * 8)()
+    rc = _lib.load().fil_seqattn_plan(int(B), int(T), int(K), int(H), int(D), plan)
+    if rc == _lib.FIL_ERR_UNSUPPORTED:
+        return dict(fits=False)
+    check(rc, "fil_seqattn_plan")
+    return dict(fits=bool(plan[0]) and bool(plan[1]), tile=plan[2], grid=plan[3], cap=plan[4], partials=plan[5], lds_fwd=plan[6],
+                lds_bwd=plan[7])
+
+
 # --------------------------------------------------------------------------------------------- A2  DCN
 class _DcnFn(torch.autograd.Function):
     @staticmethod

@@ -346,3 +346,98 @@ class GRULayer(Layer):
             return Fn.gru(x, scores, mask, self.kernel, self.recurrent_kernel, self.bias, mode=self.mode,
                           return_sequences=self.return_sequences)
         return self._composed(x, scores, mask)
+
+
+_SEQ_ATTN_FITS = {}            # (T, K, heads, head_dim) -> fil_seqattn_plan's answer
+
+
+def seq_self_attention_graph(x, mask, wq, wk, wv, heads, use_scale=True):
+    """Fn.seq_self_attention's math as torch ops on the tensors given (their dtype and device; autograd for the backward): the
+    composed path of SeqSelfAttentionLayer and the comparator of its benchmark -- three small GEMMs, a [B,H,T,T] score block written
+    and read several times, about a dozen launches per direction.  mask: [B,T] bool / uint8 or None.  The x row of a masked position
+    is replaced by zero before anything reads it; a masked key gets weight 0, a masked row (and a sample with no live slot) is 0."""
+    B, T, K = x.shape
+    H = int(heads)
+    D = wq.shape[1] // H
+    live = None if mask is None else mask.to(torch.bool)
+    if live is not None:
+        x = torch.where(live.unsqueeze(-1), x, torch.zeros((), dtype=x.dtype, device=x.device))
+    q = torch.matmul(x, wq).reshape(B, T, H, D).permute(0, 2, 1, 3)
+    k = torch.matmul(x, wk).reshape(B, T, H, D).permute(0, 2, 1, 3)
+    v = torch.matmul(x, wv).reshape(B, T, H, D).permute(0, 2, 1, 3)
+    s = torch.matmul(q, k.transpose(-1, -2))
+    if use_scale:
+        s = s * (1.0 / float(D) ** 0.5)
+    if live is not None:
+        key_live = live.reshape(B, 1, 1, T)
+        s = torch.where(key_live, s, torch.full((), -float("inf"), dtype=s.dtype, device=s.device))
+        m = torch.where(live.any(dim=1).reshape(B, 1, 1, 1), s.detach().max(dim=-1, keepdim=True).values,
+                        torch.zeros((), dtype=s.dtype, device=s.device))
+        e = torch.where(key_live, torch.exp(s - m), torch.zeros((), dtype=s.dtype, device=s.device))
+        p = e / e.sum(dim=-1, keepdim=True).clamp_min(torch.finfo(s.dtype).tiny)
+    else:
+        p = torch.softmax(s, dim=-1)
+    out = torch.matmul(p, v).permute(0, 2, 1, 3).reshape(B, T, H * D)
+    if live is not None:
+        out = torch.where(live.unsqueeze(-1), out, torch.zeros((), dtype=out.dtype, device=out.device))
+    return out
+
+
+class SeqSelfAttentionLayer(Layer):
+    """Masked multi-head scaled dot-product self-attention over a behaviour sequence (extension: the layer of "Attention is all you
+    need" as the Behaviour Sequence Transformer applies it to a history; MultHeadAttentionLayer above keeps the reference's quirks and
+    is a different layer).
+
+    call(x [B,T,K], mask=None) -> [B,T,heads * head_dim], heads concatenated.  mask: a [B,T] bool or uint8 tensor, non-zero = live;
+    the softmax runs over the live keys and a masked position's row is 0.  Weights carry the reference layer's names and shape:
+    query_w, key_w, value_w, each [K, heads, head_dim], glorot_uniform(seed) -- and value_w is used here.  No biases, no output
+    projection, no dropout, no causal mask.  One HIP kernel per direction (Fn.seq_self_attention, include/fil.h fil_seqattn_*).
+    Outside the kernel menu (fits_kernel_menu) or for a non-fp32 input the layer takes the composed path -- seq_self_attention_graph
+    on the GPU, computed in fp32 -- instead of raising."""
+
+    def __init__(self, heads, head_dim, use_scale=True, seed=2020):
+        super().__init__()
+        if int(heads) < 1 or int(head_dim) < 1:
+            raise ValueError("SeqSelfAttentionLayer: heads and head_dim must be positive, got %r and %r" % (heads, head_dim))
+        self.heads = int(heads)
+        self.head_dim = int(head_dim)
+        self.use_scale = bool(use_scale)
+        self.seed = seed
+
+    def build(self, input_shape):
+        k = int(input_shape[-1])
+        shape = [k, self.heads, self.head_dim]
+        self.query_w = self.add_weight("query_w", shape, "glorot_uniform", seed=self.seed)
+        self.key_w = self.add_weight("key_w", shape, "glorot_uniform", seed=self.seed)
+        self.value_w = self.add_weight("value_w", shape, "glorot_uniform", seed=self.seed)
+        super().build(input_shape)
+
+    def fits_kernel_menu(self, x):
+        """fil_seqattn_*'s menu (include/fil.h): K % 4 == 0, D % 4 == 0, K <= 64, H <= 8, H D <= 64, T <= 256 and a one-sample tile
+        within the LDS limit -- fil_seqattn_plan answers from the launchers' own arithmetic; the answer is cached per shape."""
+        if x.dim() != 3:
+            return False
+        key = (int(x.shape[1]), int(x.shape[2]), self.heads, self.head_dim)
+        fits = _SEQ_ATTN_FITS.get(key)
+        if fits is None:
+            fits = _SEQ_ATTN_FITS[key] = key[0] >= 1 and Fn.seq_attn_plan(1, *key)["fits"]
+        return fits
+
+    def _flat(self):
+        hd = self.heads * self.head_dim
+        return tuple(w.reshape(w.shape[0], hd) for w in (self.query_w, self.key_w, self.value_w))
+
+    def _composed(self, x, mask):
+        """seq_self_attention_graph on the GPU in fp32: it exists so that a shape outside the kernel menu never raises."""
+        Fn._require_cuda(x, mask)      # (torch ops would run on a CPU tensor: there is no CPU path in this package)
+        return seq_self_attention_graph(x.to(torch.float32), mask, *self._flat(), self.heads, use_scale=self.use_scale)
+
+    def call(self, inputs, mask=None, **kwargs):
+        x = inputs
+        if not torch.is_tensor(x) or x.dim() != 3:
+            raise ValueError("SeqSelfAttentionLayer: x must be [B,T,K], got %s" % (tuple(x.shape) if torch.is_tensor(x) else type(x).__name__,))
+        if mask is not None and (tuple(mask.shape) != tuple(x.shape[:2]) or mask.dtype not in (torch.bool, torch.uint8)):
+            raise ValueError("SeqSelfAttentionLayer: mask must be a [B,T] bool or uint8 tensor, got %s %s" % (tuple(mask.shape), mask.dtype))
+        if x.dtype == torch.float32 and self.fits_kernel_menu(x):
+            return Fn.seq_self_attention(x, mask, *self._flat(), self.heads, use_scale=self.use_scale)
+        return self._composed(x, mask)

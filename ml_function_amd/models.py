@@ -5,7 +5,8 @@ FeatureInput :65-76).  The reference builds symbolic Keras models; here every zo
 the concrete InputFeature of one batch, and ``CTRModel`` chains FeatureInput -> zoo body on raw (dense, sparse-id)
 tensors.  Hyper-parameter names and defaults are the reference's.  Sequence models are out of scope,
 except DINInput / DIN (extension): the Deep Interest Network's attention pooling of behaviour histories (layers.DinAttentionLayer),
-and DIEN (extension): the Deep Interest Evolution Network's GRU + AUGRU over the same histories (layers.GRULayer).
+DIEN (extension): the Deep Interest Evolution Network's GRU + AUGRU over the same histories (layers.GRULayer),
+and BST (extension): the Behaviour Sequence Transformer's block over them (layers.SeqSelfAttentionLayer).
 """
 from collections import namedtuple
 
@@ -13,7 +14,8 @@ import torch
 
 from . import functional as Fn
 from .layers import (CIN, AFMLayer, AttentionBaseLayer, BagEmbed, CrossLayer, DinAttentionLayer, DnnLayer, FmLayer, GRULayer, InnerLayer, IPnnLayer, MergeScoreLayer,
-                     MultHeadAttentionLayer, OPnnLayer, ScoreLayer, SparseEmbed, StackLayer)
+                     MultHeadAttentionLayer, OPnnLayer, ScoreLayer, SeqSelfAttentionLayer, SparseEmbed, StackLayer)
+from .layers.core_layer import Dense
 from .layers.base import Layer
 from .layers.interactive_layer import pack_fields
 from .layers.core_layer import keras_add
@@ -419,6 +421,78 @@ class DIEN(torch.nn.Module):
         for n, (cand, _) in enumerate(inputFea.seq_info):
             evolved.append(self.behaviors[n]([inputFea.sparse_embed[cand], keys[n]], mask=masks[n]))
         return self.score(self.dnn(self.stack(list(inputFea.dense_inputs) + list(inputFea.sparse_embed) + evolved)))
+
+
+class _BstBehavior(Layer):
+    """One behaviour of BST: a Transformer block (self-attention, residual + LayerNorm, position-wise feed-forward, residual +
+    LayerNorm) over the history followed by the candidate.  The attention is the fused layer; the block's small parts run as torch
+    ops."""
+
+    def __init__(self, att_heads, ffn_units=None, seed=2020):
+        super().__init__()
+        self.att_heads = int(att_heads)
+        self.ffn_units = ffn_units
+        self.seed = seed
+        self.ln_epsilon = 1e-3      # tf.keras.layers.LayerNormalization() default
+
+    def build(self, input_shape):
+        t, k = int(input_shape[1][1]) + 1, int(input_shape[1][-1])
+        if k % self.att_heads != 0:
+            raise ValueError("BST: att_heads=%d does not divide the embedding width K=%d" % (self.att_heads, k))
+        self.pos_embed = self.add_weight("pos_embed", [t, k], "glorot_uniform", seed=self.seed)
+        self.atten = SeqSelfAttentionLayer(self.att_heads, k // self.att_heads, seed=self.seed)
+        self.ffn1 = Dense(self.ffn_units or 4 * k, seed=self.seed)
+        self.ffn2 = Dense(k, seed=self.seed + 1)
+        self.ln1_gamma = self.add_weight("ln1_gamma", [k], "ones")
+        self.ln1_beta = self.add_weight("ln1_beta", [k], "zeros")
+        self.ln2_gamma = self.add_weight("ln2_gamma", [k], "ones")
+        self.ln2_beta = self.add_weight("ln2_beta", [k], "zeros")
+        super().build(input_shape)
+
+    def call(self, inputs, mask=None, **kwargs):
+        query, keys = inputs
+        B, T, K = keys.shape
+        seq = torch.cat([keys, query.reshape(B, 1, K)], dim=1) + self.pos_embed            # [B,T+1,K], the candidate last
+        live = torch.ones((B, T + 1), dtype=torch.bool, device=keys.device)
+        if mask is not None:
+            live = torch.cat([mask.to(torch.bool), live[:, :1]], dim=1)
+        a = self.atten(seq, mask=live)
+        y = torch.nn.functional.layer_norm(seq + a, (K,), self.ln1_gamma, self.ln1_beta, self.ln_epsilon)
+        f = self.ffn2(torch.relu(self.ffn1(y)))
+        z = torch.nn.functional.layer_norm(y + f, (K,), self.ln2_gamma, self.ln2_beta, self.ln_epsilon)
+        w = live.to(z.dtype).unsqueeze(-1)
+        mean = (z * w).sum(dim=1, keepdim=True) / w.sum(dim=1, keepdim=True)             # the candidate is live: never 0 / 0
+        return [mean, z[:, T:T + 1]]
+
+
+class BST(torch.nn.Module):
+    """Behaviour Sequence Transformer (extension; the paper's model on DINInput's features, one Transformer block).  Per behaviour:
+    the history followed by the candidate, [B,T+1,K] (the candidate's slot is always live), plus a trainable pos_embed [T+1,K];
+    a = SeqSelfAttentionLayer(att_heads, K // att_heads); y = LayerNorm(seq + a); z = LayerNorm(y + Dense(K)(relu(Dense(ffn_units or
+    4 K)(y)))) (epsilon 1e-3, gamma / beta); the behaviour's features are the mean of z over the live positions and z at the
+    candidate's position.  Then, as DIN / DIEN: StackLayer over dense + field embeddings + those features -> DnnLayer ->
+    MergeScoreLayer(use_merge=False)."""
+
+    def __init__(self, att_heads=2, ffn_units=None, hidden_units=None, seed=2020):
+        super().__init__()
+        if int(att_heads) < 1:
+            raise ValueError("BST: att_heads must be positive, got %r" % (att_heads,))
+        self.att_heads = int(att_heads)
+        self.ffn_units = ffn_units
+        self.seed = seed
+        self.behaviors = torch.nn.ModuleList()
+        self.stack = StackLayer()
+        self.dnn = DnnLayer(hidden_units=hidden_units or [200, 80])
+        self.score = MergeScoreLayer(use_merge=False)
+
+    def forward(self, inputFea):
+        keys, masks = inputFea.seq_embed_list
+        while len(self.behaviors) < len(keys):
+            self.behaviors.append(_BstBehavior(self.att_heads, self.ffn_units, seed=self.seed + 2 * len(self.behaviors)))
+        feats = []
+        for n, (cand, _) in enumerate(inputFea.seq_info):
+            feats.extend(self.behaviors[n]([inputFea.sparse_embed[cand], keys[n]], mask=masks[n]))
+        return self.score(self.dnn(self.stack(list(inputFea.dense_inputs) + list(inputFea.sparse_embed) + feats)))
 
 
 class CTRModel(torch.nn.Module):
