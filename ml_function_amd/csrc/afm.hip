@@ -18,9 +18,11 @@
 //             registers.  phase B: lane = (field, k): de[f,k] = sum over the partners j of (a_p g_k + (W du_p)_k) e_j[k] in ascending
 //             j -- no two lanes add into one de element.  phase C: lane = (k, pair group): dW[k,:] += x_p[k] du_p in registers.
 //             The parameter gradients stay in registers over all samples of a wave, are summed over the workgroup's waves in a fixed
-//             order and leave as ONE partial per workgroup; afm_param_reduce_kernel then adds the partials in a fixed order.
+//             order and leave as ONE partial per workgroup; param_reduce_kernel then adds the partials in a fixed order.
 // No atomics; every sum has a fixed order for a given B, so repeats are bit-identical.
 #include "common.h"
+#include "param_reduce.h"
+#include "tiled_launch.h"
 #include <algorithm>
 #include <math.h>
 
@@ -28,7 +30,6 @@ namespace fil {
 
 constexpr int kAfmMaxWaves = 4;        // waves (= samples in flight) per workgroup
 constexpr int kAfmGridCap = 512;       // workgroups per launch: two per CU
-constexpr int kAfmLdsLimit = 163328;   // the launchers' dynamic LDS limit (include/fil.h)
 constexpr int kAfmMaxF = 64, kAfmMaxK = 64, kAfmMaxA = 16;
 
 // LDS layout, all offsets in floats (multiples of 4: every region is read in 16-byte pieces).
@@ -76,25 +77,14 @@ static AfmLayout afm_layout(int F, int K, int A, int NW) {
 static AfmLayout afm_pick(int F, int K, int A) {
   for (int nw = kAfmMaxWaves; nw >= 1; --nw) {
     const AfmLayout L = afm_layout(F, K, A, nw);
-    if (L.lds_fwd <= kAfmLdsLimit && L.lds_bwd <= kAfmLdsLimit) return L;
+    if (L.lds_fwd <= kTiledLdsLimit && L.lds_bwd <= kTiledLdsLimit) return L;
   }
   AfmLayout L = afm_layout(F, K, A, 1);
   L.NW = 0;
   return L;
 }
 
-static inline int afm_grid(int B, int NW) { return B <= 0 ? 0 : std::min(cdiv(B, NW), kAfmGridCap); }
-
-__device__ __forceinline__ void afm_wave_sync() {
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_wave_barrier();
-}
-
-__device__ __forceinline__ float afm_wave_max(float v) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
-  return v;
-}
+static inline int afm_grid(int B, int NW) { return tiled_grid(B, NW, kAfmGridCap); }
 
 // W, b, h and the pair table -> LDS, once per workgroup (the caller synchronises)
 template <int AT>
@@ -192,7 +182,7 @@ __global__ __launch_bounds__(64 * kAfmMaxWaves) void afm_fwd_kernel(const float*
   const int kq = lane % KQ, pg = lane / KQ;
   for (long b = (long)blockIdx.x * L.NW + wave; b < B; b += (long)gridDim.x * L.NW) {
     afm_load_slab(eS, emb + b * L.F * K, L, lane);
-    afm_wave_sync();
+    wave_lds_sync();
     // pass 1: scores, their maximum, the exponentials and their sum
     float mx = -INFINITY;
     for (int p = lane; p < P; p += 64) {
@@ -203,7 +193,7 @@ __global__ __launch_bounds__(64 * kAfmMaxWaves) void afm_fwd_kernel(const float*
       scS[p] = s;
       mx = fmaxf(mx, s);
     }
-    mx = afm_wave_max(mx);
+    mx = wave_max(mx);
     float den = 0.f;
     for (int p = lane; p < P; p += 64) {
       const float w = expf(scS[p] - mx);
@@ -211,7 +201,7 @@ __global__ __launch_bounds__(64 * kAfmMaxWaves) void afm_fwd_kernel(const float*
       den += w;
     }
     den = wave_sum(den);
-    afm_wave_sync();
+    wave_lds_sync();
     // pass 2: sum_p w_p x_p, lane = (4 consecutive k, pair group)
     if (pg < NG) {
       float acc[4] = {0.f, 0.f, 0.f, 0.f};
@@ -229,7 +219,7 @@ __global__ __launch_bounds__(64 * kAfmMaxWaves) void afm_fwd_kernel(const float*
       }
       *reinterpret_cast<float4*>(redS + pg * K + kq * 4) = make_float4(acc[0], acc[1], acc[2], acc[3]);
     }
-    afm_wave_sync();
+    wave_lds_sync();
     if (lane < K) {
       float t = 0.f;
       for (int g = 0; g < NG; ++g) t += redS[g * K + lane];
@@ -239,7 +229,7 @@ __global__ __launch_bounds__(64 * kAfmMaxWaves) void afm_fwd_kernel(const float*
       stats[2 * b] = mx;
       stats[2 * b + 1] = den;
     }
-    afm_wave_sync();    // the next sample's slab overwrites this image
+    wave_lds_sync();    // the next sample's slab overwrites this image
   }
 }
 
@@ -276,7 +266,7 @@ __global__ __launch_bounds__(64 * kAfmMaxWaves) void afm_bwd_kernel(const float*
       pS[lane] = pooled[b * K + lane];
     }
     const float mx = stats[2 * b], den = stats[2 * b + 1];
-    afm_wave_sync();
+    wave_lds_sync();
     float gp = 0.f;     // g . pooled in the order of g . x_p: for one pair (F = 2) the two are the same bits and ds is exactly 0
     for (int k = 0; k < K; ++k) gp = fmaf(gS[k], pS[k], gp);
     // phase A: per pair, the score again, a_p, ds_p, du_p
@@ -309,7 +299,7 @@ __global__ __launch_bounds__(64 * kAfmMaxWaves) void afm_bwd_kernel(const float*
       for (int a = 0; a < AT; a += 4)
         *reinterpret_cast<float4*>(duS + p * AT + a) = make_float4(du[a], du[a + 1], du[a + 2], du[a + 3]);
     }
-    afm_wave_sync();
+    wave_lds_sync();
     // phase B: de[f,k] = sum over the partners j (ascending) of dx_p[k] e_j[k], dx_p = a_p g + W du_p
     if (demb != nullptr) {
       float* dst = demb + b * F * K;
@@ -361,7 +351,7 @@ __global__ __launch_bounds__(64 * kAfmMaxWaves) void afm_bwd_kernel(const float*
         }
       }
     }
-    afm_wave_sync();    // the next sample overwrites this image
+    wave_lds_sync();    // the next sample overwrites this image
   }
   if (!want_params) return;
   // the workgroup's partial: waves and pair groups in index order.  The sums overlay the waves' regions: every wave is done first.
@@ -394,31 +384,6 @@ __global__ __launch_bounds__(64 * kAfmMaxWaves) void afm_bwd_kernel(const float*
   }
 }
 
-// out[o] = sum over the partials in a fixed order: 16 slices of every 16th partial, then the slices in order.
-// out layout: dW [K A] | db [A] | dh [A], each to its own tensor.
-__global__ __launch_bounds__(256) void afm_param_reduce_kernel(const float* __restrict__ partials, int nparts, int n_out, int KA, int A,
-                                                               float* __restrict__ dW, float* __restrict__ db, float* __restrict__ dh) {
-  __shared__ float red[16][17];
-  const int ol = threadIdx.x & 15, sl = threadIdx.x >> 4;
-  const int o = blockIdx.x * 16 + ol;
-  float t = 0.f;
-  if (o < n_out)
-    for (int q = sl; q < nparts; q += 16) t += partials[(long)q * n_out + o];
-  red[sl][ol] = t;
-  __syncthreads();
-  if (sl == 0 && o < n_out) {
-    float s = 0.f;
-    for (int q = 0; q < 16; ++q) s += red[q][ol];
-    if (o < KA) {
-      if (dW != nullptr) dW[o] = s;
-    } else if (o < KA + A) {
-      if (db != nullptr) db[o - KA] = s;
-    } else {
-      if (dh != nullptr) dh[o - KA - A] = s;
-    }
-  }
-}
-
 // argument and menu checks shared by the four entry points
 static int afm_dims(const char* who, int B, int F, int K, int A, AfmLayout* L) {
   FIL_CHECK_ARG_W(who, B >= 0 && F >= 1 && K >= 1 && A >= 1);
@@ -428,20 +393,11 @@ static int afm_dims(const char* who, int B, int F, int K, int A, AfmLayout* L) {
   *L = afm_pick(F, K, A);
   if (L->NW == 0)
     return fail(FIL_ERR_UNSUPPORTED, "%s: F=%d K=%d A=%d needs %d bytes of LDS (limit %d)", who, F, K, A, std::max(L->lds_fwd, L->lds_bwd),
-                kAfmLdsLimit);
+                kTiledLdsLimit);
   return FIL_OK;
 }
 
 static size_t afm_partial_floats(int K, int A) { return (size_t)K * A + 2 * (size_t)A; }
-
-template <typename KernelT>
-static int afm_allow_lds(const char* who, KernelT kernel, int bytes) {
-  if (bytes > 48 * 1024) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-    if (e != hipSuccess) return fail(FIL_ERR_HIP, "%s: %d bytes of dynamic LDS refused: %s", who, bytes, hipGetErrorString(e));
-  }
-  return FIL_OK;
-}
 
 }  // namespace fil
 
@@ -451,15 +407,7 @@ extern "C" int fil_afm_plan(int B, int F, int K, int A, int* plan) {
   AfmLayout L;
   if (int rc = afm_dims(__func__, B, F, K, A, &L)) return rc;
   FIL_CHECK_ARG(plan != nullptr);
-  const int grid = afm_grid(B, L.NW);
-  plan[0] = 1;            // forward fits
-  plan[1] = 1;            // backward fits
-  plan[2] = L.NW;         // samples per workgroup tile
-  plan[3] = grid;
-  plan[4] = kAfmGridCap;
-  plan[5] = grid;         // parameter-gradient partials: one per workgroup
-  plan[6] = L.lds_fwd;
-  plan[7] = L.lds_bwd;
+  tiled_plan(plan, L.NW, afm_grid(B, L.NW), kAfmGridCap, L.lds_fwd, L.lds_bwd);
   return FIL_OK;
 }
 
@@ -474,10 +422,10 @@ extern "C" int fil_afm_fwd(const float* emb, const float* W, const float* b, con
   ProfScope ps("afm_fwd", st, 4.0 * ((double)B * ((double)F * K + K + 2) + (double)K * A + 2.0 * A));
   const dim3 grid(afm_grid(B, L.NW)), block(64 * L.NW);
   if (L.AT == 4) {
-    if (int rc = afm_allow_lds(__func__, afm_fwd_kernel<4>, L.lds_fwd)) return rc;
+    if (int rc = tiled_allow_lds(__func__, afm_fwd_kernel<4>, L.lds_fwd)) return rc;
     hipLaunchKernelGGL(afm_fwd_kernel<4>, grid, block, L.lds_fwd, st, emb, W, b, h, pooled, stats, B, flags, L);
   } else {
-    if (int rc = afm_allow_lds(__func__, afm_fwd_kernel<16>, L.lds_fwd)) return rc;
+    if (int rc = tiled_allow_lds(__func__, afm_fwd_kernel<16>, L.lds_fwd)) return rc;
     hipLaunchKernelGGL(afm_fwd_kernel<16>, grid, block, L.lds_fwd, st, emb, W, b, h, pooled, stats, B, flags, L);
   }
   FIL_CHECK_LAUNCH();
@@ -487,7 +435,7 @@ extern "C" int fil_afm_fwd(const float* emb, const float* W, const float* b, con
 extern "C" size_t fil_afm_bwd_workspace_bytes(int B, int F, int K, int A) {
   AfmLayout L;
   if (afm_dims(__func__, B, F, K, A, &L) != FIL_OK) return 0;
-  return align_up((size_t)afm_grid(B, L.NW) * afm_partial_floats(K, A) * sizeof(float), 256);
+  return tiled_partial_bytes(afm_grid(B, L.NW), afm_partial_floats(K, A));
 }
 
 extern "C" int fil_afm_bwd(const float* emb, const float* W, const float* b, const float* h, const float* pooled, const float* stats,
@@ -501,24 +449,24 @@ extern "C" int fil_afm_bwd(const float* emb, const float* W, const float* b, con
   const bool want_params = dW != nullptr || db != nullptr || dh != nullptr;
   FIL_CHECK_ARG(demb != nullptr || want_params);
   const int nparts = afm_grid(B, L.NW);
-  const size_t need = align_up((size_t)nparts * afm_partial_floats(K, A) * sizeof(float), 256);
-  if (want_params && (workspace == nullptr || workspace_bytes < need))
-    return fail(FIL_ERR_ARG, "fil_afm_bwd: workspace of %zu bytes, %zu needed (fil_afm_bwd_workspace_bytes)", workspace_bytes, need);
+  if (want_params)
+    if (int rc = tiled_check_workspace(__func__, workspace, workspace_bytes, nparts, afm_partial_floats(K, A))) return rc;
   hipStream_t st = (hipStream_t)stream;
   ProfScope ps("afm_bwd", st, 4.0 * ((double)B * (2.0 * F * K + 2.0 * K + 2) + 2.0 * ((double)K * A + 2.0 * A)));
   float* partials = want_params ? static_cast<float*>(workspace) : nullptr;
   const dim3 grid(nparts), block(64 * L.NW);
   if (L.AT == 4) {
-    if (int rc = afm_allow_lds(__func__, afm_bwd_kernel<4>, L.lds_bwd)) return rc;
+    if (int rc = tiled_allow_lds(__func__, afm_bwd_kernel<4>, L.lds_bwd)) return rc;
     hipLaunchKernelGGL(afm_bwd_kernel<4>, grid, block, L.lds_bwd, st, emb, W, b, h, pooled, stats, g, demb, partials, B, flags, L);
   } else {
-    if (int rc = afm_allow_lds(__func__, afm_bwd_kernel<16>, L.lds_bwd)) return rc;
+    if (int rc = tiled_allow_lds(__func__, afm_bwd_kernel<16>, L.lds_bwd)) return rc;
     hipLaunchKernelGGL(afm_bwd_kernel<16>, grid, block, L.lds_bwd, st, emb, W, b, h, pooled, stats, g, demb, partials, B, flags, L);
   }
   FIL_CHECK_LAUNCH();
   if (want_params) {
-    const int n_out = (int)afm_partial_floats(K, A);
-    hipLaunchKernelGGL(afm_param_reduce_kernel, dim3(cdiv(n_out, 16)), dim3(256), 0, st, partials, nparts, n_out, K * A, A, dW, db, dh);
+    float* const outs[3] = {dW, db, dh};
+    const int off[4] = {0, K * A, K * A + A, K * A + 2 * A};
+    param_reduce_launch(partials, nparts, outs, off, 3, st);
     FIL_CHECK_LAUNCH();
   }
   return FIL_OK;

@@ -26,9 +26,11 @@
 //             C  lane = slot: dx = du1 W1^T, 16 inputs at a time; dkeys row -> global, the dq terms -> LDS.
 //             P1 (barrier) every thread: its 4 x 16 tile(s) of dW1 += x^T du1; db1 by column.
 //             4K H1 + H1 H2 <= 16384 bounds the tiles at two per thread (128 accumulators).  One partial per workgroup;
-//             din_param_reduce_kernel adds the partials in a fixed order.
+//             param_reduce_kernel adds the partials in a fixed order.
 // No atomics; every sum has a fixed order for a given B, so repeats are bit-identical.
 #include "common.h"
+#include "param_reduce.h"
+#include "tiled_launch.h"
 #include <algorithm>
 #include <math.h>
 
@@ -36,7 +38,6 @@ namespace fil {
 
 constexpr int kDinMaxSamples = 4;      // samples in flight per workgroup
 constexpr int kDinGridCap = 512;       // workgroups per launch
-constexpr int kDinLdsLimit = 163328;   // the launchers' dynamic LDS limit (include/fil.h)
 constexpr int kDinMaxK = 64, kDinMaxT = 256, kDinMaxH1 = 128, kDinMaxH2 = 64, kDinMaxParams = 16384;
 constexpr int kDinCH = 8;              // layer-1 units per register chunk
 constexpr int kDinBwdThreads = 256;
@@ -109,25 +110,14 @@ static DinLayout din_layout(int T, int K, int H1, int H2, int NS) {
 static DinLayout din_pick(int T, int K, int H1, int H2) {
   for (int ns = kDinMaxSamples; ns >= 1; --ns) {
     const DinLayout L = din_layout(T, K, H1, H2, ns);
-    if (L.lds_fwd <= kDinLdsLimit && L.lds_bwd <= kDinLdsLimit) return L;
+    if (L.lds_fwd <= kTiledLdsLimit && L.lds_bwd <= kTiledLdsLimit) return L;
   }
   DinLayout L = din_layout(T, K, H1, H2, 1);
   L.NS = 0;
   return L;
 }
 
-static inline int din_grid(int B, int NS) { return B <= 0 ? 0 : std::min(cdiv(B, NS), kDinGridCap); }
-
-__device__ __forceinline__ void din_wave_sync() {
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_wave_barrier();
-}
-
-__device__ __forceinline__ float din_wave_max(float v) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
-  return v;
-}
+static inline int din_grid(int B, int NS) { return tiled_grid(B, NS, kDinGridCap); }
 
 // Sums v[i] over the 64 lanes for every i < N (N a power of two <= 64) by a butterfly that halves the values at each step: N - 1 +
 // (6 - log2 N) exchanges instead of 6 N.  The sum of element i = lane >> (6 - log2 N) is returned (the lanes that share i all hold
@@ -308,7 +298,7 @@ __global__ __launch_bounds__(64 * kDinMaxSamples) void din_fwd_kernel(const floa
     float mx = -INFINITY;
     for (int c0 = 0; c0 < T; c0 += 64) {
       din_load_keys(kS, keys_b, mask_b, L, c0, lane);
-      din_wave_sync();
+      wave_lds_sync();
       const int t = c0 + lane;
       float u2[H2T], h2[H2T];
       const float s = din_score<H2T, SIG, false>(S, L, qS, kS + lane * L.KP, nullptr, u2, h2);
@@ -318,11 +308,11 @@ __global__ __launch_bounds__(64 * kDinMaxSamples) void din_fwd_kernel(const floa
         stats[b * (T + 2) + t] = live ? s : 0.f;
         if (live) mx = fmaxf(mx, s);
       }
-      din_wave_sync();    // (the next 64 slots overwrite the key rows)
+      wave_lds_sync();    // (the next 64 slots overwrite the key rows)
     }
     float den = 1.f;
     if (softmax) {
-      mx = din_wave_max(mx);
+      mx = wave_max(mx);
       den = 0.f;
       for (int t = lane; t < T; t += 64) {
         const float sc = scS[t];
@@ -331,14 +321,14 @@ __global__ __launch_bounds__(64 * kDinMaxSamples) void din_fwd_kernel(const floa
         den += w;
       }
       den = wave_sum(den);
-      din_wave_sync();
+      wave_lds_sync();
     }
     // pass 2: sum_t w_t k_t, lane = (4 consecutive k, slot group)
     float acc[4] = {0.f, 0.f, 0.f, 0.f};
     for (int c0 = 0; c0 < T; c0 += 64) {
       if (T > 64) {       // (one trip: the rows of pass 1 are still there)
         din_load_keys(kS, keys_b, mask_b, L, c0, lane);
-        din_wave_sync();
+        wave_lds_sync();
       }
       const int cnt = min(64, T - c0);
       if (pg < NG) {
@@ -352,10 +342,10 @@ __global__ __launch_bounds__(64 * kDinMaxSamples) void din_fwd_kernel(const floa
           acc[3] = fmaf(w, kv.w, acc[3]);
         }
       }
-      din_wave_sync();
+      wave_lds_sync();
     }
     if (pg < NG) *reinterpret_cast<float4*>(partS + pg * K + kq * 4) = make_float4(acc[0], acc[1], acc[2], acc[3]);
-    din_wave_sync();
+    wave_lds_sync();
     if (lane < K) {
       float t = 0.f;
       for (int gq = 0; gq < NG; ++gq) t += partS[gq * K + lane];
@@ -365,7 +355,7 @@ __global__ __launch_bounds__(64 * kDinMaxSamples) void din_fwd_kernel(const floa
       stats[b * (T + 2) + T] = (softmax && den > 0.f) ? mx : 0.f;      // (raw mode, or no live slot: the backward does not use it)
       stats[b * (T + 2) + T + 1] = den;
     }
-    din_wave_sync();    // the next sample overwrites this image
+    wave_lds_sync();    // the next sample overwrites this image
   }
 }
 
@@ -504,7 +494,7 @@ __global__ __launch_bounds__(kDinBwdThreads) void din_bwd_kernel(const float* __
       }
       mx = stats[b * (T + 2) + T];
       den = stats[b * (T + 2) + T + 1];
-      din_wave_sync();
+      wave_lds_sync();
       if (softmax) {
         // g . out as sum_t a_t (g . k_t) over the very a_t and g . k_t that ds_t = a_t (g . k_t - g . out) is made of (a_t from the
         // saved scores): the sum of ds over a sample then cancels to rounding, and with one live slot (a = 1) g . out IS that
@@ -524,12 +514,12 @@ __global__ __launch_bounds__(kDinBwdThreads) void din_bwd_kernel(const float* __
         float part = 0.f;
         for (int c0 = 0; c0 < T; c0 += 64) {
           din_load_keys(kS, keys_b, mask_b, L, c0, lane);
-          din_wave_sync();
+          wave_lds_sync();
           const int t = c0 + lane;
           const bool live = t < T && (mask_b == nullptr || mask_b[t] != 0);
           const float a = live ? expf(stats[b * (T + 2) + t] - mx) / den : 0.f;
           part = fmaf(a, din_dot(gS, kS + lane * L.KP, KQ) - gc, part);
-          din_wave_sync();
+          wave_lds_sync();
         }
         gp = wave_sum(part);
       }
@@ -544,7 +534,7 @@ __global__ __launch_bounds__(kDinBwdThreads) void din_bwd_kernel(const float* __
       if (have) {
         // phase A
         din_load_keys(kS, keys_b, mask_b, L, c0, lane);
-        din_wave_sync();
+        wave_lds_sync();
         live = t < T && (mask_b == nullptr || mask_b[t] != 0);
         float u2[H2T], h2[H2T];
         const float s = din_score<H2T, SIG, true>(S, L, qS, krow, u1row, u2, h2);
@@ -646,7 +636,7 @@ __global__ __launch_bounds__(kDinBwdThreads) void din_bwd_kernel(const float* __
             }
           }
         }
-        din_wave_sync();
+        wave_lds_sync();
         // phase C: dx = du1 W1^T, the 16 inputs of a k quad at a time; dkeys row, dq terms
         for (int kq = 0; kq < KQ; ++kq) {
           float dx[16];
@@ -701,13 +691,13 @@ __global__ __launch_bounds__(kDinBwdThreads) void din_bwd_kernel(const float* __
           }
         __syncthreads();    // the next 64 slots overwrite the staged rows
       } else if (have) {
-        din_wave_sync();
+        wave_lds_sync();
       }
     }
     if (have && dq != nullptr) {
-      din_wave_sync();
+      wave_lds_sync();
       if (lane < K) dq[b * K + lane] = dqS[lane];
-      din_wave_sync();
+      wave_lds_sync();
     }
   }
   if (!want_params) return;
@@ -745,31 +735,6 @@ __global__ __launch_bounds__(kDinBwdThreads) void din_bwd_kernel(const float* __
   }
 }
 
-struct DinGradPtrs {
-  float* p[8];      // dW1, db1, dalpha1, dW2, db2, dalpha2, dw3, db3
-  int off[9];       // their offsets in a partial; off[8] = n_out
-};
-
-// out[o] = sum over the partials in a fixed order: 16 slices of every 16th partial, then the slices in order
-__global__ __launch_bounds__(256) void din_param_reduce_kernel(const float* __restrict__ partials, int nparts, DinGradPtrs G) {
-  __shared__ float red[16][17];
-  const int ol = threadIdx.x & 15, sl = threadIdx.x >> 4;
-  const int n_out = G.off[8];
-  const int o = blockIdx.x * 16 + ol;
-  float t = 0.f;
-  if (o < n_out)
-    for (int pq = sl; pq < nparts; pq += 16) t += partials[(long)pq * n_out + o];
-  red[sl][ol] = t;
-  __syncthreads();
-  if (sl == 0 && o < n_out) {
-    float s = 0.f;
-    for (int pq = 0; pq < 16; ++pq) s += red[pq][ol];
-    int w = 0;
-    while (o >= G.off[w + 1]) ++w;
-    if (G.p[w] != nullptr) G.p[w][o - G.off[w]] = s;
-  }
-}
-
 // argument and menu checks shared by the four entry points
 static int din_dims(const char* who, int B, int T, int K, int H1, int H2, DinLayout* L) {
   FIL_CHECK_ARG_W(who, B >= 0 && T >= 1 && K >= 1 && H1 >= 1 && H2 >= 1);
@@ -782,16 +747,7 @@ static int din_dims(const char* who, int B, int T, int K, int H1, int H2, DinLay
   *L = din_pick(T, K, H1, H2);
   if (L->NS == 0)
     return fail(FIL_ERR_UNSUPPORTED, "%s: T=%d K=%d H1=%d H2=%d needs %d bytes of LDS (limit %d)", who, T, K, H1, H2,
-                std::max(L->lds_fwd, L->lds_bwd), kDinLdsLimit);
-  return FIL_OK;
-}
-
-template <typename KernelT>
-static int din_allow_lds(const char* who, KernelT kernel, int bytes) {
-  if (bytes > 48 * 1024) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-    if (e != hipSuccess) return fail(FIL_ERR_HIP, "%s: %d bytes of dynamic LDS refused: %s", who, bytes, hipGetErrorString(e));
-  }
+                std::max(L->lds_fwd, L->lds_bwd), kTiledLdsLimit);
   return FIL_OK;
 }
 
@@ -804,7 +760,7 @@ struct DinFwdArgs {
 
 template <int H2T, bool SIG>
 static int din_launch_fwd(const char* who, const DinFwdArgs& a, int B, int flags, const DinLayout& L, hipStream_t st) {
-  if (int rc = din_allow_lds(who, din_fwd_kernel<H2T, SIG>, L.lds_fwd)) return rc;
+  if (int rc = tiled_allow_lds(who, din_fwd_kernel<H2T, SIG>, L.lds_fwd)) return rc;
   hipLaunchKernelGGL((din_fwd_kernel<H2T, SIG>), dim3(din_grid(B, L.NS)), dim3(64 * L.NS), L.lds_fwd, st, a.q, a.keys, a.mask, a.W1, a.b1,
                      a.al1, a.W2, a.b2, a.al2, a.w3, a.b3, a.out, a.stats, B, flags, L);
   return FIL_OK;
@@ -819,7 +775,7 @@ struct DinBwdArgs {
 
 template <int H2T, bool SIG, int NT>
 static int din_launch_bwd_nt(const char* who, const DinBwdArgs& a, int B, int flags, const DinLayout& L, hipStream_t st) {
-  if (int rc = din_allow_lds(who, din_bwd_kernel<H2T, SIG, NT>, L.lds_bwd)) return rc;
+  if (int rc = tiled_allow_lds(who, din_bwd_kernel<H2T, SIG, NT>, L.lds_bwd)) return rc;
   hipLaunchKernelGGL((din_bwd_kernel<H2T, SIG, NT>), dim3(din_grid(B, L.NS)), dim3(kDinBwdThreads), L.lds_bwd, st, a.q, a.keys, a.mask, a.W1,
                      a.b1, a.al1, a.W2, a.b2, a.al2, a.w3, a.b3, a.out, a.stats, a.g, a.dq, a.dkeys, a.partials, B, flags, L);
   return FIL_OK;
@@ -849,15 +805,7 @@ extern "C" int fil_din_plan(int B, int T, int K, int H1, int H2, int* plan) {
   DinLayout L;
   if (int rc = din_dims(__func__, B, T, K, H1, H2, &L)) return rc;
   FIL_CHECK_ARG(plan != nullptr);
-  const int grid = din_grid(B, L.NS);
-  plan[0] = 1;            // forward fits
-  plan[1] = 1;            // backward fits
-  plan[2] = L.NS;         // samples per workgroup tile
-  plan[3] = grid;
-  plan[4] = kDinGridCap;
-  plan[5] = grid;         // parameter-gradient partials: one per workgroup
-  plan[6] = L.lds_fwd;
-  plan[7] = L.lds_bwd;
+  tiled_plan(plan, L.NS, din_grid(B, L.NS), kDinGridCap, L.lds_fwd, L.lds_bwd);
   return FIL_OK;
 }
 
@@ -883,7 +831,7 @@ extern "C" int fil_din_fwd(const float* q, const float* keys, const unsigned cha
 extern "C" size_t fil_din_bwd_workspace_bytes(int B, int T, int K, int H1, int H2) {
   DinLayout L;
   if (din_dims(__func__, B, T, K, H1, H2, &L) != FIL_OK) return 0;
-  return align_up((size_t)din_grid(B, L.NS) * (size_t)L.n_out * sizeof(float), 256);
+  return tiled_partial_bytes(din_grid(B, L.NS), L.n_out);
 }
 
 extern "C" int fil_din_bwd(const float* q, const float* keys, const unsigned char* mask, const float* W1, const float* b1,
@@ -903,9 +851,8 @@ extern "C" int fil_din_bwd(const float* q, const float* keys, const unsigned cha
                            dalpha2 != nullptr || dw3 != nullptr || db3 != nullptr;
   FIL_CHECK_ARG(dq != nullptr || dkeys != nullptr || want_params);
   const int nparts = din_grid(B, L.NS);
-  const size_t need = align_up((size_t)nparts * (size_t)L.n_out * sizeof(float), 256);
-  if (want_params && (workspace == nullptr || workspace_bytes < need))
-    return fail(FIL_ERR_ARG, "fil_din_bwd: workspace of %zu bytes, %zu needed (fil_din_bwd_workspace_bytes)", workspace_bytes, need);
+  if (want_params)
+    if (int rc = tiled_check_workspace(__func__, workspace, workspace_bytes, nparts, L.n_out)) return rc;
   hipStream_t st = (hipStream_t)stream;
   ProfScope ps("din_bwd", st, 4.0 * ((double)B * (2.0 * T * K + 4.0 * K + 2) + 2.0 * (4.0 * K * H1 + (double)H1 * H2)));
   const DinBwdArgs a = {q, keys, mask, W1, b1, alpha1, W2, b2, alpha2, w3, b3, out, stats, g, dq, dkeys,
@@ -913,12 +860,9 @@ extern "C" int fil_din_bwd(const float* q, const float* keys, const unsigned cha
   if (int rc = DIN_DISPATCH(din_launch_bwd, __func__, a, B, flags, L, st)) return rc;
   FIL_CHECK_LAUNCH();
   if (want_params) {
-    DinGradPtrs G;
-    float* ptrs[8] = {dW1, db1, dalpha1, dW2, db2, dalpha2, dw3, db3};
-    const int offs[9] = {0, L.p_b1, L.p_al1, L.p_W2, L.p_b2, L.p_al2, L.p_w3, L.p_b3, L.n_out};
-    for (int i = 0; i < 8; ++i) G.p[i] = ptrs[i];
-    for (int i = 0; i < 9; ++i) G.off[i] = offs[i];
-    hipLaunchKernelGGL(din_param_reduce_kernel, dim3(cdiv(L.n_out, 16)), dim3(256), 0, st, static_cast<const float*>(workspace), nparts, G);
+    float* const outs[8] = {dW1, db1, dalpha1, dW2, db2, dalpha2, dw3, db3};
+    const int off[9] = {0, L.p_b1, L.p_al1, L.p_W2, L.p_b2, L.p_al2, L.p_w3, L.p_b3, L.n_out};
+    param_reduce_launch(static_cast<const float*>(workspace), nparts, outs, off, 8, st);
     FIL_CHECK_LAUNCH();
   }
   return FIL_OK;

@@ -20,10 +20,11 @@
 //                da[b,t] = the units' terms added in unit order;
 //                dW / dU: the thread's three columns (the gates of its unit) of the rows g, g + G, ... of [x_t ; h_prev]^T [d_xp | d_hp],
 //                summed over the tile's samples in sample order, in registers over all steps and tiles (NR x 3 accumulators, NR <= 32). (barrier)
-//             One partial per workgroup; gru_param_reduce_kernel adds the partials in a fixed order.
+//             One partial per workgroup; param_reduce_kernel adds the partials in a fixed order.
 // No atomics; every sum has a fixed order for a given shape: repeats are bit-identical.
 #include "common.h"
 #include "param_reduce.h"
+#include "tiled_launch.h"
 #include <algorithm>
 #include <math.h>
 
@@ -31,7 +32,6 @@ namespace fil {
 
 constexpr int kGruMaxK = 64, kGruMaxH = 64;
 constexpr int kGruGridCap = 1024;      // workgroups per launch
-constexpr int kGruLdsLimit = 163328;   // the launchers' dynamic LDS limit (include/fil.h)
 constexpr int kGruThreads = 256;       // the most a workgroup has
 constexpr int kGruXV = 4;              // 16-byte pieces of x_t a thread stages per step, at most
 
@@ -77,7 +77,7 @@ static GruLayout gru_layout(int B, int T, int K, int H) {
   return L;
 }
 
-static inline int gru_grid(int B, int NS) { return B <= 0 ? 0 : std::min(cdiv(B, NS), kGruGridCap); }
+static inline int gru_grid(int B, int NS) { return tiled_grid(B, NS, kGruGridCap); }
 
 __device__ __forceinline__ float gru_sigmoid(float v) { return 1.f / (1.f + expf(-v)); }
 
@@ -459,38 +459,6 @@ __global__ __launch_bounds__(kGruThreads) void gru_bwd_kernel(const float* __res
   }
 }
 
-struct GruGradPtrs {
-  float* p[3];      // dW, dU, db
-  int off[4];       // their offsets in a partial; off[3] = n_out
-};
-
-// out[o] = sum over the partials in a fixed order: 16 slices of every 16th partial, then the slices in order
-__global__ __launch_bounds__(256) void gru_param_reduce_kernel(const float* __restrict__ partials, int nparts, GruGradPtrs Gp) {
-  __shared__ float red[16][17];
-  const int ol = threadIdx.x & 15, sl = threadIdx.x >> 4;
-  const int n_out = Gp.off[3];
-  const int o = blockIdx.x * 16 + ol;
-  float t = 0.f;
-  if (o < n_out)
-    for (int pq = sl; pq < nparts; pq += 16) t += partials[(long)pq * n_out + o];
-  red[sl][ol] = t;
-  __syncthreads();
-  if (sl == 0 && o < n_out) {
-    float s = 0.f;
-    for (int pq = 0; pq < 16; ++pq) s += red[pq][ol];
-    int w = 0;
-    while (o >= Gp.off[w + 1]) ++w;
-    if (Gp.p[w] != nullptr) Gp.p[w][o - Gp.off[w]] = s;
-  }
-}
-
-void param_reduce_launch(const float* partials, int nparts, float* const outs[3], const int off[4], hipStream_t st) {
-  GruGradPtrs Gp;
-  for (int w = 0; w < 3; ++w) Gp.p[w] = outs[w];
-  for (int w = 0; w < 4; ++w) Gp.off[w] = off[w];
-  hipLaunchKernelGGL(gru_param_reduce_kernel, dim3(cdiv(off[3], 16)), dim3(256), 0, st, partials, nparts, Gp);
-}
-
 // argument and menu checks shared by the entry points
 static int gru_dims(const char* who, int B, int T, int K, int H, int mode, GruLayout* L) {
   FIL_CHECK_ARG_W(who, B >= 0 && T >= 1 && K >= 1 && H >= 1);
@@ -498,17 +466,8 @@ static int gru_dims(const char* who, int B, int T, int K, int H, int mode, GruLa
   if (K % 4 != 0 || K > kGruMaxK) return fail(FIL_ERR_UNSUPPORTED, "%s: K=%d needs K %% 4 == 0 and K <= %d", who, K, kGruMaxK);
   if (H % 4 != 0 || H > kGruMaxH) return fail(FIL_ERR_UNSUPPORTED, "%s: H=%d needs H %% 4 == 0 and H <= %d", who, H, kGruMaxH);
   *L = gru_layout(B, T, K, H);
-  if (L->lds_fwd > kGruLdsLimit || L->lds_bwd > kGruLdsLimit)
-    return fail(FIL_ERR_UNSUPPORTED, "%s: K=%d H=%d needs %d bytes of LDS (limit %d)", who, K, H, std::max(L->lds_fwd, L->lds_bwd), kGruLdsLimit);
-  return FIL_OK;
-}
-
-template <typename KernelT>
-static int gru_allow_lds(const char* who, KernelT kernel, int bytes) {
-  if (bytes > 48 * 1024) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-    if (e != hipSuccess) return fail(FIL_ERR_HIP, "%s: %d bytes of dynamic LDS refused: %s", who, bytes, hipGetErrorString(e));
-  }
+  if (L->lds_fwd > kTiledLdsLimit || L->lds_bwd > kTiledLdsLimit)
+    return fail(FIL_ERR_UNSUPPORTED, "%s: K=%d H=%d needs %d bytes of LDS (limit %d)", who, K, H, std::max(L->lds_fwd, L->lds_bwd), kTiledLdsLimit);
   return FIL_OK;
 }
 
@@ -521,7 +480,7 @@ struct GruBwdArgs {
 
 template <int NR>
 static int gru_launch_bwd(const char* who, const GruBwdArgs& p, int B, int mode, const GruLayout& L, hipStream_t st) {
-  if (int rc = gru_allow_lds(who, gru_bwd_kernel<NR>, L.lds_bwd)) return rc;
+  if (int rc = tiled_allow_lds(who, gru_bwd_kernel<NR>, L.lds_bwd)) return rc;
   hipLaunchKernelGGL((gru_bwd_kernel<NR>), dim3(gru_grid(B, L.NS)), dim3(L.threads), L.lds_bwd, st, p.x, p.a, p.mask, p.W, p.U, p.hs, p.saved,
                      p.g_hs, p.g_last, p.dx, p.da, p.partials, B, mode, L);
   return FIL_OK;
@@ -535,15 +494,7 @@ extern "C" int fil_gru_plan(int B, int T, int K, int H, int mode, int* plan) {
   GruLayout L;
   if (int rc = gru_dims(__func__, B, T, K, H, mode, &L)) return rc;
   FIL_CHECK_ARG(plan != nullptr);
-  const int grid = gru_grid(B, L.NS);
-  plan[0] = 1;            // forward fits
-  plan[1] = 1;            // backward fits
-  plan[2] = L.NS;         // samples per workgroup tile
-  plan[3] = grid;
-  plan[4] = kGruGridCap;
-  plan[5] = grid;         // parameter-gradient partials: one per workgroup
-  plan[6] = L.lds_fwd;
-  plan[7] = L.lds_bwd;
+  tiled_plan(plan, L.NS, gru_grid(B, L.NS), kGruGridCap, L.lds_fwd, L.lds_bwd);
   return FIL_OK;
 }
 
@@ -562,7 +513,7 @@ extern "C" int fil_gru_fwd(const float* x, const float* a, const unsigned char* 
   FIL_CHECK_ARG((mode == FIL_GRU_GRU) == (a == nullptr));
   hipStream_t st = (hipStream_t)stream;
   ProfScope ps("gru_fwd", st, 4.0 * (double)B * T * (K + H + (saved != nullptr ? 4.0 * H : 0.0)));
-  if (int rc = gru_allow_lds(__func__, gru_fwd_kernel, L.lds_fwd)) return rc;
+  if (int rc = tiled_allow_lds(__func__, gru_fwd_kernel, L.lds_fwd)) return rc;
   hipLaunchKernelGGL(gru_fwd_kernel, dim3(gru_grid(B, L.NS)), dim3(L.threads), L.lds_fwd, st, x, a, mask, W, U, b, hs, saved, B, mode, L);
   FIL_CHECK_LAUNCH();
   return FIL_OK;
@@ -571,7 +522,7 @@ extern "C" int fil_gru_fwd(const float* x, const float* a, const unsigned char* 
 extern "C" size_t fil_gru_bwd_workspace_bytes(int B, int T, int K, int H) {
   GruLayout L;
   if (gru_dims(__func__, B, T, K, H, FIL_GRU_GRU, &L) != FIL_OK) return 0;
-  return align_up((size_t)gru_grid(B, L.NS) * (size_t)L.n_out * sizeof(float), 256);
+  return tiled_partial_bytes(gru_grid(B, L.NS), L.n_out);
 }
 
 extern "C" int fil_gru_bwd(const float* x, const float* a, const unsigned char* mask, const float* W, const float* U, const float* hs,
@@ -587,9 +538,8 @@ extern "C" int fil_gru_bwd(const float* x, const float* a, const unsigned char* 
   const bool want_params = dW != nullptr || dU != nullptr || db != nullptr;
   FIL_CHECK_ARG(dx != nullptr || da != nullptr || want_params);
   const int nparts = gru_grid(B, L.NS);
-  const size_t need = align_up((size_t)nparts * (size_t)L.n_out * sizeof(float), 256);
-  if (want_params && (workspace == nullptr || workspace_bytes < need))
-    return fail(FIL_ERR_ARG, "fil_gru_bwd: workspace of %zu bytes, %zu needed (fil_gru_bwd_workspace_bytes)", workspace_bytes, need);
+  if (want_params)
+    if (int rc = tiled_check_workspace(__func__, workspace, workspace_bytes, nparts, L.n_out)) return rc;
   hipStream_t st = (hipStream_t)stream;
   ProfScope ps("gru_bwd", st, 4.0 * (double)B * T * (2.0 * K + 6.0 * H));
   const GruBwdArgs p = {x, a, mask, W, U, hs, saved, g_hs, g_last, dx, da, want_params ? static_cast<float*>(workspace) : nullptr};
@@ -600,7 +550,7 @@ extern "C" int fil_gru_bwd(const float* x, const float* a, const unsigned char* 
   if (want_params) {
     float* const outs[3] = {dW, dU, db};
     const int off[4] = {0, K * L.H3, (K + H) * L.H3, L.n_out};
-    param_reduce_launch(static_cast<const float*>(workspace), nparts, outs, off, st);
+    param_reduce_launch(static_cast<const float*>(workspace), nparts, outs, off, 3, st);
     FIL_CHECK_LAUNCH();
   }
   return FIL_OK;

@@ -21,11 +21,12 @@
 //                from the rows' statistics; they replace k_j, v_j in LDS (only their owner reads those).
 //             4  dx = dq Wq^T + dk Wk^T + dv Wv^T, a thread per (position, feature).
 //             5  the tile's x^T [dq | dk | dv], position order, added to the workgroup's partial in `workspace`.
-//             One partial per workgroup; gru_param_reduce_kernel's launch adds the partials in a fixed order.
+//             One partial per workgroup; param_reduce_kernel adds the partials in a fixed order.
 // No atomics; every sum has a fixed order that does not depend on the tile or the batch for out / dx: repeats are bit-identical
 // and a sample's out / dx rows do not depend on what else is in the batch.
 #include "common.h"
 #include "param_reduce.h"
+#include "tiled_launch.h"
 #include <algorithm>
 #include <math.h>
 
@@ -33,7 +34,6 @@ namespace fil {
 
 constexpr int kSaMaxK = 64, kSaMaxH = 8, kSaMaxHD = 64, kSaMaxT = 256;
 constexpr int kSaGridCap = 1024;      // workgroups per launch
-constexpr int kSaLdsLimit = 163328;   // the launchers' dynamic LDS limit (include/fil.h)
 constexpr int kSaThreads = 256;
 constexpr int kSaMaxNS = 256;         // samples per tile, at most
 constexpr int kSaStat = 5;            // floats per (sample, head, row) in the backward: max, 1/sum, abar, g.v_top, top
@@ -52,7 +52,7 @@ static inline int sa_bwd_floats(int T, int K, int H, int HD) { return T * ((K + 
 static inline int up4(int v) { return (v + 3) / 4 * 4; }
 
 // samples per tile the LDS limit leaves room for (0: the shape does not fit)
-static inline int sa_room(int per_sample_floats) { return (kSaLdsLimit / 4 - 8) / per_sample_floats; }
+static inline int sa_room(int per_sample_floats) { return (kTiledLdsLimit / 4 - 8) / per_sample_floats; }
 
 static SaLayout sa_layout(int B, int T, int K, int H, int D, int use_scale) {
   SaLayout L;
@@ -81,7 +81,7 @@ static SaLayout sa_layout(int B, int T, int K, int H, int D, int use_scale) {
   return L;
 }
 
-static inline int sa_grid(int B, int NS) { return B <= 0 ? 0 : std::min(cdiv(B, NS), kSaGridCap); }
+static inline int sa_grid(int B, int NS) { return tiled_grid(B, NS, kSaGridCap); }
 
 // q . k over the head's D = 4 DQ columns, one fmaf chain in column order (a in registers, b in LDS)
 template <int DQM>
@@ -428,25 +428,16 @@ static int sa_dims(const char* who, int B, int T, int K, int H, int D, int use_s
   if ((long)H * D > kSaMaxHD) return fail(FIL_ERR_UNSUPPORTED, "%s: H*D=%ld needs H*D <= %d", who, (long)H * D, kSaMaxHD);
   if (T > kSaMaxT) return fail(FIL_ERR_UNSUPPORTED, "%s: T=%d needs T <= %d", who, T, kSaMaxT);
   const int fb = 4 * (sa_fwd_floats(T, K, H * D) + 8), bb = 4 * (sa_bwd_floats(T, K, H, H * D) + 8);
-  if (fb > kSaLdsLimit || bb > kSaLdsLimit)
-    return fail(FIL_ERR_UNSUPPORTED, "%s: T=%d K=%d H=%d D=%d needs %d bytes of LDS (limit %d)", who, T, K, H, D, std::max(fb, bb), kSaLdsLimit);
+  if (fb > kTiledLdsLimit || bb > kTiledLdsLimit)
+    return fail(FIL_ERR_UNSUPPORTED, "%s: T=%d K=%d H=%d D=%d needs %d bytes of LDS (limit %d)", who, T, K, H, D, std::max(fb, bb), kTiledLdsLimit);
   *L = sa_layout(B, T, K, H, D, use_scale);
-  return FIL_OK;
-}
-
-template <typename KernelT>
-static int sa_allow_lds(const char* who, KernelT kernel, int bytes) {
-  if (bytes > 48 * 1024) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-    if (e != hipSuccess) return fail(FIL_ERR_HIP, "%s: %d bytes of dynamic LDS refused: %s", who, bytes, hipGetErrorString(e));
-  }
   return FIL_OK;
 }
 
 template <int DQM>
 static int sa_launch_fwd(const char* who, const float* x, const unsigned char* mask, const float* Wq, const float* Wk, const float* Wv,
                          float* out, float* saved, int B, const SaLayout& L, hipStream_t st) {
-  if (int rc = sa_allow_lds(who, seqattn_fwd_kernel<DQM>, L.lds_fwd)) return rc;
+  if (int rc = tiled_allow_lds(who, seqattn_fwd_kernel<DQM>, L.lds_fwd)) return rc;
   hipLaunchKernelGGL((seqattn_fwd_kernel<DQM>), dim3(sa_grid(B, L.NS)), dim3(kSaThreads), L.lds_fwd, st, x, mask, Wq, Wk, Wv, out, saved, B, L);
   return FIL_OK;
 }
@@ -454,7 +445,7 @@ static int sa_launch_fwd(const char* who, const float* x, const unsigned char* m
 template <int DQM>
 static int sa_launch_bwd(const char* who, const float* x, const unsigned char* mask, const float* Wq, const float* Wk, const float* Wv,
                          const float* saved, const float* g, float* dx, float* partials, int B, const SaLayout& L, hipStream_t st) {
-  if (int rc = sa_allow_lds(who, seqattn_bwd_kernel<DQM>, L.lds_bwd)) return rc;
+  if (int rc = tiled_allow_lds(who, seqattn_bwd_kernel<DQM>, L.lds_bwd)) return rc;
   hipLaunchKernelGGL((seqattn_bwd_kernel<DQM>), dim3(sa_grid(B, L.NS)), dim3(kSaThreads), L.lds_bwd, st, x, mask, Wq, Wk, Wv, saved, g, dx,
                      partials, B, L);
   return FIL_OK;
@@ -468,15 +459,7 @@ extern "C" int fil_seqattn_plan(int B, int T, int K, int H, int D, int* plan) {
   SaLayout L;
   if (int rc = sa_dims(__func__, B, T, K, H, D, 1, &L)) return rc;
   FIL_CHECK_ARG(plan != nullptr);
-  const int grid = sa_grid(B, L.NS);
-  plan[0] = 1;            // forward fits
-  plan[1] = 1;            // backward fits
-  plan[2] = L.NS;         // samples per workgroup tile
-  plan[3] = grid;
-  plan[4] = kSaGridCap;
-  plan[5] = grid;         // parameter-gradient partials: one per workgroup
-  plan[6] = L.lds_fwd;
-  plan[7] = L.lds_bwd;
+  tiled_plan(plan, L.NS, sa_grid(B, L.NS), kSaGridCap, L.lds_fwd, L.lds_bwd);
   return FIL_OK;
 }
 
@@ -507,7 +490,7 @@ extern "C" int fil_seqattn_fwd(const float* x, const unsigned char* mask, const 
 extern "C" size_t fil_seqattn_bwd_workspace_bytes(int B, int T, int K, int H, int D) {
   SaLayout L;
   if (sa_dims(__func__, B, T, K, H, D, 1, &L) != FIL_OK) return 0;
-  return align_up((size_t)sa_grid(B, L.NS) * (size_t)L.n_out * sizeof(float), 256);
+  return tiled_partial_bytes(sa_grid(B, L.NS), L.n_out);
 }
 
 extern "C" int fil_seqattn_bwd(const float* x, const unsigned char* mask, const float* Wq, const float* Wk, const float* Wv,
@@ -520,9 +503,8 @@ extern "C" int fil_seqattn_bwd(const float* x, const unsigned char* mask, const 
   const bool want_params = dWq != nullptr || dWk != nullptr || dWv != nullptr;
   FIL_CHECK_ARG(dx != nullptr || want_params);
   const int nparts = sa_grid(B, L.NS);
-  const size_t need = align_up((size_t)nparts * (size_t)L.n_out * sizeof(float), 256);
-  if (want_params && (workspace == nullptr || workspace_bytes < need))
-    return fail(FIL_ERR_ARG, "fil_seqattn_bwd: workspace of %zu bytes, %zu needed (fil_seqattn_bwd_workspace_bytes)", workspace_bytes, need);
+  if (want_params)
+    if (int rc = tiled_check_workspace(__func__, workspace, workspace_bytes, nparts, L.n_out)) return rc;
   hipStream_t st = (hipStream_t)stream;
   ProfScope ps("seqattn_bwd", st, 4.0 * (double)B * T * (2.0 * K + 4.0 * L.HD));
   float* partials = want_params ? static_cast<float*>(workspace) : nullptr;
@@ -536,7 +518,7 @@ extern "C" int fil_seqattn_bwd(const float* x, const unsigned char* mask, const 
   if (want_params) {
     const int off[4] = {0, K * L.HD, 2 * K * L.HD, L.n_out};
     float* outs[3] = {dWq, dWk, dWv};
-    param_reduce_launch(partials, nparts, outs, off, st);
+    param_reduce_launch(partials, nparts, outs, off, 3, st);
     FIL_CHECK_LAUNCH();
   }
   return FIL_OK;

@@ -148,6 +148,26 @@ def fm_pairs(emb):
     return _FmPairsFn.apply(emb)
 
 
+def _tiled_plan(name, *dims):
+    """The answer of the fil_*_plan entry point `name` for `dims`, as the dict of afm_plan / din_plan / gru_plan / seq_attn_plan."""
+    plan = (ctypes.c_int * 8)()
+    rc = getattr(_lib.load(), name)(*dims, plan)
+    if rc == _lib.FIL_ERR_UNSUPPORTED:
+        return dict(fits=False)
+    check(rc, name)
+    return dict(fits=bool(plan[0]) and bool(plan[1]), tile=plan[2], grid=plan[3], cap=plan[4], partials=plan[5], lds_fwd=plan[6],
+                lds_bwd=plan[7])
+
+
+def _seq_mask(who, mask, B, T):
+    """The [B,T] bool / uint8 mask of a behaviour-sequence op as the contiguous uint8 tensor the kernels read (None stays None)."""
+    if mask is None:
+        return None
+    if tuple(mask.shape) != (B, T) or mask.dtype not in (torch.bool, torch.uint8):
+        raise FilError("%s: mask must be a [B,T] bool or uint8 tensor, got %s %s" % (who, tuple(mask.shape), mask.dtype))
+    return (mask.to(torch.uint8) if mask.dtype == torch.bool else mask).contiguous()
+
+
 class _AfmPoolFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, emb, w, b, h, hidden_relu):
@@ -203,13 +223,7 @@ def afm_pool(emb, w, b, h, hidden_relu=False):
 def afm_plan(B, F, K, A):
     """fil_afm_plan's answer as a dict (fits, tile, grid, cap, partials, lds_fwd, lds_bwd); fits=False (and nothing else) for a shape
     outside the kernel menu."""
-    plan = (ctypes.c_int * 8)()
-    rc = _lib.load().fil_afm_plan(int(B), int(F), int(K), int(A), plan)
-    if rc == _lib.FIL_ERR_UNSUPPORTED:
-        return dict(fits=False)
-    check(rc, "fil_afm_plan")
-    return dict(fits=bool(plan[0]) and bool(plan[1]), tile=plan[2], grid=plan[3], cap=plan[4], partials=plan[5], lds_fwd=plan[6],
-                lds_bwd=plan[7])
+    return _tiled_plan("fil_afm_plan", int(B), int(F), int(K), int(A))
 
 
 DIN_ACTIVATIONS = ("prelu", "sigmoid")
@@ -239,10 +253,7 @@ class _DinAttentionFn(torch.autograd.Function):
                     raise FilError("din_attention: %s is None (only alpha1 / alpha2 may be, with the sigmoid)" % name)
             elif t.numel() != n:
                 raise FilError("din_attention: %s must hold %d values, got %s" % (name, n, tuple(t.shape)))
-        if mask is not None:
-            if tuple(mask.shape) != (B, T) or mask.dtype not in (torch.bool, torch.uint8):
-                raise FilError("din_attention: mask must be a [B,T] bool or uint8 tensor, got %s %s" % (tuple(mask.shape), mask.dtype))
-            mask = (mask.to(torch.uint8) if mask.dtype == torch.bool else mask).contiguous()
+        mask = _seq_mask("din_attention", mask, B, T)
         out = torch.empty((B, K), dtype=torch.float32, device=q.device)
         stats = torch.empty((B, T + 2), dtype=torch.float32, device=q.device)
         check(_lib.load().fil_din_fwd(ptr(q), ptr(keys), ptr(mask), ptr(w1), ptr(b1), ptr(alpha1), ptr(w2), ptr(b2), ptr(alpha2), ptr(w3),
@@ -310,13 +321,7 @@ def din_attention(q, keys, mask, W1, b1, alpha1, W2, b2, alpha2, w3, b3, softmax
 def din_plan(B, T, K, H1, H2):
     """fil_din_plan's answer as a dict (fits, tile, grid, cap, partials, lds_fwd, lds_bwd); fits=False (and nothing else) for a shape
     outside the kernel menu."""
-    plan = (ctypes.c_int * 8)()
-    rc = _lib.load().fil_din_plan(int(B), int(T), int(K), int(H1), int(H2), plan)
-    if rc == _lib.FIL_ERR_UNSUPPORTED:
-        return dict(fits=False)
-    check(rc, "fil_din_plan")
-    return dict(fits=bool(plan[0]) and bool(plan[1]), tile=plan[2], grid=plan[3], cap=plan[4], partials=plan[5], lds_fwd=plan[6],
-                lds_bwd=plan[7])
+    return _tiled_plan("fil_din_plan", int(B), int(T), int(K), int(H1), int(H2))
 
 
 GRU_MODES = {"gru": _lib.FIL_GRU_GRU, "augru": _lib.FIL_GRU_AUGRU, "agru": _lib.FIL_GRU_AGRU}
@@ -337,10 +342,7 @@ class _GruFn(torch.autograd.Function):
             raise FilError("gru: the scores a are given in the modes 'augru' and 'agru' and only there")
         if a is not None and tuple(a.shape) != (B, T):
             raise FilError("gru: a must be [B,T], got %s" % (tuple(a.shape),))
-        if mask is not None:
-            if tuple(mask.shape) != (B, T) or mask.dtype not in (torch.bool, torch.uint8):
-                raise FilError("gru: mask must be a [B,T] bool or uint8 tensor, got %s %s" % (tuple(mask.shape), mask.dtype))
-            mask = (mask.to(torch.uint8) if mask.dtype == torch.bool else mask).contiguous()
+        mask = _seq_mask("gru", mask, B, T)
         lib = _lib.load()
         hs = torch.empty((B, T, H), dtype=torch.float32, device=x.device)
         need = ctx.needs_input_grad
@@ -407,13 +409,7 @@ def gru(x, a, mask, W, U, b, mode="gru", return_sequences=True):
 def gru_plan(B, T, K, H, mode="gru"):
     """fil_gru_plan's answer as a dict (fits, tile, grid, cap, partials, lds_fwd, lds_bwd); fits=False (and nothing else) for a shape
     outside the kernel menu."""
-    plan = (ctypes.c_int * 8)()
-    rc = _lib.load().fil_gru_plan(int(B), int(T), int(K), int(H), GRU_MODES[mode], plan)
-    if rc == _lib.FIL_ERR_UNSUPPORTED:
-        return dict(fits=False)
-    check(rc, "fil_gru_plan")
-    return dict(fits=bool(plan[0]) and bool(plan[1]), tile=plan[2], grid=plan[3], cap=plan[4], partials=plan[5], lds_fwd=plan[6],
-                lds_bwd=plan[7])
+    return _tiled_plan("fil_gru_plan", int(B), int(T), int(K), int(H), GRU_MODES[mode])
 
 
 class _SeqAttnFn(torch.autograd.Function):
@@ -430,10 +426,7 @@ class _SeqAttnFn(torch.autograd.Function):
         if heads < 1 or HD % heads != 0:
             raise FilError("seq_self_attention: %d heads do not divide the %d projection columns" % (heads, HD))
         H, D = heads, HD // heads
-        if mask is not None:
-            if tuple(mask.shape) != (B, T) or mask.dtype not in (torch.bool, torch.uint8):
-                raise FilError("seq_self_attention: mask must be a [B,T] bool or uint8 tensor, got %s %s" % (tuple(mask.shape), mask.dtype))
-            mask = (mask.to(torch.uint8) if mask.dtype == torch.bool else mask).contiguous()
+        mask = _seq_mask("seq_self_attention", mask, B, T)
         lib = _lib.load()
         out = torch.empty((B, T, HD), dtype=torch.float32, device=x.device)
         need = ctx.needs_input_grad
@@ -488,13 +481,7 @@ def seq_self_attention(x, mask, Wq, Wk, Wv, heads, use_scale=True):
 def seq_attn_plan(B, T, K, H, D):
     """fil_seqattn_plan's answer as a dict (fits, tile, grid, cap, partials, lds_fwd, lds_bwd); fits=False (and nothing else) for a
     shape outside the kernel menu."""
-    plan = (ctypes.c_int * 8)()
-    rc = _lib.load().fil_seqattn_plan(int(B), int(T), int(K), int(H), int(D), plan)
-    if rc == _lib.FIL_ERR_UNSUPPORTED:
-        return dict(fits=False)
-    check(rc, "fil_seqattn_plan")
-    return dict(fits=bool(plan[0]) and bool(plan[1]), tile=plan[2], grid=plan[3], cap=plan[4], partials=plan[5], lds_fwd=plan[6],
-                lds_bwd=plan[7])
+    return _tiled_plan("fil_seqattn_plan", int(B), int(T), int(K), int(H), int(D))
 
 
 # --------------------------------------------------------------------------------------------- A2  DCN

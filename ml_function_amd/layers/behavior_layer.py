@@ -4,6 +4,7 @@ sigmoid (:286,308), V is projected with key_w (:360; value_w exists but never re
 epsilon is Keras' default 1e-3, the output is head-major [H,B,F,A].
 DinAttentionLayer (extension): the Deep Interest Network's attention pooling of a behaviour sequence, one fused kernel per direction."""
 import ctypes
+import functools
 
 import torch
 
@@ -128,7 +129,13 @@ class MultHeadAttentionLayer(Layer):
         return [atten_v, res]
 
 
-_DIN_FITS = {}                 # (T, K, H1, H2) -> fil_din_plan's answer
+@functools.lru_cache(maxsize=None)
+def _menu_fits(plan, *dims):
+    """Whether the shape `dims` is in the kernel menu that Fn.<op>_plan `plan` speaks for: the plan's "fits" at B = 1, cached per
+    shape (the plan is fixed for the life of the process)."""
+    return plan(1, *dims)["fits"]
+
+
 _DIN_ACTIVATIONS = ("prelu", "relu", "sigmoid")
 
 
@@ -212,11 +219,7 @@ class DinAttentionLayer(Layer):
         fil_din_plan answers from the launchers' own arithmetic; the answer is cached per shape."""
         if keys.dim() != 3:
             return False
-        key = (int(keys.shape[1]), int(keys.shape[2]), *self.hidden_units)
-        fits = _DIN_FITS.get(key)
-        if fits is None:
-            fits = _DIN_FITS[key] = Fn.din_plan(1, *key)["fits"]
-        return fits
+        return _menu_fits(Fn.din_plan, int(keys.shape[1]), int(keys.shape[2]), *self.hidden_units)
 
     def _composed(self, q, keys, mask):
         """din_attention_graph on the GPU in fp32: a dozen launches and two [B,T,n] blocks per direction where the fused kernel makes
@@ -242,7 +245,6 @@ class DinAttentionLayer(Layer):
         return pooled.unsqueeze(1)
 
 
-_GRU_FITS = {}                 # (K, H, mode) -> fil_gru_plan's answer
 _GRU_MODES = ("gru", "augru", "agru")
 
 
@@ -314,11 +316,7 @@ class GRULayer(Layer):
         arithmetic; the answer is cached per shape."""
         if x.dim() != 3:
             return False
-        key = (int(x.shape[2]), self.units, self.mode)
-        fits = _GRU_FITS.get(key)
-        if fits is None:
-            fits = _GRU_FITS[key] = Fn.gru_plan(1, 1, key[0], key[1], key[2])["fits"]
-        return fits
+        return _menu_fits(Fn.gru_plan, 1, int(x.shape[2]), self.units, self.mode)
 
     def _composed(self, x, scores, mask):
         """gru_graph on the GPU in fp32: about a dozen launches per step where the fused kernel makes one per direction -- it exists so
@@ -346,9 +344,6 @@ class GRULayer(Layer):
             return Fn.gru(x, scores, mask, self.kernel, self.recurrent_kernel, self.bias, mode=self.mode,
                           return_sequences=self.return_sequences)
         return self._composed(x, scores, mask)
-
-
-_SEQ_ATTN_FITS = {}            # (T, K, heads, head_dim) -> fil_seqattn_plan's answer
 
 
 def seq_self_attention_graph(x, mask, wq, wk, wv, heads, use_scale=True):
@@ -417,11 +412,7 @@ class SeqSelfAttentionLayer(Layer):
         within the LDS limit -- fil_seqattn_plan answers from the launchers' own arithmetic; the answer is cached per shape."""
         if x.dim() != 3:
             return False
-        key = (int(x.shape[1]), int(x.shape[2]), self.heads, self.head_dim)
-        fits = _SEQ_ATTN_FITS.get(key)
-        if fits is None:
-            fits = _SEQ_ATTN_FITS[key] = key[0] >= 1 and Fn.seq_attn_plan(1, *key)["fits"]
-        return fits
+        return x.shape[1] >= 1 and _menu_fits(Fn.seq_attn_plan, int(x.shape[1]), int(x.shape[2]), self.heads, self.head_dim)
 
     def _flat(self):
         hd = self.heads * self.head_dim

@@ -193,7 +193,7 @@ MASK_SHAPES = ((3, 8, 20, 32), (3, 36, 100, 10), (3, 64, 56, 33), (64, 28, 9, 64
 
 def B_EDGES(NS):
     """NS - 1, NS, NS + 1: one partial, then two, the last one short; 15 NS, 16 NS, 16 NS + 1: the partial count on both sides of one
-    round of din_param_reduce_kernel's 16 slices; 512 NS + 1: a second grid-stride trip that one workgroup makes with one sample."""
+    round of param_reduce_kernel's 16 slices; 512 NS + 1: a second grid-stride trip that one workgroup makes with one sample."""
     return tuple(b for b in (NS - 1, NS, NS + 1, 15 * NS, 16 * NS, 16 * NS + 1, GRID_CAP * NS + 1) if b >= 1)
 
 

@@ -10,7 +10,7 @@ instantiations of the paths no other test reaches to the same bars on din_attn_r
 
 What these tests see was checked with value-only mutants of csrc/din.hip, each built and run once (MI355X), counted in the raw-mode
 test: `u >= 0.f` in the backward's du1 fails all 90 cases (and no test of tests/test_din_attn_gpu.py); the second tile of an NT = 2
-thread zeroed fails the 36 NT = 2 cases and no other; din_param_reduce_kernel without slice 15 the 25 cases with 16 or more partials;
+thread zeroed fails the 36 NT = 2 cases and no other; param_reduce_kernel without slice 15 the 25 cases with 16 or more partials;
 dalpha1 of the last unit zeroed where H1 % 8 != 0 43 of those 47 cases (in four small ones the reference's value is 0); the layer-2
 accumulator m = 16 dropped in the H2T = 32 forward 30 of the 31 H2T = 32 cases.  The softmax test found that the backward lost
 2^-24 / eps of ds where one weight was 1 - eps (dq off by up to 14 %); din_bwd_kernel's gc is the fix.

@@ -1,0 +1,152 @@
+"""The shared fixed-order sum of parameter-gradient partials (csrc/param_reduce.hip), reached through each of its four launchers:
+fil_afm_bwd, fil_din_bwd, fil_gru_bwd and fil_seqattn_bwd.  The raw entry points run with a workspace the test owns; the workspace
+is then read back as [partials][n_out] fp32 (a partial is the outputs' elements back to back in ABI order) and the sum is redone in
+numpy fp32 in the kernel's order: 16 slices of every 16th partial, each from 0.f in increasing order, then the slices 0 .. 15 from
+0.f.  The returned gradients must have those bits.  A parity test against fp64 cannot see a changed order or a dropped slice; this
+one can.  Shapes: the smallest of each menu, B from the plan so that there are 1, 2, 15, 16, 17 and 33 partials (one slice entry,
+the last slice empty / just filled, a second round, a third); the plan's partial count is asserted so that a changed tile cannot
+silently skip a count.  Inputs are plain seeded normals: nothing is compared against fp64."""
+import functools
+
+import numpy as np
+import pytest
+import torch
+
+from ml_function_amd import _lib
+from ml_function_amd import functional as Fn
+from ml_function_amd._lib import check, ptr, stream_ptr
+from tests import guarded
+
+pytestmark = pytest.mark.gpu
+
+COUNTS = (1, 2, 15, 16, 17, 33)
+
+
+def _afm(F, K, A):
+    def run(lib, t, B, outs, ws, nws):
+        pooled, stats = _scratch(B * K), _scratch(B * 2)
+        check(lib.fil_afm_fwd(ptr(t["emb"]), ptr(t["W"]), ptr(t["b"]), ptr(t["h"]), ptr(pooled), ptr(stats), B, F, K, A, 0, stream_ptr()),
+              "fil_afm_fwd")
+        check(lib.fil_afm_bwd(ptr(t["emb"]), ptr(t["W"]), ptr(t["b"]), ptr(t["h"]), ptr(pooled), ptr(stats), ptr(t["g"]), None, *outs,
+                              ptr(ws), nws, B, F, K, A, 0, stream_ptr()), "fil_afm_bwd")
+    return dict(plan=lambda B: Fn.afm_plan(B, F, K, A), ws_bytes=lambda lib, B: lib.fil_afm_bwd_workspace_bytes(B, F, K, A),
+                inputs=lambda B: dict(emb=(B, F, K), W=(K, A), b=(A,), h=(A,), g=(B, K)),
+                outs=(("dW", K * A), ("db", A), ("dh", A)), n_out=K * A + 2 * A, run=run, lone="db")
+
+
+def _din(T, K, H1, H2):
+    def run(lib, t, B, outs, ws, nws):
+        out, stats = _scratch(B * K), _scratch(B * (T + 2))
+        w = [ptr(t[k]) for k in ("W1", "b1", "al1", "W2", "b2", "al2", "w3", "b3")]
+        check(lib.fil_din_fwd(ptr(t["q"]), ptr(t["keys"]), None, *w, ptr(out), ptr(stats), B, T, K, H1, H2, 0, stream_ptr()), "fil_din_fwd")
+        check(lib.fil_din_bwd(ptr(t["q"]), ptr(t["keys"]), None, *w, ptr(out), ptr(stats), ptr(t["g"]), None, None, *outs, ptr(ws), nws,
+                              B, T, K, H1, H2, 0, stream_ptr()), "fil_din_bwd")
+    return dict(plan=lambda B: Fn.din_plan(B, T, K, H1, H2), ws_bytes=lambda lib, B: lib.fil_din_bwd_workspace_bytes(B, T, K, H1, H2),
+                inputs=lambda B: dict(q=(B, K), keys=(B, T, K), W1=(4 * K, H1), b1=(H1,), al1=(H1,), W2=(H1, H2), b2=(H2,), al2=(H2,),
+                                      w3=(H2,), b3=(1,), g=(B, K)),
+                outs=(("dW1", 4 * K * H1), ("db1", H1), ("dalpha1", H1), ("dW2", H1 * H2), ("db2", H2), ("dalpha2", H2), ("dw3", H2),
+                      ("db3", 1)),
+                n_out=4 * K * H1 + H1 * H2 + 2 * H1 + 3 * H2 + 1, run=run, lone="dW2")
+
+
+def _gru(T, K, H):
+    def run(lib, t, B, outs, ws, nws):
+        hs, saved = _scratch(B * T * H), _scratch(max(int(lib.fil_gru_saved_bytes(B, T, K, H)), 256) // 4)
+        check(lib.fil_gru_fwd(ptr(t["x"]), None, None, ptr(t["W"]), ptr(t["U"]), ptr(t["b"]), ptr(hs), ptr(saved), B, T, K, H,
+                              _lib.FIL_GRU_GRU, stream_ptr()), "fil_gru_fwd")
+        check(lib.fil_gru_bwd(ptr(t["x"]), None, None, ptr(t["W"]), ptr(t["U"]), ptr(hs), ptr(saved), ptr(t["g"]), None, None, None, *outs,
+                              ptr(ws), nws, B, T, K, H, _lib.FIL_GRU_GRU, stream_ptr()), "fil_gru_bwd")
+    return dict(plan=lambda B: Fn.gru_plan(B, T, K, H), ws_bytes=lambda lib, B: lib.fil_gru_bwd_workspace_bytes(B, T, K, H),
+                inputs=lambda B: dict(x=(B, T, K), W=(K, 3 * H), U=(H, 3 * H), b=(2, 3 * H), g=(B, T, H)),
+                outs=(("dW", K * 3 * H), ("dU", H * 3 * H), ("db", 2 * 3 * H)), n_out=(K + H + 2) * 3 * H, run=run, lone="dU")
+
+
+def _seq_attn(T, K, H, D):
+    def run(lib, t, B, outs, ws, nws):
+        out, saved = _scratch(B * T * H * D), _scratch(max(int(lib.fil_seqattn_saved_bytes(B, T, K, H, D)), 256) // 4)
+        check(lib.fil_seqattn_fwd(ptr(t["x"]), None, ptr(t["Wq"]), ptr(t["Wk"]), ptr(t["Wv"]), ptr(out), ptr(saved), B, T, K, H, D, 1,
+                                  stream_ptr()), "fil_seqattn_fwd")
+        check(lib.fil_seqattn_bwd(ptr(t["x"]), None, ptr(t["Wq"]), ptr(t["Wk"]), ptr(t["Wv"]), ptr(out), ptr(saved), ptr(t["g"]), None, *outs,
+                                  ptr(ws), nws, B, T, K, H, D, 1, stream_ptr()), "fil_seqattn_bwd")
+    return dict(plan=lambda B: Fn.seq_attn_plan(B, T, K, H, D), ws_bytes=lambda lib, B: lib.fil_seqattn_bwd_workspace_bytes(B, T, K, H, D),
+                inputs=lambda B: dict(x=(B, T, K), Wq=(K, H * D), Wk=(K, H * D), Wv=(K, H * D), g=(B, T, H * D)),
+                outs=(("dWq", K * H * D), ("dWk", K * H * D), ("dWv", K * H * D)), n_out=3 * K * H * D, run=run, lone="dWk")
+
+
+# op -> (its launcher's description at the smallest shape of its menu, B for 1, 2, 15, 16, 17, 33 partials)
+OPS = {
+    "afm": (_afm(3, 4, 2), (1, 5, 57, 61, 65, 129)),
+    "din": (_din(3, 4, 4, 4), (1, 5, 57, 61, 65, 129)),
+    "gru": (_gru(3, 4, 8), (1, 33, 449, 481, 513, 1025)),
+    "seq_attn": (_seq_attn(3, 4, 1, 4), (1, 86, 1191, 1276, 1361, 2721)),
+}
+CASES = [(op, n) for op in OPS for n in COUNTS]
+
+
+def _scratch(n):
+    return torch.empty(n, dtype=torch.float32, device="cuda")
+
+
+def fixed_order_sum(parts):
+    """parts [nparts][n_out] fp32 -> the kernel's sum, one fp32 addition at a time (numpy's own sum is pairwise: not used)."""
+    slices = np.zeros((16, parts.shape[1]), np.float32)
+    for q in range(parts.shape[0]):
+        slices[q % 16] += parts[q]
+    total = np.zeros(parts.shape[1], np.float32)
+    for sl in range(16):
+        total += slices[sl]
+    return total
+
+
+def run_raw(op, nparts, wanted=None):
+    """-> (the wanted outputs' words by name, the workspace's partials [nparts][n_out] fp32, the allocations that were NOT passed).
+    Every output sits in a sentinel-guarded allocation, the unwanted ones too; the workspace is guarded behind its bytes."""
+    spec, Bs = OPS[op]
+    B = Bs[COUNTS.index(nparts)]
+    assert spec["plan"](B)["partials"] == nparts, (op, B, spec["plan"](B))
+    assert sum(n for _, n in spec["outs"]) == spec["n_out"]
+    lib = _lib.load()
+    rng = np.random.default_rng(1000 * nparts + len(op))
+    t = {k: torch.from_numpy(rng.standard_normal(shape).astype(np.float32)).cuda() for k, shape in spec["inputs"](B).items()}
+    bufs = {k: guarded.GuardedOutput((n,), np.uint32, k) for k, n in spec["outs"]}
+    nws = int(spec["ws_bytes"](lib, B))
+    assert nws >= nparts * spec["n_out"] * 4
+    ws = guarded.workspace(nws)
+    spec["run"](lib, t, B, [bufs[k].ptr if wanted is None or k in wanted else None for k, _ in spec["outs"]], ws, nws)
+    torch.cuda.synchronize()
+    guarded.assert_workspace_guard(ws, nws, op)
+    parts = ws[:nparts * spec["n_out"] * 4].cpu().numpy().view(np.float32).reshape(nparts, spec["n_out"])
+    got = {k: b.read(op + " " + k) for k, b in bufs.items() if wanted is None or k in wanted}
+    return got, parts, {k: b for k, b in bufs.items() if k not in got}
+
+
+@functools.lru_cache(maxsize=None)
+def full_run(op, nparts):
+    got, parts, _ = run_raw(op, nparts)
+    return got, parts
+
+
+@pytest.mark.parametrize("op,nparts", CASES, ids=["%s-%d" % c for c in CASES])
+def test_gradients_are_the_fixed_order_sum_of_the_partials(op, nparts):
+    got, parts = full_run(op, nparts)
+    want = fixed_order_sum(parts).view(np.uint32)
+    assert np.isfinite(parts).all()
+    o = 0
+    for k, n in OPS[op][0]["outs"]:
+        diff = np.nonzero(got[k] != want[o:o + n])[0]
+        assert diff.size == 0, "%s, %d partials: %d of %d words of %s differ from the fixed-order sum (first at %s)" % (
+            op, nparts, diff.size, n, k, diff[:8])
+        o += n
+
+
+@pytest.mark.parametrize("op", list(OPS))
+def test_one_wanted_output_has_the_bits_of_the_full_call(op):
+    """A NULL output is skipped: the one wanted output (a middle one) has the full call's bits, its own guard words are untouched
+    (GuardedOutput.read) and so is every word of its neighbours' allocations, which were not passed."""
+    lone = OPS[op][0]["lone"]
+    full, _ = full_run(op, 17)
+    got, _, unpassed = run_raw(op, 17, wanted=(lone,))
+    assert (got[lone] == full[lone]).all(), "%s: %s alone differs from the full call" % (op, lone)
+    for k, b in unpassed.items():
+        words = b.t.cpu().numpy().view(np.uint32)
+        assert (words == guarded.SENTINEL).all(), "%s: %s was not passed and was written" % (op, k)
