@@ -74,6 +74,39 @@ def release_scratch():
     _WS_LAST_USE.clear()
 
 
+def _partials_scratch(entry, tag, wanted, device, *dims):
+    """(workspace, bytes) for the parameter-gradient partials of a tiled backward: what the library's `entry`
+    (fil_*_bwd_workspace_bytes) asks for at `dims`, from _scratch under `tag` -- or (None, 0) when no parameter gradient is wanted
+    (the kernel then skips the partials and the library is not asked)."""
+    if not wanted:
+        return None, 0
+    nws = getattr(_lib.load(), entry)(*dims)
+    return _scratch(nws, device, tag), nws
+
+
+def _saved_floats(nbytes, device):
+    """The fp32 `saved` buffer a forward hands to its backward, for the byte count the library's fil_*_saved_bytes gave."""
+    return torch.empty(max(int(nbytes), 256) // 4, dtype=torch.float32, device=device)
+
+
+def _grad(want, shape, device):
+    """An uninitialised fp32 gradient of `shape`, or None when it is not wanted (the kernels skip a null output)."""
+    return torch.empty(shape, dtype=torch.float32, device=device) if want else None
+
+
+def _save(ctx, *tensors):
+    """ctx.save_for_backward of the tensors that are there (so autograd's version check covers every one of them); which places
+    were None is kept on ctx for _saved."""
+    ctx.saved_places = tuple(t is not None for t in tensors)
+    ctx.save_for_backward(*[t for t in tensors if t is not None])
+
+
+def _saved(ctx):
+    """What _save was given, in its order: the saved tensors with None back in the places that were None."""
+    it = iter(ctx.saved_tensors)
+    return tuple(next(it) if there else None for there in ctx.saved_places)
+
+
 # --------------------------------------------------------------------------------------------- A1  FM
 class _FmFn(torch.autograd.Function):
     @staticmethod
@@ -198,14 +231,12 @@ class _AfmPoolFn(torch.autograd.Function):
         if not any(need[:4]):
             return None, None, None, None, None
         lib = _lib.load()
-        demb = torch.empty_like(emb) if need[0] else None
-        dw = torch.empty_like(w) if need[1] else None
-        db = torch.empty(ctx.shapes[0], dtype=torch.float32, device=emb.device) if need[2] else None
-        dh = torch.empty(ctx.shapes[1], dtype=torch.float32, device=emb.device) if need[3] else None
-        ws, nws = None, 0
-        if need[1] or need[2] or need[3]:
-            nws = lib.fil_afm_bwd_workspace_bytes(B, F, K, A)
-            ws = _scratch(nws, emb.device, "afm_bwd")
+        dev = emb.device
+        demb = _grad(need[0], emb.shape, dev)
+        dw = _grad(need[1], w.shape, dev)
+        db = _grad(need[2], ctx.shapes[0], dev)
+        dh = _grad(need[3], ctx.shapes[1], dev)
+        ws, nws = _partials_scratch("fil_afm_bwd_workspace_bytes", "afm_bwd", need[1] or need[2] or need[3], dev, B, F, K, A)
         check(lib.fil_afm_bwd(ptr(emb), ptr(w), ptr(b), ptr(h), ptr(pooled), ptr(stats), ptr(_f32c(g)), ptr(demb), ptr(dw), ptr(db),
                               ptr(dh), ptr(ws), nws, B, F, K, A, ctx.flags, stream_ptr()), "fil_afm_bwd")
         return demb, dw, db, dh, None
@@ -258,8 +289,7 @@ class _DinAttentionFn(torch.autograd.Function):
         stats = torch.empty((B, T + 2), dtype=torch.float32, device=q.device)
         check(_lib.load().fil_din_fwd(ptr(q), ptr(keys), ptr(mask), ptr(w1), ptr(b1), ptr(alpha1), ptr(w2), ptr(b2), ptr(alpha2), ptr(w3),
                                       ptr(b3), ptr(out), ptr(stats), B, T, K, H1, H2, flags, stream_ptr()), "fil_din_fwd")
-        ctx.has = (mask is not None, alpha1 is not None, alpha2 is not None)
-        ctx.save_for_backward(*[t for t in (q, keys, mask, w1, b1, alpha1, w2, b2, alpha2, w3, b3, out, stats) if t is not None])
+        _save(ctx, q, keys, mask, w1, b1, alpha1, w2, b2, alpha2, w3, b3, out, stats)
         ctx.flags = flags
         ctx.shapes = {n: tuple(t.shape) for n, t in (("b1", b1), ("alpha1", alpha1), ("b2", b2), ("alpha2", alpha2), ("w3", w3), ("b3", b3))
                       if t is not None}
@@ -267,38 +297,27 @@ class _DinAttentionFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g):
-        sv = list(ctx.saved_tensors)
-        has_mask, has_a1, has_a2 = ctx.has
-        q, keys = sv.pop(0), sv.pop(0)
-        mask = sv.pop(0) if has_mask else None
-        w1, b1 = sv.pop(0), sv.pop(0)
-        alpha1 = sv.pop(0) if has_a1 else None
-        w2, b2 = sv.pop(0), sv.pop(0)
-        alpha2 = sv.pop(0) if has_a2 else None
-        w3, b3, out, stats = sv
+        q, keys, mask, w1, b1, alpha1, w2, b2, alpha2, w3, b3, out, stats = _saved(ctx)
         B, T, K = keys.shape
         H1, H2 = w1.shape[1], w2.shape[1]
         need = ctx.needs_input_grad
         none = (None,) * 12
         if not any(need):
             return none
-        dev = q.device
-        new = lambda shape: torch.empty(shape, dtype=torch.float32, device=dev)
-        dq = new(q.shape) if need[0] else None
-        dkeys = new(keys.shape) if need[1] else None
-        dw1 = new(w1.shape) if need[3] else None
-        db1 = new(ctx.shapes["b1"]) if need[4] else None
-        da1 = new(ctx.shapes["alpha1"]) if (need[5] and has_a1) else None
-        dw2 = new(w2.shape) if need[6] else None
-        db2 = new(ctx.shapes["b2"]) if need[7] else None
-        da2 = new(ctx.shapes["alpha2"]) if (need[8] and has_a2) else None
-        dw3 = new(ctx.shapes["w3"]) if need[9] else None
-        db3 = new(ctx.shapes["b3"]) if need[10] else None
+        dev, shapes = q.device, ctx.shapes
+        dq = _grad(need[0], q.shape, dev)
+        dkeys = _grad(need[1], keys.shape, dev)
+        dw1 = _grad(need[3], w1.shape, dev)
+        db1 = _grad(need[4], shapes["b1"], dev)
+        da1 = _grad(need[5] and alpha1 is not None, shapes.get("alpha1"), dev)      # a slope that was None gets no gradient
+        dw2 = _grad(need[6], w2.shape, dev)
+        db2 = _grad(need[7], shapes["b2"], dev)
+        da2 = _grad(need[8] and alpha2 is not None, shapes.get("alpha2"), dev)
+        dw3 = _grad(need[9], shapes["w3"], dev)
+        db3 = _grad(need[10], shapes["b3"], dev)
         lib = _lib.load()
-        ws, nws = None, 0
-        if any(t is not None for t in (dw1, db1, da1, dw2, db2, da2, dw3, db3)):
-            nws = lib.fil_din_bwd_workspace_bytes(B, T, K, H1, H2)
-            ws = _scratch(nws, dev, "din_bwd")
+        ws, nws = _partials_scratch("fil_din_bwd_workspace_bytes", "din_bwd",
+                                    any(t is not None for t in (dw1, db1, da1, dw2, db2, da2, dw3, db3)), dev, B, T, K, H1, H2)
         check(lib.fil_din_bwd(ptr(q), ptr(keys), ptr(mask), ptr(w1), ptr(b1), ptr(alpha1), ptr(w2), ptr(b2), ptr(alpha2), ptr(w3), ptr(b3),
                               ptr(out), ptr(stats), ptr(_f32c(g)), ptr(dq), ptr(dkeys), ptr(dw1), ptr(db1), ptr(da1), ptr(dw2), ptr(db2),
                               ptr(da2), ptr(dw3), ptr(db3), ptr(ws), nws, B, T, K, H1, H2, ctx.flags, stream_ptr()), "fil_din_bwd")
@@ -348,11 +367,10 @@ class _GruFn(torch.autograd.Function):
         need = ctx.needs_input_grad
         saved = None
         if any(need[i] for i in (0, 1, 3, 4, 5)):
-            saved = torch.empty(max(int(lib.fil_gru_saved_bytes(B, T, K, H)), 256) // 4, dtype=torch.float32, device=x.device)
+            saved = _saved_floats(lib.fil_gru_saved_bytes(B, T, K, H), x.device)
         check(lib.fil_gru_fwd(ptr(x), ptr(a), ptr(mask), ptr(w), ptr(u), ptr(b), ptr(hs), ptr(saved), B, T, K, H, mode, stream_ptr()),
               "fil_gru_fwd")
-        ctx.has = (a is not None, mask is not None)
-        ctx.save_for_backward(*[t for t in (x, a, mask, w, u, hs, saved) if t is not None])
+        _save(ctx, x, a, mask, w, u, hs, saved)
         ctx.mode, ctx.return_sequences = mode, return_sequences
         if return_sequences:
             return hs
@@ -360,33 +378,24 @@ class _GruFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g):
-        sv = list(ctx.saved_tensors)
-        has_a, has_mask = ctx.has
-        x = sv.pop(0)
-        a = sv.pop(0) if has_a else None
-        mask = sv.pop(0) if has_mask else None
-        w, u, hs, saved = sv
+        x, a, mask, w, u, hs, saved = _saved(ctx)
         B, T, K = x.shape
         H = u.shape[0]
         need = ctx.needs_input_grad
         none = (None,) * 8
-        want_da = need[1] and has_a
+        want_da = need[1] and a is not None      # scores that were None get no gradient
         if not (need[0] or want_da or need[3] or need[4] or need[5]):
             return none
         dev = x.device
-        new = lambda shape: torch.empty(shape, dtype=torch.float32, device=dev)
-        dx = new(x.shape) if need[0] else None
-        da = new(a.shape) if want_da else None
-        dw = new(w.shape) if need[3] else None
-        du = new(u.shape) if need[4] else None
-        db = new((2, 3 * H)) if need[5] else None
+        dx = _grad(need[0], x.shape, dev)
+        da = _grad(want_da, (B, T), dev)
+        dw = _grad(need[3], w.shape, dev)
+        du = _grad(need[4], u.shape, dev)
+        db = _grad(need[5], (2, 3 * H), dev)
         g = _f32c(g)
         g_hs, g_last = (g, None) if ctx.return_sequences else (None, g)
         lib = _lib.load()
-        ws, nws = None, 0
-        if dw is not None or du is not None or db is not None:
-            nws = lib.fil_gru_bwd_workspace_bytes(B, T, K, H)
-            ws = _scratch(nws, dev, "gru_bwd")
+        ws, nws = _partials_scratch("fil_gru_bwd_workspace_bytes", "gru_bwd", need[3] or need[4] or need[5], dev, B, T, K, H)
         check(lib.fil_gru_bwd(ptr(x), ptr(a), ptr(mask), ptr(w), ptr(u), ptr(hs), ptr(saved), ptr(g_hs), ptr(g_last), ptr(dx), ptr(da),
                               ptr(dw), ptr(du), ptr(db), ptr(ws), nws, B, T, K, H, ctx.mode, stream_ptr()), "fil_gru_bwd")
         return dx, da, None, dw, du, db, None, None
@@ -432,37 +441,29 @@ class _SeqAttnFn(torch.autograd.Function):
         need = ctx.needs_input_grad
         saved = None
         if any(need[i] for i in (0, 2, 3, 4)):
-            saved = torch.empty(max(int(lib.fil_seqattn_saved_bytes(B, T, K, H, D)), 256) // 4, dtype=torch.float32, device=x.device)
+            saved = _saved_floats(lib.fil_seqattn_saved_bytes(B, T, K, H, D), x.device)
         check(lib.fil_seqattn_fwd(ptr(x), ptr(mask), ptr(wq), ptr(wk), ptr(wv), ptr(out), ptr(saved), B, T, K, H, D, int(use_scale),
                                   stream_ptr()), "fil_seqattn_fwd")
-        ctx.has_mask = mask is not None
-        ctx.save_for_backward(*[t for t in (x, mask, wq, wk, wv, out, saved) if t is not None])
+        _save(ctx, x, mask, wq, wk, wv, out, saved)
         ctx.dims = (H, D, int(use_scale))
         return out
 
     @staticmethod
     def backward(ctx, g):
-        sv = list(ctx.saved_tensors)
-        x = sv.pop(0)
-        mask = sv.pop(0) if ctx.has_mask else None
         need = ctx.needs_input_grad
         if not (need[0] or need[2] or need[3] or need[4]):
             return (None,) * 7
-        wq, wk, wv, out, saved = sv
+        x, mask, wq, wk, wv, out, saved = _saved(ctx)
         B, T, K = x.shape
         H, D, use_scale = ctx.dims
         dev = x.device
-        new = lambda shape: torch.empty(shape, dtype=torch.float32, device=dev)
-        dx = new(x.shape) if need[0] else None
-        dwq = new(wq.shape) if need[2] else None
-        dwk = new(wk.shape) if need[3] else None
-        dwv = new(wv.shape) if need[4] else None
+        dx = _grad(need[0], x.shape, dev)
+        dwq = _grad(need[2], wq.shape, dev)
+        dwk = _grad(need[3], wk.shape, dev)
+        dwv = _grad(need[4], wv.shape, dev)
         g = _f32c(g)
         lib = _lib.load()
-        ws, nws = None, 0
-        if dwq is not None or dwk is not None or dwv is not None:
-            nws = lib.fil_seqattn_bwd_workspace_bytes(B, T, K, H, D)
-            ws = _scratch(nws, dev, "seqattn_bwd")
+        ws, nws = _partials_scratch("fil_seqattn_bwd_workspace_bytes", "seqattn_bwd", need[2] or need[3] or need[4], dev, B, T, K, H, D)
         check(lib.fil_seqattn_bwd(ptr(x), ptr(mask), ptr(wq), ptr(wk), ptr(wv), ptr(out), ptr(saved), ptr(g), ptr(dx), ptr(dwq), ptr(dwk),
                                   ptr(dwv), ptr(ws), nws, B, T, K, H, D, use_scale, stream_ptr()), "fil_seqattn_bwd")
         return dx, None, dwq, dwk, dwv, None, None
@@ -482,6 +483,18 @@ def seq_attn_plan(B, T, K, H, D):
     """fil_seqattn_plan's answer as a dict (fits, tile, grid, cap, partials, lds_fwd, lds_bwd); fits=False (and nothing else) for a
     shape outside the kernel menu."""
     return _tiled_plan("fil_seqattn_plan", int(B), int(T), int(K), int(H), int(D))
+
+
+def attn_plan(F, K, H, A, precision="f32"):
+    """fil_attn_plan's answer for AutoInt's fused interacting layer (the plan does not depend on the batch) as a dict: fits = the
+    dynamic LDS of BOTH the forward and the backward within the launchers' limit in this precision, fwd_ok, bwd_ok; fits=False (and
+    nothing else) for a shape outside the kernel menu."""
+    plan = (ctypes.c_int * 10)()
+    rc = _lib.load().fil_attn_plan(int(F), int(K), int(H), int(A), _precision(precision), plan)
+    if rc == _lib.FIL_ERR_UNSUPPORTED:
+        return dict(fits=False)
+    check(rc, "fil_attn_plan")
+    return dict(fits=bool(plan[0]) and bool(plan[4]), fwd_ok=bool(plan[0]), bwd_ok=bool(plan[4]))
 
 
 # --------------------------------------------------------------------------------------------- A2  DCN
@@ -656,18 +669,15 @@ class _CinFn(torch.autograd.Function):
         out, pooled, saved = cin_forward_raw(x, Ws, bs, dense_w, dense_b, output_dim, mode, xt=xt, precision=precision)
         # xt (the gather's second output, same values as x) goes through save_for_backward too: an in-place edit between the
         # forward and the backward then trips autograd's version check instead of silently feeding stale rows to the kernels
-        ctx.save_for_backward(x, dense_w, pooled, saved, *Ws, *bs, *([xt] if xt is not None else []))
-        ctx.cfg = (L, output_dim, mode, xt is not None, precision)
+        _save(ctx, x, dense_w, pooled, saved, xt, *Ws, *bs)
+        ctx.cfg = (L, output_dim, mode, precision)
         return out if output_dim == 1 else pooled
 
     @staticmethod
     def backward(ctx, g):
-        L, output_dim, mode, has_xt, precision = ctx.cfg
-        x, dense_w, pooled, saved = ctx.saved_tensors[:4]
-        Ws = list(ctx.saved_tensors[4:4 + L])
-        bs = list(ctx.saved_tensors[4 + L:4 + 2 * L])
-        xt = ctx.saved_tensors[4 + 2 * L] if has_xt else None
-        gr = cin_backward_raw(x, Ws, bs, dense_w, pooled, saved, _f32c(g), output_dim, mode, xt=xt, precision=precision)
+        L, output_dim, mode, precision = ctx.cfg
+        x, dense_w, pooled, saved, xt, *params = _saved(ctx)
+        gr = cin_backward_raw(x, params[:L], params[L:], dense_w, pooled, saved, _f32c(g), output_dim, mode, xt=xt, precision=precision)
         return (gr["dx"], gr["ddw"], gr["ddb"], None, None, None, None, *gr["dW"], *gr["db"])
 
 
@@ -718,11 +728,8 @@ class _AttnFn(torch.autograd.Function):
                                float(scale), float(eps), int(bool(fuse_relu)), int(precision), x_chunk, None, 0, stream_ptr()),
               "fil_attn_fwd")
         keep_y = bool(fuse_relu) and (av is not None or gamma is None)   # the fused ReLU mask is y > 0
-        ctx.save_for_backward(x, Wq, Wk, *[t for t in (Wr, gamma, beta) if t is not None],
-                              *([av, rstd] if av is not None else []), *([y] if keep_y else []))
-        ctx.extra = (av is not None, keep_y)
-        ctx.cfg = (Wr is not None, gamma is not None, float(scale), float(eps), bool(fuse_relu), int(precision), x_chunk,
-                   (B, F, K))
+        _save(ctx, x, Wq, Wk, Wr, gamma, beta, av, rstd, y if keep_y else None)
+        ctx.cfg = (float(scale), float(eps), bool(fuse_relu), int(precision), x_chunk, (B, F, K))
         if fuse_relu:
             return y
         if res is None:
@@ -731,17 +738,9 @@ class _AttnFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dy, dres=None):
-        has_res, has_ln, scale, eps, fuse_relu, precision, x_chunk, (B, F, K) = ctx.cfg
-        sv = list(ctx.saved_tensors)
-        x, Wq, Wk = sv[:3]
-        rest = sv[3:]
-        Wr = rest.pop(0) if has_res else None
-        gamma = rest.pop(0) if has_ln else None
-        beta = rest.pop(0) if has_ln else None
-        has_av, has_y = ctx.extra
-        av_saved = rest.pop(0) if has_av else None
-        rstd_saved = rest.pop(0) if has_av else None
-        y_saved = rest.pop(0) if has_y else None
+        scale, eps, fuse_relu, precision, x_chunk, (B, F, K) = ctx.cfg
+        x, Wq, Wk, Wr, gamma, beta, av_saved, rstd_saved, y_saved = _saved(ctx)
+        has_res, has_ln = Wr is not None, gamma is not None
         _, H, A = Wq.shape
         lib = _lib.load()
         dy = _f32c(dy) if dy is not None else torch.zeros((H, B, F, A), dtype=torch.float32, device=x.device)
@@ -812,16 +811,14 @@ class _PAttnFn(torch.autograd.Function):
         out = torch.empty((N, Fq, Av), dtype=torch.float32, device=q.device)
         check(_lib.load().fil_pattn_fwd(ptr(q), ptr(k), ptr(v), ptr(mask), ptr(out), N, Fq, Fk, A, Av, float(scale), int(mask_period),
                                         stream_ptr()), "fil_pattn_fwd")
-        ctx.save_for_backward(q, k, v, *([mask] if mask is not None else []))
-        ctx.cfg = (float(scale), int(mask_period), mask is not None)
+        _save(ctx, q, k, v, mask)
+        ctx.cfg = (float(scale), int(mask_period))
         return out
 
     @staticmethod
     def backward(ctx, dout):
-        scale, mask_period, has_mask = ctx.cfg
-        sv = list(ctx.saved_tensors)
-        q, k, v = sv[:3]
-        mask = sv[3] if has_mask else None
+        scale, mask_period = ctx.cfg
+        q, k, v, mask = _saved(ctx)
         N, Fq, A = q.shape
         _, Fk, Av = v.shape
         dq, dk, dv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
@@ -1322,18 +1319,14 @@ class _EmbedFn(torch.autograd.Function):
         else:
             check(_lib.load().fil_embed_gather_dt(ptr(table), ptr(offsets), ptr(sizes), ptr(idx), ptr(out), ptr(oob_count), B, F, K,
                                                   FIL_F32 if out_dtype == torch.float32 else FIL_BF16, stream_ptr()), "fil_embed_gather_dt")
-        ctx.save_for_backward(offsets, idx, *[t for t in (sizes, frozen) if t is not None])
-        ctx.cfg = (tuple(table.shape), sizes is not None, frozen is not None, bool(sparse_grad), bool(atomic), layout_key)
+        _save(ctx, offsets, idx, sizes, frozen)
+        ctx.cfg = (tuple(table.shape), bool(sparse_grad), bool(atomic), layout_key)
         return out
 
     @staticmethod
     def backward(ctx, g):
-        table_shape, has_sizes, has_frozen, sparse_grad, atomic, layout_key = ctx.cfg
-        sv = list(ctx.saved_tensors)
-        offsets, idx = sv[:2]
-        rest = sv[2:]
-        sizes = rest.pop(0) if has_sizes else None
-        frozen = rest.pop(0) if has_frozen else None
+        table_shape, sparse_grad, atomic, layout_key = ctx.cfg
+        offsets, idx, sizes, frozen = _saved(ctx)
         B, F = idx.shape
         K = table_shape[1]
         # (a bf16 block's gradient arrives as bf16: the dense deterministic path reads it as it is, the others take fp32)
@@ -1422,18 +1415,14 @@ class _EmbedBagFn(torch.autograd.Function):
         count = torch.empty((B, F), dtype=torch.int32, device=table.device)
         check(_lib.load().fil_embed_bag_fwd(ptr(table), ptr(offsets), ptr(sizes), ptr(idx), pad_id, ptr(out), ptr(count), ptr(oob_count),
                                             B, F, T, K, combiner, stream_ptr()), "fil_embed_bag_fwd")
-        ctx.save_for_backward(offsets, idx, count, *[t for t in (sizes, frozen) if t is not None])
-        ctx.cfg = (tuple(table.shape), sizes is not None, frozen is not None, bool(sparse_grad), combiner, pad_id)
+        _save(ctx, offsets, idx, count, sizes, frozen)
+        ctx.cfg = (tuple(table.shape), bool(sparse_grad), combiner, pad_id)
         return out
 
     @staticmethod
     def backward(ctx, g):
-        table_shape, has_sizes, has_frozen, sparse_grad, combiner, pad_id = ctx.cfg
-        sv = list(ctx.saved_tensors)
-        offsets, idx, count = sv[:3]
-        rest = sv[3:]
-        sizes = rest.pop(0) if has_sizes else None
-        frozen = rest.pop(0) if has_frozen else None
+        table_shape, sparse_grad, combiner, pad_id = ctx.cfg
+        offsets, idx, count, sizes, frozen = _saved(ctx)
         B, F, T = idx.shape
         K = table_shape[1]
         R = B * F * T
@@ -1448,7 +1437,7 @@ class _EmbedBagFn(torch.autograd.Function):
         row_ids = torch.empty(R, dtype=torch.int64, device=g.device)
         check(lib.fil_embed_bag_row_ids(ptr(offsets), ptr(sizes), ptr(frozen), ptr(idx), pad_id, ptr(row_ids), B, F, T, stream_ptr()),
               "fil_embed_bag_row_ids")
-        if has_sizes and table_shape[0] < 2 ** 31 and R > 0:
+        if sizes is not None and table_shape[0] < 2 ** 31 and R > 0:
             s32, perm = torch.sort(row_ids.to(torch.int32), stable=True)
             sorted_ids = s32.to(torch.int64)
         else:

@@ -5,9 +5,18 @@ hyper-parameters, ``build(input_shape)`` runs lazily on the first call and creat
 ``add_weight(name, shape, initializer)``, ``call(inputs, **kwargs)`` is pure.  This base class reproduces that
 lifecycle so the re-hosted layers keep the reference's constructor kwargs, weight names and call signatures.
 """
+import functools
 import math
 
 import torch
+
+
+@functools.lru_cache(maxsize=None)
+def _menu_fits(plan, *dims):
+    """Whether the shape `dims` is in the kernel menu that functional.<op>_plan `plan` speaks for: the plan's "fits", cached per plan
+    and shape -- the layers ask at batch 1, hidden sizes, mode and precision are part of `dims` (the plan is fixed for the life of the
+    process)."""
+    return plan(*dims)["fits"]
 
 
 def shape_of(inputs):

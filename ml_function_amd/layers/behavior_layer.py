@@ -2,19 +2,13 @@
 MultHeadAttentionLayer (:313-380) of the reference.  Reference quirks are kept on purpose: the "softmax" is a
 sigmoid (:286,308), V is projected with key_w (:360; value_w exists but never receives a gradient), LayerNorm
 epsilon is Keras' default 1e-3, the output is head-major [H,B,F,A].
-DinAttentionLayer (extension): the Deep Interest Network's attention pooling of a behaviour sequence, one fused kernel per direction."""
-import ctypes
-import functools
-
+Behaviour-sequence layers (extensions), each one fused kernel per direction with a composed torch path outside the kernel menu:
+DinAttentionLayer (the Deep Interest Network's attention pooling), GRULayer (a GRU and the Deep Interest Evolution Network's AUGRU /
+AGRU) and SeqSelfAttentionLayer (the Behaviour Sequence Transformer's masked self-attention)."""
 import torch
 
-from .. import _lib
 from .. import functional as Fn
-from .._lib import FilError
-from .base import Layer
-
-_FIL_ERR_UNSUPPORTED = -4      # include/fil.h
-_PLAN_FITS = {}                # (F, K, H, A, precision) -> fil_attn_plan's answer (the plan is fixed for the life of the process)
+from .base import Layer, _menu_fits
 
 
 class ProductAttentionLayer(Layer):
@@ -81,15 +75,8 @@ class MultHeadAttentionLayer(Layer):
         (e.g. attention_dim = 32, or 8 heads over 129 fields in f32) takes the composed path below instead of raising."""
         if inputs.dim() != 3:
             return False
-        key = (int(inputs.shape[1]), int(inputs.shape[2]), int(self.attention_head_dim), int(self.attention_dim), Fn._precision(self.precision))
-        fits = _PLAN_FITS.get(key)
-        if fits is None:
-            plan = (ctypes.c_int * 10)()
-            rc = _lib.load().fil_attn_plan(*key, plan)
-            if rc != _FIL_ERR_UNSUPPORTED:
-                _lib.check(rc, "fil_attn_plan")
-            fits = _PLAN_FITS[key] = rc == 0 and bool(plan[0]) and bool(plan[4])      # fwd_ok and bwd_ok
-        return fits
+        return _menu_fits(Fn.attn_plan, int(inputs.shape[1]), int(inputs.shape[2]), int(self.attention_head_dim), int(self.attention_dim),
+                          self.precision)
 
     def _composed(self, inputs, mask):
         """The reference's op order (:358-369) with the attention core on the stand-alone kernel (fil_pattn_*: A <= 64, any mask) --
@@ -129,11 +116,21 @@ class MultHeadAttentionLayer(Layer):
         return [atten_v, res]
 
 
-@functools.lru_cache(maxsize=None)
-def _menu_fits(plan, *dims):
-    """Whether the shape `dims` is in the kernel menu that Fn.<op>_plan `plan` speaks for: the plan's "fits" at B = 1, cached per
-    shape (the plan is fixed for the life of the process)."""
-    return plan(1, *dims)["fits"]
+def _check_seq_mask(who, mask, B, T):
+    """The behaviour-sequence layers' mask: None, or a [B,T] bool / uint8 tensor (non-zero = live)."""
+    if mask is not None and (tuple(mask.shape) != (B, T) or mask.dtype not in (torch.bool, torch.uint8)):
+        raise ValueError("%s: mask must be a [B,T] bool or uint8 tensor, got %s %s" % (who, tuple(mask.shape), mask.dtype))
+
+
+def _masked_softmax(s, live):
+    """The softmax of the scores s [B,T] over the live slots (live [B,T] bool; None = all live); a sample without a live slot gets
+    weight 0 everywhere."""
+    if live is not None:
+        s = s.masked_fill(~live, float("-inf"))
+    mx = s.max(dim=1, keepdim=True).values
+    mx = torch.where(torch.isfinite(mx), mx, torch.zeros_like(mx))
+    w = torch.exp(s - mx)
+    return w / w.sum(dim=1, keepdim=True).clamp_min(torch.finfo(w.dtype).tiny)      # no live slot: 0 / tiny = 0
 
 
 _DIN_ACTIVATIONS = ("prelu", "relu", "sigmoid")
@@ -155,14 +152,7 @@ def din_attention_graph(q, keys, mask, w1, b1, alpha1, w2, b2, alpha2, w3, b3, s
     h1 = act(torch.matmul(x, w1) + b1, alpha1)
     h2 = act(torch.matmul(h1, w2) + b2, alpha2)
     s = torch.matmul(h2, w3.reshape(-1, 1)).squeeze(-1) + b3.reshape(())
-    if softmax:
-        sm = s.masked_fill(~live, float("-inf"))
-        mx = sm.max(dim=1, keepdim=True).values
-        mx = torch.where(torch.isfinite(mx), mx, torch.zeros_like(mx))
-        w = torch.exp(sm - mx)
-        a = w / w.sum(dim=1, keepdim=True).clamp_min(torch.finfo(w.dtype).tiny)      # no live slot: 0 / tiny = 0
-    else:
-        a = s * live.to(s.dtype)
+    a = _masked_softmax(s, live) if softmax else s * live.to(s.dtype)
     return (a.unsqueeze(-1) * keys).sum(dim=1)
 
 
@@ -219,7 +209,7 @@ class DinAttentionLayer(Layer):
         fil_din_plan answers from the launchers' own arithmetic; the answer is cached per shape."""
         if keys.dim() != 3:
             return False
-        return _menu_fits(Fn.din_plan, int(keys.shape[1]), int(keys.shape[2]), *self.hidden_units)
+        return _menu_fits(Fn.din_plan, 1, int(keys.shape[1]), int(keys.shape[2]), *self.hidden_units)
 
     def _composed(self, q, keys, mask):
         """din_attention_graph on the GPU in fp32: a dozen launches and two [B,T,n] blocks per direction where the fused kernel makes
@@ -235,8 +225,7 @@ class DinAttentionLayer(Layer):
             raise ValueError("DinAttentionLayer: query must be [B,1,K] or [B,K] and keys [B,T,K], got %s and %s"
                              % (tuple(query.shape), tuple(keys.shape)))
         q = query.reshape(keys.shape[0], keys.shape[2])
-        if mask is not None and (tuple(mask.shape) != tuple(keys.shape[:2]) or mask.dtype not in (torch.bool, torch.uint8)):
-            raise ValueError("DinAttentionLayer: mask must be a [B,T] bool or uint8 tensor, got %s %s" % (tuple(mask.shape), mask.dtype))
+        _check_seq_mask("DinAttentionLayer", mask, keys.shape[0], keys.shape[1])
         if q.dtype == torch.float32 and keys.dtype == torch.float32 and self.fits_kernel_menu(q, keys):
             pooled = Fn.din_attention(q, keys, mask, *self._weights(), softmax=self.softmax,
                                       activation="sigmoid" if self.activation == "sigmoid" else "prelu")
@@ -316,7 +305,7 @@ class GRULayer(Layer):
         arithmetic; the answer is cached per shape."""
         if x.dim() != 3:
             return False
-        return _menu_fits(Fn.gru_plan, 1, int(x.shape[2]), self.units, self.mode)
+        return _menu_fits(Fn.gru_plan, 1, 1, int(x.shape[2]), self.units, self.mode)      # (the menu does not depend on T either)
 
     def _composed(self, x, scores, mask):
         """gru_graph on the GPU in fp32: about a dozen launches per step where the fused kernel makes one per direction -- it exists so
@@ -338,8 +327,7 @@ class GRULayer(Layer):
             raise ValueError("GRULayer: x must be [B,T,K], got %s" % (tuple(x.shape),))
         if scores is not None and tuple(scores.shape) != tuple(x.shape[:2]):
             raise ValueError("GRULayer: scores must be [B,T] = %s, got %s" % (tuple(x.shape[:2]), tuple(scores.shape)))
-        if mask is not None and (tuple(mask.shape) != tuple(x.shape[:2]) or mask.dtype not in (torch.bool, torch.uint8)):
-            raise ValueError("GRULayer: mask must be a [B,T] bool or uint8 tensor, got %s %s" % (tuple(mask.shape), mask.dtype))
+        _check_seq_mask("GRULayer", mask, x.shape[0], x.shape[1])
         if x.dtype == torch.float32 and (scores is None or scores.dtype == torch.float32) and self.fits_kernel_menu(x):
             return Fn.gru(x, scores, mask, self.kernel, self.recurrent_kernel, self.bias, mode=self.mode,
                           return_sequences=self.return_sequences)
@@ -412,7 +400,7 @@ class SeqSelfAttentionLayer(Layer):
         within the LDS limit -- fil_seqattn_plan answers from the launchers' own arithmetic; the answer is cached per shape."""
         if x.dim() != 3:
             return False
-        return x.shape[1] >= 1 and _menu_fits(Fn.seq_attn_plan, int(x.shape[1]), int(x.shape[2]), self.heads, self.head_dim)
+        return x.shape[1] >= 1 and _menu_fits(Fn.seq_attn_plan, 1, int(x.shape[1]), int(x.shape[2]), self.heads, self.head_dim)
 
     def _flat(self):
         hd = self.heads * self.head_dim
@@ -427,8 +415,7 @@ class SeqSelfAttentionLayer(Layer):
         x = inputs
         if not torch.is_tensor(x) or x.dim() != 3:
             raise ValueError("SeqSelfAttentionLayer: x must be [B,T,K], got %s" % (tuple(x.shape) if torch.is_tensor(x) else type(x).__name__,))
-        if mask is not None and (tuple(mask.shape) != tuple(x.shape[:2]) or mask.dtype not in (torch.bool, torch.uint8)):
-            raise ValueError("SeqSelfAttentionLayer: mask must be a [B,T] bool or uint8 tensor, got %s %s" % (tuple(mask.shape), mask.dtype))
+        _check_seq_mask("SeqSelfAttentionLayer", mask, x.shape[0], x.shape[1])
         if x.dtype == torch.float32 and self.fits_kernel_menu(x):
             return Fn.seq_self_attention(x, mask, *self._flat(), self.heads, use_scale=self.use_scale)
         return self._composed(x, mask)

@@ -12,7 +12,7 @@ import torch
 
 from .. import functional as Fn
 from ..optim import deferred_state
-from .base import Layer, glorot_uniform_, merge_packed_views
+from .base import Layer, _menu_fits, glorot_uniform_, merge_packed_views
 
 
 def pack_fields(inputs):
@@ -194,9 +194,6 @@ class AttentionBaseLayer(Layer):
         return self.output_layer(self._pool(pack_fields(inputs), self.softmax_axis))
 
 
-_AFM_FITS = {}                 # (F, K, A) -> fil_afm_plan's answer (the menu is fixed for the life of the process)
-
-
 class AFMLayer(AttentionBaseLayer):
     """AFM's attention pooling with the softmax over the PAIRS (extension: the paper's layer; AttentionBaseLayer above is the
     reference's, whose softmax over a size-1 axis leaves every weight at 1 and the score weights without gradient).
@@ -217,11 +214,7 @@ class AFMLayer(AttentionBaseLayer):
         launchers' own arithmetic; the answer is cached per shape."""
         if inputs.dim() != 3:
             return False
-        key = (int(inputs.shape[1]), int(inputs.shape[2]), int(self.atten_dim))
-        fits = _AFM_FITS.get(key)
-        if fits is None:
-            fits = _AFM_FITS[key] = Fn.afm_plan(1, *key)["fits"]
-        return fits
+        return _menu_fits(Fn.afm_plan, 1, int(inputs.shape[1]), int(inputs.shape[2]), int(self.atten_dim))
 
     def _composed(self, emb):
         """Fn.fm_pairs (HIP) + the torch graph of AttentionBaseLayer(softmax_axis=1), in fp32: six passes over [B,P,K] per direction

@@ -17,6 +17,7 @@ from .layers import (CIN, AFMLayer, AttentionBaseLayer, BagEmbed, CrossLayer, Di
                      MultHeadAttentionLayer, OPnnLayer, ScoreLayer, SeqSelfAttentionLayer, SparseEmbed, StackLayer)
 from .layers.core_layer import Dense
 from .layers.base import Layer
+from .layers.behavior_layer import _masked_softmax
 from .layers.interactive_layer import pack_fields
 from .layers.core_layer import keras_add
 
@@ -342,27 +343,51 @@ class DINInput(Layer):
                             [hist_idx[:, n] for n in range(N)], None, embed, [keys, masks])
 
 
-class DIN(torch.nn.Module):
-    """Deep Interest Network (extension; the paper's model on DINInput's features): one DinAttentionLayer per behaviour pools the
-    history with the candidate's embedding as the query, then StackLayer over dense + field embeddings + pooled histories ->
-    DnnLayer -> MergeScoreLayer(use_merge=False)."""
+class _BehaviorModel(torch.nn.Module):
+    """What DIN, DIEN and BST share on DINInput's features: one module per behaviour, in the ModuleList named `_list`, built by
+    `_behavior(n)` on the first call that brings behaviour n and called with ([the candidate's embedding, the history's keys],
+    mask=the history's mask); `_collect` turns its result into the list of tensors it contributes.  Then StackLayer over dense +
+    field embeddings + those tensors -> DnnLayer -> MergeScoreLayer(use_merge=False)."""
 
-    def __init__(self, att_hidden_units=(80, 40), att_activation="prelu", att_softmax=False, hidden_units=None):
+    _list = "behaviors"
+
+    def __init__(self, hidden_units=None):
         super().__init__()
-        self.att_args = dict(hidden_units=tuple(att_hidden_units), activation=att_activation, softmax=att_softmax)
-        self.atten = torch.nn.ModuleList()
+        setattr(self, self._list, torch.nn.ModuleList())
         self.stack = StackLayer()
         self.dnn = DnnLayer(hidden_units=hidden_units or [200, 80])
         self.score = MergeScoreLayer(use_merge=False)
 
+    def _behavior(self, n):
+        raise NotImplementedError
+
+    def _collect(self, out):
+        return [out]
+
     def forward(self, inputFea):
         keys, masks = inputFea.seq_embed_list
-        while len(self.atten) < len(keys):
-            self.atten.append(DinAttentionLayer(**self.att_args))
-        pooled = []
+        behaviors = getattr(self, self._list)
+        while len(behaviors) < len(keys):
+            behaviors.append(self._behavior(len(behaviors)))
+        feats = []
         for n, (cand, _) in enumerate(inputFea.seq_info):
-            pooled.append(self.atten[n]([inputFea.sparse_embed[cand], keys[n]], mask=masks[n]))
-        return self.score(self.dnn(self.stack(list(inputFea.dense_inputs) + list(inputFea.sparse_embed) + pooled)))
+            feats += self._collect(behaviors[n]([inputFea.sparse_embed[cand], keys[n]], mask=masks[n]))
+        return self.score(self.dnn(self.stack(list(inputFea.dense_inputs) + list(inputFea.sparse_embed) + feats)))
+
+
+class DIN(_BehaviorModel):
+    """Deep Interest Network (extension; the paper's model on DINInput's features): one DinAttentionLayer per behaviour pools the
+    history with the candidate's embedding as the query, then StackLayer over dense + field embeddings + pooled histories ->
+    DnnLayer -> MergeScoreLayer(use_merge=False)."""
+
+    _list = "atten"
+
+    def __init__(self, att_hidden_units=(80, 40), att_activation="prelu", att_softmax=False, hidden_units=None):
+        super().__init__(hidden_units)
+        self.att_args = dict(hidden_units=tuple(att_hidden_units), activation=att_activation, softmax=att_softmax)
+
+    def _behavior(self, n):
+        return DinAttentionLayer(**self.att_args)
 
 
 class _DienBehavior(Layer):
@@ -385,16 +410,11 @@ class _DienBehavior(Layer):
         q = query.reshape(keys.shape[0], keys.shape[2])
         interests = self.extract(keys, mask=mask)                                # [B,T,H]
         s = torch.matmul(interests, torch.matmul(q, self.att_w.t()).unsqueeze(-1)).squeeze(-1)      # s_t = h_t . (A q)
-        if mask is not None:
-            s = s.masked_fill(~mask.to(torch.bool), float("-inf"))
-        mx = s.max(dim=1, keepdim=True).values
-        mx = torch.where(torch.isfinite(mx), mx, torch.zeros_like(mx))
-        w = torch.exp(s - mx)
-        scores = w / w.sum(dim=1, keepdim=True).clamp_min(torch.finfo(w.dtype).tiny)      # no live slot: 0 / tiny = 0
+        scores = _masked_softmax(s, None if mask is None else mask.to(torch.bool))
         return self.evolve([interests, scores], mask=mask).unsqueeze(1)          # [B,1,H]
 
 
-class DIEN(torch.nn.Module):
+class DIEN(_BehaviorModel):
     """Deep Interest Evolution Network (extension; the paper's model on DINInput's features, without the auxiliary loss).  Per
     behaviour: a GRU over the history keys extracts the interest states (GRULayer(K), Keras' masking), the candidate scores every
     state, s_t = h_t . (A q) with a trainable att_w = A [H,K], softmax over the live slots (the paper's eq. 14), and a second
@@ -403,24 +423,14 @@ class DIEN(torch.nn.Module):
     MergeScoreLayer(use_merge=False)."""
 
     def __init__(self, gru_type="augru", hidden_units=None, seed=2020):
-        super().__init__()
         if gru_type not in ("gru", "augru", "agru"):
             raise ValueError("DIEN: gru_type %r (gru, augru, agru)" % (gru_type,))
+        super().__init__(hidden_units)
         self.gru_type = gru_type
         self.seed = seed
-        self.behaviors = torch.nn.ModuleList()
-        self.stack = StackLayer()
-        self.dnn = DnnLayer(hidden_units=hidden_units or [200, 80])
-        self.score = MergeScoreLayer(use_merge=False)
 
-    def forward(self, inputFea):
-        keys, masks = inputFea.seq_embed_list
-        while len(self.behaviors) < len(keys):
-            self.behaviors.append(_DienBehavior(self.gru_type, seed=self.seed + 2 * len(self.behaviors)))
-        evolved = []
-        for n, (cand, _) in enumerate(inputFea.seq_info):
-            evolved.append(self.behaviors[n]([inputFea.sparse_embed[cand], keys[n]], mask=masks[n]))
-        return self.score(self.dnn(self.stack(list(inputFea.dense_inputs) + list(inputFea.sparse_embed) + evolved)))
+    def _behavior(self, n):
+        return _DienBehavior(self.gru_type, seed=self.seed + 2 * n)
 
 
 class _BstBehavior(Layer):
@@ -465,7 +475,7 @@ class _BstBehavior(Layer):
         return [mean, z[:, T:T + 1]]
 
 
-class BST(torch.nn.Module):
+class BST(_BehaviorModel):
     """Behaviour Sequence Transformer (extension; the paper's model on DINInput's features, one Transformer block).  Per behaviour:
     the history followed by the candidate, [B,T+1,K] (the candidate's slot is always live), plus a trainable pos_embed [T+1,K];
     a = SeqSelfAttentionLayer(att_heads, K // att_heads); y = LayerNorm(seq + a); z = LayerNorm(y + Dense(K)(relu(Dense(ffn_units or
@@ -474,25 +484,18 @@ class BST(torch.nn.Module):
     MergeScoreLayer(use_merge=False)."""
 
     def __init__(self, att_heads=2, ffn_units=None, hidden_units=None, seed=2020):
-        super().__init__()
         if int(att_heads) < 1:
             raise ValueError("BST: att_heads must be positive, got %r" % (att_heads,))
+        super().__init__(hidden_units)
         self.att_heads = int(att_heads)
         self.ffn_units = ffn_units
         self.seed = seed
-        self.behaviors = torch.nn.ModuleList()
-        self.stack = StackLayer()
-        self.dnn = DnnLayer(hidden_units=hidden_units or [200, 80])
-        self.score = MergeScoreLayer(use_merge=False)
 
-    def forward(self, inputFea):
-        keys, masks = inputFea.seq_embed_list
-        while len(self.behaviors) < len(keys):
-            self.behaviors.append(_BstBehavior(self.att_heads, self.ffn_units, seed=self.seed + 2 * len(self.behaviors)))
-        feats = []
-        for n, (cand, _) in enumerate(inputFea.seq_info):
-            feats.extend(self.behaviors[n]([inputFea.sparse_embed[cand], keys[n]], mask=masks[n]))
-        return self.score(self.dnn(self.stack(list(inputFea.dense_inputs) + list(inputFea.sparse_embed) + feats)))
+    def _behavior(self, n):
+        return _BstBehavior(self.att_heads, self.ffn_units, seed=self.seed + 2 * n)
+
+    def _collect(self, out):      # [the mean over the live positions, the candidate's position]
+        return out
 
 
 class CTRModel(torch.nn.Module):

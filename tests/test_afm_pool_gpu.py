@@ -14,18 +14,13 @@ from ml_function_amd import _lib, capture, layers, losses, models, optim
 from ml_function_amd import functional as Fn
 from ml_function_amd._lib import check, ptr, stream_ptr
 from tests import afm_pool_ref as ref
+from tests.seq_common import PAD, SENTINEL, bits, dev, guarded, guards_intact
 
 pytestmark = pytest.mark.gpu
 
-SENTINEL = 12345.678
-PAD = 64                       # guard floats on either side of a guarded tensor (keeps its 256-byte alignment)
 FORMS = [False, True]
 FORM_IDS = ["reference", "paper"]
 KEYS = ("pooled", "de", "dW", "db", "dh")
-
-
-def dev(a):
-    return torch.tensor(np.asarray(a), dtype=torch.float32, device="cuda")
 
 
 @functools.lru_cache(maxsize=None)
@@ -86,16 +81,6 @@ def test_the_largest_shape_of_the_menu_runs():
 
 
 # ---------------------------------------------------------------------------------------------------- 2. batch, tile and grid edges
-def guarded(shape):
-    n = int(np.prod(shape))
-    buf = torch.full((PAD + n + PAD,), SENTINEL, dtype=torch.float32, device="cuda")
-    return buf, buf[PAD:PAD + n].view(*shape)
-
-
-def guards_intact(buf):
-    return bool((buf[:PAD] == SENTINEL).all()) and bool((buf[-PAD:] == SENTINEL).all())
-
-
 def run_raw(case):
     """The two entry points called directly: outputs inside sentinel-guarded allocations, the workspace NaN-poisoned."""
     lib = _lib.load()
@@ -149,10 +134,6 @@ def test_empty_batch_is_a_no_op():
 
 
 # ---------------------------------------------------------------------------------------------------- 3. exact cases
-def bits(a):
-    return np.ascontiguousarray(np.asarray(a, np.float32)).view(np.int32)
-
-
 @pytest.mark.parametrize("hidden_relu", FORMS, ids=FORM_IDS)
 @pytest.mark.parametrize("shape", [(6, 2, 8, 4), (5, 2, 64, 16), (3, 2, 4, 1)], ids=lambda s: "x".join(map(str, s)))
 def test_one_pair_is_the_pair_product_bit_for_bit(shape, hidden_relu):

@@ -14,11 +14,10 @@ from ml_function_amd import _lib, capture, layers, losses, models, optim
 from ml_function_amd import functional as Fn
 from ml_function_amd._lib import check, ptr, stream_ptr
 from tests import din_attn_ref as ref
+from tests.seq_common import PAD, SENTINEL, behaviour_inputs, behaviour_model, bits, dev, dev_mask, guarded, guards_intact
 
 pytestmark = pytest.mark.gpu
 
-SENTINEL = 12345.678
-PAD = 64                       # guard floats on either side of a guarded tensor (keeps its 256-byte alignment)
 ACTS = ["prelu", "sigmoid"]
 MODES = [False, True]
 MODE_IDS = ["raw", "softmax"]
@@ -26,21 +25,9 @@ NAMES = ("q", "keys") + ref.PARAMS
 both = lambda f: pytest.mark.parametrize("softmax", MODES, ids=MODE_IDS)(pytest.mark.parametrize("activation", ACTS)(f))
 
 
-def dev(a, dtype=torch.float32):
-    return torch.tensor(np.asarray(a), dtype=dtype, device="cuda")
-
-
-def dev_mask(case):
-    return None if case.get("mask") is None else dev(case["mask"], torch.uint8)
-
-
 @functools.lru_cache(maxsize=None)
 def case_of(shape, activation, softmax, seed=0, mask="ragged", alpha_max=0.3):
     return ref.make_case(*shape, activation, softmax, seed, mask=mask, alpha_max=alpha_max)
-
-
-def bits(a):
-    return np.ascontiguousarray(np.asarray(a, np.float32)).view(np.int32)
 
 
 def run_op(case, wanted=NAMES):
@@ -104,16 +91,6 @@ def test_the_corners_of_the_menu(shape, softmax):
 
 
 # ---------------------------------------------------------------------------------------------------- 2. batch, tile and grid edges
-def guarded(shape):
-    n = int(np.prod(shape))
-    buf = torch.full((PAD + n + PAD,), SENTINEL, dtype=torch.float32, device="cuda")
-    return buf, buf[PAD:PAD + n].view(*shape)
-
-
-def guards_intact(buf):
-    return bool((buf[:PAD] == SENTINEL).all()) and bool((buf[-PAD:] == SENTINEL).all())
-
-
 def run_raw(case):
     """The two entry points called directly: outputs inside sentinel-guarded allocations, the workspace NaN-poisoned."""
     lib = _lib.load()
@@ -446,28 +423,15 @@ def test_layer_computes_a_half_precision_input_in_fp32():
     assert ref.norm_rel(half["out"], full["out"]) < 1e-5
 
 
-def _din_inputs(B, vocab, T, seed, n_dense=0):
-    rng = np.random.default_rng(seed)
-    idx = torch.tensor(np.stack([rng.integers(1, v, B) for v in vocab], 1), device="cuda")
-    hist = rng.integers(1, vocab[0], (B, T))
-    lens = rng.integers(1, T + 1, B)
-    hist[np.arange(T)[None, :] >= lens[:, None]] = 0              # id 0 = padding
-    hist = hist.reshape(B, 1, T)
-    dense = torch.tensor(rng.random((B, n_dense)), dtype=torch.float32, device="cuda") if n_dense else None
-    return dense, idx, torch.tensor(hist, device="cuda")
-
-
 def _din_model(vocab, T, K, seed, **kw):
-    torch.manual_seed(seed)
-    info = models.make_sparse_info(vocab, embed_dim=K, names=["item", "user", "ctx"][:len(vocab)])
-    return models.CTRModel(models.DINInput(info, behavior=[("item", T)]), models.DIN(att_hidden_units=(16, 8), hidden_units=[32, 16], **kw)).cuda()
+    return behaviour_model(lambda: models.DIN(att_hidden_units=(16, 8), hidden_units=[32, 16], **kw), vocab, T, K, seed)
 
 
 @pytest.mark.parametrize("softmax", MODES, ids=MODE_IDS)
 def test_din_trains(softmax):
     vocab, T, K, B = [12, 5, 7], 6, 8, 64
     model = _din_model(vocab, T, K, 0, att_softmax=softmax)
-    dense, idx, hist = _din_inputs(B, vocab, T, seed=1, n_dense=2)
+    dense, idx, hist = behaviour_inputs(B, vocab, T, seed=1, n_dense=2)
     y = torch.tensor(np.random.default_rng(2).integers(0, 2, B), dtype=torch.float32, device="cuda")
     out = model(dense, idx, hist)
     assert out.shape == (B, 2)                      # MergeScoreLayer's softmax over two classes
@@ -491,7 +455,7 @@ def test_shared_table_gradient_is_the_sum_of_the_two_gathers():
     vocab, T, K, B = [12, 5], 6, 8, 33
     info = models.make_sparse_info(vocab, embed_dim=K, names=["item", "user"])
     fi = models.DINInput(info, behavior=[("item", T)]).cuda()
-    _, idx, hist = _din_inputs(B, vocab, T, seed=3)
+    _, idx, hist = behaviour_inputs(B, vocab, T, seed=3)
     fea = fi((None, idx, hist))
     keys, masks = fea.seq_embed_list
     assert len(fea.sparse_embed) == 2 and keys[0].shape == (B, T, K) and masks[0].shape == (B, T) and masks[0].dtype == torch.bool
@@ -517,7 +481,7 @@ def test_captured_din_step_replays_the_eager_steps_bits():
     rng = np.random.default_rng(5)
     batches = []
     for s in range(3):
-        _, idx, hist = _din_inputs(B, vocab, T, seed=40 + s)
+        _, idx, hist = behaviour_inputs(B, vocab, T, seed=40 + s)
         batches.append((idx, hist, torch.tensor(rng.integers(0, 2, B), dtype=torch.float32, device="cuda")))
 
     def make():

@@ -14,6 +14,7 @@ from ml_function_amd import functional as Fn
 from ml_function_amd._lib import check, ptr, stream_ptr
 from tests import gru_ref as ref
 from tests import guarded
+from tests.seq_common import behaviour_inputs, behaviour_model, bits, dev, dev_mask, same_bits
 
 pytestmark = pytest.mark.gpu
 
@@ -23,27 +24,9 @@ modes = pytest.mark.parametrize("mode", MODES)
 ids_of = lambda s: "x".join(map(str, s))
 
 
-def dev(a, dtype=torch.float32):
-    return torch.tensor(np.asarray(a), dtype=dtype, device="cuda")
-
-
-def dev_mask(case):
-    return None if case.get("mask") is None else dev(case["mask"], torch.uint8)
-
-
 @functools.lru_cache(maxsize=None)
 def case_of(shape, mode, seed=0, mask="ragged", grads="both"):
     return ref.make_case(*shape, mode, seed, mask=mask, grads=grads)
-
-
-def bits(a):
-    return np.ascontiguousarray(np.asarray(a, np.float32)).view(np.int32)
-
-
-def same_bits(a, b, what=""):
-    for k, v in a.items():
-        if v is not None:
-            assert np.array_equal(bits(v), bits(b[k])), (what, k)
 
 
 def run_op(case, wanted=NAMES):
@@ -360,19 +343,8 @@ def test_layer_computes_a_half_precision_input_in_fp32(mode):
     check_parity(half, case16, keys=("hs", "dW", "dU", "db"), label="bf16 in")
 
 
-def _dien_inputs(B, vocab, T, seed):
-    rng = np.random.default_rng(seed)
-    idx = torch.tensor(np.stack([rng.integers(1, v, B) for v in vocab], 1), device="cuda")
-    hist = rng.integers(1, vocab[0], (B, T))
-    lens = rng.integers(1, T + 1, B)
-    hist[np.arange(T)[None, :] >= lens[:, None]] = 0              # id 0 = padding
-    return idx, torch.tensor(hist.reshape(B, 1, T), device="cuda")
-
-
 def _dien_model(vocab, T, K, seed, **kw):
-    torch.manual_seed(seed)
-    info = models.make_sparse_info(vocab, embed_dim=K, names=["item", "user", "ctx"][:len(vocab)])
-    return models.CTRModel(models.DINInput(info, behavior=[("item", T)]), models.DIEN(hidden_units=[32, 16], **kw)).cuda()
+    return behaviour_model(lambda: models.DIEN(hidden_units=[32, 16], **kw), vocab, T, K, seed)
 
 
 @pytest.mark.parametrize("gru_type", ["augru", "agru"])
@@ -381,7 +353,7 @@ def test_dien_against_the_model_built_from_the_composed_layers(gru_type, monkeyp
     and every parameter gradient agree within 1e-5, the floor of the bars max(1e-5, 4 E32) (no fp64 model is built here, so the
     term that could only widen the bar is left out)."""
     vocab, T, K, B = [12, 5, 7], 6, 8, 5
-    idx, hist = _dien_inputs(B, vocab, T, seed=1)
+    _, idx, hist = behaviour_inputs(B, vocab, T, seed=1)
     y = torch.tensor([1.0, 0.0, 1.0, 1.0, 0.0], device="cuda")
     model = _dien_model(vocab, T, K, 3, gru_type=gru_type)
 
@@ -413,7 +385,7 @@ def test_dien_trains_under_captured_adam_and_replays_the_eager_bits():
     rng = np.random.default_rng(5)
     batches = []
     for s in range(3):
-        idx, hist = _dien_inputs(B, vocab, T, seed=40 + s)
+        _, idx, hist = behaviour_inputs(B, vocab, T, seed=40 + s)
         batches.append((idx, hist, torch.tensor(rng.integers(0, 2, B), dtype=torch.float32, device="cuda")))
 
     def make():
