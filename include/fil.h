@@ -466,6 +466,59 @@ int fil_gru_bwd(const float* x, const float* a, const unsigned char* mask, const
                 void* workspace, size_t workspace_bytes, int B, int T, int K, int H, int mode, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * N3  LSTM over a sequence, one direction or both in one launch (extension: TF 2 Keras' LSTM with its defaults -- sigmoid / tanh,
+ *     one bias, no dropout -- and Keras' Bidirectional(LSTM), the session interest interacting layer of the Deep Session Interest
+ *     Network paper; the reference's rnn_demo.py is not restated, its source was not available).  All tensors fp32 except mask.
+ *     Entry points added only: the ABI version stays.
+ *   dirs: FIL_LSTM_FORWARD, FIL_LSTM_REVERSE or FIL_LSTM_BIDIR; ndir = 2 for FIL_LSTM_BIDIR, else 1.
+ *   x [B,T,K] the sequence; mask [B,T] uint8, non-zero = live, NULL = all live (live slots may sit anywhere); per direction W [K,4H],
+ *   U [H,4H] in Keras' column order i | f | c | o and ONE bias b [4H]: W [ndir,K,4H], U [ndir,H,4H], b [ndir,4H], the forward
+ *   direction first; hs [B,T,ndir*H] the output, the forward direction in the columns 0 .. H-1 and the reverse in H .. 2H-1 (the
+ *   concatenation is fused).  One live step, h and c = the previous states, h_0 = c_0 = 0:
+ *     z = x_t W + h U + b;  i = sigmoid(z_i);  f = sigmoid(z_f);  g = tanh(z_c);  o = sigmoid(z_o);
+ *     c_new = fma(f, c, i * g);  h_new = o * tanh(c_new).
+ *   A masked step carries BOTH states: hs[b,t] = h bit for bit (zeros before the first live step); its x_t is never read.
+ *   The forward direction walks t = 0 .. T-1, the reverse t = T-1 .. 0 and stores the state reached after step t at position t (Keras'
+ *   go_backwards with the output turned back): its last state is hs[:,0].  REVERSE on the time-reversed inputs returns FORWARD's bits,
+ *   time-reversed, and one BIDIR call returns the bits of a FORWARD and a REVERSE call on the two halves of the weights.
+ *   fil_lstm_fwd: hs, and `saved` [ndir,B,T,5,H] = (i, f, g, o) of the live steps and the cell c after EVERY step (c_prev of a live step
+ *     is the cell carried across masked steps) for the backward (fil_lstm_saved_bytes; opaque to the caller; the gates of masked steps
+ *     are left unwritten; NULL: nothing is saved, for inference).  x_t W is fused into the step.
+ *   fil_lstm_bwd: g_hs [B,T,ndir*H] and / or g_last [B,ndir*H] (the gradient of the directions' last states, the forward hs[:,T-1,:H]
+ *     and the reverse hs[:,0,H:], for return_sequences=False; either may be NULL, not both) -> dx [B,T,K], dW, dU, db in the shapes of
+ *     W, U, b.  No product is recomputed: the gates come from `saved`, the previous h from hs; tanh(c_new) is taken again from the
+ *     saved cell.  A masked step passes both state gradients through unchanged; dx is exactly 0 there (in BIDIR: the sum of two
+ *     zeros).  Each output may be NULL and is then not computed, the others keep the bits of the full call (dW, dU, db all NULL: no
+ *     parameter pass; all four NULL: FIL_ERR_ARG).  The parameter gradients leave the main launch as one partial per workgroup in
+ *     `workspace` and a small launch per direction adds that direction's partials in a fixed order; in BIDIR the reverse direction's
+ *     dx goes to the workspace as well and one more small launch adds it to dx.  The workspace (fil_lstm_bwd_workspace_bytes; every
+ *     byte that is read was written by the main launch) is needed for a parameter gradient, and in BIDIR for dx.
+ *   One main launch per pass, both directions of BIDIR in it (a grid dimension selects the direction; a workgroup stages only its
+ *   own direction's weights).  No atomics; every sum has a fixed order for a given shape: the same inputs give the same bits on
+ *   every call.
+ *   Menu: any T >= 1; K % 4 == 0, H % 4 == 0, K <= 64, H <= 64, and both passes within 163,328 bytes of dynamic LDS: every such
+ *   shape with H <= 56, H = 60 with K <= 52, H = 64 with K <= 40 (the backward's 4 ((K + H) 4H + (2 (K + H) + 4H) (NS + 4) + NS 4H +
+ *   2 NS) bytes with NS = 16 there decide it: 159,104 at K = 64, H = 56; 188,544 at K = H = 64).  FIL_ERR_UNSUPPORTED otherwise, the
+ *   needed and the allowed bytes in the message.
+ *   B == 0 returns FIL_OK before any pointer is looked at.  A workspace smaller than needed: FIL_ERR_ARG, the needed size in the message.
+ *   fil_lstm_plan: the launchers' own arithmetic (no GPU call): plan[8] = {fwd_ok, bwd_ok, samples per workgroup tile, workgroups per
+ *     direction, their cap, parameter-gradient partials (= ndir * workgroups per direction), forward LDS bytes, backward LDS bytes}.
+ *     The tile grows with B (small batches take small tiles and more workgroups).  Returns FIL_OK, or the argument / menu error the
+ *     launch would give.
+ */
+#define FIL_LSTM_FORWARD 0
+#define FIL_LSTM_REVERSE 1
+#define FIL_LSTM_BIDIR 2
+int fil_lstm_plan(int B, int T, int K, int H, int dirs, int* plan /* [8] */);
+size_t fil_lstm_saved_bytes(int B, int T, int K, int H, int dirs);
+int fil_lstm_fwd(const float* x, const unsigned char* mask, const float* W, const float* U, const float* b, float* hs, float* saved,
+                 int B, int T, int K, int H, int dirs, void* stream);
+size_t fil_lstm_bwd_workspace_bytes(int B, int T, int K, int H, int dirs);
+int fil_lstm_bwd(const float* x, const unsigned char* mask, const float* W, const float* U, const float* hs, const float* saved,
+                 const float* g_hs, const float* g_last, float* dx, float* dW, float* dU, float* db, void* workspace,
+                 size_t workspace_bytes, int B, int T, int K, int H, int dirs, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * N3  Masked multi-head self-attention over a behaviour sequence (extension: the scaled dot-product layer of "Attention is all you
  *     need" as the Behaviour Sequence Transformer applies it to a history; NOT the reference's MultHeadAttentionLayer, which
  *     fil_attn_* / fil_pattn_* restate and which stays as it is).  All tensors fp32 except mask.  Entry points added only: the ABI

@@ -42,6 +42,7 @@ FIL_BAG_MAX_BLOCKS = 2048        # fil_embed_bag_fwd's grid cap (workgroups of 2
 FIL_AFM_HIDDEN_RELU = 1          # fil_afm_*'s flag bit 0: s_p = relu(u_p) . h (the paper's form)
 FIL_DIN_SOFTMAX, FIL_DIN_SIGMOID = 1, 2   # fil_din_*'s flag bits: softmax over the live slots; sigmoid instead of PReLU
 FIL_GRU_GRU, FIL_GRU_AUGRU, FIL_GRU_AGRU = 0, 1, 2   # fil_gru_*'s mode
+FIL_LSTM_FORWARD, FIL_LSTM_REVERSE, FIL_LSTM_BIDIR = 0, 1, 2   # fil_lstm_*'s dirs
 FIL_ERR_UNSUPPORTED = -4
 
 _c = ctypes
@@ -109,6 +110,12 @@ SIGNATURES = {
     "fil_gru_fwd": (_I, [_P] * 8 + [_I] * 5 + [_P]),
     "fil_gru_bwd_workspace_bytes": (_Z, [_I, _I, _I, _I]),
     "fil_gru_bwd": (_I, [_P] * 15 + [_Z] + [_I] * 5 + [_P]),
+    # N3: LSTM over a sequence, one direction or both in one launch
+    "fil_lstm_plan": (_I, [_I, _I, _I, _I, _I, _P]),
+    "fil_lstm_saved_bytes": (_Z, [_I, _I, _I, _I, _I]),
+    "fil_lstm_fwd": (_I, [_P] * 7 + [_I] * 5 + [_P]),
+    "fil_lstm_bwd_workspace_bytes": (_Z, [_I, _I, _I, _I, _I]),
+    "fil_lstm_bwd": (_I, [_P] * 13 + [_Z] + [_I] * 5 + [_P]),
     # N3: masked multi-head self-attention over a behaviour sequence
     "fil_seqattn_plan": (_I, [_I, _I, _I, _I, _I, _P]),
     "fil_seqattn_saved_bytes": (_Z, [_I, _I, _I, _I, _I]),

@@ -421,6 +421,93 @@ def gru_plan(B, T, K, H, mode="gru"):
     return _tiled_plan("fil_gru_plan", int(B), int(T), int(K), int(H), GRU_MODES[mode])
 
 
+LSTM_DIRECTIONS = {"forward": _lib.FIL_LSTM_FORWARD, "reverse": _lib.FIL_LSTM_REVERSE, "bidirectional": _lib.FIL_LSTM_BIDIR}
+
+
+def _lstm_last(hs, dirs, H):
+    """The directions' last states [B, ndir H] from hs [B,T,ndir H]: the forward direction's sits at T - 1, the reverse one's at 0."""
+    if dirs == _lib.FIL_LSTM_FORWARD:
+        return hs[:, -1].clone()
+    if dirs == _lib.FIL_LSTM_REVERSE:
+        return hs[:, 0].clone()
+    return torch.cat([hs[:, -1, :H], hs[:, 0, H:]], dim=1)
+
+
+class _LstmFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, mask, w, u, b, dirs, return_sequences):
+        _require_cuda(x, mask, w, u, b)
+        x, w, u, b = (_f32c(t) for t in (x, w, u, b))
+        ndir = 2 if dirs == _lib.FIL_LSTM_BIDIR else 1
+        lead = (2,) if ndir == 2 else ()
+        if x.dim() != 3 or u.dim() != len(lead) + 2:
+            raise FilError("lstm: x must be [B,T,K] and U %s, got %s and %s"
+                           % ("[2,H,4H]" if lead else "[H,4H]", tuple(x.shape), tuple(u.shape)))
+        B, T, K = x.shape
+        H = u.shape[-2]
+        if tuple(w.shape) != lead + (K, 4 * H) or tuple(u.shape) != lead + (H, 4 * H) or tuple(b.shape) != lead + (4 * H,):
+            raise FilError("lstm: W, U and b must be %s with K = %d and H = %d, got %s, %s and %s"
+                           % ("[2,K,4H], [2,H,4H] and [2,4H]" if lead else "[K,4H], [H,4H] and [4H]", K, H, tuple(w.shape), tuple(u.shape),
+                              tuple(b.shape)))
+        mask = _seq_mask("lstm", mask, B, T)
+        lib = _lib.load()
+        hs = torch.empty((B, T, ndir * H), dtype=torch.float32, device=x.device)
+        need = ctx.needs_input_grad
+        saved = None
+        if any(need[i] for i in (0, 2, 3, 4)):
+            saved = _saved_floats(lib.fil_lstm_saved_bytes(B, T, K, H, dirs), x.device)
+        check(lib.fil_lstm_fwd(ptr(x), ptr(mask), ptr(w), ptr(u), ptr(b), ptr(hs), ptr(saved), B, T, K, H, dirs, stream_ptr()), "fil_lstm_fwd")
+        _save(ctx, x, mask, w, u, hs, saved)
+        ctx.dirs, ctx.return_sequences = dirs, return_sequences
+        if return_sequences:
+            return hs
+        return _lstm_last(hs, dirs, H) if B > 0 else hs.new_zeros((0, ndir * H))
+
+    @staticmethod
+    def backward(ctx, g):
+        need = ctx.needs_input_grad
+        if not (need[0] or need[2] or need[3] or need[4]):
+            return (None,) * 7
+        x, mask, w, u, hs, saved = _saved(ctx)
+        B, T, K = x.shape
+        H = u.shape[-2]
+        dev = x.device
+        dx = _grad(need[0], x.shape, dev)
+        dw = _grad(need[2], w.shape, dev)
+        du = _grad(need[3], u.shape, dev)
+        db = _grad(need[4], u.shape[:-2] + (4 * H,), dev)
+        if B == 0:      # the library's no-op writes nothing: the sums over no sample are zero
+            return (dx,) + (None,) + tuple(None if t is None else t.zero_() for t in (dw, du, db)) + (None, None)
+        g = _f32c(g)
+        g_hs, g_last = (g, None) if ctx.return_sequences else (None, g)
+        # the partials of the parameter gradients, and with both directions in one launch the second direction's dx
+        uses_ws = need[2] or need[3] or need[4] or (ctx.dirs == _lib.FIL_LSTM_BIDIR and need[0])
+        ws, nws = _partials_scratch("fil_lstm_bwd_workspace_bytes", "lstm_bwd", uses_ws, dev, B, T, K, H, ctx.dirs)
+        check(_lib.load().fil_lstm_bwd(ptr(x), ptr(mask), ptr(w), ptr(u), ptr(hs), ptr(saved), ptr(g_hs), ptr(g_last), ptr(dx), ptr(dw),
+                                       ptr(du), ptr(db), ptr(ws), nws, B, T, K, H, ctx.dirs, stream_ptr()), "fil_lstm_bwd")
+        return dx, None, dw, du, db, None, None
+
+
+def lstm(x, mask, W, U, b, direction="forward", return_sequences=True):
+    """An LSTM over a sequence, in one direction or in both (extension; include/fil.h fil_lstm_*): x [B,T,K], mask [B,T] bool / uint8
+    (non-zero = live; None = all live), W [K,4H], U [H,4H] (Keras' column order i | f | c | o), b [4H] -> hs [B,T,H].  direction
+    "reverse" walks t = T-1 .. 0 and leaves the state reached after step t at position t (Keras' go_backwards with the output turned
+    back); "bidirectional" takes W [2,K,4H], U [2,H,4H], b [2,4H] (forward, reverse) and returns [B,T,2H], the forward direction in
+    the first H columns -- both directions run in ONE launch per pass.  With return_sequences=False the result is the directions' last
+    states [B, ndir H] (the forward hs[:,T-1], the reverse hs[:,0]); their gradient enters the backward as [B, ndir H]: no zero
+    [B,T,.] block is made.  A masked step repeats both states (Keras' masking).  Only the gradients that are asked for are computed.
+    GPU only; shapes outside the kernel menu raise FilError (layers.LSTMLayer / BiLSTMLayer take their composed path there)."""
+    if direction not in LSTM_DIRECTIONS:
+        raise ValueError("lstm: direction %r (%s)" % (direction, ", ".join(LSTM_DIRECTIONS)))
+    return _LstmFn.apply(x, mask, W, U, b, LSTM_DIRECTIONS[direction], bool(return_sequences))
+
+
+def lstm_plan(B, T, K, H, direction="forward"):
+    """fil_lstm_plan's answer as a dict (fits, tile, grid, cap, partials, lds_fwd, lds_bwd; grid and cap count the workgroups of one
+    direction); fits=False (and nothing else) for a shape outside the kernel menu."""
+    return _tiled_plan("fil_lstm_plan", int(B), int(T), int(K), int(H), LSTM_DIRECTIONS[direction])
+
+
 class _SeqAttnFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, mask, wq, wk, wv, heads, use_scale):

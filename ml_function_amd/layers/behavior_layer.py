@@ -4,7 +4,8 @@ sigmoid (:286,308), V is projected with key_w (:360; value_w exists but never re
 epsilon is Keras' default 1e-3, the output is head-major [H,B,F,A].
 Behaviour-sequence layers (extensions), each one fused kernel per direction with a composed torch path outside the kernel menu:
 DinAttentionLayer (the Deep Interest Network's attention pooling), GRULayer (a GRU and the Deep Interest Evolution Network's AUGRU /
-AGRU) and SeqSelfAttentionLayer (the Behaviour Sequence Transformer's masked self-attention)."""
+AGRU), LSTMLayer / BiLSTMLayer (Keras' LSTM and Bidirectional(LSTM), the Deep Session Interest Network's session interest
+interacting layer) and SeqSelfAttentionLayer (the Behaviour Sequence Transformer's masked self-attention)."""
 import torch
 
 from .. import functional as Fn
@@ -332,6 +333,159 @@ class GRULayer(Layer):
             return Fn.gru(x, scores, mask, self.kernel, self.recurrent_kernel, self.bias, mode=self.mode,
                           return_sequences=self.return_sequences)
         return self._composed(x, scores, mask)
+
+
+_LSTM_DIRECTIONS = ("forward", "reverse", "bidirectional")
+
+
+def lstm_graph(x, mask, w, u, b, direction="forward", return_sequences=True):
+    """Fn.lstm's math as torch ops on the tensors given (their dtype and device; autograd for the backward), one step at a time: the
+    composed path of LSTMLayer / BiLSTMLayer and the comparator of their benchmark -- about a dozen launches per step and direction.
+    mask: [B,T] bool or None.  x_t of a masked step is replaced by zero before anything reads it.  "bidirectional": w [2,K,4H],
+    u [2,H,4H], b [2,4H] -> [B,T,2H] (or the two last states [B,2H]), the forward direction first."""
+    if direction == "bidirectional":
+        return torch.cat([lstm_graph(x, mask, w[i], u[i], b[i], d, return_sequences) for i, d in enumerate(_LSTM_DIRECTIONS[:2])], dim=-1)
+    B, T, K = x.shape
+    H = u.shape[0]
+    live = None if mask is None else mask.to(torch.bool)
+    if live is not None:
+        x = torch.where(live.unsqueeze(-1), x, torch.zeros((), dtype=x.dtype, device=x.device))
+    h = torch.zeros((B, H), dtype=x.dtype, device=x.device)
+    c = torch.zeros((B, H), dtype=x.dtype, device=x.device)
+    out = [None] * T
+    for t in (range(T - 1, -1, -1) if direction == "reverse" else range(T)):
+        z = torch.matmul(x[:, t], w) + torch.matmul(h, u) + b
+        i, f, o = torch.sigmoid(z[:, :H]), torch.sigmoid(z[:, H:2 * H]), torch.sigmoid(z[:, 3 * H:])
+        cn = f * c + i * torch.tanh(z[:, 2 * H:3 * H])
+        hn = o * torch.tanh(cn)
+        if live is not None:
+            cn, hn = torch.where(live[:, t:t + 1], cn, c), torch.where(live[:, t:t + 1], hn, h)
+        h, c = hn, cn
+        out[t] = h
+    return torch.stack(out, dim=1) if return_sequences else h
+
+
+class _LstmBase(Layer):
+    """What LSTMLayer and BiLSTMLayer share: the input checks and the choice between the fused op and the composed path."""
+
+    direction = None
+
+    def _weights(self):
+        raise NotImplementedError
+
+    def fits_kernel_menu(self, x):
+        """fil_lstm_*'s menu (include/fil.h): K % 4 == 0, H % 4 == 0, K <= 64, H <= 64 and both passes within the LDS limit (every such
+        shape with H <= 56, H = 60 with K <= 52, H = 64 with K <= 40) -- fil_lstm_plan answers from the launchers' own arithmetic;
+        the answer is cached per shape."""
+        if x.dim() != 3:
+            return False
+        return _menu_fits(Fn.lstm_plan, 1, 1, int(x.shape[2]), self.units, self.direction)      # (the menu does not depend on T)
+
+    def _composed(self, x, mask):
+        """lstm_graph on the GPU in fp32: about a dozen launches per step and direction where the fused kernel makes one per pass --
+        it exists so that a shape outside the kernel menu never raises."""
+        Fn._require_cuda(x, mask)      # (torch ops would run on a CPU tensor: there is no CPU path in this package)
+        return lstm_graph(x.to(torch.float32), mask, *self._weights(), direction=self.direction, return_sequences=self.return_sequences)
+
+    def _run(self, x, mask):
+        who = type(self).__name__
+        if not torch.is_tensor(x) or x.dim() != 3:
+            raise ValueError("%s: x must be [B,T,K], got %s" % (who, tuple(x.shape) if torch.is_tensor(x) else type(x).__name__))
+        _check_seq_mask(who, mask, x.shape[0], x.shape[1])
+        if x.dtype == torch.float32 and self.fits_kernel_menu(x):
+            return Fn.lstm(x, mask, *self._weights(), direction=self.direction, return_sequences=self.return_sequences)
+        return self._composed(x, mask)
+
+
+def _lstm_bias(p):
+    """Keras' LSTM bias with unit_forget_bias=True: zeros, the forget block (the second quarter) at ones."""
+    with torch.no_grad():
+        p.zero_()
+        h = p.shape[0] // 4
+        p[h:2 * h] = 1.0
+
+
+class LSTMLayer(_LstmBase):
+    """An LSTM over a sequence (extension: TF 2 Keras' LSTM with its defaults -- sigmoid / tanh, unit_forget_bias, no dropout).
+
+    call(x [B,T,K], mask=None) -> hs [B,T,units], or the last state [B,units] with return_sequences=False.  go_backwards=True walks
+    t = T-1 .. 0; the sequence it returns is turned back, so hs[:, t] is the state reached after step t and the last state is
+    hs[:, 0] (Keras returns the walking order: flip(1) gives it).  mask: a [B,T] bool or uint8 tensor, non-zero = live; a masked step
+    repeats both states, zeros before the first live step (Keras' masking).  Weights carry Keras' names and defaults: kernel
+    [K,4 units] glorot_uniform(seed), recurrent_kernel [units,4 units] orthogonal(seed), bias [4 units] zeros with the forget block at
+    ones; the column order is i | f | c | o.  The whole recurrence runs in ONE HIP kernel per pass (Fn.lstm, include/fil.h
+    fil_lstm_*).  Outside the kernel menu (fits_kernel_menu) or for a non-fp32 input the layer takes the composed path -- lstm_graph
+    on the GPU, computed in fp32 -- instead of raising."""
+
+    def __init__(self, units, return_sequences=True, go_backwards=False, seed=2020):
+        super().__init__()
+        if int(units) < 1:
+            raise ValueError("LSTMLayer: units must be positive, got %r" % (units,))
+        self.units = int(units)
+        self.return_sequences = bool(return_sequences)
+        self.go_backwards = bool(go_backwards)
+        self.direction = "reverse" if self.go_backwards else "forward"
+        self.seed = seed
+
+    def build(self, input_shape):
+        k, h = int(input_shape[-1]), self.units
+        self.kernel = self.add_weight("kernel", [k, 4 * h], "glorot_uniform", seed=self.seed)
+        self.recurrent_kernel = self.add_weight("recurrent_kernel", [h, 4 * h], "orthogonal", seed=self.seed)
+        self.bias = self.add_weight("bias", [4 * h], _lstm_bias)
+        super().build(input_shape)
+
+    def _weights(self):
+        return self.kernel, self.recurrent_kernel, self.bias
+
+    def call(self, inputs, mask=None, **kwargs):
+        return self._run(inputs, mask)
+
+
+_MERGE_MODES = ("concat", "sum", "ave")
+
+
+class BiLSTMLayer(_LstmBase):
+    """Keras' Bidirectional(LSTM(units)) (extension; the session interest interacting layer of the Deep Session Interest Network).
+
+    call(x [B,T,K], mask=None) -> [B,T,2 units] with merge_mode "concat" (the forward direction first), [B,T,units] with "sum" or
+    "ave"; with return_sequences=False the directions' last states (the forward one's after t = T-1, the backward one's after t = 0)
+    merged the same way.  Weights: forward_kernel, forward_recurrent_kernel, forward_bias and backward_* with LSTMLayer's shapes and
+    initialisers (the backward direction seeded with seed + 1).  Both directions run in ONE launch per pass (Fn.lstm with direction
+    "bidirectional"), which writes the concatenation; "sum" and "ave" are torch ops on its two halves.  Masking, the kernel menu and
+    the composed path are LSTMLayer's."""
+
+    direction = "bidirectional"
+
+    def __init__(self, units, merge_mode="concat", return_sequences=True, seed=2020):
+        super().__init__()
+        if int(units) < 1:
+            raise ValueError("BiLSTMLayer: units must be positive, got %r" % (units,))
+        if merge_mode not in _MERGE_MODES:
+            raise ValueError("BiLSTMLayer: merge_mode %r (%s)" % (merge_mode, ", ".join(_MERGE_MODES)))
+        self.units = int(units)
+        self.merge_mode = merge_mode
+        self.return_sequences = bool(return_sequences)
+        self.seed = seed
+
+    def build(self, input_shape):
+        k, h = int(input_shape[-1]), self.units
+        for n, name in enumerate(("forward", "backward")):
+            setattr(self, name + "_kernel", self.add_weight(name + "_kernel", [k, 4 * h], "glorot_uniform", seed=self.seed + n))
+            setattr(self, name + "_recurrent_kernel", self.add_weight(name + "_recurrent_kernel", [h, 4 * h], "orthogonal", seed=self.seed + n))
+            setattr(self, name + "_bias", self.add_weight(name + "_bias", [4 * h], _lstm_bias))
+        super().build(input_shape)
+
+    def _weights(self):
+        return (torch.stack([self.forward_kernel, self.backward_kernel]),
+                torch.stack([self.forward_recurrent_kernel, self.backward_recurrent_kernel]),
+                torch.stack([self.forward_bias, self.backward_bias]))
+
+    def call(self, inputs, mask=None, **kwargs):
+        out = self._run(inputs, mask)
+        if self.merge_mode == "concat":
+            return out
+        fwd, bwd = out[..., :self.units], out[..., self.units:]
+        return fwd + bwd if self.merge_mode == "sum" else (fwd + bwd) * 0.5
 
 
 def seq_self_attention_graph(x, mask, wq, wk, wv, heads, use_scale=True):

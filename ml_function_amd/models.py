@@ -6,14 +6,15 @@ the concrete InputFeature of one batch, and ``CTRModel`` chains FeatureInput -> 
 tensors.  Hyper-parameter names and defaults are the reference's.  Sequence models are out of scope,
 except DINInput / DIN (extension): the Deep Interest Network's attention pooling of behaviour histories (layers.DinAttentionLayer),
 DIEN (extension): the Deep Interest Evolution Network's GRU + AUGRU over the same histories (layers.GRULayer),
-and BST (extension): the Behaviour Sequence Transformer's block over them (layers.SeqSelfAttentionLayer).
+BST (extension): the Behaviour Sequence Transformer's block over them (layers.SeqSelfAttentionLayer),
+and DSIN (extension): the Deep Session Interest Network's sessions, self-attention and bidirectional LSTM (layers.BiLSTMLayer).
 """
 from collections import namedtuple
 
 import torch
 
 from . import functional as Fn
-from .layers import (CIN, AFMLayer, AttentionBaseLayer, BagEmbed, CrossLayer, DinAttentionLayer, DnnLayer, FmLayer, GRULayer, InnerLayer, IPnnLayer, MergeScoreLayer,
+from .layers import (CIN, AFMLayer, AttentionBaseLayer, BagEmbed, BiLSTMLayer, CrossLayer, DinAttentionLayer, DnnLayer, FmLayer, GRULayer, InnerLayer, IPnnLayer, MergeScoreLayer,
                      MultHeadAttentionLayer, OPnnLayer, ScoreLayer, SeqSelfAttentionLayer, SparseEmbed, StackLayer)
 from .layers.core_layer import Dense
 from .layers.base import Layer
@@ -433,10 +434,10 @@ class DIEN(_BehaviorModel):
         return _DienBehavior(self.gru_type, seed=self.seed + 2 * n)
 
 
-class _BstBehavior(Layer):
-    """One behaviour of BST: a Transformer block (self-attention, residual + LayerNorm, position-wise feed-forward, residual +
-    LayerNorm) over the history followed by the candidate.  The attention is the fused layer; the block's small parts run as torch
-    ops."""
+class _TransformerBlock(Layer):
+    """What one behaviour of BST and of DSIN share: a Transformer block (self-attention, residual + LayerNorm, position-wise
+    feed-forward, residual + LayerNorm) whose weights sit on the behaviour itself.  The attention is the fused layer; the block's
+    small parts run as torch ops."""
 
     def __init__(self, att_heads, ffn_units=None, seed=2020):
         super().__init__()
@@ -445,11 +446,7 @@ class _BstBehavior(Layer):
         self.seed = seed
         self.ln_epsilon = 1e-3      # tf.keras.layers.LayerNormalization() default
 
-    def build(self, input_shape):
-        t, k = int(input_shape[1][1]) + 1, int(input_shape[1][-1])
-        if k % self.att_heads != 0:
-            raise ValueError("BST: att_heads=%d does not divide the embedding width K=%d" % (self.att_heads, k))
-        self.pos_embed = self.add_weight("pos_embed", [t, k], "glorot_uniform", seed=self.seed)
+    def _build_block(self, k):
         self.atten = SeqSelfAttentionLayer(self.att_heads, k // self.att_heads, seed=self.seed)
         self.ffn1 = Dense(self.ffn_units or 4 * k, seed=self.seed)
         self.ffn2 = Dense(k, seed=self.seed + 1)
@@ -457,6 +454,24 @@ class _BstBehavior(Layer):
         self.ln1_beta = self.add_weight("ln1_beta", [k], "zeros")
         self.ln2_gamma = self.add_weight("ln2_gamma", [k], "ones")
         self.ln2_beta = self.add_weight("ln2_beta", [k], "zeros")
+
+    def _block(self, seq, live):
+        K = seq.shape[-1]
+        a = self.atten(seq, mask=live)
+        y = torch.nn.functional.layer_norm(seq + a, (K,), self.ln1_gamma, self.ln1_beta, self.ln_epsilon)
+        f = self.ffn2(torch.relu(self.ffn1(y)))
+        return torch.nn.functional.layer_norm(y + f, (K,), self.ln2_gamma, self.ln2_beta, self.ln_epsilon)
+
+
+class _BstBehavior(_TransformerBlock):
+    """One behaviour of BST: the Transformer block over the history followed by the candidate."""
+
+    def build(self, input_shape):
+        t, k = int(input_shape[1][1]) + 1, int(input_shape[1][-1])
+        if k % self.att_heads != 0:
+            raise ValueError("BST: att_heads=%d does not divide the embedding width K=%d" % (self.att_heads, k))
+        self.pos_embed = self.add_weight("pos_embed", [t, k], "glorot_uniform", seed=self.seed)
+        self._build_block(k)
         super().build(input_shape)
 
     def call(self, inputs, mask=None, **kwargs):
@@ -466,10 +481,7 @@ class _BstBehavior(Layer):
         live = torch.ones((B, T + 1), dtype=torch.bool, device=keys.device)
         if mask is not None:
             live = torch.cat([mask.to(torch.bool), live[:, :1]], dim=1)
-        a = self.atten(seq, mask=live)
-        y = torch.nn.functional.layer_norm(seq + a, (K,), self.ln1_gamma, self.ln1_beta, self.ln_epsilon)
-        f = self.ffn2(torch.relu(self.ffn1(y)))
-        z = torch.nn.functional.layer_norm(y + f, (K,), self.ln2_gamma, self.ln2_beta, self.ln_epsilon)
+        z = self._block(seq, live)
         w = live.to(z.dtype).unsqueeze(-1)
         mean = (z * w).sum(dim=1, keepdim=True) / w.sum(dim=1, keepdim=True)             # the candidate is live: never 0 / 0
         return [mean, z[:, T:T + 1]]
@@ -495,6 +507,74 @@ class BST(_BehaviorModel):
         return _BstBehavior(self.att_heads, self.ffn_units, seed=self.seed + 2 * n)
 
     def _collect(self, out):      # [the mean over the live positions, the candidate's position]
+        return out
+
+
+class _DsinBehavior(_TransformerBlock):
+    """One behaviour of DSIN: the history cut into sess_count sessions; bias encoding, the Transformer block inside every session, a
+    bidirectional LSTM over the session interests, and the candidate's attention over both sequences."""
+
+    def __init__(self, sess_count, att_heads, att_hidden_units, ffn_units=None, seed=2020):
+        super().__init__(att_heads, ffn_units, seed)
+        self.sess_count = int(sess_count)
+        self.att_hidden_units = tuple(att_hidden_units)
+
+    def build(self, input_shape):
+        t, k = int(input_shape[1][1]), int(input_shape[1][-1])
+        if t % self.sess_count != 0:
+            raise ValueError("DSIN: the history length T=%d is not sess_count=%d sessions of one length" % (t, self.sess_count))
+        if k % self.att_heads != 0:
+            raise ValueError("DSIN: att_heads=%d does not divide the embedding width K=%d" % (self.att_heads, k))
+        self.sess_bias = self.add_weight("sess_bias", [self.sess_count, 1, 1], "zeros")
+        self.pos_bias = self.add_weight("pos_bias", [1, t // self.sess_count, 1], "zeros")
+        self.unit_bias = self.add_weight("unit_bias", [1, 1, k], "zeros")
+        self._build_block(k)
+        self.interact = BiLSTMLayer(k, merge_mode="ave", seed=self.seed)
+        self.att_extract = DinAttentionLayer(hidden_units=self.att_hidden_units, softmax=True, seed=self.seed)
+        self.att_interact = DinAttentionLayer(hidden_units=self.att_hidden_units, softmax=True, seed=self.seed + 1)
+        super().build(input_shape)
+
+    def call(self, inputs, mask=None, **kwargs):
+        query, keys = inputs
+        B, T, K = keys.shape
+        S = self.sess_count
+        Ts = T // S
+        live = torch.ones((B, T), dtype=torch.bool, device=keys.device) if mask is None else mask.to(torch.bool)
+        q = keys.reshape(B, S, Ts, K) + self.sess_bias + self.pos_bias + self.unit_bias          # the bias encoding (eq. 2)
+        slot = live.reshape(B * S, Ts)
+        z = self._block(q.reshape(B * S, Ts, K), slot)                     # one block for every session
+        w = slot.to(z.dtype).unsqueeze(-1)
+        interests = ((z * w).sum(dim=1) / w.sum(dim=1).clamp_min(1.0)).reshape(B, S, K)          # a session with no live slot: 0
+        sess_live = live.reshape(B, S, Ts).any(dim=-1)
+        evolved = self.interact(interests, mask=sess_live)                 # [B,S,K]
+        return [self.att_extract([query, interests], mask=sess_live), self.att_interact([query, evolved], mask=sess_live)]
+
+
+class DSIN(_BehaviorModel):
+    """Deep Session Interest Network (extension; the paper's model on DINInput's features).  The history of length T is sess_count
+    sessions of Ts = T / sess_count slots, slot t in session t // Ts (ValueError on the first call otherwise).  Per behaviour: the
+    bias encoding Q = keys [B,S,Ts,K] + sess_bias [S,1,1] + pos_bias [1,Ts,1] + unit_bias [1,1,K] (trainable, zeros); one Transformer
+    block shared by all sessions on [B S,Ts,K] under the slot mask -- SeqSelfAttentionLayer(att_heads, K // att_heads), residual +
+    LayerNorm (epsilon 1e-3), Dense(ffn_units or 4 K), relu, Dense(K), residual + LayerNorm, BST's parts -- whose mean over a session's
+    live slots is the session interest I [B,S,K] (a session with no live slot is zero and dead); Hs = BiLSTMLayer(K,
+    merge_mode="ave")(I, mask=the live sessions); two DinAttentionLayer(att_hidden_units, softmax=True) with the candidate as the
+    query and the live sessions as the mask, one over I and one over Hs, give the behaviour's two [B,1,K] features.  Then, as DIN /
+    DIEN / BST: StackLayer over dense + field embeddings + those features -> DnnLayer -> MergeScoreLayer(use_merge=False)."""
+
+    def __init__(self, sess_count, att_heads=2, att_hidden_units=(80, 40), ffn_units=None, hidden_units=None, seed=2020):
+        if int(sess_count) < 1 or int(att_heads) < 1:
+            raise ValueError("DSIN: sess_count and att_heads must be positive, got %r and %r" % (sess_count, att_heads))
+        super().__init__(hidden_units)
+        self.sess_count = int(sess_count)
+        self.att_heads = int(att_heads)
+        self.att_hidden_units = tuple(att_hidden_units)
+        self.ffn_units = ffn_units
+        self.seed = seed
+
+    def _behavior(self, n):
+        return _DsinBehavior(self.sess_count, self.att_heads, self.att_hidden_units, self.ffn_units, seed=self.seed + 2 * n)
+
+    def _collect(self, out):      # [the attention over the session interests, the attention over the LSTM's states]
         return out
 
 
