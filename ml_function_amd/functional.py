@@ -94,6 +94,18 @@ def _grad(want, shape, device):
     return torch.empty(shape, dtype=torch.float32, device=device) if want else None
 
 
+def _no_samples(B, *param_grads):
+    """True for the backward of an empty batch.  The library answers B == 0 with a no-op that writes nothing, so the parameter
+    gradients -- sums over no sample -- are zeroed here (they came uninitialised from _grad) and the library is not called; the input
+    gradients are empty as they are."""
+    if B > 0:
+        return False
+    for t in param_grads:
+        if t is not None:
+            t.zero_()
+    return True
+
+
 def _save(ctx, *tensors):
     """ctx.save_for_backward of the tensors that are there (so autograd's version check covers every one of them); which places
     were None is kept on ctx for _saved."""
@@ -236,6 +248,8 @@ class _AfmPoolFn(torch.autograd.Function):
         dw = _grad(need[1], w.shape, dev)
         db = _grad(need[2], ctx.shapes[0], dev)
         dh = _grad(need[3], ctx.shapes[1], dev)
+        if _no_samples(B, dw, db, dh):
+            return demb, dw, db, dh, None
         ws, nws = _partials_scratch("fil_afm_bwd_workspace_bytes", "afm_bwd", need[1] or need[2] or need[3], dev, B, F, K, A)
         check(lib.fil_afm_bwd(ptr(emb), ptr(w), ptr(b), ptr(h), ptr(pooled), ptr(stats), ptr(_f32c(g)), ptr(demb), ptr(dw), ptr(db),
                               ptr(dh), ptr(ws), nws, B, F, K, A, ctx.flags, stream_ptr()), "fil_afm_bwd")
@@ -315,6 +329,8 @@ class _DinAttentionFn(torch.autograd.Function):
         da2 = _grad(need[8] and alpha2 is not None, shapes.get("alpha2"), dev)
         dw3 = _grad(need[9], shapes["w3"], dev)
         db3 = _grad(need[10], shapes["b3"], dev)
+        if _no_samples(B, dw1, db1, da1, dw2, db2, da2, dw3, db3):
+            return dq, dkeys, None, dw1, db1, da1, dw2, db2, da2, dw3, db3, None
         lib = _lib.load()
         ws, nws = _partials_scratch("fil_din_bwd_workspace_bytes", "din_bwd",
                                     any(t is not None for t in (dw1, db1, da1, dw2, db2, da2, dw3, db3)), dev, B, T, K, H1, H2)
@@ -392,6 +408,8 @@ class _GruFn(torch.autograd.Function):
         dw = _grad(need[3], w.shape, dev)
         du = _grad(need[4], u.shape, dev)
         db = _grad(need[5], (2, 3 * H), dev)
+        if _no_samples(B, dw, du, db):
+            return dx, da, None, dw, du, db, None, None
         g = _f32c(g)
         g_hs, g_last = (g, None) if ctx.return_sequences else (None, g)
         lib = _lib.load()
@@ -476,8 +494,8 @@ class _LstmFn(torch.autograd.Function):
         dw = _grad(need[2], w.shape, dev)
         du = _grad(need[3], u.shape, dev)
         db = _grad(need[4], u.shape[:-2] + (4 * H,), dev)
-        if B == 0:      # the library's no-op writes nothing: the sums over no sample are zero
-            return (dx,) + (None,) + tuple(None if t is None else t.zero_() for t in (dw, du, db)) + (None, None)
+        if _no_samples(B, dw, du, db):
+            return dx, None, dw, du, db, None, None
         g = _f32c(g)
         g_hs, g_last = (g, None) if ctx.return_sequences else (None, g)
         # the partials of the parameter gradients, and with both directions in one launch the second direction's dx
@@ -548,6 +566,8 @@ class _SeqAttnFn(torch.autograd.Function):
         dwq = _grad(need[2], wq.shape, dev)
         dwk = _grad(need[3], wk.shape, dev)
         dwv = _grad(need[4], wv.shape, dev)
+        if _no_samples(B, dwq, dwk, dwv):
+            return dx, None, dwq, dwk, dwv, None, None
         g = _f32c(g)
         lib = _lib.load()
         ws, nws = _partials_scratch("fil_seqattn_bwd_workspace_bytes", "seqattn_bwd", need[2] or need[3] or need[4], dev, B, T, K, H, D)

@@ -10,6 +10,7 @@ GUARD_BYTES = 256                          # in front of and behind every output
 TAIL = 64                                  # poisoned words behind every input
 WS_GUARD = 256                             # bytes behind a workspace
 WS_FILL = 0xA5
+WS_NAN_FILL = 0xFF                         # all-ones words: a NaN in fp32 and in bf16, so a partial read past the written ones shows in the sum
 
 _SIGNED = {np.dtype(np.uint32): (np.int32, torch.int32), np.dtype(np.uint16): (np.int16, torch.int16)}
 
@@ -43,12 +44,13 @@ class GuardedOutput:
         return w[self.guard:self.guard + self.n].reshape(self.shape).copy()
 
 
-def workspace(nbytes):
-    return torch.full((nbytes + WS_GUARD,), WS_FILL, dtype=torch.uint8, device="cuda")
+def workspace(nbytes, fill=WS_FILL):
+    """nbytes of workspace and WS_GUARD bytes behind them, every byte `fill` (WS_FILL: -2.9e-16 as an fp32 word; WS_NAN_FILL: a NaN)."""
+    return torch.full((nbytes + WS_GUARD,), fill, dtype=torch.uint8, device="cuda")
 
 
-def assert_workspace_guard(ws, nbytes, what):
-    assert (ws[nbytes:].cpu().numpy() == WS_FILL).all(), "%s: a store behind the workspace's %d bytes" % (what, nbytes)
+def assert_workspace_guard(ws, nbytes, what, fill=WS_FILL):
+    assert (ws[nbytes:].cpu().numpy() == fill).all(), "%s: a store behind the workspace's %d bytes" % (what, nbytes)
 
 
 def bf16_words(a):

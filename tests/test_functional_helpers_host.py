@@ -64,6 +64,16 @@ def test_an_unwanted_gradient_is_none_and_a_wanted_one_is_fp32_of_the_shape():
     assert g.shape == (2, 3) and g.dtype == torch.float32 and g.device.type == "cpu"
 
 
+def test_an_empty_batch_zeroes_the_parameter_gradients_and_a_batch_leaves_them():
+    nan = lambda: torch.full((2, 3), float("nan"))
+    a, b = nan(), nan()
+    assert Fn._no_samples(0, a, None, b) is True
+    assert not a.view(torch.int32).any() and not b.view(torch.int32).any()
+    c = nan()
+    assert Fn._no_samples(1, c, None) is False and bool(torch.isnan(c).all())
+    assert Fn._no_samples(0) is True and Fn._no_samples(0, None) is True
+
+
 def test_no_partials_workspace_without_a_wanted_parameter_gradient(monkeypatch):
     def load():
         raise AssertionError("the library was asked")

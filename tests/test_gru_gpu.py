@@ -113,14 +113,14 @@ def run_raw(case, subset=ref.GRADS):
     check(lib.fil_gru_fwd(ptr(t["x"]), ptr(t["a"]), ptr(mask), ptr(t["W"]), ptr(t["U"]), ptr(t["b"]), bufs["hs"].ptr, saved.ptr, B, T, K, H, mode,
                           stream_ptr()), "fil_gru_fwd")
     nws = lib.fil_gru_bwd_workspace_bytes(B, T, K, H)
-    ws = guarded.workspace(nws)
+    ws = guarded.workspace(nws, fill=guarded.WS_NAN_FILL)
     out = lambda k: bufs[k].ptr if k in bufs else None
     params = any(k in bufs for k in ("dW", "dU", "db"))
     check(lib.fil_gru_bwd(ptr(t["x"]), ptr(t["a"]), ptr(mask), ptr(t["W"]), ptr(t["U"]), bufs["hs"].ptr, saved.ptr, ptr(t["g_hs"]), ptr(t["g_last"]),
                           out("dx"), out("da"), out("dW"), out("dU"), out("db"), ptr(ws) if params else None, nws if params else 0, B, T, K, H, mode,
                           stream_ptr()), "fil_gru_bwd")
     torch.cuda.synchronize()
-    guarded.assert_workspace_guard(ws, nws, "fil_gru_bwd")
+    guarded.assert_workspace_guard(ws, nws, "fil_gru_bwd", fill=guarded.WS_NAN_FILL)
     saved.read("saved")
     return {k: guarded.words_f32(b.read(k)).astype(np.float64) for k, b in bufs.items()}
 

@@ -116,14 +116,14 @@ def run_raw(case, subset=ref.GRADS):
     check(lib.fil_lstm_fwd(ptr(t["x"]), ptr(mask), ptr(t["W"]), ptr(t["U"]), ptr(t["b"]), bufs["hs"].ptr, saved.ptr, B, T, K, H, dirs, stream_ptr()),
           "fil_lstm_fwd")
     nws = lib.fil_lstm_bwd_workspace_bytes(B, T, K, H, dirs)
-    ws = guarded.workspace(nws)
+    ws = guarded.workspace(nws, fill=guarded.WS_NAN_FILL)
     out = lambda k: bufs[k].ptr if k in bufs else None
     uses_ws = any(k in bufs for k in ("dW", "dU", "db")) or (n == 2 and "dx" in bufs)
     check(lib.fil_lstm_bwd(ptr(t["x"]), ptr(mask), ptr(t["W"]), ptr(t["U"]), bufs["hs"].ptr, saved.ptr, ptr(t["g_hs"]), ptr(t["g_last"]), out("dx"),
                            out("dW"), out("dU"), out("db"), ptr(ws) if uses_ws else None, nws if uses_ws else 0, B, T, K, H, dirs, stream_ptr()),
           "fil_lstm_bwd")
     torch.cuda.synchronize()
-    guarded.assert_workspace_guard(ws, nws, "fil_lstm_bwd")
+    guarded.assert_workspace_guard(ws, nws, "fil_lstm_bwd", fill=guarded.WS_NAN_FILL)
     saved.read("saved")
     return {k: guarded.words_f32(b.read(k)).astype(np.float64).reshape(shapes[k]) for k, b in bufs.items()}
 

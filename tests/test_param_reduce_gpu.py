@@ -111,10 +111,10 @@ def run_raw(op, nparts, wanted=None):
     bufs = {k: guarded.GuardedOutput((n,), np.uint32, k) for k, n in spec["outs"]}
     nws = int(spec["ws_bytes"](lib, B))
     assert nws >= nparts * spec["n_out"] * 4
-    ws = guarded.workspace(nws)
+    ws = guarded.workspace(nws, fill=guarded.WS_NAN_FILL)
     spec["run"](lib, t, B, [bufs[k].ptr if wanted is None or k in wanted else None for k, _ in spec["outs"]], ws, nws)
     torch.cuda.synchronize()
-    guarded.assert_workspace_guard(ws, nws, op)
+    guarded.assert_workspace_guard(ws, nws, op, fill=guarded.WS_NAN_FILL)
     parts = ws[:nparts * spec["n_out"] * 4].cpu().numpy().view(np.float32).reshape(nparts, spec["n_out"])
     got = {k: b.read(op + " " + k) for k, b in bufs.items() if wanted is None or k in wanted}
     return got, parts, {k: b for k, b in bufs.items() if k not in got}

@@ -108,14 +108,14 @@ def run_raw(case, subset=ref.GRADS):
     check(lib.fil_seqattn_fwd(ptr(t["x"]), ptr(mask), ptr(t["Wq"]), ptr(t["Wk"]), ptr(t["Wv"]), bufs["out"].ptr, saved.ptr, B, T, K, H, D, us,
                               stream_ptr()), "fil_seqattn_fwd")
     nws = lib.fil_seqattn_bwd_workspace_bytes(B, T, K, H, D)
-    ws = guarded.workspace(nws)
+    ws = guarded.workspace(nws, fill=guarded.WS_NAN_FILL)
     out = lambda k: bufs[k].ptr if k in bufs else None
     params = any(k in bufs for k in ("dWq", "dWk", "dWv"))
     check(lib.fil_seqattn_bwd(ptr(t["x"]), ptr(mask), ptr(t["Wq"]), ptr(t["Wk"]), ptr(t["Wv"]), bufs["out"].ptr, saved.ptr, ptr(t["g"]),
                               out("dx"), out("dWq"), out("dWk"), out("dWv"), ptr(ws) if params else None, nws if params else 0, B, T, K, H, D,
                               us, stream_ptr()), "fil_seqattn_bwd")
     torch.cuda.synchronize()
-    guarded.assert_workspace_guard(ws, nws, "fil_seqattn_bwd")
+    guarded.assert_workspace_guard(ws, nws, "fil_seqattn_bwd", fill=guarded.WS_NAN_FILL)
     saved.read("saved")
     return {k: guarded.words_f32(b.read(k)).astype(np.float64) for k, b in bufs.items()}
 
