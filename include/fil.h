@@ -561,6 +561,48 @@ int fil_seqattn_bwd(const float* x, const unsigned char* mask, const float* Wq, 
                     size_t workspace_bytes, int B, int T, int K, int H, int D, int use_scale, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * N3  Top-k retrieval over a LONG behaviour history (extension: the General Search Unit of the Search-based Interest Model): score
+ *     every live slot of a history straight from the embedding table, keep the k best, return them in time order.  Forward only,
+ *     integer results, nothing to differentiate: fil_embed_gather on the selected ids and fil_din_* then run over k slots instead
+ *     of T.  Entry points added only: the ABI version stays.
+ *   hist_idx: B rows of T field-local ids (int64), row b at hist_idx + b * hist_stride (hist_stride >= T, in elements);
+ *   offset, size: the field's first row in the concatenated table and its vocabulary (size < 0: ids are trusted); pad_id;
+ *   mask [B,T] uint8, non-zero = live, NULL = all live.
+ *   Soft part (both or neither): table [V,K] fp32, 16-byte aligned; q: B rows of K fp32, row b at q + b * q_stride (>= K).
+ *   Hard part (both or neither): attr: B rows of T int64, row b at attr + b * attr_stride (>= T); cand [B] int64.
+ *   At least one part must be given (FIL_ERR_ARG otherwise); both may be.
+ *   A slot is LIVE iff id != pad_id, 0 <= id < size, mask is NULL or non-zero there, and attr is NULL or attr[b,t] == cand[b].  An id
+ *   that is not pad_id and lies outside [0, size) is not live and is counted in *oob_count (device int, may be NULL; the caller zeroes
+ *   it), whatever mask and attr say -- as the gather counts it.  A slot that is not live issues NO table read.
+ *   Score of a live slot: s = +0; for j = 0 .. K-1: s = s + (table[offset + id, j] * q[b, j]), every multiply and every add rounded
+ *     to fp32 on its own, in ascending j, by one lane: no fused multiply-add, no tree.  Without the soft part the score is +0.
+ *   Order of scores: by the key bits ^ (bits >> 31 ? 0xFFFFFFFF : 0x80000000) of their fp32 bits, compared as unsigned integers:
+ *     -0 < +0, +-inf are ordinary values.  NaN scores give an unspecified but valid selection (distinct live slots, ascending, n of them).
+ *   Selection: the n = min(k, live slots) largest by (key descending, position ascending); with FIL_SEARCH_PREFER_LAST the second
+ *     criterion is position descending.  The hard part alone therefore returns the first k matches, with PREFER_LAST the last k.
+ *   Output, the selected slots in ASCENDING position (time order): sel_pos [B,k] int32 the positions, sel_idx [B,k] int64 the ids,
+ *     sel_score [B,k] fp32 the scores (NULL: not written); the tail n .. k-1 is -1 / pad_id / +0; count [B] int32 = n.
+ *   One launch.  One workgroup per sample (64 threads for T <= 64, 256 otherwise), at most 4096 workgroups, past that a workgroup walks
+ *   several samples.  The keys stay in LDS: a radix select (four 8-bit passes, integer LDS histograms) finds the k-th key, ballots and
+ *   popcounts order the ties and compact the result.  No float atomics, no [B,T] or [B,T,K] block in global memory, no host
+ *   synchronisation, no data-dependent size (graph-capture safe); repeats are bit-identical and a sample's result does not depend on
+ *   the rest of the batch.
+ *   Menu: K % 4 == 0, K <= 64 (also without the soft part, where K is otherwise unused), 1 <= k <= 256 (what fil_din_* takes),
+ *   1 <= T <= 16384, B T < 2^31, dynamic LDS 4 (K + T rounded up to 4) + 8 ceil(T / 64) + 1088 bytes within 163,328
+ *   (FIL_ERR_UNSUPPORTED otherwise, the limit in the message).  k may exceed T.  Unknown flag bits: FIL_ERR_ARG.
+ *   B == 0 returns FIL_OK before any pointer is looked at.
+ *   fil_seq_search_plan: the launcher's own arithmetic (no GPU call): plan[8] = {1, 1, samples per workgroup tile (= 1), grid, grid cap,
+ *     grid, LDS bytes, 0} -- the layout of the other fil_*_plan entry points; there is no backward, its fields are 1 / 0.  Returns
+ *     FIL_OK, or the argument / menu error the launch would give.
+ */
+#define FIL_SEARCH_PREFER_LAST 1
+int fil_seq_search_plan(int B, int T, int K, int k, int* plan /* [8] */);
+int fil_seq_search(const int64_t* hist_idx, int64_t hist_stride, int64_t offset, int64_t size, int64_t pad_id,
+                   const unsigned char* mask, const float* table, const float* q, int64_t q_stride, const int64_t* attr,
+                   int64_t attr_stride, const int64_t* cand, int* sel_pos, int64_t* sel_idx, int* count, float* sel_score,
+                   int* oob_count, int B, int T, int K, int k, int flags, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * N2  The score head and the loss behind the interaction layers (all tensors fp32, n = batch rows).
  *   ScoreLayer(use_add=True).call (kon/model/ctr_model/layer/core_layer/core_layer.py:58-84): keras Add over the [B,1] parts,
  *   then sigmoid.  fil_score_add_sigmoid_fwd: out[i] = sigmoid(((a[i] + b[i]) + c[i]) + d[i]) -- left to right like the

@@ -43,6 +43,7 @@ FIL_AFM_HIDDEN_RELU = 1          # fil_afm_*'s flag bit 0: s_p = relu(u_p) . h (
 FIL_DIN_SOFTMAX, FIL_DIN_SIGMOID = 1, 2   # fil_din_*'s flag bits: softmax over the live slots; sigmoid instead of PReLU
 FIL_GRU_GRU, FIL_GRU_AUGRU, FIL_GRU_AGRU = 0, 1, 2   # fil_gru_*'s mode
 FIL_LSTM_FORWARD, FIL_LSTM_REVERSE, FIL_LSTM_BIDIR = 0, 1, 2   # fil_lstm_*'s dirs
+FIL_SEARCH_PREFER_LAST = 1       # fil_seq_search's flag bit 0: among equal scores the later positions win
 FIL_ERR_UNSUPPORTED = -4
 
 _c = ctypes
@@ -50,6 +51,7 @@ _P = _c.c_void_p
 _I = _c.c_int
 _Z = _c.c_size_t
 _F = _c.c_float
+_L = _c.c_int64
 
 # name -> (restype, argtypes); mirrors include/fil.h one to one
 SIGNATURES = {
@@ -122,6 +124,9 @@ SIGNATURES = {
     "fil_seqattn_fwd": (_I, [_P] * 7 + [_I] * 6 + [_P]),
     "fil_seqattn_bwd_workspace_bytes": (_Z, [_I, _I, _I, _I, _I]),
     "fil_seqattn_bwd": (_I, [_P] * 13 + [_Z] + [_I] * 6 + [_P]),
+    # N3: top-k retrieval over a long behaviour history (forward only)
+    "fil_seq_search_plan": (_I, [_I, _I, _I, _I, _P]),
+    "fil_seq_search": (_I, [_P, _L, _L, _L, _L, _P, _P, _P, _L, _P, _L, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
     "fil_score_add_sigmoid_fwd": (_I, [_P, _P, _P, _P, _P, _I, _P]),
     "fil_score_add_sigmoid_bwd": (_I, [_P, _P, _P, _I, _P]),
     "fil_bce_mean_fwd": (_I, [_P, _P, _F, _P, _P, _I, _P]),

@@ -592,6 +592,139 @@ def seq_attn_plan(B, T, K, H, D):
     return _tiled_plan("fil_seqattn_plan", int(B), int(T), int(K), int(H), int(D))
 
 
+# --------------------------------------------------------------------------------------------- N3  top-k retrieval over a long history
+SEARCH_PREFER = {"first": 0, "last": _lib.FIL_SEARCH_PREFER_LAST}
+
+
+def _search_args(who, hist_idx, k, table, offset, size, query, attr, cand, mask, prefer):
+    """The checks seq_search and seq_search_graph share -> (B, T, K, soft, hard, the mask as uint8); K = 4 without the soft part
+    (unused there)."""
+    if prefer not in SEARCH_PREFER:
+        raise ValueError("%s: prefer %r (%s)" % (who, prefer, ", ".join(SEARCH_PREFER)))
+    if hist_idx.dim() != 2 or hist_idx.dtype != torch.int64:
+        raise FilError("%s: hist_idx must be a [B,T] int64 tensor, got %s %s" % (who, tuple(hist_idx.shape), hist_idx.dtype))
+    B, T = hist_idx.shape
+    if int(k) < 1 or T < 1:
+        raise FilError("%s: k and T must be positive, got k=%d, T=%d" % (who, k, T))
+    if (table is None) != (query is None) or (attr is None) != (cand is None) or (table is None and attr is None):
+        raise FilError("%s: give table and query (the soft search), attr and cand (the hard search), or both pairs" % who)
+    K = 4
+    if table is not None:
+        if table.dim() != 2 or query.dim() != 2 or tuple(query.shape) != (B, table.shape[1]) or table.dtype != torch.float32 or \
+                query.dtype != torch.float32:
+            raise FilError("%s: table must be [V,K] and query [B,K], float32, got %s %s and %s %s"
+                           % (who, tuple(table.shape), table.dtype, tuple(query.shape), query.dtype))
+        K = table.shape[1]
+        rows = int(offset) + (table.shape[0] - int(offset) if size is None else int(size))
+        if int(offset) < 0 or rows > table.shape[0]:
+            raise FilError("%s: the field's rows [%d, %d) are not inside the table of %d rows" % (who, offset, rows, table.shape[0]))
+    if attr is not None and (tuple(attr.shape) != (B, T) or attr.dtype != torch.int64 or tuple(cand.shape) != (B,) or cand.dtype != torch.int64):
+        raise FilError("%s: attr must be [B,T] and cand [B], int64, got %s %s and %s %s"
+                       % (who, tuple(attr.shape), attr.dtype, tuple(cand.shape), cand.dtype))
+    return B, T, K, table is not None, attr is not None, _seq_mask(who, mask, B, T)
+
+
+def seq_search_graph(hist_idx, k, table=None, offset=0, size=None, query=None, attr=None, cand=None, mask=None, padding_id=0,
+                     prefer="first", return_scores=False, oob_count=None):
+    """seq_search's definition in torch ops (include/fil.h fil_seq_search), bit-equal to the kernel: what seq_search runs outside the
+    kernel menu, and the second reference of its tests.  The score is K elementwise multiply and add steps in ascending j (separate
+    ops: nothing is contracted), the selection a stable sort on integers, the output order a second one.  It gathers the [B,T,K]
+    rows the kernel never materialises.  No host synchronisation, no data-dependent shape."""
+    B, T, K, soft, hard, mask = _search_args("seq_search_graph", hist_idx, k, table, offset, size, query, attr, cand, mask, prefer)
+    k = int(k)
+    dev = hist_idx.device
+    slot = hist_idx != padding_id
+    ok = torch.ones_like(slot) if size is None else (hist_idx >= 0) & (hist_idx < int(size))
+    live = slot & ok
+    if oob_count is not None:
+        oob_count += (slot & ~ok).sum().to(oob_count.dtype)
+    if mask is not None:
+        live = live & (mask != 0)
+    if hard:
+        live = live & (attr == cand[:, None])
+    if soft:
+        rows = table.detach()[torch.where(live, hist_idx + int(offset), torch.zeros_like(hist_idx))]          # [B,T,K]
+        q = query.detach()
+        score = torch.zeros((B, T), dtype=torch.float32, device=dev)
+        for j in range(K):
+            p = rows[:, :, j] * q[:, j:j + 1]
+            score = score + p
+        score = torch.where(live, score, torch.zeros_like(score))
+    else:
+        score = torch.zeros((B, T), dtype=torch.float32, device=dev)
+    bits = score.contiguous().view(torch.int32).to(torch.int64) & 0xFFFFFFFF
+    key = bits ^ torch.where(bits >> 31 != 0, torch.full_like(bits, 0xFFFFFFFF), torch.full_like(bits, 0x80000000))
+    pos = torch.arange(T, dtype=torch.int64, device=dev).expand(B, T)
+    # ascending in (dead last, key descending, position ascending -- descending for prefer="last")
+    rank = torch.where(live, 0xFFFFFFFF - key, torch.full_like(key, 1 << 32)) * T + (pos if prefer == "first" else T - 1 - pos)
+    order = torch.sort(rank, dim=1, stable=True)[1]
+    n = live.sum(1).clamp(max=k)
+    kk = min(k, T)
+    taken = torch.arange(kk, dtype=torch.int64, device=dev)[None, :] < n[:, None]
+    chosen = torch.where(taken, order[:, :kk], torch.full_like(order[:, :kk], T))
+    chosen = torch.sort(chosen, dim=1, stable=True)[0]                                              # back to time order
+    safe = chosen.clamp(max=T - 1)
+    sel_pos = torch.where(taken, chosen, torch.full_like(chosen, -1)).to(torch.int32)
+    sel_idx = torch.where(taken, hist_idx.gather(1, safe), torch.full_like(chosen, padding_id))
+    sel_score = torch.where(taken, score.gather(1, safe), torch.zeros((B, kk), dtype=torch.float32, device=dev))
+    if kk < k:
+        sel_pos = torch.nn.functional.pad(sel_pos, (0, k - kk), value=-1)
+        sel_idx = torch.nn.functional.pad(sel_idx, (0, k - kk), value=padding_id)
+        sel_score = torch.nn.functional.pad(sel_score, (0, k - kk), value=0.0)
+    out = (sel_idx, sel_pos, n.to(torch.int32))
+    return out + (sel_score,) if return_scores else out
+
+
+def _row_strided(t):
+    """A 2-D tensor as (tensor, row stride in elements) the search kernel can read in place -- rows contiguous, any row stride -- or its
+    contiguous copy."""
+    if (t.shape[1] > 1 and t.stride(1) != 1) or (t.shape[0] > 1 and t.stride(0) < t.shape[1]):
+        t = t.contiguous()
+    return t, max(t.stride(0), t.shape[1])
+
+
+def seq_search(hist_idx, k, table=None, offset=0, size=None, query=None, attr=None, cand=None, mask=None, padding_id=0, prefer="first",
+               return_scores=False, oob_count=None):
+    """Top-k retrieval over a long behaviour history (extension; include/fil.h fil_seq_search): hist_idx [B,T] int64 field-local ids of
+    the field whose rows start at `offset` of `table` [V,K] and number `size` (None: ids are trusted) -> (sel_idx [B,k] int64,
+    sel_pos [B,k] int32, count [B] int32[, scores [B,k] fp32]).  Soft search: table and query [B,K], the score of a slot is the fp32
+    inner product of its row with the query, summed sequentially; hard search: attr [B,T] and cand [B] int64, a slot takes part only
+    where attr == cand; both may be given.  A slot also drops out where its id is padding_id, out of range (counted in oob_count, an
+    int32 device scalar) or mask [B,T] is zero.  The min(k, live) best slots -- ties to the earlier position, to the later with
+    prefer="last" -- come back in time order; the tail is padding_id / -1 / +0.  Integer results: there is no autograd node, query and
+    table are read as data.  One launch, no host synchronisation; rows of hist_idx, attr and query may be strided.  GPU only; a shape
+    outside the kernel menu runs seq_search_graph, the same definition in torch ops."""
+    _require_cuda(hist_idx, table, query, attr, cand, mask, oob_count)
+    B, T, K, soft, hard, mask = _search_args("seq_search", hist_idx, k, table, offset, size, query, attr, cand, mask, prefer)
+    k = int(k)
+    if not seq_search_plan(B, T, K, k)["fits"]:
+        return seq_search_graph(hist_idx, k, table, offset, size, query, attr, cand, mask, padding_id, prefer, return_scores, oob_count)
+    dev = hist_idx.device
+    hist_idx, hs = _row_strided(hist_idx)
+    qs = as_ = 0
+    if soft:
+        table = _f32c(table.detach())
+        query, qs = _row_strided(query.detach())
+    if hard:
+        attr, as_ = _row_strided(attr)
+        cand = cand.contiguous()
+    sel_idx = torch.empty((B, k), dtype=torch.int64, device=dev)
+    sel_pos = torch.empty((B, k), dtype=torch.int32, device=dev)
+    count = torch.empty((B,), dtype=torch.int32, device=dev)
+    scores = torch.empty((B, k), dtype=torch.float32, device=dev) if return_scores else None
+    check(_lib.load().fil_seq_search(ptr(hist_idx), hs, int(offset), -1 if size is None else int(size), int(padding_id), ptr(mask),
+                                     ptr(table), ptr(query), qs, ptr(attr), as_, ptr(cand), ptr(sel_pos), ptr(sel_idx), ptr(count),
+                                     ptr(scores), ptr(oob_count), B, T, K, k, SEARCH_PREFER[prefer], stream_ptr()), "fil_seq_search")
+    out = (sel_idx, sel_pos, count)
+    return out + (scores,) if return_scores else out
+
+
+def seq_search_plan(B, T, K, k):
+    """fil_seq_search_plan's answer as a dict (fits, tile, grid, cap, partials, lds_fwd, lds_bwd); fits=False (and nothing else) for a
+    shape outside the kernel menu."""
+    return _tiled_plan("fil_seq_search_plan", int(B), int(T), int(K), int(k))
+
+
 def attn_plan(F, K, H, A, precision="f32"):
     """fil_attn_plan's answer for AutoInt's fused interacting layer (the plan does not depend on the batch) as a dict: fits = the
     dynamic LDS of BOTH the forward and the backward within the launchers' limit in this precision, fwd_ok, bwd_ok; fits=False (and

@@ -7,7 +7,8 @@ tensors.  Hyper-parameter names and defaults are the reference's.  Sequence mode
 except DINInput / DIN (extension): the Deep Interest Network's attention pooling of behaviour histories (layers.DinAttentionLayer),
 DIEN (extension): the Deep Interest Evolution Network's GRU + AUGRU over the same histories (layers.GRULayer),
 BST (extension): the Behaviour Sequence Transformer's block over them (layers.SeqSelfAttentionLayer),
-and DSIN (extension): the Deep Session Interest Network's sessions, self-attention and bidirectional LSTM (layers.BiLSTMLayer).
+DSIN (extension): the Deep Session Interest Network's sessions, self-attention and bidirectional LSTM (layers.BiLSTMLayer),
+and SIMInput / SIM (extension): the Search-based Interest Model's top-k retrieval over long histories (functional.seq_search).
 """
 from collections import namedtuple
 
@@ -391,6 +392,143 @@ class DIN(_BehaviorModel):
         return DinAttentionLayer(**self.att_args)
 
 
+class SIMInput(DINInput):
+    """Feature input of a Search-based Interest Model (extension): DINInput's fields and short histories plus, per LONG behaviour, the
+    k items of a history of thousands that a General Search Unit retrieves for this candidate (Fn.seq_search, one fused launch that
+    scores the history straight from the shared table and writes [B,k] ids).
+
+    long_behavior: [(candidate_fea_name, T_long, k, mode, attr_fea_name or None), ...]; mode "soft" = the top k by inner product with
+    the candidate's own embedding row (read under no_grad: the selection is not differentiable), "hard" = the slots whose attribute
+    (long_attr, e.g. the item's category) equals the sample's id of the field attr_fea_name, "both" = the top k among those.  `prefer`
+    decides among equal scores: "last" (default) keeps the most recent, so the hard search returns the last k matches.
+    call((dense, sparse_idx [B,F], hist_idx [B,N,T] or None, long_idx [B,M,T_long], long_attr [B,M,T_long] or None)) -- or, as CTRModel
+    passes it, (dense, sparse_idx, (hist_idx, long_idx, long_attr)): model(dense, sparse_idx, (None, long_idx, None)) -- -> DINInput's
+    InputFeature with one more (keys [B,k,K], mask sel_idx != padding_id) entry per long behaviour in seq_embed_list and seq_info,
+    and the retrieved ids appended to seq_inputs.  The F + N T + sum k ids go through ONE Fn.embed_gather, exactly as DINInput's: the
+    table gradient is the same dense one, over k rows per sample instead of T_long."""
+
+    MODES = ("soft", "hard", "both")
+
+    def __init__(self, sparseInfo, behavior, long_behavior, denseInfo=None, padding_id=0, prefer="last"):
+        super().__init__(sparseInfo, behavior or [], denseInfo=denseInfo, padding_id=padding_id)
+        if prefer not in Fn.SEARCH_PREFER:
+            raise ValueError("SIMInput: prefer %r (%s)" % (prefer, ", ".join(Fn.SEARCH_PREFER)))
+        self.prefer = prefer
+        self.search_fn = Fn.seq_search      # Fn.seq_search_graph: the same search in torch ops (tools/seq_search_bench.py times both)
+        names = [i.fea_name for i in self.sparse_info]
+        sizes = [int(i.word_size) for i in self.sparse_info]
+        self.long_behavior = []
+        for entry in long_behavior or []:
+            name, TL, k, mode, attr_name = entry
+            if name not in names or int(TL) < 1 or int(k) < 1 or mode not in self.MODES:
+                raise ValueError("SIMInput: long behaviour %r: the candidate must be one of %s, T_long and k >= 1 and the mode one of %s"
+                                 % (tuple(entry), names, self.MODES))
+            if (mode != "soft") != (attr_name is not None) or (attr_name is not None and attr_name not in names):
+                raise ValueError("SIMInput: long behaviour %r: modes 'hard' and 'both' name the attribute's field (one of %s), 'soft' "
+                                 "names None" % (tuple(entry), names))
+            f = names.index(name)
+            self.long_behavior.append(dict(field=f, T=int(TL), k=int(k), mode=mode, offset=sum(sizes[:f]), size=sizes[f],
+                                           attr_field=None if attr_name is None else names.index(attr_name)))
+        if not self.long_behavior:
+            raise ValueError("SIMInput: no long behaviour (DINInput is the input without one)")
+        if len({e["T"] for e in self.long_behavior}) > 1:
+            raise ValueError("SIMInput: one history length T_long for all long behaviours (long_idx is [B,M,T_long])")
+
+    def build(self, input_shape):
+        super().build(input_shape)
+        emb = self.sparse_embed
+        fields = (list(range(len(self.sparse_info))) + [f for f, T in self.behavior for _ in range(T)]
+                  + [e["field"] for e in self.long_behavior for _ in range(e["k"])])
+        sel = torch.tensor(fields, dtype=torch.int64, device=self._build_device)
+        self.gather_offsets = emb.offsets[sel].contiguous()
+        self.gather_sizes = emb.sizes[sel].contiguous()
+        cands = torch.tensor([e["field"] for e in self.long_behavior], dtype=torch.int64, device=self._build_device)
+        self.register_buffer("cand_fields", cands)
+        self.register_buffer("cand_offsets", emb.offsets[cands].contiguous())
+        self.register_buffer("cand_sizes", emb.sizes[cands].contiguous())
+
+    def search(self, sparse_idx, long_idx, long_attr):
+        """The retrieved ids of every long behaviour, M x [B,k] int64, by self.search_fn."""
+        table = self.sparse_embed.embeddings
+        soft = any(e["mode"] != "hard" for e in self.long_behavior)
+        with torch.no_grad():
+            queries = Fn.embed_gather(table, self.cand_offsets, sparse_idx[:, self.cand_fields], sizes=self.cand_sizes) if soft else None
+            out = []
+            for m, e in enumerate(self.long_behavior):
+                args = dict(mask=None, padding_id=self.padding_id, prefer=self.prefer)
+                if e["mode"] != "hard":
+                    args.update(table=table, offset=e["offset"], size=e["size"], query=queries[:, m])
+                else:
+                    args.update(size=e["size"])
+                if e["mode"] != "soft":
+                    args.update(attr=long_attr[:, m], cand=sparse_idx[:, e["attr_field"]])
+                out.append(self.search_fn(long_idx[:, m], e["k"], **args)[0])
+        return out
+
+    def call(self, inputs, **kwargs):
+        if len(inputs) == 3 and isinstance(inputs[2], (tuple, list)):
+            inputs = tuple(inputs[:2]) + tuple(inputs[2])
+        if len(inputs) != 5:
+            raise ValueError("SIMInput: the call takes (dense, sparse_idx, hist_idx, long_idx, long_attr) or (dense, sparse_idx, (hist_idx, "
+                             "long_idx, long_attr)), got %d inputs" % len(inputs))
+        dense, sparse_idx, hist_idx, long_idx, long_attr = inputs
+        if sparse_idx is None or long_idx is None:
+            raise ValueError("SIMInput: sparse_idx and long_idx are required")
+        Fn._require_cuda(sparse_idx, hist_idx, long_idx, long_attr, dense)
+        F, N, M = len(self.sparse_info), len(self.behavior), len(self.long_behavior)
+        T, TL = (self.behavior[0][1] if N else 0), self.long_behavior[0]["T"]
+        needs_attr = any(e["mode"] != "soft" for e in self.long_behavior)
+        if sparse_idx.dim() != 2 or sparse_idx.shape[1] != F or tuple(long_idx.shape[1:]) != (M, TL) or \
+                (hist_idx is None) != (N == 0) or (hist_idx is not None and tuple(hist_idx.shape[1:]) != (N, T)) or \
+                (needs_attr and long_attr is None) or (long_attr is not None and tuple(long_attr.shape) != tuple(long_idx.shape)):
+            raise ValueError("SIMInput: sparse_idx must be [B,%d], hist_idx %s, long_idx [B,%d,%d] and long_attr %s, got %s, %s, %s and %s"
+                             % (F, "[B,%d,%d]" % (N, T) if N else "None", M, TL,
+                                "of long_idx's shape" if needs_attr else "of long_idx's shape or None", tuple(sparse_idx.shape),
+                                None if hist_idx is None else tuple(hist_idx.shape), tuple(long_idx.shape),
+                                None if long_attr is None else tuple(long_attr.shape)))
+        B = sparse_idx.shape[0]
+        sparse_idx = sparse_idx.to(torch.int64)
+        long_idx = long_idx.to(torch.int64)
+        long_attr = None if long_attr is None else long_attr.to(torch.int64)
+        found = self.search(sparse_idx, long_idx, long_attr)
+        parts = [sparse_idx]
+        if N:
+            hist_idx = hist_idx.to(torch.int64)
+            parts.append(hist_idx.reshape(B, N * T))
+        idx = torch.cat(parts + found, dim=1)
+        block = Fn.embed_gather(self.sparse_embed.embeddings, self.gather_offsets, idx, sizes=self.gather_sizes)   # [B, F + N T + sum k, K]
+        embed = list(block[:, :F].split(1, dim=1))
+        keys = [block[:, F + n * T:F + (n + 1) * T] for n in range(N)]
+        masks = [hist_idx[:, n] != self.padding_id for n in range(N)]
+        at = F + N * T
+        for e, ids in zip(self.long_behavior, found):
+            keys.append(block[:, at:at + e["k"]])
+            masks.append(ids != self.padding_id)
+            at += e["k"]
+        dense_inputs = [] if dense is None else [dense[:, i:i + 1] for i in range(dense.shape[1])]
+        sparse_inputs = [sparse_idx[:, i:i + 1] for i in range(F)]
+        seq_info = list(self.behavior) + [(e["field"], e["k"]) for e in self.long_behavior]
+        return InputFeature(self.dense_info, self.sparse_info, seq_info, dense_inputs, sparse_inputs,
+                            [hist_idx[:, n] for n in range(N)] + found, None, embed, [keys, masks])
+
+
+class SIM(_BehaviorModel):
+    """Search-based Interest Model (extension; the paper's two-stage model on SIMInput's features): the General Search Unit runs in
+    SIMInput; here the Exact Search Unit is one DinAttentionLayer(att_hidden_units, softmax=True) per entry of seq_embed_list -- short
+    histories and retrieved sets alike -- with the candidate's embedding as the query, then StackLayer over dense + field embeddings
+    + pooled sets -> DnnLayer -> MergeScoreLayer(use_merge=False).  Not restated: the paper's auxiliary soft-search tower with its
+    own embeddings, time-interval embeddings, multi-head attention as the exact unit, offline hard-search indexes."""
+
+    _list = "atten"
+
+    def __init__(self, att_hidden_units=(80, 40), att_activation="prelu", hidden_units=None):
+        super().__init__(hidden_units)
+        self.att_args = dict(hidden_units=tuple(att_hidden_units), activation=att_activation, softmax=True)
+
+    def _behavior(self, n):
+        return DinAttentionLayer(**self.att_args)
+
+
 class _DienBehavior(Layer):
     """One behaviour of DIEN: interest extraction, the candidate's scores against every interest state, interest evolution."""
 
@@ -580,7 +718,8 @@ class DSIN(_BehaviorModel):
 
 class CTRModel(torch.nn.Module):
     """FeatureInput + zoo body on raw batch tensors: model(dense [B, n_dense] or None, sparse_ids [B, F]), and with multi-valued
-    fields (FeatureInput(seqInfo=...)) model(dense, sparse_ids, seq_ids [B, F_seq, T])."""
+    fields (FeatureInput(seqInfo=...)) model(dense, sparse_ids, seq_ids [B, F_seq, T]).  seq_ids goes to the feature input as it is:
+    SIMInput takes the tuple (hist_ids or None, long_ids, long_attr or None) there."""
 
     def __init__(self, feature_input, body):
         super().__init__()
