@@ -528,7 +528,7 @@ int fil_lstm_bwd(const float* x, const unsigned char* mask, const float* W, cons
  *   (columns hD .. hD+D-1):
  *     s_ij = q_i . k_j (* 1/sqrt(D) when use_scale != 0);  p_ij = softmax of s_ij over the LIVE j (max-subtracted);
  *     out_i = sum_j p_ij v_j for a live i;  out_i = 0 for a masked i (a sample with no live slot: zeros).
- *   No biases, no output projection, no dropout, no causal mask.  A masked position's x row is never read.
+ *   No biases, no output projection, no dropout.  A masked position's x row is never read.
  *   fil_seqattn_fwd: out, and `saved` [B,T,3,H*D] = (q, k, v) of the live positions for the backward (fil_seqattn_saved_bytes; opaque
  *     to the caller; masked positions are left unwritten; NULL: nothing is saved, for inference).
  *   fil_seqattn_bwd: g [B,T,H*D] -> dx [B,T,K], dWq, dWk, dWv [K, H*D].  A masked position's g row is never read; dx is exactly 0
@@ -559,6 +559,36 @@ size_t fil_seqattn_bwd_workspace_bytes(int B, int T, int K, int H, int D);
 int fil_seqattn_bwd(const float* x, const unsigned char* mask, const float* Wq, const float* Wk, const float* Wv, const float* out,
                     const float* saved, const float* g, float* dx, float* dWq, float* dWk, float* dWv, void* workspace,
                     size_t workspace_bytes, int B, int T, int K, int H, int D, int use_scale, void* stream);
+
+/* The same operator under a structure mask (view) and with a pooled output (extension: the three views of the Sequence-Aware
+ * Factorization Machine and its intra-view mean pooling).  The same kernels: fil_seqattn_fwd / _bwd are these calls with
+ * FIL_SEQ_VIEW_FULL, split 0, rows out and g.  fil_seqattn_plan, _saved_bytes and _bwd_workspace_bytes serve both families; the menu
+ * and both LDS images are the same.  Entry points added only: the ABI version stays.
+ *   The keys row i may see are A_i = { j : j live and allowed(i, j) }:
+ *     FIL_SEQ_VIEW_FULL    every j                     (split must be 0)
+ *     FIL_SEQ_VIEW_CAUSAL  j <= i                      (split must be 0)
+ *     FIL_SEQ_VIEW_CROSS   (i < split) != (j < split), 1 <= split <= T - 1: the first `split` rows see only the others and the
+ *                          others see only them
+ *   p_ij = max-subtracted softmax of s_ij over A_i, out_i = sum over A_i of p_ij v_j in ascending j.  A masked i, and a live i with an
+ *   empty A_i (a static row of a sample whose history is all padding), gives out_i = 0 and sends no gradient anywhere.  Keys outside
+ *   A_i are not visited.  The softmax gradient is relative to the row's first maximal key of A_i (one allowed key: ds = 0 exactly).
+ *   fil_seqattn_fwd_v: out [B,T,H*D] or NULL; pooled [B,H*D] or NULL: pooled[b] = (sum of out_i over the live i, ascending, fp32) /
+ *     n_b with n_b the number of live rows, one division; n_b = 0 gives zeros.  At least one of the two; both given: both written.
+ *     With out = NULL nothing of size [B,T,H*D] but `saved` is written.
+ *   fil_seqattn_bwd_v: exactly one of g [B,T,H*D] and gpool [B,H*D]; with gpool every live row takes g_i = gpool[b] / n_b (one fp32
+ *     division per element).  No `out` argument (the first form does not read its own).  Outputs, NULL subsets, workspace, B == 0 and
+ *     the fixed summation order are those of fil_seqattn_bwd.
+ *   FIL_ERR_ARG, the entry point and the offending value in the message: a view outside 0 .. 2; split != 0 with FULL or CAUSAL; CROSS
+ *     with split < 1 or split >= T; out and pooled both NULL; g and gpool both or neither given.  Menu errors as above.
+ */
+#define FIL_SEQ_VIEW_FULL 0
+#define FIL_SEQ_VIEW_CAUSAL 1
+#define FIL_SEQ_VIEW_CROSS 2
+int fil_seqattn_fwd_v(const float* x, const unsigned char* mask, const float* Wq, const float* Wk, const float* Wv, float* out,
+                      float* pooled, float* saved, int B, int T, int K, int H, int D, int use_scale, int view, int split, void* stream);
+int fil_seqattn_bwd_v(const float* x, const unsigned char* mask, const float* Wq, const float* Wk, const float* Wv, const float* saved,
+                      const float* g, const float* gpool, float* dx, float* dWq, float* dWk, float* dWv, void* workspace,
+                      size_t workspace_bytes, int B, int T, int K, int H, int D, int use_scale, int view, int split, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * N3  Top-k retrieval over a LONG behaviour history (extension: the General Search Unit of the Search-based Interest Model): score

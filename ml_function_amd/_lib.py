@@ -44,6 +44,7 @@ FIL_DIN_SOFTMAX, FIL_DIN_SIGMOID = 1, 2   # fil_din_*'s flag bits: softmax over 
 FIL_GRU_GRU, FIL_GRU_AUGRU, FIL_GRU_AGRU = 0, 1, 2   # fil_gru_*'s mode
 FIL_LSTM_FORWARD, FIL_LSTM_REVERSE, FIL_LSTM_BIDIR = 0, 1, 2   # fil_lstm_*'s dirs
 FIL_SEARCH_PREFER_LAST = 1       # fil_seq_search's flag bit 0: among equal scores the later positions win
+FIL_SEQ_VIEW_FULL, FIL_SEQ_VIEW_CAUSAL, FIL_SEQ_VIEW_CROSS = 0, 1, 2      # fil_seqattn_*_v's structure masks
 FIL_ERR_UNSUPPORTED = -4
 
 _c = ctypes
@@ -124,6 +125,8 @@ SIGNATURES = {
     "fil_seqattn_fwd": (_I, [_P] * 7 + [_I] * 6 + [_P]),
     "fil_seqattn_bwd_workspace_bytes": (_Z, [_I, _I, _I, _I, _I]),
     "fil_seqattn_bwd": (_I, [_P] * 13 + [_Z] + [_I] * 6 + [_P]),
+    "fil_seqattn_fwd_v": (_I, [_P] * 8 + [_I] * 8 + [_P]),
+    "fil_seqattn_bwd_v": (_I, [_P] * 13 + [_Z] + [_I] * 8 + [_P]),
     # N3: top-k retrieval over a long behaviour history (forward only)
     "fil_seq_search_plan": (_I, [_I, _I, _I, _I, _P]),
     "fil_seq_search": (_I, [_P, _L, _L, _L, _L, _P, _P, _P, _L, _P, _L, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),

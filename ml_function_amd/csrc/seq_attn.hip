@@ -5,6 +5,16 @@
 //     q = x Wq, k = x Wk, v = x Wv;  per head h (columns hD .. hD+D-1):  s_ij = q_i . k_j (* 1/sqrt(D))
 //     p_ij = softmax of s_ij over the LIVE j;  out_i = sum_j p_ij v_j  for live i, 0 for masked i.
 //
+// The _v entry points add a structure mask (view) and a pooled output (the three views of the Sequence-Aware Factorization
+// Machine).  The keys a row may see are one RANGE of positions -- FULL: [0,T); CAUSAL: [0,i]; CROSS with split S: [S,T) for a row
+// i < S and [0,S) for a row i >= S -- so the key loops below keep their form and their ascending order and only get other bounds
+// (sa_range; the column pass of the backward walks the transposed range).  A live row whose range holds no live key gives out_i = 0
+// and sends no gradient (its 1/sum statistic is stored as 0 and the column pass skips it).  Pooled: the row pass leaves out_i in
+// the LDS slot of q_i (which only its owner thread reads), and one more pass adds the live rows of a sample in position order and
+// divides by their number; the backward builds its g rows as gpool[b] / n_b while staging them.  Each kernel has two instantiations
+// per head width: GEN = false is the first form exactly (FULL view, rows out, g rows in: uniform loop bounds, no pooling code, the
+// registers and occupancy it had), GEN = true takes the view and the pointers as run-time arguments (uniform branches).
+//
 // Structure (both directions).  A workgroup of 256 threads owns a tile of NS samples; everything of the tile sits in LDS (rows
 // padded by 4 floats), nothing of size [T,T] exists anywhere: the scores are recomputed where they are needed.  The products run on
 // FMAs (DESIGN 6t says why).  The weights are read through the caches, not staged: at K = H D = 64 they would take 48 KB that the
@@ -45,6 +55,7 @@ struct SaLayout {
   int b_g, b_q, b_k, b_v, b_dq, b_st, b_live, lds_bwd;       // backward: x | g | q | k (dk) | v (dv) | dq | stats [NS][H][T][5] | live
   int n_out;                                                 // one partial: dWq | dWk | dWv, each [K][HD]
   float scale;
+  int view, split;                                           // FIL_SEQ_VIEW_*; set by the _v entry points (0, 0 otherwise)
 };
 
 static inline int sa_fwd_floats(int T, int K, int HD) { return T * ((K + 4) + 3 * (HD + 4) + 1); }
@@ -78,10 +89,21 @@ static SaLayout sa_layout(int B, int T, int K, int H, int D, int use_scale) {
   L.lds_bwd = 4 * (L.b_live + up4(NT));
   L.n_out = 3 * K * L.HD;
   L.scale = use_scale ? 1.0f / sqrtf((float)D) : 1.0f;
+  L.view = FIL_SEQ_VIEW_FULL; L.split = 0;
   return L;
 }
 
 static inline int sa_grid(int B, int NS) { return tiled_grid(B, NS, kSaGridCap); }
+
+// [lo, hi): the keys row `at` may see -- or, transposed, the rows that may see key `at`
+__device__ __forceinline__ void sa_range(int view, int split, bool transposed, int at, int T, int& lo, int& hi) {
+  lo = 0; hi = T;
+  if (view == FIL_SEQ_VIEW_CAUSAL) {
+    if (transposed) lo = at; else hi = at + 1;
+  } else if (view == FIL_SEQ_VIEW_CROSS) {
+    if (at < split) lo = split; else hi = split;
+  }
+}
 
 // q . k over the head's D = 4 DQ columns, one fmaf chain in column order (a in registers, b in LDS)
 template <int DQM>
@@ -138,11 +160,12 @@ __device__ __forceinline__ void sa_stage_live(float* live, const unsigned char* 
   }
 }
 
-template <int DQM>
+template <int DQM, bool GEN>
 __global__ __launch_bounds__(kSaThreads) void seqattn_fwd_kernel(const float* __restrict__ x, const unsigned char* __restrict__ mask,
                                                                 const float* __restrict__ Wq, const float* __restrict__ Wk,
                                                                 const float* __restrict__ Wv, float* __restrict__ out,
-                                                                float* __restrict__ saved, int B, SaLayout L) {
+                                                                float* __restrict__ pooled, float* __restrict__ saved, int B,
+                                                                SaLayout L) {
   extern __shared__ __attribute__((aligned(16))) float sa_smem[];
   const int tid = threadIdx.x, nthr = blockDim.x;
   const int T = L.T, K = L.K, H = L.H, D = L.D, HD = L.HD, KP = L.KP, HDP = L.HDP, NS = L.NS, DQ = L.D / 4;
@@ -202,7 +225,6 @@ __global__ __launch_bounds__(kSaThreads) void seqattn_fwd_kernel(const float* __
         const long bb = b0 + s;
         if (bb >= B) continue;
         const float* lv = live + s * T;
-        float* o = out + (bb * T + i) * HD + h * D;
         float4 acc[DQM];
 #pragma unroll
         for (int d = 0; d < DQM; ++d) acc[d] = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -213,34 +235,63 @@ __global__ __launch_bounds__(kSaThreads) void seqattn_fwd_kernel(const float* __
             qr[d] = d < DQ ? *reinterpret_cast<const float4*>(qs + (s * T + i) * HDP + h * D + 4 * d) : make_float4(0.f, 0.f, 0.f, 0.f);
           const float* kh = ks + s * T * HDP + h * D;
           const float* vh = vs + s * T * HDP + h * D;
+          int j0 = 0, j1 = T;
+          if (GEN) sa_range(L.view, L.split, false, i, T, j0, j1);
           float m = -INFINITY;
-          for (int j = 0; j < T; ++j)
+          for (int j = j0; j < j1; ++j)
             if (lv[j] != 0.f) m = fmaxf(m, sa_dot<DQM>(qr, kh + j * HDP, DQ) * L.scale);
           float sum = 0.f;
-          for (int j = 0; j < T; ++j)
+          for (int j = j0; j < j1; ++j)
             if (lv[j] != 0.f) {
               const float e = expf(sa_dot<DQM>(qr, kh + j * HDP, DQ) * L.scale - m);
               sum += e;
               sa_axpy<DQM>(acc, e, vh + j * HDP, DQ);
             }
-          const float inv = 1.f / sum;
+          const float inv = GEN && sum == 0.f ? 0.f : 1.f / sum;      // no live key in the range: the row is 0
 #pragma unroll
           for (int d = 0; d < DQM; ++d) { acc[d].x *= inv; acc[d].y *= inv; acc[d].z *= inv; acc[d].w *= inv; }
-        }
+          // out_i takes the place of q_i (which only this thread reads) for the pooling pass
+          if (GEN && pooled != nullptr) {
 #pragma unroll
-        for (int d = 0; d < DQM; ++d)
-          if (d < DQ) *reinterpret_cast<float4*>(o + 4 * d) = acc[d];
+            for (int d = 0; d < DQM; ++d)
+              if (d < DQ) *reinterpret_cast<float4*>(qs + (s * T + i) * HDP + h * D + 4 * d) = acc[d];
+          }
+        }
+        if (!GEN || out != nullptr) {
+          float* o = out + (bb * T + i) * HD + h * D;
+#pragma unroll
+          for (int d = 0; d < DQM; ++d)
+            if (d < DQ) *reinterpret_cast<float4*>(o + 4 * d) = acc[d];
+        }
+      }
+    }
+    // pooled[b] = (sum of out_i over the live i, in position order) / (their number); a thread per (sample, column)
+    if (GEN && pooled != nullptr) {
+      __syncthreads();
+      const int n = NS * HD;
+      for (int idx = tid; idx < n; idx += nthr) {
+        const int s = idx / HD, c = idx - s * HD;
+        const long bb = b0 + s;
+        if (bb >= B) continue;
+        const float* lv = live + s * T;
+        const float* os = qs + s * T * HDP + c;
+        float acc = 0.f;
+        int cnt = 0;
+        for (int i = 0; i < T; ++i)
+          if (lv[i] != 0.f) { acc += os[i * HDP]; ++cnt; }
+        pooled[bb * HD + c] = cnt > 0 ? acc / (float)cnt : 0.f;
       }
     }
   }
 }
 
-template <int DQM>
+template <int DQM, bool GEN>
 __global__ __launch_bounds__(kSaThreads) void seqattn_bwd_kernel(const float* __restrict__ x, const unsigned char* __restrict__ mask,
                                                                 const float* __restrict__ Wq, const float* __restrict__ Wk,
                                                                 const float* __restrict__ Wv, const float* __restrict__ saved,
-                                                                const float* __restrict__ g, float* __restrict__ dx,
-                                                                float* __restrict__ partials, int B, SaLayout L) {
+                                                                const float* __restrict__ g, const float* __restrict__ gpool,
+                                                                float* __restrict__ dx, float* __restrict__ partials, int B,
+                                                                SaLayout L) {
   extern __shared__ __attribute__((aligned(16))) float sa_smem[];
   const int tid = threadIdx.x, nthr = blockDim.x;
   const int T = L.T, K = L.K, H = L.H, D = L.D, HD = L.HD, KP = L.KP, HDP = L.HDP, NS = L.NS, DQ = L.D / 4;
@@ -260,7 +311,28 @@ __global__ __launch_bounds__(kSaThreads) void seqattn_bwd_kernel(const float* __
     sa_stage_live(live, mask, b0, B, NS, T);
     __syncthreads();
     if (want_params) sa_stage_rows(xs, KP, x, K, K, live, b0, NS, T);
-    sa_stage_rows(gs, HDP, g, HD, HD, live, b0, NS, T);
+    if (!GEN || g != nullptr) {
+      sa_stage_rows(gs, HDP, g, HD, HD, live, b0, NS, T);
+    } else {
+      // the pooled form: g_i = gpool[b] / n_b at every live i.  n_b waits in the statistics' place, which the row pass writes later
+      for (int s = tid; s < NS; s += nthr) {
+        int cnt = 0;
+        for (int i = 0; i < T; ++i) cnt += live[s * T + i] != 0.f;
+        st[s] = (float)cnt;
+      }
+      __syncthreads();
+      const int WQ = HD / 4, n = NS * T * WQ;
+      for (int idx = tid; idx < n; idx += nthr) {
+        const int pos = idx / WQ, wq = idx - pos * WQ, s = pos / T;
+        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (live[pos] != 0.f) {
+          const float4 gp = *reinterpret_cast<const float4*>(gpool + (b0 + s) * HD + wq * 4);
+          const float nb = st[s];
+          v = make_float4(gp.x / nb, gp.y / nb, gp.z / nb, gp.w / nb);
+        }
+        *reinterpret_cast<float4*>(gs + pos * HDP + wq * 4) = v;
+      }
+    }
     sa_stage_rows(qs, HDP, saved, HD, 3L * HD, live, b0, NS, T);
     sa_stage_rows(ks, HDP, saved + HD, HD, 3L * HD, live, b0, NS, T);
     sa_stage_rows(vs, HDP, saved + 2 * HD, HD, 3L * HD, live, b0, NS, T);
@@ -283,9 +355,11 @@ __global__ __launch_bounds__(kSaThreads) void seqattn_bwd_kernel(const float* __
           const float* kh = ks + s * T * HDP + h * D;
           const float* vh = vs + s * T * HDP + h * D;
           const float* gi = gs + (s * T + i) * HDP + h * D;
+          int j0 = 0, j1 = T;
+          if (GEN) sa_range(L.view, L.split, false, i, T, j0, j1);
           float m = -INFINITY;
-          int top = i;      // row i is live, so key i is
-          for (int j = 0; j < T; ++j)
+          int top = GEN ? j0 : i;      // (every view but CROSS: row i is live, so key i is)
+          for (int j = j0; j < j1; ++j)
             if (lv[j] != 0.f) {
               const float sc = sa_dot<DQM>(qr, kh + j * HDP, DQ) * L.scale;
               if (sc > m) { m = sc; top = j; }
@@ -293,16 +367,16 @@ __global__ __launch_bounds__(kSaThreads) void seqattn_bwd_kernel(const float* __
           // everything relative to the top key: a row with one live key gives ds = 0 exactly, a peaked row keeps its digits
           const float c = sa_dot_lds(gi, vh + top * HDP, DQ);
           float sum = 0.f, wsum = 0.f;
-          for (int j = 0; j < T; ++j)
+          for (int j = j0; j < j1; ++j)
             if (lv[j] != 0.f) {
               const float e = expf(sa_dot<DQM>(qr, kh + j * HDP, DQ) * L.scale - m);
               const float a = j == top ? 0.f : sa_dot_lds(gi, vh + j * HDP, DQ) - c;
               sum += e;
               wsum = fmaf(e, a, wsum);
             }
-          const float inv = 1.f / sum;
+          const float inv = GEN && sum == 0.f ? 0.f : 1.f / sum;      // no live key in the range: the row sends nothing
           const float abar = wsum * inv;
-          for (int j = 0; j < T; ++j)
+          for (int j = j0; j < j1; ++j)
             if (lv[j] != 0.f) {
               const float e = expf(sa_dot<DQM>(qr, kh + j * HDP, DQ) * L.scale - m);
               const float a = j == top ? 0.f : sa_dot_lds(gi, vh + j * HDP, DQ) - c;
@@ -340,11 +414,14 @@ __global__ __launch_bounds__(kSaThreads) void seqattn_bwd_kernel(const float* __
         const float* qh = qs + s * T * HDP + h * D;
         const float* gh = gs + s * T * HDP + h * D;
         const float* sth = st + (long)sh * T * kSaStat;
-        for (int i = 0; i < T; ++i)
+        int i0 = 0, i1 = T;
+        if (GEN) sa_range(L.view, L.split, true, j, T, i0, i1);
+        for (int i = i0; i < i1; ++i)
           if (lv[i] != 0.f) {
             const float* sr = sth + i * kSaStat;
             const float m = sr[0], inv = sr[1], abar = sr[2], c = sr[3];
             const int top = __float_as_int(sr[4]);
+            if (GEN && inv == 0.f) continue;      // a row without keys
             // q_i . k_j with the operands' roles as in the row pass: the same bits
             float sc = 0.f;
 #pragma unroll
@@ -434,20 +511,91 @@ static int sa_dims(const char* who, int B, int T, int K, int H, int D, int use_s
   return FIL_OK;
 }
 
-template <int DQM>
+template <int DQM, bool GEN>
 static int sa_launch_fwd(const char* who, const float* x, const unsigned char* mask, const float* Wq, const float* Wk, const float* Wv,
-                         float* out, float* saved, int B, const SaLayout& L, hipStream_t st) {
-  if (int rc = tiled_allow_lds(who, seqattn_fwd_kernel<DQM>, L.lds_fwd)) return rc;
-  hipLaunchKernelGGL((seqattn_fwd_kernel<DQM>), dim3(sa_grid(B, L.NS)), dim3(kSaThreads), L.lds_fwd, st, x, mask, Wq, Wk, Wv, out, saved, B, L);
+                         float* out, float* pooled, float* saved, int B, const SaLayout& L, hipStream_t st) {
+  if (int rc = tiled_allow_lds(who, seqattn_fwd_kernel<DQM, GEN>, L.lds_fwd)) return rc;
+  hipLaunchKernelGGL((seqattn_fwd_kernel<DQM, GEN>), dim3(sa_grid(B, L.NS)), dim3(kSaThreads), L.lds_fwd, st, x, mask, Wq, Wk, Wv, out,
+                     pooled, saved, B, L);
   return FIL_OK;
 }
 
-template <int DQM>
+template <int DQM, bool GEN>
 static int sa_launch_bwd(const char* who, const float* x, const unsigned char* mask, const float* Wq, const float* Wk, const float* Wv,
-                         const float* saved, const float* g, float* dx, float* partials, int B, const SaLayout& L, hipStream_t st) {
-  if (int rc = tiled_allow_lds(who, seqattn_bwd_kernel<DQM>, L.lds_bwd)) return rc;
-  hipLaunchKernelGGL((seqattn_bwd_kernel<DQM>), dim3(sa_grid(B, L.NS)), dim3(kSaThreads), L.lds_bwd, st, x, mask, Wq, Wk, Wv, saved, g, dx,
-                     partials, B, L);
+                         const float* saved, const float* g, const float* gpool, float* dx, float* partials, int B, const SaLayout& L,
+                         hipStream_t st) {
+  if (int rc = tiled_allow_lds(who, seqattn_bwd_kernel<DQM, GEN>, L.lds_bwd)) return rc;
+  hipLaunchKernelGGL((seqattn_bwd_kernel<DQM, GEN>), dim3(sa_grid(B, L.NS)), dim3(kSaThreads), L.lds_bwd, st, x, mask, Wq, Wk, Wv, saved,
+                     g, gpool, dx, partials, B, L);
+  return FIL_OK;
+}
+
+// the view's own argument rules (after sa_dims: T is known to be positive)
+static int sa_view(const char* who, int T, int view, int split, SaLayout* L) {
+  if (view != FIL_SEQ_VIEW_FULL && view != FIL_SEQ_VIEW_CAUSAL && view != FIL_SEQ_VIEW_CROSS)
+    return fail(FIL_ERR_ARG, "%s: view=%d is none of FIL_SEQ_VIEW_FULL (0), _CAUSAL (1), _CROSS (2)", who, view);
+  if (view != FIL_SEQ_VIEW_CROSS && split != 0)
+    return fail(FIL_ERR_ARG, "%s: split=%d needs the cross view (view=%d takes split = 0)", who, split, view);
+  if (view == FIL_SEQ_VIEW_CROSS && (split < 1 || split >= T))
+    return fail(FIL_ERR_ARG, "%s: split=%d of the cross view needs 1 <= split <= T - 1 = %d", who, split, T - 1);
+  L->view = view; L->split = split;
+  return FIL_OK;
+}
+
+// the body of both forward entry points
+static int sa_fwd(const char* who, const float* x, const unsigned char* mask, const float* Wq, const float* Wk, const float* Wv, float* out,
+                  float* pooled, float* saved, int B, int T, int K, int H, int D, int use_scale, int view, int split, void* stream) {
+  SaLayout L;
+  if (int rc = sa_dims(who, B, T, K, H, D, use_scale, &L)) return rc;
+  if (int rc = sa_view(who, T, view, split, &L)) return rc;
+  if (B == 0) return FIL_OK;
+  FIL_CHECK_ARG_W(who, x != nullptr && Wq != nullptr && Wk != nullptr && Wv != nullptr);
+  if (out == nullptr && pooled == nullptr) return fail(FIL_ERR_ARG, "%s: out and pooled are both NULL: nothing to write", who);
+  hipStream_t st = (hipStream_t)stream;
+  ProfScope ps("seqattn_fwd", st,
+               4.0 * (double)B * (T * (K + (out != nullptr ? L.HD : 0) + (saved != nullptr ? 3.0 * L.HD : 0.0)) + (pooled != nullptr ? L.HD : 0)));
+  const int DQ = D / 4;
+#define SA_FWD(DQM, V) sa_launch_fwd<DQM, V>(who, x, mask, Wq, Wk, Wv, out, pooled, saved, B, L, st)
+  const int rc = view == FIL_SEQ_VIEW_FULL && pooled == nullptr ? (DQ <= 2 ? SA_FWD(2, false) : DQ <= 4 ? SA_FWD(4, false) : DQ <= 8 ? SA_FWD(8, false) : SA_FWD(16, false))
+                                                                : (DQ <= 2 ? SA_FWD(2, true) : DQ <= 4 ? SA_FWD(4, true) : DQ <= 8 ? SA_FWD(8, true) : SA_FWD(16, true));
+#undef SA_FWD
+  if (rc) return rc;
+  FIL_CHECK_LAUNCH_W(who);
+  return FIL_OK;
+}
+
+// the body of both backward entry points
+static int sa_bwd(const char* who, const float* x, const unsigned char* mask, const float* Wq, const float* Wk, const float* Wv,
+                  const float* saved, const float* g, const float* gpool, float* dx, float* dWq, float* dWk, float* dWv, void* workspace,
+                  size_t workspace_bytes, int B, int T, int K, int H, int D, int use_scale, int view, int split, void* stream) {
+  SaLayout L;
+  if (int rc = sa_dims(who, B, T, K, H, D, use_scale, &L)) return rc;
+  if (int rc = sa_view(who, T, view, split, &L)) return rc;
+  if (B == 0) return FIL_OK;
+  FIL_CHECK_ARG_W(who, x != nullptr && Wq != nullptr && Wk != nullptr && Wv != nullptr && saved != nullptr);
+  if ((g != nullptr) == (gpool != nullptr))
+    return fail(FIL_ERR_ARG, "%s: exactly one of g and gpool is given, got %s", who, g != nullptr ? "both" : "neither");
+  const bool want_params = dWq != nullptr || dWk != nullptr || dWv != nullptr;
+  FIL_CHECK_ARG_W(who, dx != nullptr || want_params);
+  const int nparts = sa_grid(B, L.NS);
+  if (want_params)
+    if (int rc = tiled_check_workspace(who, workspace, workspace_bytes, nparts, L.n_out)) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  ProfScope ps("seqattn_bwd", st, 4.0 * (double)B * (T * (2.0 * K + 3.0 * L.HD) + (g != nullptr ? T : 1) * L.HD));
+  float* partials = want_params ? static_cast<float*>(workspace) : nullptr;
+  const int DQ = D / 4;
+#define SA_BWD(DQM, V) sa_launch_bwd<DQM, V>(who, x, mask, Wq, Wk, Wv, saved, g, gpool, dx, partials, B, L, st)
+  const int rc = view == FIL_SEQ_VIEW_FULL && gpool == nullptr ? (DQ <= 2 ? SA_BWD(2, false) : DQ <= 4 ? SA_BWD(4, false) : DQ <= 8 ? SA_BWD(8, false) : SA_BWD(16, false))
+                                                               : (DQ <= 2 ? SA_BWD(2, true) : DQ <= 4 ? SA_BWD(4, true) : DQ <= 8 ? SA_BWD(8, true) : SA_BWD(16, true));
+#undef SA_BWD
+  if (rc) return rc;
+  FIL_CHECK_LAUNCH_W(who);
+  if (want_params) {
+    const int off[4] = {0, K * L.HD, 2 * K * L.HD, L.n_out};
+    float* outs[3] = {dWq, dWk, dWv};
+    param_reduce_launch(partials, nparts, outs, off, 3, st);
+    FIL_CHECK_LAUNCH_W(who);
+  }
   return FIL_OK;
 }
 
@@ -469,57 +617,36 @@ extern "C" size_t fil_seqattn_saved_bytes(int B, int T, int K, int H, int D) {
   return align_up((size_t)B * (size_t)T * 3 * (size_t)L.HD * sizeof(float), 256);
 }
 
-extern "C" int fil_seqattn_fwd(const float* x, const unsigned char* mask, const float* Wq, const float* Wk, const float* Wv, float* out,
-                               float* saved, int B, int T, int K, int H, int D, int use_scale, void* stream) {
-  SaLayout L;
-  if (int rc = sa_dims(__func__, B, T, K, H, D, use_scale, &L)) return rc;
-  if (B == 0) return FIL_OK;
-  FIL_CHECK_ARG(x != nullptr && Wq != nullptr && Wk != nullptr && Wv != nullptr && out != nullptr);
-  hipStream_t st = (hipStream_t)stream;
-  ProfScope ps("seqattn_fwd", st, 4.0 * (double)B * T * (K + L.HD + (saved != nullptr ? 3.0 * L.HD : 0.0)));
-  const int DQ = D / 4;
-  if (int rc = DQ <= 2 ? sa_launch_fwd<2>(__func__, x, mask, Wq, Wk, Wv, out, saved, B, L, st)
-             : DQ <= 4 ? sa_launch_fwd<4>(__func__, x, mask, Wq, Wk, Wv, out, saved, B, L, st)
-             : DQ <= 8 ? sa_launch_fwd<8>(__func__, x, mask, Wq, Wk, Wv, out, saved, B, L, st)
-                       : sa_launch_fwd<16>(__func__, x, mask, Wq, Wk, Wv, out, saved, B, L, st))
-    return rc;
-  FIL_CHECK_LAUNCH();
-  return FIL_OK;
-}
-
 extern "C" size_t fil_seqattn_bwd_workspace_bytes(int B, int T, int K, int H, int D) {
   SaLayout L;
   if (sa_dims(__func__, B, T, K, H, D, 1, &L) != FIL_OK) return 0;
   return tiled_partial_bytes(sa_grid(B, L.NS), L.n_out);
 }
 
+extern "C" int fil_seqattn_fwd_v(const float* x, const unsigned char* mask, const float* Wq, const float* Wk, const float* Wv, float* out,
+                                 float* pooled, float* saved, int B, int T, int K, int H, int D, int use_scale, int view, int split,
+                                 void* stream) {
+  return sa_fwd(__func__, x, mask, Wq, Wk, Wv, out, pooled, saved, B, T, K, H, D, use_scale, view, split, stream);
+}
+
+extern "C" int fil_seqattn_bwd_v(const float* x, const unsigned char* mask, const float* Wq, const float* Wk, const float* Wv,
+                                 const float* saved, const float* g, const float* gpool, float* dx, float* dWq, float* dWk, float* dWv,
+                                 void* workspace, size_t workspace_bytes, int B, int T, int K, int H, int D, int use_scale, int view,
+                                 int split, void* stream) {
+  return sa_bwd(__func__, x, mask, Wq, Wk, Wv, saved, g, gpool, dx, dWq, dWk, dWv, workspace, workspace_bytes, B, T, K, H, D, use_scale,
+                view, split, stream);
+}
+
+// the first form: the FULL view, rows out, g rows in
+extern "C" int fil_seqattn_fwd(const float* x, const unsigned char* mask, const float* Wq, const float* Wk, const float* Wv, float* out,
+                               float* saved, int B, int T, int K, int H, int D, int use_scale, void* stream) {
+  return sa_fwd(__func__, x, mask, Wq, Wk, Wv, out, nullptr, saved, B, T, K, H, D, use_scale, FIL_SEQ_VIEW_FULL, 0, stream);
+}
+
 extern "C" int fil_seqattn_bwd(const float* x, const unsigned char* mask, const float* Wq, const float* Wk, const float* Wv,
                                const float* out, const float* saved, const float* g, float* dx, float* dWq, float* dWk, float* dWv,
                                void* workspace, size_t workspace_bytes, int B, int T, int K, int H, int D, int use_scale, void* stream) {
-  SaLayout L;
-  if (int rc = sa_dims(__func__, B, T, K, H, D, use_scale, &L)) return rc;
-  if (B == 0) return FIL_OK;
-  FIL_CHECK_ARG(x != nullptr && Wq != nullptr && Wk != nullptr && Wv != nullptr && out != nullptr && saved != nullptr && g != nullptr);
-  const bool want_params = dWq != nullptr || dWk != nullptr || dWv != nullptr;
-  FIL_CHECK_ARG(dx != nullptr || want_params);
-  const int nparts = sa_grid(B, L.NS);
-  if (want_params)
-    if (int rc = tiled_check_workspace(__func__, workspace, workspace_bytes, nparts, L.n_out)) return rc;
-  hipStream_t st = (hipStream_t)stream;
-  ProfScope ps("seqattn_bwd", st, 4.0 * (double)B * T * (2.0 * K + 4.0 * L.HD));
-  float* partials = want_params ? static_cast<float*>(workspace) : nullptr;
-  const int DQ = D / 4;
-  if (int rc = DQ <= 2 ? sa_launch_bwd<2>(__func__, x, mask, Wq, Wk, Wv, saved, g, dx, partials, B, L, st)
-             : DQ <= 4 ? sa_launch_bwd<4>(__func__, x, mask, Wq, Wk, Wv, saved, g, dx, partials, B, L, st)
-             : DQ <= 8 ? sa_launch_bwd<8>(__func__, x, mask, Wq, Wk, Wv, saved, g, dx, partials, B, L, st)
-                       : sa_launch_bwd<16>(__func__, x, mask, Wq, Wk, Wv, saved, g, dx, partials, B, L, st))
-    return rc;
-  FIL_CHECK_LAUNCH();
-  if (want_params) {
-    const int off[4] = {0, K * L.HD, 2 * K * L.HD, L.n_out};
-    float* outs[3] = {dWq, dWk, dWv};
-    param_reduce_launch(partials, nparts, outs, off, 3, st);
-    FIL_CHECK_LAUNCH();
-  }
-  return FIL_OK;
+  if (B > 0 && T >= 1 && K >= 1 && H >= 1 && D >= 1) FIL_CHECK_ARG(out != nullptr);      // (kept for a caller-side check; not read)
+  return sa_bwd(__func__, x, mask, Wq, Wk, Wv, saved, g, nullptr, dx, dWq, dWk, dWv, workspace, workspace_bytes, B, T, K, H, D, use_scale,
+                FIL_SEQ_VIEW_FULL, 0, stream);
 }

@@ -526,64 +526,97 @@ def lstm_plan(B, T, K, H, direction="forward"):
     return _tiled_plan("fil_lstm_plan", int(B), int(T), int(K), int(H), LSTM_DIRECTIONS[direction])
 
 
+SEQ_VIEWS = {"full": _lib.FIL_SEQ_VIEW_FULL, "causal": _lib.FIL_SEQ_VIEW_CAUSAL, "cross": _lib.FIL_SEQ_VIEW_CROSS}
+
+
+def seq_view_check(who, view, split, T=None):
+    """ValueError for a view that is not one of SEQ_VIEWS or a split that contradicts it (full / causal: 0; cross: 1 .. T-1, the
+    upper end only once T is known) -- the rule of fil_seqattn_*_v, for the callers that want it before a tensor exists."""
+    if view not in SEQ_VIEWS:
+        raise ValueError("%s: view %r (%s)" % (who, view, ", ".join(SEQ_VIEWS)))
+    split = int(split)
+    if view != "cross" and split != 0:
+        raise ValueError("%s: split=%d needs view='cross' (view=%r takes split=0)" % (who, split, view))
+    if view == "cross" and (split < 1 or (T is not None and split >= T)):
+        raise ValueError("%s: view='cross' needs 1 <= split <= T-1, got split=%d%s" % (who, split, "" if T is None else " at T=%d" % T))
+    return SEQ_VIEWS[view], split
+
+
 class _SeqAttnFn(torch.autograd.Function):
+    """seq_self_attention and seq_view_attention: fil_seqattn_fwd_v / _bwd_v (the first is the full view with rows out)."""
+
     @staticmethod
-    def forward(ctx, x, mask, wq, wk, wv, heads, use_scale):
+    def forward(ctx, x, mask, wq, wk, wv, who, heads, use_scale, view, split, pool):
         _require_cuda(x, mask, wq, wk, wv)
         x, wq, wk, wv = (_f32c(t) for t in (x, wq, wk, wv))
         if (x.dim() != 3 or wq.dim() != 2 or wq.shape[0] != x.shape[2] or tuple(wk.shape) != tuple(wq.shape)
                 or tuple(wv.shape) != tuple(wq.shape)):
-            raise FilError("seq_self_attention: x must be [B,T,K] and Wq, Wk, Wv [K,H*D], got %s, %s, %s and %s"
-                           % (tuple(x.shape), tuple(wq.shape), tuple(wk.shape), tuple(wv.shape)))
+            raise FilError("%s: x must be [B,T,K] and Wq, Wk, Wv [K,H*D], got %s, %s, %s and %s"
+                           % (who, tuple(x.shape), tuple(wq.shape), tuple(wk.shape), tuple(wv.shape)))
         B, T, K = x.shape
         HD = wq.shape[1]
         if heads < 1 or HD % heads != 0:
-            raise FilError("seq_self_attention: %d heads do not divide the %d projection columns" % (heads, HD))
+            raise FilError("%s: %d heads do not divide the %d projection columns" % (who, heads, HD))
         H, D = heads, HD // heads
-        mask = _seq_mask("seq_self_attention", mask, B, T)
+        mask = _seq_mask(who, mask, B, T)
         lib = _lib.load()
-        out = torch.empty((B, T, HD), dtype=torch.float32, device=x.device)
+        res = torch.empty((B, HD) if pool else (B, T, HD), dtype=torch.float32, device=x.device)
         need = ctx.needs_input_grad
         saved = None
         if any(need[i] for i in (0, 2, 3, 4)):
             saved = _saved_floats(lib.fil_seqattn_saved_bytes(B, T, K, H, D), x.device)
-        check(lib.fil_seqattn_fwd(ptr(x), ptr(mask), ptr(wq), ptr(wk), ptr(wv), ptr(out), ptr(saved), B, T, K, H, D, int(use_scale),
-                                  stream_ptr()), "fil_seqattn_fwd")
-        _save(ctx, x, mask, wq, wk, wv, out, saved)
-        ctx.dims = (H, D, int(use_scale))
-        return out
+        check(lib.fil_seqattn_fwd_v(ptr(x), ptr(mask), ptr(wq), ptr(wk), ptr(wv), None if pool else ptr(res), ptr(res) if pool else None,
+                                    ptr(saved), B, T, K, H, D, int(use_scale), view, split, stream_ptr()), "fil_seqattn_fwd_v")
+        _save(ctx, x, mask, wq, wk, wv, saved)
+        ctx.dims = (H, D, int(use_scale), view, split, pool)
+        return res
 
     @staticmethod
     def backward(ctx, g):
         need = ctx.needs_input_grad
         if not (need[0] or need[2] or need[3] or need[4]):
-            return (None,) * 7
-        x, mask, wq, wk, wv, out, saved = _saved(ctx)
+            return (None,) * 11
+        x, mask, wq, wk, wv, saved = _saved(ctx)
         B, T, K = x.shape
-        H, D, use_scale = ctx.dims
+        H, D, use_scale, view, split, pool = ctx.dims
         dev = x.device
         dx = _grad(need[0], x.shape, dev)
         dwq = _grad(need[2], wq.shape, dev)
         dwk = _grad(need[3], wk.shape, dev)
         dwv = _grad(need[4], wv.shape, dev)
+        grads = (dx, None, dwq, dwk, dwv) + (None,) * 6
         if _no_samples(B, dwq, dwk, dwv):
-            return dx, None, dwq, dwk, dwv, None, None
+            return grads
         g = _f32c(g)
         lib = _lib.load()
         ws, nws = _partials_scratch("fil_seqattn_bwd_workspace_bytes", "seqattn_bwd", need[2] or need[3] or need[4], dev, B, T, K, H, D)
-        check(lib.fil_seqattn_bwd(ptr(x), ptr(mask), ptr(wq), ptr(wk), ptr(wv), ptr(out), ptr(saved), ptr(g), ptr(dx), ptr(dwq), ptr(dwk),
-                                  ptr(dwv), ptr(ws), nws, B, T, K, H, D, use_scale, stream_ptr()), "fil_seqattn_bwd")
-        return dx, None, dwq, dwk, dwv, None, None
+        check(lib.fil_seqattn_bwd_v(ptr(x), ptr(mask), ptr(wq), ptr(wk), ptr(wv), ptr(saved), None if pool else ptr(g), ptr(g) if pool else None,
+                                    ptr(dx), ptr(dwq), ptr(dwk), ptr(dwv), ptr(ws), nws, B, T, K, H, D, use_scale, view, split,
+                                    stream_ptr()), "fil_seqattn_bwd_v")
+        return grads
 
 
 def seq_self_attention(x, mask, Wq, Wk, Wv, heads, use_scale=True):
     """Masked multi-head scaled dot-product self-attention over a behaviour sequence (extension; include/fil.h fil_seqattn_*):
     x [B,T,K], mask [B,T] bool / uint8 (non-zero = live; None = all live), Wq, Wk, Wv [K,H*D] with H = heads -> [B,T,H*D], heads
     concatenated.  The softmax runs over the live keys; a masked position's row is 0 and its x row is never read.  No biases, no
-    output projection, no dropout, no causal mask.  One launch per direction (plus the small fixed-order sum of the
-    parameter-gradient partials); only the gradients that are asked for are written.  GPU only; shapes outside the kernel menu raise
-    FilError (layers.SeqSelfAttentionLayer takes its composed path there)."""
-    return _SeqAttnFn.apply(x, mask, Wq, Wk, Wv, int(heads), bool(use_scale))
+    output projection, no dropout; seq_view_attention adds a structure mask and a pooled output.  One launch per direction (plus the
+    small fixed-order sum of the parameter-gradient partials); only the gradients that are asked for are written.  GPU only; shapes
+    outside the kernel menu raise FilError (layers.SeqSelfAttentionLayer takes its composed path there)."""
+    return _SeqAttnFn.apply(x, mask, Wq, Wk, Wv, "seq_self_attention", int(heads), bool(use_scale), _lib.FIL_SEQ_VIEW_FULL, 0, False)
+
+
+def seq_view_attention(x, mask, Wq, Wk, Wv, heads, use_scale=True, view="full", split=0, pool=False):
+    """seq_self_attention under a structure mask, with an optional mean over the rows (extension; include/fil.h fil_seqattn_*_v: the
+    views of the Sequence-Aware Factorization Machine).  view: "full" (every live key), "causal" (row i sees the live keys j <= i) or
+    "cross" (the first `split` rows see only the live keys of the others and the others only theirs; 1 <= split <= T-1).  A live row
+    with no key to see is 0 and sends no gradient.  pool=False -> [B,T,H*D]; pool=True -> [B,H*D], the mean of the live rows (0 for a
+    sample without one), summed inside the kernel: no [B,T,H*D] tensor exists in either direction.  The same kernels as
+    seq_self_attention, which is view="full", pool=False bit for bit.  A bad view / split raises ValueError; GPU only; shapes outside the
+    kernel menu raise FilError (layers.SeqViewAttentionLayer takes its composed path there)."""
+    T = x.shape[1] if torch.is_tensor(x) and x.dim() == 3 else None
+    v, s = seq_view_check("seq_view_attention", view, split, T)
+    return _SeqAttnFn.apply(x, mask, Wq, Wk, Wv, "seq_view_attention", int(heads), bool(use_scale), v, s, bool(pool))
 
 
 def seq_attn_plan(B, T, K, H, D):

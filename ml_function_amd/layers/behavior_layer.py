@@ -528,7 +528,8 @@ class SeqSelfAttentionLayer(Layer):
     call(x [B,T,K], mask=None) -> [B,T,heads * head_dim], heads concatenated.  mask: a [B,T] bool or uint8 tensor, non-zero = live;
     the softmax runs over the live keys and a masked position's row is 0.  Weights carry the reference layer's names and shape:
     query_w, key_w, value_w, each [K, heads, head_dim], glorot_uniform(seed) -- and value_w is used here.  No biases, no output
-    projection, no dropout, no causal mask.  One HIP kernel per direction (Fn.seq_self_attention, include/fil.h fil_seqattn_*).
+    projection, no dropout (SeqViewAttentionLayer adds the causal and the cross mask).  One HIP kernel per direction
+    (Fn.seq_self_attention, include/fil.h fil_seqattn_*).
     Outside the kernel menu (fits_kernel_menu) or for a non-fp32 input the layer takes the composed path -- seq_self_attention_graph
     on the GPU, computed in fp32 -- instead of raising."""
 
@@ -572,4 +573,79 @@ class SeqSelfAttentionLayer(Layer):
         _check_seq_mask("SeqSelfAttentionLayer", mask, x.shape[0], x.shape[1])
         if x.dtype == torch.float32 and self.fits_kernel_menu(x):
             return Fn.seq_self_attention(x, mask, *self._flat(), self.heads, use_scale=self.use_scale)
+        return self._composed(x, mask)
+
+
+def seq_view_attention_graph(x, mask, wq, wk, wv, heads, use_scale=True, view="full", split=0, pool=False):
+    """Fn.seq_view_attention's math as torch ops on the tensors given (their dtype and device; autograd for the backward): the
+    composed path of SeqViewAttentionLayer and the comparator of its benchmark.  On top of seq_self_attention_graph's launches it
+    builds the view's [T,T] structure mask and broadcasts it over the [B,H,T,T] score block, and the pooled form adds a masked mean
+    over the rows.  A row that may see no live key is 0 and sends no gradient; a sample without a live row pools to 0."""
+    Fn.seq_view_check("seq_view_attention_graph", view, split, x.shape[1])
+    B, T, K = x.shape
+    H = int(heads)
+    D = wq.shape[1] // H
+    zero = torch.zeros((), dtype=x.dtype, device=x.device)
+    live = torch.ones((B, T), dtype=torch.bool, device=x.device) if mask is None else mask.to(torch.bool)
+    if mask is not None:
+        x = torch.where(live.unsqueeze(-1), x, zero)
+    q = torch.matmul(x, wq).reshape(B, T, H, D).permute(0, 2, 1, 3)
+    k = torch.matmul(x, wk).reshape(B, T, H, D).permute(0, 2, 1, 3)
+    v = torch.matmul(x, wv).reshape(B, T, H, D).permute(0, 2, 1, 3)
+    s = torch.matmul(q, k.transpose(-1, -2))
+    if use_scale:
+        s = s * (1.0 / float(D) ** 0.5)
+    allowed = live.reshape(B, 1, 1, T)
+    if view != "full":
+        pos = torch.arange(T, device=x.device)
+        if view == "causal":
+            structure = pos.reshape(1, T) <= pos.reshape(T, 1)
+        else:
+            structure = (pos.reshape(T, 1) < int(split)) != (pos.reshape(1, T) < int(split))
+        allowed = allowed & structure.reshape(1, 1, T, T)
+    s = torch.where(allowed, s, torch.full((), -float("inf"), dtype=s.dtype, device=s.device))
+    some = allowed.any(dim=-1, keepdim=True)
+    m = torch.where(some, s.detach().max(dim=-1, keepdim=True).values, zero)
+    e = torch.where(allowed, torch.exp(s - m), zero)
+    p = e / e.sum(dim=-1, keepdim=True).clamp_min(torch.finfo(s.dtype).tiny)
+    out = torch.matmul(p, v).permute(0, 2, 1, 3).reshape(B, T, H * D)
+    out = torch.where(live.unsqueeze(-1), out, zero)
+    if not pool:
+        return out
+    n = live.sum(dim=1, keepdim=True).to(out.dtype)
+    return torch.where(n > 0, out.sum(dim=1) / n.clamp_min(1.0), zero)
+
+
+class SeqViewAttentionLayer(SeqSelfAttentionLayer):
+    """SeqSelfAttentionLayer under a structure mask, with an optional mean over the rows (extension: a view of the Sequence-Aware
+    Factorization Machine and its intra-view pooling).
+
+    view: "full"; "causal" -- row i sees the live keys j <= i; "cross" -- the first `split` rows (the static block) see only the live
+    keys of the others (the history) and the others only theirs, 1 <= split <= T-1.  A live row with no key to see is 0.  pool=True:
+    call(x [B,T,K], mask=None) -> [B, heads * head_dim], the mean of the live rows, taken inside the kernel (Fn.seq_view_attention:
+    no [B,T,H D] tensor in either direction).  The weights, their names, the kernel menu and the composed path outside it (here
+    seq_view_attention_graph) are SeqSelfAttentionLayer's."""
+
+    def __init__(self, heads, head_dim, use_scale=True, seed=2020, view="full", split=0, pool=False):
+        super().__init__(heads, head_dim, use_scale=use_scale, seed=seed)
+        Fn.seq_view_check("SeqViewAttentionLayer", view, split)
+        self.view = view
+        self.split = int(split)
+        self.pool = bool(pool)
+
+    def _composed(self, x, mask):
+        """seq_view_attention_graph on the GPU in fp32: it exists so that a shape outside the kernel menu never raises."""
+        Fn._require_cuda(x, mask)
+        return seq_view_attention_graph(x.to(torch.float32), mask, *self._flat(), self.heads, use_scale=self.use_scale, view=self.view,
+                                        split=self.split, pool=self.pool)
+
+    def call(self, inputs, mask=None, **kwargs):
+        x = inputs
+        if not torch.is_tensor(x) or x.dim() != 3:
+            raise ValueError("SeqViewAttentionLayer: x must be [B,T,K], got %s" % (tuple(x.shape) if torch.is_tensor(x) else type(x).__name__,))
+        _check_seq_mask("SeqViewAttentionLayer", mask, x.shape[0], x.shape[1])
+        Fn.seq_view_check("SeqViewAttentionLayer", self.view, self.split, x.shape[1])
+        if x.dtype == torch.float32 and self.fits_kernel_menu(x):
+            return Fn.seq_view_attention(x, mask, *self._flat(), self.heads, use_scale=self.use_scale, view=self.view, split=self.split,
+                                         pool=self.pool)
         return self._composed(x, mask)

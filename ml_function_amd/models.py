@@ -8,7 +8,8 @@ except DINInput / DIN (extension): the Deep Interest Network's attention pooling
 DIEN (extension): the Deep Interest Evolution Network's GRU + AUGRU over the same histories (layers.GRULayer),
 BST (extension): the Behaviour Sequence Transformer's block over them (layers.SeqSelfAttentionLayer),
 DSIN (extension): the Deep Session Interest Network's sessions, self-attention and bidirectional LSTM (layers.BiLSTMLayer),
-and SIMInput / SIM (extension): the Search-based Interest Model's top-k retrieval over long histories (functional.seq_search).
+SIMInput / SIM (extension): the Search-based Interest Model's top-k retrieval over long histories (functional.seq_search),
+and SeqFM (extension): the Sequence-Aware Factorization Machine's static, dynamic and cross views (layers.SeqViewAttentionLayer).
 """
 from collections import namedtuple
 
@@ -16,9 +17,9 @@ import torch
 
 from . import functional as Fn
 from .layers import (CIN, AFMLayer, AttentionBaseLayer, BagEmbed, BiLSTMLayer, CrossLayer, DinAttentionLayer, DnnLayer, FmLayer, GRULayer, InnerLayer, IPnnLayer, MergeScoreLayer,
-                     MultHeadAttentionLayer, OPnnLayer, ScoreLayer, SeqSelfAttentionLayer, SparseEmbed, StackLayer)
+                     MultHeadAttentionLayer, OPnnLayer, ScoreLayer, SeqSelfAttentionLayer, SeqViewAttentionLayer, SparseEmbed, StackLayer)
 from .layers.core_layer import Dense
-from .layers.base import Layer
+from .layers.base import Layer, merge_packed_views
 from .layers.behavior_layer import _masked_softmax
 from .layers.interactive_layer import pack_fields
 from .layers.core_layer import keras_add
@@ -646,6 +647,84 @@ class BST(_BehaviorModel):
 
     def _collect(self, out):      # [the mean over the live positions, the candidate's position]
         return out
+
+
+class _SeqFmFfn(Layer):
+    """One residual feed-forward layer of SeqFM, shared by all views: h + relu(Dense(K)(LayerNorm(h))), as torch ops."""
+
+    def __init__(self, seed=2020):
+        super().__init__()
+        self.seed = seed
+        self.ln_epsilon = 1e-3      # tf.keras.layers.LayerNormalization() default
+
+    def build(self, input_shape):
+        k = int(input_shape[-1])
+        self.ln_gamma = self.add_weight("ln_gamma", [k], "ones")
+        self.ln_beta = self.add_weight("ln_beta", [k], "zeros")
+        self.dense = Dense(k, seed=self.seed)
+        super().build(input_shape)
+
+    def call(self, inputs, **kwargs):
+        h = inputs
+        y = torch.nn.functional.layer_norm(h, (h.shape[-1],), self.ln_gamma, self.ln_beta, self.ln_epsilon)
+        return h + torch.relu(self.dense(y))
+
+
+class SeqFM(torch.nn.Module):
+    """Sequence-Aware Factorization Machine (extension; the paper's multi-view self-attention on DINInput's features).  With
+    S0 = the F one-id field embeddings [B,F,K] and, per behaviour n, the history keys[n] [B,T,K] under masks[n]:
+      static view          SeqViewAttentionLayer(att_heads, K // att_heads, view="full", pool=True)(S0)
+      dynamic view of n    ... view="causal", pool=True on keys[n] under masks[n]
+      cross view of n      ... view="cross", split=F, pool=True on [S0 ; keys[n]] under [ones ; masks[n]]
+    each one launch per direction that returns the view's mean over its live rows (the intra-view pooling) as [B,K].
+    h = stack(views) [B,1+2N,K]; ffn_layers times h = h + relu(Dense_l(LayerNorm_l(h))) with the weights shared by all views
+    (epsilon 1e-3, gamma / beta; torch ops); then MergeScoreLayer(use_merge=False) on StackLayer()(dense inputs + [h]).
+    Left out: dropout, position embeddings, the linear and global-bias terms of the paper's output."""
+
+    def __init__(self, att_heads=1, ffn_layers=1, seed=2020):
+        super().__init__()
+        if int(att_heads) < 1:
+            raise ValueError("SeqFM: att_heads must be positive, got %r" % (att_heads,))
+        if int(ffn_layers) < 0:
+            raise ValueError("SeqFM: ffn_layers must not be negative, got %r" % (ffn_layers,))
+        self.att_heads = int(att_heads)
+        self.ffn_layers = int(ffn_layers)
+        self.seed = seed
+        self.static_view = None
+        self.dynamic_views = torch.nn.ModuleList()
+        self.cross_views = torch.nn.ModuleList()
+        self.ffn = torch.nn.ModuleList(_SeqFmFfn(seed=seed + 100 + l) for l in range(self.ffn_layers))
+        self.stack = StackLayer()
+        self.score = MergeScoreLayer(use_merge=False)
+
+    def _view(self, k, seed, **kw):
+        return SeqViewAttentionLayer(self.att_heads, k // self.att_heads, seed=seed, pool=True, **kw)
+
+    def forward(self, inputFea):
+        keys, masks = inputFea.seq_embed_list or (None, None)
+        if not keys:
+            raise ValueError("SeqFM: the input carries no behaviour sequence (DINInput(..., behavior=[...]) with at least one)")
+        fields = merge_packed_views(list(inputFea.sparse_embed))
+        s0 = fields[0] if len(fields) == 1 else torch.cat(fields, dim=1)            # [B,F,K]
+        B, F, K = s0.shape
+        if K % self.att_heads != 0:
+            raise ValueError("SeqFM: att_heads=%d does not divide the embedding width K=%d" % (self.att_heads, K))
+        if self.static_view is None:
+            self.static_view = self._view(K, self.seed, view="full")
+        while len(self.dynamic_views) < len(keys):
+            n = len(self.dynamic_views)
+            self.dynamic_views.append(self._view(K, self.seed + 1 + 2 * n, view="causal"))
+            self.cross_views.append(self._view(K, self.seed + 2 + 2 * n, view="cross", split=F))
+        views = [self.static_view(s0)]
+        static_live = torch.ones((B, F), dtype=torch.bool, device=s0.device)
+        for n, (hist, mask) in enumerate(zip(keys, masks)):
+            views.append(self.dynamic_views[n](hist, mask=mask))
+            live = torch.ones(hist.shape[:2], dtype=torch.bool, device=s0.device) if mask is None else mask.to(torch.bool)
+            views.append(self.cross_views[n](torch.cat([s0, hist], dim=1), mask=torch.cat([static_live, live], dim=1)))
+        h = torch.stack(views, dim=1)                                                # [B,1+2N,K]
+        for ffn in self.ffn:
+            h = ffn(h)
+        return self.score(self.stack(list(inputFea.dense_inputs) + [h]))
 
 
 class _DsinBehavior(_TransformerBlock):
