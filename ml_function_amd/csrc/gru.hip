@@ -5,12 +5,7 @@
 //     z = sigmoid(xp_z + hp_z);  r = sigmoid(xp_r + hp_r);  c = tanh(xp_h + r hp_h);  u = 1 - z
 //     u' = u (GRU) | a_t u (AUGRU) | a_t (AGRU);   h_new = (1 - u') h + u' c;   a masked step carries h.
 //
-// Structure (both directions).  A workgroup owns a tile of NS = 4 G samples for all T steps; a thread owns ONE hidden unit j of FOUR
-// samples (g = its sample quad), so that every weight read from LDS feeds four samples.  The weights are staged once per workgroup
-// (forward: W, U as given, lanes = consecutive columns; backward: their transposes, and nothing else -- the backward recomputes no
-// product, it reads z, r, c and hp_h from `saved`).  x_t and the hidden state sit in LDS TRANSPOSED ([feature][sample], row stride
-// NS + 4) so that one 16-byte read gives a feature of the thread's four samples; they are double buffered and the global loads of
-// the next step are in flight during the arithmetic of this one (the step is a dependent chain: nothing else hides the load).
+// Structure (both directions): rnn_tile.h's sample-quad tiling and schedule, with three gates, two bias rows and the scores.
 //   forward   per step: 3 (K + H) weight reads + (K + H) state reads for 12 (K + H) FMAs per thread; the gates; hs, saved -> global;
 //             the new state -> LDS.  One barrier.
 //   backward  t = T-1 .. 0, dh (the gradient of the state) in registers.  Per step:
@@ -24,97 +19,16 @@
 // No atomics; every sum has a fixed order for a given shape: repeats are bit-identical.
 #include "common.h"
 #include "param_reduce.h"
-#include "tiled_launch.h"
-#include <algorithm>
+#include "rnn_tile.h"
 #include <math.h>
 
 namespace fil {
 
-constexpr int kGruMaxK = 64, kGruMaxH = 64;
-constexpr int kGruGridCap = 1024;      // workgroups per launch
-constexpr int kGruThreads = 256;       // the most a workgroup has
-constexpr int kGruXV = 4;              // 16-byte pieces of x_t a thread stages per step, at most
-
-// all LDS offsets in floats (multiples of 4)
-struct GruLayout {
-  int T, K, H, H3, G, NS, NSP, threads, NR;
-  int f_U, f_b, f_x, f_h, f_live, f_a, lds_fwd;              // forward:  W | U | b [2][3H] | xT [2][K][NSP] | hT [2][H][NSP] | live [2][NS] | a [2][NS]
-  int b_UT, b_in, b_dT, b_dS, b_da, b_live, b_a, lds_bwd;    // backward: WT [3H][K] | UT [3H][H] | inT [2][K+H][NSP] | dT [4H][NSP] | dS [NS][4H] |
-                                                             //           da terms [H][NSP] | live [2][NS] | a [2][NS]
-  int n_out;                                                 // one partial: dW [K][3H] | dU [H][3H] | db [2][3H]
-};
-
-static GruLayout gru_layout(int B, int T, int K, int H) {
-  GruLayout L;
-  L.T = T; L.K = K; L.H = H; L.H3 = 3 * H;
-  const int P = std::max(H, K / 4);                         // threads per sample quad: a unit each, and enough to stage x_t in kGruXV pieces
-  const int Gmax = kGruThreads / P;                         // >= 4
-  const int Gmin = std::min(Gmax, cdiv(64, P));             // a full wave where the shape allows
-  const int Glow = std::max(Gmin, cdiv(K + H, 32));         // at most 32 rows of [dW ; dU] per thread
-  const long want = ((long)B + 4L * kGruGridCap - 1) / (4L * kGruGridCap);      // small batches: small tiles, more workgroups
-  L.G = (int)std::min((long)Gmax, std::max((long)Glow, want));
-  L.NS = 4 * L.G;
-  L.NSP = L.NS + 4;
-  L.threads = (L.G * P + 63) / 64 * 64;
-  const int nr = cdiv(K + H, L.G);
-  L.NR = nr <= 8 ? 8 : (nr <= 16 ? 16 : 32);
-  L.f_U = K * L.H3;
-  L.f_b = L.f_U + H * L.H3;
-  L.f_x = L.f_b + 2 * L.H3;
-  L.f_h = L.f_x + 2 * K * L.NSP;
-  L.f_live = L.f_h + 2 * H * L.NSP;
-  L.f_a = L.f_live + 2 * L.NS;
-  L.lds_fwd = 4 * (L.f_a + 2 * L.NS);
-  L.b_UT = K * L.H3;
-  L.b_in = L.b_UT + H * L.H3;
-  L.b_dT = L.b_in + 2 * (K + H) * L.NSP;
-  L.b_dS = L.b_dT + 4 * H * L.NSP;
-  L.b_da = L.b_dS + L.NS * 4 * H;
-  L.b_live = L.b_da + H * L.NSP;
-  L.b_a = L.b_live + 2 * L.NS;
-  L.lds_bwd = 4 * (L.b_a + 2 * L.NS);
-  L.n_out = (K + H + 2) * L.H3;
-  return L;
-}
-
-static inline int gru_grid(int B, int NS) { return tiled_grid(B, NS, kGruGridCap); }
-
-__device__ __forceinline__ float gru_sigmoid(float v) { return 1.f / (1.f + expf(-v)); }
-
-// 16-byte pieces of x_t of the tile's samples -> registers; a masked step's (and a sample past B's) row is never read: zeros
-__device__ __forceinline__ void gru_load_x(float4 (&xr)[kGruXV], const float* __restrict__ x, const unsigned char* __restrict__ mask, long b0,
-                                           int B, int t, const GruLayout& L) {
-  const int KQ = L.K / 4, n = L.NS * KQ;
-#pragma unroll
-  for (int i = 0; i < kGruXV; ++i) {
-    const int idx = threadIdx.x + i * blockDim.x;
-    xr[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (idx < n) {
-      const int s = idx / KQ, kq = idx - s * KQ;
-      const long bb = b0 + s;
-      if (bb < B && (mask == nullptr || mask[bb * L.T + t] != 0))
-        xr[i] = *reinterpret_cast<const float4*>(x + (bb * L.T + t) * L.K + kq * 4);
-    }
-  }
-}
-
-// ... -> the transposed LDS image xT [K][NSP]
-__device__ __forceinline__ void gru_store_x(const float4 (&xr)[kGruXV], float* xT, const GruLayout& L) {
-  const int KQ = L.K / 4, n = L.NS * KQ;
-#pragma unroll
-  for (int i = 0; i < kGruXV; ++i) {
-    const int idx = threadIdx.x + i * blockDim.x;
-    if (idx < n) {
-      const int s = idx / KQ, kq = idx - s * KQ;
-      float* d = xT + (kq * 4) * L.NSP + s;
-      d[0] = xr[i].x; d[L.NSP] = xr[i].y; d[2 * L.NSP] = xr[i].z; d[3 * L.NSP] = xr[i].w;
-    }
-  }
-}
+constexpr int kGruGates = 3, kGruBiasRows = 2;
 
 // live flag (1 / 0) and score of sample b0 + threadIdx.x at step t (threads below NS)
 __device__ __forceinline__ void gru_load_step(float& lv, float& av, const float* __restrict__ a, const unsigned char* __restrict__ mask, long b0,
-                                              int B, int t, const GruLayout& L) {
+                                              int B, int t, const RnnLayout& L) {
   lv = 0.f; av = 0.f;
   if ((int)threadIdx.x < L.NS) {
     const long bb = b0 + threadIdx.x;
@@ -125,16 +39,16 @@ __device__ __forceinline__ void gru_load_step(float& lv, float& av, const float*
   }
 }
 
-__global__ __launch_bounds__(kGruThreads) void gru_fwd_kernel(const float* __restrict__ x, const float* __restrict__ a,
+__global__ __launch_bounds__(kRnnThreads) void gru_fwd_kernel(const float* __restrict__ x, const float* __restrict__ a,
                                                              const unsigned char* __restrict__ mask, const float* __restrict__ W,
                                                              const float* __restrict__ U, const float* __restrict__ bias, float* __restrict__ hs,
-                                                             float* __restrict__ saved, int B, int mode, GruLayout L) {
+                                                             float* __restrict__ saved, int B, int mode, RnnLayout L) {
   extern __shared__ __attribute__((aligned(16))) float gru_smem[];
-  const int tid = threadIdx.x, nthr = blockDim.x;
-  const int T = L.T, K = L.K, H = L.H, H3 = L.H3, NS = L.NS, NSP = L.NSP;
-  for (int i = tid; i < K * H3; i += nthr) gru_smem[i] = W[i];
-  for (int i = tid; i < H * H3; i += nthr) gru_smem[L.f_U + i] = U[i];
-  for (int i = tid; i < 2 * H3; i += nthr) gru_smem[L.f_b + i] = bias[i];
+  const int tid = threadIdx.x;
+  const int T = L.T, K = L.K, H = L.H, H3 = L.HG, NS = L.NS, NSP = L.NSP;
+  rnn_stage(gru_smem, W, K * H3);
+  rnn_stage(gru_smem + L.f_U, U, H * H3);
+  rnn_stage(gru_smem + L.f_b, bias, kGruBiasRows * H3);
   const float* Ws = gru_smem;
   const float* Us = gru_smem + L.f_U;
   const float* bs = gru_smem + L.f_b;
@@ -144,22 +58,20 @@ __global__ __launch_bounds__(kGruThreads) void gru_fwd_kernel(const float* __res
   for (long tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
     const long b0 = tile * NS;
     float h[4] = {0.f, 0.f, 0.f, 0.f};
-    float4 xr[kGruXV];
+    float4 xr[kRnnXV];
     float lvn, avn;
     __syncthreads();      // the weights are staged; the previous tile's images are free
-    gru_load_x(xr, x, mask, b0, B, 0, L);
+    rnn_load_x(xr, x, mask, b0, B, 0, L);
     gru_load_step(lvn, avn, a, mask, b0, B, 0, L);
-    gru_store_x(xr, gru_smem + L.f_x, L);
+    rnn_store_x(xr, gru_smem + L.f_x, L);
     if (tid < NS) { gru_smem[L.f_live + tid] = lvn; gru_smem[L.f_a + tid] = avn; }
     if (active) *reinterpret_cast<float4*>(gru_smem + L.f_h + j * NSP + 4 * g) = make_float4(0.f, 0.f, 0.f, 0.f);
     if (T > 1) {
-      gru_load_x(xr, x, mask, b0, B, 1, L);
+      rnn_load_x(xr, x, mask, b0, B, 1, L);
       gru_load_step(lvn, avn, a, mask, b0, B, 1, L);
     }
     __syncthreads();
-    // Order within a step: the arithmetic; the registers loaded a step ago -> LDS (the wait for them also covers the stores of the
-    // step before, long under way); this step's stores; the loads of the step after next.  A wait right behind fresh stores would
-    // put their latency on the chain.
+    // the order within a step: rnn_tile.h, Schedule
     for (int t = 0; t < T; ++t) {
       const int cur = t & 1, nxt = cur ^ 1;
       float zv[4], rv[4], cv[4], pv[4];
@@ -174,35 +86,15 @@ __global__ __launch_bounds__(kGruThreads) void gru_fwd_kernel(const float* __res
         }
         const float* xc = gru_smem + L.f_x + cur * K * NSP + 4 * g;
         const float* hc = gru_smem + L.f_h + cur * H * NSP + 4 * g;
-#pragma unroll 4
-        for (int k = 0; k < K; ++k) {
-          const float4 v = *reinterpret_cast<const float4*>(xc + k * NSP);
-          const float ve[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-          for (int c = 0; c < 3; ++c) {
-            const float w = Ws[k * H3 + c * H + j];
-#pragma unroll
-            for (int e = 0; e < 4; ++e) ax[c][e] = fmaf(ve[e], w, ax[c][e]);
-          }
-        }
-#pragma unroll 4
-        for (int k = 0; k < H; ++k) {
-          const float4 v = *reinterpret_cast<const float4*>(hc + k * NSP);
-          const float ve[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-          for (int c = 0; c < 3; ++c) {
-            const float w = Us[k * H3 + c * H + j];
-#pragma unroll
-            for (int e = 0; e < 4; ++e) ah[c][e] = fmaf(ve[e], w, ah[c][e]);
-          }
-        }
+        rnn_fwd_products(ax, xc, Ws, K, j, L);
+        rnn_fwd_products(ah, hc, Us, H, j, L);
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
           const int s = 4 * g + e;
           lv[e] = gru_smem[L.f_live + cur * NS + s] != 0.f;
           const float at = gru_smem[L.f_a + cur * NS + s];
-          const float z = gru_sigmoid(ax[0][e] + ah[0][e]);
-          const float r = gru_sigmoid(ax[1][e] + ah[1][e]);
+          const float z = rnn_sigmoid(ax[0][e] + ah[0][e]);
+          const float r = rnn_sigmoid(ax[1][e] + ah[1][e]);
           const float c = tanhf(ax[2][e] + r * ah[2][e]);
           const float u = 1.f - z;
           const float up = mode == FIL_GRU_AGRU ? at : (mode == FIL_GRU_AUGRU ? at * u : u);
@@ -213,7 +105,7 @@ __global__ __launch_bounds__(kGruThreads) void gru_fwd_kernel(const float* __res
         *reinterpret_cast<float4*>(gru_smem + L.f_h + nxt * H * NSP + j * NSP + 4 * g) = make_float4(h[0], h[1], h[2], h[3]);
       }
       if (t + 1 < T) {
-        gru_store_x(xr, gru_smem + L.f_x + nxt * K * NSP, L);
+        rnn_store_x(xr, gru_smem + L.f_x + nxt * K * NSP, L);
         if (tid < NS) { gru_smem[L.f_live + nxt * NS + tid] = lvn; gru_smem[L.f_a + nxt * NS + tid] = avn; }
       }
       if (active) {
@@ -228,7 +120,7 @@ __global__ __launch_bounds__(kGruThreads) void gru_fwd_kernel(const float* __res
         }
       }
       if (t + 2 < T) {
-        gru_load_x(xr, x, mask, b0, B, t + 2, L);
+        rnn_load_x(xr, x, mask, b0, B, t + 2, L);
         gru_load_step(lvn, avn, a, mask, b0, B, t + 2, L);
       }
       __syncthreads();
@@ -237,23 +129,17 @@ __global__ __launch_bounds__(kGruThreads) void gru_fwd_kernel(const float* __res
 }
 
 template <int NR>
-__global__ __launch_bounds__(kGruThreads) void gru_bwd_kernel(const float* __restrict__ x, const float* __restrict__ a,
+__global__ __launch_bounds__(kRnnThreads) void gru_bwd_kernel(const float* __restrict__ x, const float* __restrict__ a,
                                                              const unsigned char* __restrict__ mask, const float* __restrict__ W,
                                                              const float* __restrict__ U, const float* __restrict__ hs,
                                                              const float* __restrict__ saved, const float* __restrict__ g_hs,
                                                              const float* __restrict__ g_last, float* __restrict__ dx, float* __restrict__ da,
-                                                             float* __restrict__ partials, int B, int mode, GruLayout L) {
+                                                             float* __restrict__ partials, int B, int mode, RnnLayout L) {
   extern __shared__ __attribute__((aligned(16))) float gru_smem[];
   const int tid = threadIdx.x, nthr = blockDim.x;
-  const int T = L.T, K = L.K, H = L.H, H3 = L.H3, NS = L.NS, NSP = L.NSP, G = L.G, KH = L.K + L.H;
-  for (int i = tid; i < K * H3; i += nthr) {       // WT [m][k] = W [k][m]
-    const int k = i / H3, m = i - k * H3;
-    gru_smem[m * K + k] = W[i];
-  }
-  for (int i = tid; i < H * H3; i += nthr) {
-    const int k = i / H3, m = i - k * H3;
-    gru_smem[L.b_UT + m * H + k] = U[i];
-  }
+  const int T = L.T, K = L.K, H = L.H, H3 = L.HG, NS = L.NS, NSP = L.NSP, G = L.G, KH = L.K + L.H;
+  rnn_stage_transposed(gru_smem, W, K, L);
+  rnn_stage_transposed(gru_smem + L.b_UT, U, H, L);
   const float* WT = gru_smem;
   const float* UT = gru_smem + L.b_UT;
   float* dT = gru_smem + L.b_dT;
@@ -262,7 +148,7 @@ __global__ __launch_bounds__(kGruThreads) void gru_bwd_kernel(const float* __res
   const bool active = tid < G * H;
   const int g = tid / H, j = tid - g * H;
   const bool want_params = partials != nullptr;
-  float acc[NR][3];
+  float acc[NR][kGruGates];
 #pragma unroll
   for (int r = 0; r < NR; ++r) acc[r][0] = acc[r][1] = acc[r][2] = 0.f;
   float dbs[4] = {0.f, 0.f, 0.f, 0.f};      // the thread's samples' dz, dr, dc (input side), dc r (recurrent side)
@@ -271,10 +157,10 @@ __global__ __launch_bounds__(kGruThreads) void gru_bwd_kernel(const float* __res
     const long b0 = tile * NS;
     float dh[4] = {0.f, 0.f, 0.f, 0.f};
     float svn[4][4], hpn[4], ghn[4], lvn, avn;
-    float4 xr[kGruXV];
+    float4 xr[kRnnXV];
     // what step tt needs, of the thread's unit and samples -> registers
     auto prefetch = [&](int tt) {
-      if (want_params) gru_load_x(xr, x, mask, b0, B, tt, L);
+      if (want_params) rnn_load_x(xr, x, mask, b0, B, tt, L);
       gru_load_step(lvn, avn, a, mask, b0, B, tt, L);
       if (active) {
 #pragma unroll
@@ -295,7 +181,7 @@ __global__ __launch_bounds__(kGruThreads) void gru_bwd_kernel(const float* __res
     auto commit = [&](int buf) {
       float* inT = gru_smem + L.b_in + buf * KH * NSP;
       if (want_params) {
-        gru_store_x(xr, inT, L);
+        rnn_store_x(xr, inT, L);
         if (active) *reinterpret_cast<float4*>(inT + (K + j) * NSP + 4 * g) = make_float4(hpn[0], hpn[1], hpn[2], hpn[3]);
       }
       if (tid < NS) { gru_smem[L.b_live + buf * NS + tid] = lvn; gru_smem[L.b_a + buf * NS + tid] = avn; }
@@ -360,45 +246,12 @@ __global__ __launch_bounds__(kGruThreads) void gru_bwd_kernel(const float* __res
       if (active) {
         // dh_prev = dh (1 - u') + d_hp U^T: rows z, r of dT, then the recurrent side's dc r
         float nh[4] = {0.f, 0.f, 0.f, 0.f};
-        if (t > 0) {
-#pragma unroll 4
-          for (int m = 0; m < H3; ++m) {
-            const float4 d = *reinterpret_cast<const float4*>(dT + (m < 2 * H ? m : m + H) * NSP + 4 * g);
-            const float w = UT[m * H + j];
-            nh[0] = fmaf(d.x, w, nh[0]); nh[1] = fmaf(d.y, w, nh[1]); nh[2] = fmaf(d.z, w, nh[2]); nh[3] = fmaf(d.w, w, nh[3]);
-          }
-        }
+        if (t > 0) rnn_bwd_matvec<true>(nh, dT + 4 * g, UT, H, j, L);
 #pragma unroll
         for (int e = 0; e < 4; ++e) dh[e] = keep[e] + nh[e];
-        if (want_params) {
-          const float* inT = gru_smem + L.b_in + cur * KH * NSP;
-          for (int s4 = 0; s4 < NS; s4 += 4) {
-            float ez[4], er[4], ex[4], eh[4];
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-              const float* d = dS + (s4 + e) * 4 * H + j;
-              ez[e] = d[0]; er[e] = d[H]; ex[e] = d[2 * H]; eh[e] = d[3 * H];
-            }
-#pragma unroll
-            for (int r = 0; r < NR; ++r) {
-              const int i = g + r * G;
-              if (i < KH) {
-                const float4 v = *reinterpret_cast<const float4*>(inT + i * NSP + s4);
-                const float ve[4] = {v.x, v.y, v.z, v.w};
-                const bool xrow = i < K;
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                  acc[r][0] = fmaf(ve[e], ez[e], acc[r][0]);
-                  acc[r][1] = fmaf(ve[e], er[e], acc[r][1]);
-                  acc[r][2] = fmaf(ve[e], xrow ? ex[e] : eh[e], acc[r][2]);
-                }
-              }
-            }
-          }
-        }
+        if (want_params) rnn_bwd_accumulate(acc, gru_smem + L.b_in + cur * KH * NSP, dS, g, j, L);
       }
-      // the registers loaded at the top of the step -> LDS BEFORE this step's stores are issued: the wait for those loads would
-      // otherwise also sit out the fresh stores, on the chain
+      // the registers loaded at the top of the step -> LDS BEFORE this step's stores are issued (rnn_tile.h, Schedule)
       if (t > 0) commit((t - 1) & 1);
       if (da != nullptr && tid < NS) {
         const long bb = b0 + tid;
@@ -408,50 +261,17 @@ __global__ __launch_bounds__(kGruThreads) void gru_bwd_kernel(const float* __res
           da[bb * T + t] = sum;
         }
       }
-      if (active) {
-        if (dx != nullptr) {
-          for (int k = j; k < K; k += H) {
-            float v[4] = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll 4
-            for (int m = 0; m < H3; ++m) {
-              const float4 d = *reinterpret_cast<const float4*>(dT + m * NSP + 4 * g);
-              const float w = WT[m * K + k];
-              v[0] = fmaf(d.x, w, v[0]); v[1] = fmaf(d.y, w, v[1]); v[2] = fmaf(d.z, w, v[2]); v[3] = fmaf(d.w, w, v[3]);
-            }
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-              const long bb = b0 + 4 * g + e;
-              const bool live = gru_smem[L.b_live + cur * NS + 4 * g + e] != 0.f;
-              if (bb < B) dx[(bb * T + t) * K + k] = live ? v[e] : 0.f;
-            }
-          }
-        }
-      }
+      if (active && dx != nullptr) rnn_bwd_dx(dx, dT + 4 * g, WT, gru_smem + L.b_live + cur * NS + 4 * g, b0 + 4 * g, B, t, j, L);
       __syncthreads();
     }
   }
   if (!want_params) return;
-  // the workgroup's partial: the accumulators as they stand; db = the quads' sums in quad order
+  // the workgroup's partial; db = the four sums on the two bias rows: dz, dr on both, dc on the input side's, dc r on the recurrent side's
   float* part = partials + (long)blockIdx.x * L.n_out;
-  if (active) {
-#pragma unroll
-    for (int r = 0; r < NR; ++r) {
-      const int i = g + r * G;
-      if (i < KH) {
-        part[i * H3 + j] = acc[r][0];
-        part[i * H3 + H + j] = acc[r][1];
-        part[i * H3 + 2 * H + j] = acc[r][2];
-      }
-    }
-    // (the last barrier of the step loop has passed: dS is free)
-#pragma unroll
-    for (int c = 0; c < 4; ++c) dS[(g * 4 + c) * H + j] = dbs[c];
-  }
-  __syncthreads();
+  rnn_bwd_write_partial(part, acc, dbs, dS, active, g, j, L);
   for (int o = tid; o < 4 * H; o += nthr) {
     const int c = o / H, jj = o - c * H;
-    float sum = 0.f;
-    for (int gg = 0; gg < G; ++gg) sum += dS[(gg * 4 + c) * H + jj];
+    const float sum = rnn_bwd_quad_sum(dS, o, L);
     float* db = part + KH * H3;
     if (c < 2) { db[c * H + jj] = sum; db[H3 + c * H + jj] = sum; }
     else if (c == 2) db[2 * H + jj] = sum;
@@ -460,30 +280,10 @@ __global__ __launch_bounds__(kGruThreads) void gru_bwd_kernel(const float* __res
 }
 
 // argument and menu checks shared by the entry points
-static int gru_dims(const char* who, int B, int T, int K, int H, int mode, GruLayout* L) {
+static int gru_dims(const char* who, int B, int T, int K, int H, int mode, RnnLayout* L) {
   FIL_CHECK_ARG_W(who, B >= 0 && T >= 1 && K >= 1 && H >= 1);
   FIL_CHECK_ARG_W(who, mode == FIL_GRU_GRU || mode == FIL_GRU_AUGRU || mode == FIL_GRU_AGRU);
-  if (K % 4 != 0 || K > kGruMaxK) return fail(FIL_ERR_UNSUPPORTED, "%s: K=%d needs K %% 4 == 0 and K <= %d", who, K, kGruMaxK);
-  if (H % 4 != 0 || H > kGruMaxH) return fail(FIL_ERR_UNSUPPORTED, "%s: H=%d needs H %% 4 == 0 and H <= %d", who, H, kGruMaxH);
-  *L = gru_layout(B, T, K, H);
-  if (L->lds_fwd > kTiledLdsLimit || L->lds_bwd > kTiledLdsLimit)
-    return fail(FIL_ERR_UNSUPPORTED, "%s: K=%d H=%d needs %d bytes of LDS (limit %d)", who, K, H, std::max(L->lds_fwd, L->lds_bwd), kTiledLdsLimit);
-  return FIL_OK;
-}
-
-struct GruBwdArgs {
-  const float *x, *a;
-  const unsigned char* mask;
-  const float *W, *U, *hs, *saved, *g_hs, *g_last;
-  float *dx, *da, *partials;
-};
-
-template <int NR>
-static int gru_launch_bwd(const char* who, const GruBwdArgs& p, int B, int mode, const GruLayout& L, hipStream_t st) {
-  if (int rc = tiled_allow_lds(who, gru_bwd_kernel<NR>, L.lds_bwd)) return rc;
-  hipLaunchKernelGGL((gru_bwd_kernel<NR>), dim3(gru_grid(B, L.NS)), dim3(L.threads), L.lds_bwd, st, p.x, p.a, p.mask, p.W, p.U, p.hs, p.saved,
-                     p.g_hs, p.g_last, p.dx, p.da, p.partials, B, mode, L);
-  return FIL_OK;
+  return rnn_dims(who, B, T, K, H, kGruGates, kGruBiasRows, true, L);
 }
 
 }  // namespace fil
@@ -491,22 +291,22 @@ static int gru_launch_bwd(const char* who, const GruBwdArgs& p, int B, int mode,
 using namespace fil;
 
 extern "C" int fil_gru_plan(int B, int T, int K, int H, int mode, int* plan) {
-  GruLayout L;
+  RnnLayout L;
   if (int rc = gru_dims(__func__, B, T, K, H, mode, &L)) return rc;
   FIL_CHECK_ARG(plan != nullptr);
-  tiled_plan(plan, L.NS, gru_grid(B, L.NS), kGruGridCap, L.lds_fwd, L.lds_bwd);
+  tiled_plan(plan, L.NS, rnn_grid(B, L.NS), kRnnGridCap, L.lds_fwd, L.lds_bwd);
   return FIL_OK;
 }
 
 extern "C" size_t fil_gru_saved_bytes(int B, int T, int K, int H) {
-  GruLayout L;
+  RnnLayout L;
   if (gru_dims(__func__, B, T, K, H, FIL_GRU_GRU, &L) != FIL_OK) return 0;
   return align_up((size_t)B * (size_t)T * 4 * (size_t)H * sizeof(float), 256);
 }
 
 extern "C" int fil_gru_fwd(const float* x, const float* a, const unsigned char* mask, const float* W, const float* U, const float* b,
                            float* hs, float* saved, int B, int T, int K, int H, int mode, void* stream) {
-  GruLayout L;
+  RnnLayout L;
   if (int rc = gru_dims(__func__, B, T, K, H, mode, &L)) return rc;
   if (B == 0) return FIL_OK;
   FIL_CHECK_ARG(x != nullptr && W != nullptr && U != nullptr && b != nullptr && hs != nullptr);
@@ -514,21 +314,21 @@ extern "C" int fil_gru_fwd(const float* x, const float* a, const unsigned char* 
   hipStream_t st = (hipStream_t)stream;
   ProfScope ps("gru_fwd", st, 4.0 * (double)B * T * (K + H + (saved != nullptr ? 4.0 * H : 0.0)));
   if (int rc = tiled_allow_lds(__func__, gru_fwd_kernel, L.lds_fwd)) return rc;
-  hipLaunchKernelGGL(gru_fwd_kernel, dim3(gru_grid(B, L.NS)), dim3(L.threads), L.lds_fwd, st, x, a, mask, W, U, b, hs, saved, B, mode, L);
+  hipLaunchKernelGGL(gru_fwd_kernel, dim3(rnn_grid(B, L.NS)), dim3(L.threads), L.lds_fwd, st, x, a, mask, W, U, b, hs, saved, B, mode, L);
   FIL_CHECK_LAUNCH();
   return FIL_OK;
 }
 
 extern "C" size_t fil_gru_bwd_workspace_bytes(int B, int T, int K, int H) {
-  GruLayout L;
+  RnnLayout L;
   if (gru_dims(__func__, B, T, K, H, FIL_GRU_GRU, &L) != FIL_OK) return 0;
-  return tiled_partial_bytes(gru_grid(B, L.NS), L.n_out);
+  return tiled_partial_bytes(rnn_grid(B, L.NS), L.n_out);
 }
 
 extern "C" int fil_gru_bwd(const float* x, const float* a, const unsigned char* mask, const float* W, const float* U, const float* hs,
                            const float* saved, const float* g_hs, const float* g_last, float* dx, float* da, float* dW, float* dU, float* db,
                            void* workspace, size_t workspace_bytes, int B, int T, int K, int H, int mode, void* stream) {
-  GruLayout L;
+  RnnLayout L;
   if (int rc = gru_dims(__func__, B, T, K, H, mode, &L)) return rc;
   if (B == 0) return FIL_OK;
   FIL_CHECK_ARG(x != nullptr && W != nullptr && U != nullptr && hs != nullptr && saved != nullptr);
@@ -537,19 +337,18 @@ extern "C" int fil_gru_bwd(const float* x, const float* a, const unsigned char* 
   FIL_CHECK_ARG(da == nullptr || mode != FIL_GRU_GRU);
   const bool want_params = dW != nullptr || dU != nullptr || db != nullptr;
   FIL_CHECK_ARG(dx != nullptr || da != nullptr || want_params);
-  const int nparts = gru_grid(B, L.NS);
+  const int nparts = rnn_grid(B, L.NS);
   if (want_params)
     if (int rc = tiled_check_workspace(__func__, workspace, workspace_bytes, nparts, L.n_out)) return rc;
   hipStream_t st = (hipStream_t)stream;
   ProfScope ps("gru_bwd", st, 4.0 * (double)B * T * (2.0 * K + 6.0 * H));
-  const GruBwdArgs p = {x, a, mask, W, U, hs, saved, g_hs, g_last, dx, da, want_params ? static_cast<float*>(workspace) : nullptr};
-  if (int rc = L.NR == 8 ? gru_launch_bwd<8>(__func__, p, B, mode, L, st)
-                         : (L.NR == 16 ? gru_launch_bwd<16>(__func__, p, B, mode, L, st) : gru_launch_bwd<32>(__func__, p, B, mode, L, st)))
+  if (int rc = rnn_launch_bwd(__func__, [](auto nr) { return gru_bwd_kernel<decltype(nr)::value>; }, L, dim3(nparts), st, x, a, mask, W, U, hs,
+                              saved, g_hs, g_last, dx, da, want_params ? static_cast<float*>(workspace) : nullptr, B, mode))
     return rc;
   FIL_CHECK_LAUNCH();
   if (want_params) {
     float* const outs[3] = {dW, dU, db};
-    const int off[4] = {0, K * L.H3, (K + H) * L.H3, L.n_out};
+    const int off[4] = {0, K * L.HG, (K + H) * L.HG, L.n_out};
     param_reduce_launch(static_cast<const float*>(workspace), nparts, outs, off, 3, st);
     FIL_CHECK_LAUNCH();
   }

@@ -5,10 +5,9 @@
 //     i = sigmoid(z_i);  f = sigmoid(z_f);  g = tanh(z_c);  o = sigmoid(z_o);   c_new = f c + i g;   h_new = o tanh(c_new)
 //     a masked step carries h and c.
 //
-// Structure: gru.hip's, widened to four gates.  A workgroup owns a tile of NS = 4 G samples for all T steps of ONE direction
-// (blockIdx.y selects it: its weights are the only ones staged); a thread owns ONE hidden unit j of FOUR samples, and with it the
-// cell: c (forward) and dc (backward) live in registers.  x_t and h sit in LDS transposed ([feature][sample], row stride NS + 4),
-// double buffered, the global loads of the next step in flight during the arithmetic of this one.  A direction walks its steps
+// Structure: rnn_tile.h's sample-quad tiling and schedule, with four gates and one bias row.  A workgroup owns its tile for all T
+// steps of ONE direction (blockIdx.y selects it: its weights are the only ones staged); a thread owns, with its unit of four
+// samples, the cell: c (forward) and dc (backward) live in registers.  A direction walks its steps
 // s = 0 .. T-1 at the time positions t = s (forward) or t = T-1-s (reverse) and leaves the state reached after step s at position t.
 //   forward   per step: 4 (K + H) weight reads + (K + H) state reads for 16 (K + H) FMAs per thread; the gates; hs, saved -> global;
 //             the new h -> LDS.  One barrier.  saved [B,T,5,H] per direction = (i, f, g, o) of the live steps and the cell c after
@@ -24,118 +23,33 @@
 // No atomics; every sum has a fixed order for a given shape: repeats are bit-identical.
 #include "common.h"
 #include "param_reduce.h"
-#include "tiled_launch.h"
+#include "rnn_tile.h"
 #include <algorithm>
 #include <math.h>
 
 namespace fil {
 
-constexpr int kLstmMaxK = 64, kLstmMaxH = 64;
-constexpr int kLstmGridCap = 1024;      // workgroups per launch and direction
-constexpr int kLstmThreads = 256;       // the most a workgroup has
-constexpr int kLstmXV = 4;              // 16-byte pieces of x_t a thread stages per step, at most
+constexpr int kLstmGates = 4, kLstmBiasRows = 1;
 constexpr int kLstmSaved = 5;           // planes of `saved` per step: i, f, g, o, c
 
-// all LDS offsets in floats (multiples of 4)
-struct LstmLayout {
-  int T, K, H, H4, G, NS, NSP, threads, NR;
-  int f_U, f_b, f_x, f_h, f_live, lds_fwd;                   // forward:  W | U | b [4H] | xT [2][K][NSP] | hT [2][H][NSP] | live [2][NS]
-  int b_UT, b_in, b_dT, b_dS, b_live, lds_bwd;               // backward: WT [4H][K] | UT [4H][H] | inT [2][K+H][NSP] | dT [4H][NSP] | dS [NS][4H] |
-                                                             //           live [2][NS]
-  int n_out;                                                 // one partial: dW [K][4H] | dU [H][4H] | db [4H]
-};
-
-static LstmLayout lstm_layout(int B, int T, int K, int H) {
-  LstmLayout L;
-  L.T = T; L.K = K; L.H = H; L.H4 = 4 * H;
-  const int P = std::max(H, K / 4);                         // threads per sample quad: a unit each, and enough to stage x_t in kLstmXV pieces
-  const int Gmax = kLstmThreads / P;                        // >= 4
-  const int Gmin = std::min(Gmax, cdiv(64, P));             // a full wave where the shape allows
-  const int Glow = std::max(Gmin, cdiv(K + H, 32));         // at most 32 rows of [dW ; dU] per thread
-  const long want = ((long)B + 4L * kLstmGridCap - 1) / (4L * kLstmGridCap);     // small batches: small tiles, more workgroups
-  L.G = (int)std::min((long)Gmax, std::max((long)Glow, want));
-  L.NS = 4 * L.G;
-  L.NSP = L.NS + 4;
-  L.threads = (L.G * P + 63) / 64 * 64;
-  const int nr = cdiv(K + H, L.G);
-  L.NR = nr <= 8 ? 8 : (nr <= 16 ? 16 : 32);
-  L.f_U = K * L.H4;
-  L.f_b = L.f_U + H * L.H4;
-  L.f_x = L.f_b + L.H4;
-  L.f_h = L.f_x + 2 * K * L.NSP;
-  L.f_live = L.f_h + 2 * H * L.NSP;
-  L.lds_fwd = 4 * (L.f_live + 2 * L.NS);
-  L.b_UT = K * L.H4;
-  L.b_in = L.b_UT + H * L.H4;
-  L.b_dT = L.b_in + 2 * (K + H) * L.NSP;
-  L.b_dS = L.b_dT + L.H4 * L.NSP;
-  L.b_live = L.b_dS + L.NS * L.H4;
-  L.lds_bwd = 4 * (L.b_live + 2 * L.NS);
-  L.n_out = (K + H + 1) * L.H4;
-  return L;
-}
-
-static inline int lstm_grid(int B, int NS) { return tiled_grid(B, NS, kLstmGridCap); }
 static inline int lstm_ndir(int dirs) { return dirs == FIL_LSTM_BIDIR ? 2 : 1; }
 
 // the workspace of a backward, in floats: the partials of every direction (rounded up to 256 bytes), then, with both directions in
 // one launch, the reverse direction's dx [B,T,K]
-static inline size_t lstm_workspace_floats(int B, int dirs, const LstmLayout& L) {
-  const size_t parts = tiled_partial_bytes(lstm_ndir(dirs) * lstm_grid(B, L.NS), L.n_out) / sizeof(float);
+static inline size_t lstm_workspace_floats(int B, int dirs, const RnnLayout& L) {
+  const size_t parts = tiled_partial_bytes(lstm_ndir(dirs) * rnn_grid(B, L.NS), L.n_out) / sizeof(float);
   return parts + (dirs == FIL_LSTM_BIDIR ? (size_t)B * L.T * L.K : 0);
-}
-
-__device__ __forceinline__ float lstm_sigmoid(float v) { return 1.f / (1.f + expf(-v)); }
-
-// 16-byte pieces of x_t of the tile's samples -> registers; a masked step's (and a sample past B's) row is never read: zeros
-__device__ __forceinline__ void lstm_load_x(float4 (&xr)[kLstmXV], const float* __restrict__ x, const unsigned char* __restrict__ mask, long b0,
-                                            int B, int t, const LstmLayout& L) {
-  const int KQ = L.K / 4, n = L.NS * KQ;
-#pragma unroll
-  for (int i = 0; i < kLstmXV; ++i) {
-    const int idx = threadIdx.x + i * blockDim.x;
-    xr[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (idx < n) {
-      const int s = idx / KQ, kq = idx - s * KQ;
-      const long bb = b0 + s;
-      if (bb < B && (mask == nullptr || mask[bb * L.T + t] != 0))
-        xr[i] = *reinterpret_cast<const float4*>(x + (bb * L.T + t) * L.K + kq * 4);
-    }
-  }
-}
-
-// ... -> the transposed LDS image xT [K][NSP]
-__device__ __forceinline__ void lstm_store_x(const float4 (&xr)[kLstmXV], float* xT, const LstmLayout& L) {
-  const int KQ = L.K / 4, n = L.NS * KQ;
-#pragma unroll
-  for (int i = 0; i < kLstmXV; ++i) {
-    const int idx = threadIdx.x + i * blockDim.x;
-    if (idx < n) {
-      const int s = idx / KQ, kq = idx - s * KQ;
-      float* d = xT + (kq * 4) * L.NSP + s;
-      d[0] = xr[i].x; d[L.NSP] = xr[i].y; d[2 * L.NSP] = xr[i].z; d[3 * L.NSP] = xr[i].w;
-    }
-  }
-}
-
-// live flag (1 / 0) of sample b0 + threadIdx.x at time position t (threads below NS)
-__device__ __forceinline__ float lstm_load_live(const unsigned char* __restrict__ mask, long b0, int B, int t, const LstmLayout& L) {
-  if ((int)threadIdx.x < L.NS) {
-    const long bb = b0 + threadIdx.x;
-    if (bb < B && (mask == nullptr || mask[bb * L.T + t] != 0)) return 1.f;
-  }
-  return 0.f;
 }
 
 // blockIdx.y = the direction's index among those of the call (its weights, its columns of hs, its block of saved); dir0 = the first
 // one's direction (FIL_LSTM_FORWARD or FIL_LSTM_REVERSE), ndir = how many the call runs
-__global__ __launch_bounds__(kLstmThreads) void lstm_fwd_kernel(const float* __restrict__ x, const unsigned char* __restrict__ mask,
+__global__ __launch_bounds__(kRnnThreads) void lstm_fwd_kernel(const float* __restrict__ x, const unsigned char* __restrict__ mask,
                                                                const float* __restrict__ W, const float* __restrict__ U,
                                                                const float* __restrict__ bias, float* __restrict__ hs, float* __restrict__ saved,
-                                                               int B, int dir0, int ndir, LstmLayout L) {
+                                                               int B, int dir0, int ndir, RnnLayout L) {
   extern __shared__ __attribute__((aligned(16))) float lstm_smem[];
-  const int tid = threadIdx.x, nthr = blockDim.x;
-  const int T = L.T, K = L.K, H = L.H, H4 = L.H4, NS = L.NS, NSP = L.NSP;
+  const int tid = threadIdx.x;
+  const int T = L.T, K = L.K, H = L.H, H4 = L.HG, NS = L.NS, NSP = L.NSP;
   const int d = blockIdx.y, HO = ndir * H;
   const bool rev = dir0 + d == FIL_LSTM_REVERSE;
   W += (long)d * K * H4;
@@ -143,9 +57,9 @@ __global__ __launch_bounds__(kLstmThreads) void lstm_fwd_kernel(const float* __r
   bias += (long)d * H4;
   hs += d * H;
   if (saved != nullptr) saved += (long)d * B * T * kLstmSaved * H;
-  for (int i = tid; i < K * H4; i += nthr) lstm_smem[i] = W[i];
-  for (int i = tid; i < H * H4; i += nthr) lstm_smem[L.f_U + i] = U[i];
-  for (int i = tid; i < H4; i += nthr) lstm_smem[L.f_b + i] = bias[i];
+  rnn_stage(lstm_smem, W, K * H4);
+  rnn_stage(lstm_smem + L.f_U, U, H * H4);
+  rnn_stage(lstm_smem + L.f_b, bias, kLstmBiasRows * H4);
   const float* Ws = lstm_smem;
   const float* Us = lstm_smem + L.f_U;
   const float* bs = lstm_smem + L.f_b;
@@ -155,21 +69,20 @@ __global__ __launch_bounds__(kLstmThreads) void lstm_fwd_kernel(const float* __r
   for (long tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
     const long b0 = tile * NS;
     float h[4] = {0.f, 0.f, 0.f, 0.f}, c[4] = {0.f, 0.f, 0.f, 0.f};
-    float4 xr[kLstmXV];
+    float4 xr[kRnnXV];
     float lvn;
     __syncthreads();      // the weights are staged; the previous tile's images are free
-    lstm_load_x(xr, x, mask, b0, B, rev ? T - 1 : 0, L);
-    lvn = lstm_load_live(mask, b0, B, rev ? T - 1 : 0, L);
-    lstm_store_x(xr, lstm_smem + L.f_x, L);
+    rnn_load_x(xr, x, mask, b0, B, rev ? T - 1 : 0, L);
+    lvn = rnn_load_live(mask, b0, B, rev ? T - 1 : 0, L);
+    rnn_store_x(xr, lstm_smem + L.f_x, L);
     if (tid < NS) lstm_smem[L.f_live + tid] = lvn;
     if (active) *reinterpret_cast<float4*>(lstm_smem + L.f_h + j * NSP + 4 * g) = make_float4(0.f, 0.f, 0.f, 0.f);
     if (T > 1) {
-      lstm_load_x(xr, x, mask, b0, B, rev ? T - 2 : 1, L);
-      lvn = lstm_load_live(mask, b0, B, rev ? T - 2 : 1, L);
+      rnn_load_x(xr, x, mask, b0, B, rev ? T - 2 : 1, L);
+      lvn = rnn_load_live(mask, b0, B, rev ? T - 2 : 1, L);
     }
     __syncthreads();
-    // Order within a step as in gru_fwd_kernel: the arithmetic; the registers loaded a step ago -> LDS; this step's stores; the
-    // loads of the step after next.
+    // the order within a step: rnn_tile.h, Schedule
     for (int s = 0; s < T; ++s) {
       const int t = rev ? T - 1 - s : s;
       const int cur = s & 1, nxt = cur ^ 1;
@@ -185,6 +98,8 @@ __global__ __launch_bounds__(kLstmThreads) void lstm_fwd_kernel(const float* __r
         }
         const float* xc = lstm_smem + L.f_x + cur * K * NSP + 4 * g;
         const float* hc = lstm_smem + L.f_h + cur * H * NSP + 4 * g;
+        // (written out, not rnn_fwd_products: from the helper the compiler orders these two blocks' instructions differently, and the
+        // bare forward measured 0.3 to 0.8 % slower)
 #pragma unroll 4
         for (int k = 0; k < K; ++k) {
           const float4 v = *reinterpret_cast<const float4*>(xc + k * NSP);
@@ -210,10 +125,10 @@ __global__ __launch_bounds__(kLstmThreads) void lstm_fwd_kernel(const float* __r
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
           lv[e] = lstm_smem[L.f_live + cur * NS + 4 * g + e] != 0.f;
-          const float iv = lstm_sigmoid(az[0][e]);
-          const float fv = lstm_sigmoid(az[1][e]);
+          const float iv = rnn_sigmoid(az[0][e]);
+          const float fv = rnn_sigmoid(az[1][e]);
           const float gg = tanhf(az[2][e]);
-          const float ov = lstm_sigmoid(az[3][e]);
+          const float ov = rnn_sigmoid(az[3][e]);
           const float cn = fmaf(fv, c[e], iv * gg);
           const float hn = ov * tanhf(cn);
           if (lv[e]) { c[e] = cn; h[e] = hn; }
@@ -222,7 +137,7 @@ __global__ __launch_bounds__(kLstmThreads) void lstm_fwd_kernel(const float* __r
         *reinterpret_cast<float4*>(lstm_smem + L.f_h + nxt * H * NSP + j * NSP + 4 * g) = make_float4(h[0], h[1], h[2], h[3]);
       }
       if (s + 1 < T) {
-        lstm_store_x(xr, lstm_smem + L.f_x + nxt * K * NSP, L);
+        rnn_store_x(xr, lstm_smem + L.f_x + nxt * K * NSP, L);
         if (tid < NS) lstm_smem[L.f_live + nxt * NS + tid] = lvn;
       }
       if (active) {
@@ -240,8 +155,8 @@ __global__ __launch_bounds__(kLstmThreads) void lstm_fwd_kernel(const float* __r
         }
       }
       if (s + 2 < T) {
-        lstm_load_x(xr, x, mask, b0, B, rev ? T - 3 - s : s + 2, L);
-        lvn = lstm_load_live(mask, b0, B, rev ? T - 3 - s : s + 2, L);
+        rnn_load_x(xr, x, mask, b0, B, rev ? T - 3 - s : s + 2, L);
+        lvn = rnn_load_live(mask, b0, B, rev ? T - 3 - s : s + 2, L);
       }
       __syncthreads();
     }
@@ -249,15 +164,15 @@ __global__ __launch_bounds__(kLstmThreads) void lstm_fwd_kernel(const float* __r
 }
 
 template <int NR>
-__global__ __launch_bounds__(kLstmThreads) void lstm_bwd_kernel(const float* __restrict__ x, const unsigned char* __restrict__ mask,
+__global__ __launch_bounds__(kRnnThreads) void lstm_bwd_kernel(const float* __restrict__ x, const unsigned char* __restrict__ mask,
                                                                const float* __restrict__ W, const float* __restrict__ U,
                                                                const float* __restrict__ hs, const float* __restrict__ saved,
                                                                const float* __restrict__ g_hs, const float* __restrict__ g_last,
                                                                float* __restrict__ dx, float* __restrict__ dx_second,
-                                                               float* __restrict__ partials, int B, int dir0, int ndir, LstmLayout L) {
+                                                               float* __restrict__ partials, int B, int dir0, int ndir, RnnLayout L) {
   extern __shared__ __attribute__((aligned(16))) float lstm_smem[];
   const int tid = threadIdx.x, nthr = blockDim.x;
-  const int T = L.T, K = L.K, H = L.H, H4 = L.H4, NS = L.NS, NSP = L.NSP, G = L.G, KH = L.K + L.H;
+  const int T = L.T, K = L.K, H = L.H, H4 = L.HG, NS = L.NS, NSP = L.NSP, G = L.G, KH = L.K + L.H;
   const int d = blockIdx.y, HO = ndir * H;
   const bool rev = dir0 + d == FIL_LSTM_REVERSE;
   W += (long)d * K * H4;
@@ -267,14 +182,8 @@ __global__ __launch_bounds__(kLstmThreads) void lstm_bwd_kernel(const float* __r
   if (g_hs != nullptr) g_hs += d * H;
   if (g_last != nullptr) g_last += d * H;
   if (d == 1) dx = dx_second;            // (both null when dx is not wanted)
-  for (int i = tid; i < K * H4; i += nthr) {       // WT [m][k] = W [k][m]
-    const int k = i / H4, m = i - k * H4;
-    lstm_smem[m * K + k] = W[i];
-  }
-  for (int i = tid; i < H * H4; i += nthr) {
-    const int k = i / H4, m = i - k * H4;
-    lstm_smem[L.b_UT + m * H + k] = U[i];
-  }
+  rnn_stage_transposed(lstm_smem, W, K, L);
+  rnn_stage_transposed(lstm_smem + L.b_UT, U, H, L);
   const float* WT = lstm_smem;
   const float* UT = lstm_smem + L.b_UT;
   float* dT = lstm_smem + L.b_dT;
@@ -282,7 +191,7 @@ __global__ __launch_bounds__(kLstmThreads) void lstm_bwd_kernel(const float* __r
   const bool active = tid < G * H;
   const int g = tid / H, j = tid - g * H;
   const bool want_params = partials != nullptr;
-  float acc[NR][4];
+  float acc[NR][kLstmGates];
 #pragma unroll
   for (int r = 0; r < NR; ++r) acc[r][0] = acc[r][1] = acc[r][2] = acc[r][3] = 0.f;
   float dbs[4] = {0.f, 0.f, 0.f, 0.f};      // the thread's samples' dz_i, dz_f, dz_c, dz_o
@@ -291,13 +200,13 @@ __global__ __launch_bounds__(kLstmThreads) void lstm_bwd_kernel(const float* __r
     const long b0 = tile * NS;
     float dh[4] = {0.f, 0.f, 0.f, 0.f}, dc[4] = {0.f, 0.f, 0.f, 0.f};
     float svn[4][4], cnn[4], cpn[4], hpn[4], ghn[4], lvn;
-    float4 xr[kLstmXV];
+    float4 xr[kRnnXV];
     // what step ss needs, of the thread's unit and samples -> registers
     auto prefetch = [&](int ss) {
       const int tt = rev ? T - 1 - ss : ss;           // the step's time position, and the one of the step before it
       const int tp = rev ? tt + 1 : tt - 1;
-      if (want_params) lstm_load_x(xr, x, mask, b0, B, tt, L);
-      lvn = lstm_load_live(mask, b0, B, tt, L);
+      if (want_params) rnn_load_x(xr, x, mask, b0, B, tt, L);
+      lvn = rnn_load_live(mask, b0, B, tt, L);
       if (active) {
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
@@ -319,7 +228,7 @@ __global__ __launch_bounds__(kLstmThreads) void lstm_bwd_kernel(const float* __r
     auto commit = [&](int buf) {
       float* inT = lstm_smem + L.b_in + buf * KH * NSP;
       if (want_params) {
-        lstm_store_x(xr, inT, L);
+        rnn_store_x(xr, inT, L);
         if (active) *reinterpret_cast<float4*>(inT + (K + j) * NSP + 4 * g) = make_float4(hpn[0], hpn[1], hpn[2], hpn[3]);
       }
       if (tid < NS) lstm_smem[L.b_live + buf * NS + tid] = lvn;
@@ -380,86 +289,22 @@ __global__ __launch_bounds__(kLstmThreads) void lstm_bwd_kernel(const float* __r
       if (active) {
         // dh_prev = dz U^T (a masked step: dz = 0, the gradient passes through)
         float nh[4] = {0.f, 0.f, 0.f, 0.f};
-        if (s > 0) {
-#pragma unroll 4
-          for (int m = 0; m < H4; ++m) {
-            const float4 dd = *reinterpret_cast<const float4*>(dT + m * NSP + 4 * g);
-            const float w = UT[m * H + j];
-            nh[0] = fmaf(dd.x, w, nh[0]); nh[1] = fmaf(dd.y, w, nh[1]); nh[2] = fmaf(dd.z, w, nh[2]); nh[3] = fmaf(dd.w, w, nh[3]);
-          }
-        }
+        if (s > 0) rnn_bwd_matvec<false>(nh, dT + 4 * g, UT, H, j, L);
 #pragma unroll
         for (int e = 0; e < 4; ++e) dh[e] = keep[e] + nh[e];
-        if (want_params) {
-          const float* inT = lstm_smem + L.b_in + cur * KH * NSP;
-          for (int s4 = 0; s4 < NS; s4 += 4) {
-            float ez[4][4];
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-              const float* dd = dS + (s4 + e) * H4 + j;
-              ez[0][e] = dd[0]; ez[1][e] = dd[H]; ez[2][e] = dd[2 * H]; ez[3][e] = dd[3 * H];
-            }
-#pragma unroll
-            for (int r = 0; r < NR; ++r) {
-              const int i = g + r * G;
-              if (i < KH) {
-                const float4 v = *reinterpret_cast<const float4*>(inT + i * NSP + s4);
-                const float ve[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-#pragma unroll
-                  for (int q = 0; q < 4; ++q) acc[r][q] = fmaf(ve[e], ez[q][e], acc[r][q]);
-                }
-              }
-            }
-          }
-        }
+        if (want_params) rnn_bwd_accumulate(acc, lstm_smem + L.b_in + cur * KH * NSP, dS, g, j, L);
       }
-      // the registers loaded at the top of the step -> LDS BEFORE this step's stores are issued (as in gru_bwd_kernel)
+      // the registers loaded at the top of the step -> LDS BEFORE this step's stores are issued (rnn_tile.h, Schedule)
       if (s > 0) commit((s - 1) & 1);
-      if (active && dx != nullptr) {
-        for (int k = j; k < K; k += H) {
-          float v[4] = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll 4
-          for (int m = 0; m < H4; ++m) {
-            const float4 dd = *reinterpret_cast<const float4*>(dT + m * NSP + 4 * g);
-            const float w = WT[m * K + k];
-            v[0] = fmaf(dd.x, w, v[0]); v[1] = fmaf(dd.y, w, v[1]); v[2] = fmaf(dd.z, w, v[2]); v[3] = fmaf(dd.w, w, v[3]);
-          }
-#pragma unroll
-          for (int e = 0; e < 4; ++e) {
-            const long bb = b0 + 4 * g + e;
-            const bool live = lstm_smem[L.b_live + cur * NS + 4 * g + e] != 0.f;
-            if (bb < B) dx[(bb * T + t) * K + k] = live ? v[e] : 0.f;
-          }
-        }
-      }
+      if (active && dx != nullptr) rnn_bwd_dx(dx, dT + 4 * g, WT, lstm_smem + L.b_live + cur * NS + 4 * g, b0 + 4 * g, B, t, j, L);
       __syncthreads();
     }
   }
   if (!want_params) return;
-  // the workgroup's partial: the accumulators as they stand; db = the quads' sums in quad order
+  // the workgroup's partial; db = the quads' sums in quad order
   float* part = partials + ((long)d * gridDim.x + blockIdx.x) * L.n_out;
-  if (active) {
-#pragma unroll
-    for (int r = 0; r < NR; ++r) {
-      const int i = g + r * G;
-      if (i < KH) {
-#pragma unroll
-        for (int q = 0; q < 4; ++q) part[i * H4 + q * H + j] = acc[r][q];
-      }
-    }
-    // (the last barrier of the step loop has passed: dS is free)
-#pragma unroll
-    for (int q = 0; q < 4; ++q) dS[(g * 4 + q) * H + j] = dbs[q];
-  }
-  __syncthreads();
-  for (int o = tid; o < H4; o += nthr) {
-    const int q = o / H, jj = o - q * H;
-    float sum = 0.f;
-    for (int gq = 0; gq < G; ++gq) sum += dS[(gq * 4 + q) * H + jj];
-    part[KH * H4 + o] = sum;
-  }
+  rnn_bwd_write_partial(part, acc, dbs, dS, active, g, j, L);
+  for (int o = tid; o < H4; o += nthr) part[KH * H4 + o] = rnn_bwd_quad_sum(dS, o, L);
 }
 
 // dx += the reverse direction's dx (both directions in one launch)
@@ -473,30 +318,10 @@ __global__ __launch_bounds__(256) void lstm_dx_sum_kernel(float* __restrict__ dx
 }
 
 // argument and menu checks shared by the entry points
-static int lstm_dims(const char* who, int B, int T, int K, int H, int dirs, LstmLayout* L) {
+static int lstm_dims(const char* who, int B, int T, int K, int H, int dirs, RnnLayout* L) {
   FIL_CHECK_ARG_W(who, B >= 0 && T >= 1 && K >= 1 && H >= 1);
   FIL_CHECK_ARG_W(who, dirs == FIL_LSTM_FORWARD || dirs == FIL_LSTM_REVERSE || dirs == FIL_LSTM_BIDIR);
-  if (K % 4 != 0 || K > kLstmMaxK) return fail(FIL_ERR_UNSUPPORTED, "%s: K=%d needs K %% 4 == 0 and K <= %d", who, K, kLstmMaxK);
-  if (H % 4 != 0 || H > kLstmMaxH) return fail(FIL_ERR_UNSUPPORTED, "%s: H=%d needs H %% 4 == 0 and H <= %d", who, H, kLstmMaxH);
-  *L = lstm_layout(B, T, K, H);
-  if (L->lds_fwd > kTiledLdsLimit || L->lds_bwd > kTiledLdsLimit)
-    return fail(FIL_ERR_UNSUPPORTED, "%s: K=%d H=%d needs %d bytes of LDS (limit %d)", who, K, H, std::max(L->lds_fwd, L->lds_bwd), kTiledLdsLimit);
-  return FIL_OK;
-}
-
-struct LstmBwdArgs {
-  const float* x;
-  const unsigned char* mask;
-  const float *W, *U, *hs, *saved, *g_hs, *g_last;
-  float *dx, *dx_second, *partials;
-};
-
-template <int NR>
-static int lstm_launch_bwd(const char* who, const LstmBwdArgs& p, int B, int dirs, const LstmLayout& L, hipStream_t st) {
-  if (int rc = tiled_allow_lds(who, lstm_bwd_kernel<NR>, L.lds_bwd)) return rc;
-  hipLaunchKernelGGL((lstm_bwd_kernel<NR>), dim3(lstm_grid(B, L.NS), lstm_ndir(dirs)), dim3(L.threads), L.lds_bwd, st, p.x, p.mask, p.W, p.U, p.hs,
-                     p.saved, p.g_hs, p.g_last, p.dx, p.dx_second, p.partials, B, dirs == FIL_LSTM_REVERSE ? 1 : 0, lstm_ndir(dirs), L);
-  return FIL_OK;
+  return rnn_dims(who, B, T, K, H, kLstmGates, kLstmBiasRows, false, L);
 }
 
 }  // namespace fil
@@ -504,23 +329,23 @@ static int lstm_launch_bwd(const char* who, const LstmBwdArgs& p, int B, int dir
 using namespace fil;
 
 extern "C" int fil_lstm_plan(int B, int T, int K, int H, int dirs, int* plan) {
-  LstmLayout L;
+  RnnLayout L;
   if (int rc = lstm_dims(__func__, B, T, K, H, dirs, &L)) return rc;
   FIL_CHECK_ARG(plan != nullptr);
-  tiled_plan(plan, L.NS, lstm_grid(B, L.NS), kLstmGridCap, L.lds_fwd, L.lds_bwd);
+  tiled_plan(plan, L.NS, rnn_grid(B, L.NS), kRnnGridCap, L.lds_fwd, L.lds_bwd);
   plan[5] *= lstm_ndir(dirs);      // grid and cap count the workgroups of ONE direction; every workgroup leaves a partial
   return FIL_OK;
 }
 
 extern "C" size_t fil_lstm_saved_bytes(int B, int T, int K, int H, int dirs) {
-  LstmLayout L;
+  RnnLayout L;
   if (lstm_dims(__func__, B, T, K, H, dirs, &L) != FIL_OK) return 0;
   return align_up((size_t)lstm_ndir(dirs) * (size_t)B * (size_t)T * kLstmSaved * (size_t)H * sizeof(float), 256);
 }
 
 extern "C" int fil_lstm_fwd(const float* x, const unsigned char* mask, const float* W, const float* U, const float* b, float* hs, float* saved,
                             int B, int T, int K, int H, int dirs, void* stream) {
-  LstmLayout L;
+  RnnLayout L;
   if (int rc = lstm_dims(__func__, B, T, K, H, dirs, &L)) return rc;
   if (B == 0) return FIL_OK;
   FIL_CHECK_ARG(x != nullptr && W != nullptr && U != nullptr && b != nullptr && hs != nullptr);
@@ -528,14 +353,14 @@ extern "C" int fil_lstm_fwd(const float* x, const unsigned char* mask, const flo
   const int ndir = lstm_ndir(dirs);
   ProfScope ps("lstm_fwd", st, 4.0 * (double)B * T * (K + ndir * (H + (saved != nullptr ? (double)kLstmSaved * H : 0.0))));
   if (int rc = tiled_allow_lds(__func__, lstm_fwd_kernel, L.lds_fwd)) return rc;
-  hipLaunchKernelGGL(lstm_fwd_kernel, dim3(lstm_grid(B, L.NS), ndir), dim3(L.threads), L.lds_fwd, st, x, mask, W, U, b, hs, saved, B,
+  hipLaunchKernelGGL(lstm_fwd_kernel, dim3(rnn_grid(B, L.NS), ndir), dim3(L.threads), L.lds_fwd, st, x, mask, W, U, b, hs, saved, B,
                      dirs == FIL_LSTM_REVERSE ? 1 : 0, ndir, L);
   FIL_CHECK_LAUNCH();
   return FIL_OK;
 }
 
 extern "C" size_t fil_lstm_bwd_workspace_bytes(int B, int T, int K, int H, int dirs) {
-  LstmLayout L;
+  RnnLayout L;
   if (lstm_dims(__func__, B, T, K, H, dirs, &L) != FIL_OK) return 0;
   return tiled_partial_bytes(1, lstm_workspace_floats(B, dirs, L));
 }
@@ -543,14 +368,14 @@ extern "C" size_t fil_lstm_bwd_workspace_bytes(int B, int T, int K, int H, int d
 extern "C" int fil_lstm_bwd(const float* x, const unsigned char* mask, const float* W, const float* U, const float* hs, const float* saved,
                             const float* g_hs, const float* g_last, float* dx, float* dW, float* dU, float* db, void* workspace,
                             size_t workspace_bytes, int B, int T, int K, int H, int dirs, void* stream) {
-  LstmLayout L;
+  RnnLayout L;
   if (int rc = lstm_dims(__func__, B, T, K, H, dirs, &L)) return rc;
   if (B == 0) return FIL_OK;
   FIL_CHECK_ARG(x != nullptr && W != nullptr && U != nullptr && hs != nullptr && saved != nullptr);
   FIL_CHECK_ARG(g_hs != nullptr || g_last != nullptr);
   const bool want_params = dW != nullptr || dU != nullptr || db != nullptr;
   FIL_CHECK_ARG(dx != nullptr || want_params);
-  const int ndir = lstm_ndir(dirs), grid = lstm_grid(B, L.NS);
+  const int ndir = lstm_ndir(dirs), grid = rnn_grid(B, L.NS);
   const bool second_dx = ndir == 2 && dx != nullptr;
   if (want_params || second_dx)
     if (int rc = tiled_check_workspace(__func__, workspace, workspace_bytes, 1, lstm_workspace_floats(B, dirs, L))) return rc;
@@ -558,9 +383,8 @@ extern "C" int fil_lstm_bwd(const float* x, const unsigned char* mask, const flo
   ProfScope ps("lstm_bwd", st, 4.0 * (double)B * T * (2.0 * K + ndir * 8.0 * H));
   float* const parts = static_cast<float*>(workspace);
   float* const dx_second = second_dx ? parts + tiled_partial_bytes(ndir * grid, L.n_out) / sizeof(float) : nullptr;
-  const LstmBwdArgs p = {x, mask, W, U, hs, saved, g_hs, g_last, dx, dx_second, want_params ? parts : nullptr};
-  if (int rc = L.NR == 8 ? lstm_launch_bwd<8>(__func__, p, B, dirs, L, st)
-                         : (L.NR == 16 ? lstm_launch_bwd<16>(__func__, p, B, dirs, L, st) : lstm_launch_bwd<32>(__func__, p, B, dirs, L, st)))
+  if (int rc = rnn_launch_bwd(__func__, [](auto nr) { return lstm_bwd_kernel<decltype(nr)::value>; }, L, dim3(grid, ndir), st, x, mask, W, U, hs,
+                              saved, g_hs, g_last, dx, dx_second, want_params ? parts : nullptr, B, dirs == FIL_LSTM_REVERSE ? 1 : 0, ndir))
     return rc;
   FIL_CHECK_LAUNCH();
   if (second_dx) {
@@ -569,10 +393,10 @@ extern "C" int fil_lstm_bwd(const float* x, const unsigned char* mask, const flo
     FIL_CHECK_LAUNCH();
   }
   if (want_params) {
-    const int off[4] = {0, K * L.H4, (K + H) * L.H4, L.n_out};
+    const int off[4] = {0, K * L.HG, (K + H) * L.HG, L.n_out};
     for (int d = 0; d < ndir; ++d) {
-      float* const outs[3] = {dW != nullptr ? dW + (long)d * K * L.H4 : nullptr, dU != nullptr ? dU + (long)d * H * L.H4 : nullptr,
-                              db != nullptr ? db + (long)d * L.H4 : nullptr};
+      float* const outs[3] = {dW != nullptr ? dW + (long)d * K * L.HG : nullptr, dU != nullptr ? dU + (long)d * H * L.HG : nullptr,
+                              db != nullptr ? db + (long)d * L.HG : nullptr};
       param_reduce_launch(parts + (long)d * grid * L.n_out, grid, outs, off, 3, st);
       FIL_CHECK_LAUNCH();
     }

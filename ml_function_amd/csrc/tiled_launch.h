@@ -1,5 +1,5 @@
 // The launch kit of the ops that give every workgroup tiles of samples and leave ONE parameter-gradient partial per workgroup
-// (afm.hip, din.hip, gru.hip, seq_attn.hip; param_reduce.h then adds the partials): the LDS limit and opt-in, the grid, the plan
+// (afm.hip, din.hip, gru.hip, lstm.hip, seq_attn.hip; param_reduce.h then adds the partials): the LDS limit and opt-in, the grid, the plan
 // and the partial workspace, each defined once.  Host code only.
 #pragma once
 #include "common.h"

@@ -77,6 +77,7 @@ def check_parity(got, case, keys=None, label=""):
 PARITY_SHAPES = [(1, 1, 4, 4),           # the minimum
                  (3, 2, 4, 8),           # two steps
                  (5, 50, 16, 16),        # the benchmark's
+                 (3, 5, 24, 24),         # NR = 16
                  (3, 7, 12, 20),         # K / 4 and H / 4 odd, K != H
                  (2, 300, 8, 4)]         # many steps, narrow state
 CORNERS = [(3, 64, 64, 56), (2, 5, 40, 64), (2, 5, 64, 4), (2, 5, 4, 64)]      # the menu's edge towards the LDS limit, and the narrow sides
