@@ -633,6 +633,53 @@ int fil_seq_search(const int64_t* hist_idx, int64_t hist_stride, int64_t offset,
                    int* oob_count, int B, int T, int K, int k, int flags, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * N4  Neural Turing Machine memory read / write over a sequence (extension: the memory of the Multi-channel user Interest Memory
+ *     Network, "Practice on Long Sequential User Behavior Modeling for CTR Prediction", section 4.1 -- content addressing by cosine
+ *     similarity, one read head, one erase / add write head; the reference's ReadLayer / WriteLayer / AddressCalLayer /
+ *     ControlWrapLayer are not restated, their source was not available).  All tensors fp32 except mask.  Entry points added only:
+ *     the ABI version stays.
+ *   h [B,T,H] the controller's states; mask [B,T] uint8, non-zero = live, NULL = all live (live slots may sit anywhere); Wp [H,4D+2]
+ *   and bp [4D+2] in the column order kr (D) | kw (D) | e (D) | a (D) | beta_r | beta_w; M0 [m,D] the initial memory, shared by all
+ *   samples.  The state is M [m,D] (M0 before the first live step) and r [D] (zeros).  One live step, M = the previous memory:
+ *     p = h_t Wp + bp;  kr = tanh(p_kr);  kw = tanh(p_kw);  e = sigmoid(p_e);  a = tanh(p_a);
+ *     beta = softplus(p_beta) + 1 for both heads, softplus(v) = max(v, 0) + log1p(exp(-|v|));
+ *     c_i(k) = (M_i . k) / sqrt((|M_i|^2 + eps) (|k|^2 + eps)), eps = 1e-6: one square root of the product, smooth at M_i = 0 and k = 0;
+ *     wr = softmax_i(beta_r c_i(kr));  ww = softmax_i(beta_w c_i(kw)): both on the PREVIOUS M, the row maximum subtracted;
+ *     r_t = sum_i wr_i M_i (the read comes before the write);  M_t[i] = M_i (1 - ww_i e) + ww_i a (erase, then add).
+ *   A masked step carries M and r bit for bit (rs[b,t] = zeros before the first live step); its h_t is never read.
+ *   fil_ntm_fwd: rs [B,T,D] the reads, r_last [B,D] = rs[:,T-1], MT [B,m,D] the final memory (each may be NULL and is then not
+ *     written; all three NULL: FIL_ERR_ARG), and `saved` for the backward (fil_ntm_saved_bytes; opaque to the caller; per live step
+ *     the memory BEFORE the step [m,D], the activations [4D] and 6 + 5m scalars: the betas and their sigmoids, the key norms, and per
+ *     slot both weights, both cosines and the row norm; masked steps are left unwritten; NULL: nothing is saved, for inference).
+ *     h_t Wp is fused into the step: besides h, rs and saved nothing of size B T n touches global memory.
+ *   fil_ntm_bwd: g_rs [B,T,D] or g_last [B,D] (the gradient of rs[:,T-1]) and / or g_M [B,m,D] (any may be NULL, not all) ->
+ *     dh [B,T,H], dWp, dbp, dM0.  No product and no exponential is taken again: everything comes from `saved`.  A masked step passes
+ *     the gradients of M and r through unchanged; dh is exactly 0 there.  A sample without a live step sends g_M[b] to dM0.  Each
+ *     output may be NULL and is then not computed, the others keep the bits of the full call (dWp, dbp, dM0 all NULL: no parameter
+ *     pass, no workspace; all four NULL: FIL_ERR_ARG).  The parameter gradients leave the main launch as one partial per workgroup in
+ *     `workspace` (fil_ntm_bwd_workspace_bytes; every byte that is read was written by that launch) and a second small launch adds
+ *     the partials in a fixed order.
+ *   One launch per direction (plus the partial sum).  No atomics; every sum has a fixed order for a given shape: the same inputs give
+ *   the same bits on every call, a sample's bits depend neither on its place in the batch nor on B, and the sums over d behind
+ *   M_i . k, |M_i|^2 and |k|^2 run in one order for every slot: slots with identical rows get identical bits.
+ *   Menu: any T >= 1; H % 4 == 0, H <= 64; D % 4 == 0, D <= 64; 1 <= m <= 16; both passes within 163,328 bytes of dynamic LDS, which
+ *   every such shape is (129,168 in the forward and 128,384 in the backward at H = 64, m = 16, D = 64 with tiles of 16 samples).  FIL_ERR_UNSUPPORTED
+ *   otherwise, the limit in the message.
+ *   B == 0 returns FIL_OK before any pointer is looked at.  A workspace smaller than needed: FIL_ERR_ARG, the needed size in the message.
+ *   fil_ntm_plan: the launchers' own arithmetic (no GPU call): plan[8] = {fwd_ok, bwd_ok, samples per workgroup tile, grid, grid cap,
+ *     parameter-gradient partials (= grid), forward LDS bytes, backward LDS bytes}.  The tile grows with B (small batches take small
+ *     tiles and more workgroups).  Returns FIL_OK, or the argument / menu error the launch would give.
+ */
+int fil_ntm_plan(int B, int T, int H, int m, int D, int* plan /* [8] */);
+size_t fil_ntm_saved_bytes(int B, int T, int H, int m, int D);
+int fil_ntm_fwd(const float* h, const unsigned char* mask, const float* Wp, const float* bp, const float* M0, float* rs, float* r_last,
+                float* MT, float* saved, int B, int T, int H, int m, int D, void* stream);
+size_t fil_ntm_bwd_workspace_bytes(int B, int T, int H, int m, int D);
+int fil_ntm_bwd(const float* h, const unsigned char* mask, const float* Wp, const float* saved, const float* g_rs, const float* g_last,
+                const float* g_M, float* dh, float* dWp, float* dbp, float* dM0, void* workspace, size_t workspace_bytes, int B, int T,
+                int H, int m, int D, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * N2  The score head and the loss behind the interaction layers (all tensors fp32, n = batch rows).
  *   ScoreLayer(use_add=True).call (kon/model/ctr_model/layer/core_layer/core_layer.py:58-84): keras Add over the [B,1] parts,
  *   then sigmoid.  fil_score_add_sigmoid_fwd: out[i] = sigmoid(((a[i] + b[i]) + c[i]) + d[i]) -- left to right like the

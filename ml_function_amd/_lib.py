@@ -130,6 +130,12 @@ SIGNATURES = {
     # N3: top-k retrieval over a long behaviour history (forward only)
     "fil_seq_search_plan": (_I, [_I, _I, _I, _I, _P]),
     "fil_seq_search": (_I, [_P, _L, _L, _L, _L, _P, _P, _P, _L, _P, _L, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
+    # N4: Neural Turing Machine memory read / write over a sequence
+    "fil_ntm_plan": (_I, [_I, _I, _I, _I, _I, _P]),
+    "fil_ntm_saved_bytes": (_Z, [_I, _I, _I, _I, _I]),
+    "fil_ntm_fwd": (_I, [_P] * 9 + [_I] * 5 + [_P]),
+    "fil_ntm_bwd_workspace_bytes": (_Z, [_I, _I, _I, _I, _I]),
+    "fil_ntm_bwd": (_I, [_P] * 12 + [_Z] + [_I] * 5 + [_P]),
     "fil_score_add_sigmoid_fwd": (_I, [_P, _P, _P, _P, _P, _I, _P]),
     "fil_score_add_sigmoid_bwd": (_I, [_P, _P, _P, _I, _P]),
     "fil_bce_mean_fwd": (_I, [_P, _P, _F, _P, _P, _I, _P]),

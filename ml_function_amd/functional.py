@@ -526,6 +526,77 @@ def lstm_plan(B, T, K, H, direction="forward"):
     return _tiled_plan("fil_lstm_plan", int(B), int(T), int(K), int(H), LSTM_DIRECTIONS[direction])
 
 
+class _NtmFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, h, mask, wp, bp, m0, return_sequences):
+        _require_cuda(h, mask, wp, bp, m0)
+        h, wp, bp, m0 = (_f32c(t) for t in (h, wp, bp, m0))
+        if h.dim() != 3 or m0.dim() != 2:
+            raise FilError("ntm_memory: h must be [B,T,H] and M0 [m,D], got %s and %s" % (tuple(h.shape), tuple(m0.shape)))
+        B, T, H = h.shape
+        m, D = m0.shape
+        if tuple(wp.shape) != (H, 4 * D + 2) or tuple(bp.shape) != (4 * D + 2,):
+            raise FilError("ntm_memory: Wp and bp must be [H,4D+2] and [4D+2] with H = %d and D = %d, got %s and %s"
+                           % (H, D, tuple(wp.shape), tuple(bp.shape)))
+        mask = _seq_mask("ntm_memory", mask, B, T)
+        lib = _lib.load()
+        dev = h.device
+        rs = torch.empty((B, T, D), dtype=torch.float32, device=dev) if return_sequences else None
+        r_last = None if return_sequences else torch.empty((B, D), dtype=torch.float32, device=dev)
+        mt = torch.empty((B, m, D), dtype=torch.float32, device=dev)
+        need = ctx.needs_input_grad
+        saved = None
+        if any(need[i] for i in (0, 2, 3, 4)):
+            saved = _saved_floats(lib.fil_ntm_saved_bytes(B, T, H, m, D), dev)
+        check(lib.fil_ntm_fwd(ptr(h), ptr(mask), ptr(wp), ptr(bp), ptr(m0), ptr(rs), ptr(r_last), ptr(mt), ptr(saved), B, T, H, m, D,
+                              stream_ptr()), "fil_ntm_fwd")
+        _save(ctx, h, mask, wp, saved)
+        ctx.return_sequences, ctx.dims = return_sequences, (B, T, H, m, D)
+        ctx.set_materialize_grads(False)
+        return (rs if return_sequences else r_last), mt
+
+    @staticmethod
+    def backward(ctx, g, g_m):
+        need = ctx.needs_input_grad
+        none = (None,) * 6
+        if not (need[0] or need[2] or need[3] or need[4]) or (g is None and g_m is None):
+            return none
+        h, mask, wp, saved = _saved(ctx)
+        B, T, H, m, D = ctx.dims
+        dev = h.device
+        dh = _grad(need[0], h.shape, dev)
+        dwp = _grad(need[2], wp.shape, dev)
+        dbp = _grad(need[3], (4 * D + 2,), dev)
+        dm0 = _grad(need[4], (m, D), dev)
+        if _no_samples(B, dwp, dbp, dm0):
+            return dh, None, dwp, dbp, dm0, None
+        g, g_m = _f32c(g), _f32c(g_m)
+        g_rs, g_last = (g, None) if ctx.return_sequences else (None, g)
+        ws, nws = _partials_scratch("fil_ntm_bwd_workspace_bytes", "ntm_bwd", need[2] or need[3] or need[4], dev, B, T, H, m, D)
+        check(_lib.load().fil_ntm_bwd(ptr(h), ptr(mask), ptr(wp), ptr(saved), ptr(g_rs), ptr(g_last), ptr(g_m), ptr(dh), ptr(dwp), ptr(dbp),
+                                      ptr(dm0), ptr(ws), nws, B, T, H, m, D, stream_ptr()), "fil_ntm_bwd")
+        return dh, None, dwp, dbp, dm0, None
+
+
+def ntm_memory(h, mask, Wp, bp, M0, return_sequences=True):
+    """A Neural Turing Machine memory read and written over a sequence (extension: the memory of the Multi-channel user Interest
+    Memory Network; include/fil.h fil_ntm_*): h [B,T,H] the controller's states, mask [B,T] bool / uint8 (non-zero = live; None = all
+    live), Wp [H,4D+2] and bp [4D+2] (columns kr | kw | e | a | beta_r | beta_w), M0 [m,D] the initial memory shared by all samples ->
+    (rs [B,T,D], M_T [B,m,D]), or (rs[:, -1] [B,D], M_T) with return_sequences=False (its gradient then enters the backward as [B,D]:
+    no zero [B,T,D] block is made).  Per live step the slots are addressed by cosine similarity (two softmaxes with learned
+    sharpness), read, then erased and added to; a masked step carries the memory and the read.  One launch per direction (plus the
+    small fixed-order sum of the parameter-gradient partials); an output that received no gradient enters the backward as NULL and
+    only the gradients that are asked for are computed.  GPU only; shapes outside the kernel menu raise FilError
+    (layers.NTMMemoryLayer takes its composed path there)."""
+    return _NtmFn.apply(h, mask, Wp, bp, M0, bool(return_sequences))
+
+
+def ntm_plan(B, T, H, m, D):
+    """fil_ntm_plan's answer as a dict (fits, tile, grid, cap, partials, lds_fwd, lds_bwd); fits=False (and nothing else) for a shape
+    outside the kernel menu."""
+    return _tiled_plan("fil_ntm_plan", int(B), int(T), int(H), int(m), int(D))
+
+
 SEQ_VIEWS = {"full": _lib.FIL_SEQ_VIEW_FULL, "causal": _lib.FIL_SEQ_VIEW_CAUSAL, "cross": _lib.FIL_SEQ_VIEW_CROSS}
 
 

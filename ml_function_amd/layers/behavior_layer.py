@@ -5,7 +5,8 @@ epsilon is Keras' default 1e-3, the output is head-major [H,B,F,A].
 Behaviour-sequence layers (extensions), each one fused kernel per direction with a composed torch path outside the kernel menu:
 DinAttentionLayer (the Deep Interest Network's attention pooling), GRULayer (a GRU and the Deep Interest Evolution Network's AUGRU /
 AGRU), LSTMLayer / BiLSTMLayer (Keras' LSTM and Bidirectional(LSTM), the Deep Session Interest Network's session interest
-interacting layer) and SeqSelfAttentionLayer (the Behaviour Sequence Transformer's masked self-attention)."""
+interacting layer), SeqSelfAttentionLayer (the Behaviour Sequence Transformer's masked self-attention) and NTMMemoryLayer (the
+Multi-channel user Interest Memory Network's Neural Turing Machine memory)."""
 import torch
 
 from .. import functional as Fn
@@ -486,6 +487,131 @@ class BiLSTMLayer(_LstmBase):
             return out
         fwd, bwd = out[..., :self.units], out[..., self.units:]
         return fwd + bwd if self.merge_mode == "sum" else (fwd + bwd) * 0.5
+
+
+NTM_EPS = 1e-6
+
+
+def ntm_cosine(M, k):
+    """The memory's content addressing: c_i = (M_i . k) / sqrt((|M_i|^2 + eps)(|k|^2 + eps)) for M [B,m,D] and k [B,D] -> [B,m]; one
+    square root of the product, smooth at M_i = 0 and at k = 0."""
+    dot = (M * k.unsqueeze(1)).sum(-1)
+    return dot / torch.sqrt(((M * M).sum(-1) + NTM_EPS) * ((k * k).sum(-1, keepdim=True) + NTM_EPS))
+
+
+def ntm_beta(p):
+    """The sharpness of an addressing softmax: softplus(p) + 1, softplus(v) = max(v, 0) + log1p(exp(-|v|))."""
+    return torch.clamp_min(p, 0) + torch.log1p(torch.exp(-torch.abs(p))) + 1
+
+
+def ntm_address(M, k, beta):
+    """softmax_i(beta c_i(k)) for M [B,m,D], k [B,D], beta [B,1] or a scalar -> [B,m], the row maximum subtracted."""
+    s = beta * ntm_cosine(M, k)
+    w = torch.exp(s - s.max(dim=1, keepdim=True).values)
+    return w / w.sum(dim=1, keepdim=True)
+
+
+def ntm_memory_graph(h, mask, wp, bp, m0, return_sequences=True):
+    """Fn.ntm_memory's math as torch ops on the tensors given (their dtype and device; autograd for the backward), one step at a time:
+    the composed path of NTMMemoryLayer and the comparator of its benchmark -- about thirty launches per step.  mask: [B,T] bool or
+    None.  h_t of a masked step is replaced by zero before anything reads it.  -> (rs [B,T,D] or the last read [B,D], M_T [B,m,D])."""
+    B, T, H = h.shape
+    m, D = m0.shape
+    live = None if mask is None else mask.to(torch.bool)
+    if live is not None:
+        h = torch.where(live.unsqueeze(-1), h, torch.zeros((), dtype=h.dtype, device=h.device))
+    M = m0.unsqueeze(0).expand(B, m, D)
+    r = torch.zeros((B, D), dtype=h.dtype, device=h.device)
+    out = []
+    for t in range(T):
+        p = torch.matmul(h[:, t], wp) + bp
+        kr, kw = torch.tanh(p[:, :D]), torch.tanh(p[:, D:2 * D])
+        e, a = torch.sigmoid(p[:, 2 * D:3 * D]), torch.tanh(p[:, 3 * D:4 * D])
+        wr = ntm_address(M, kr, ntm_beta(p[:, 4 * D:4 * D + 1]))
+        ww = ntm_address(M, kw, ntm_beta(p[:, 4 * D + 1:4 * D + 2])).unsqueeze(-1)
+        rn = (wr.unsqueeze(-1) * M).sum(1)
+        Mn = M * (1 - ww * e.unsqueeze(1)) + ww * a.unsqueeze(1)
+        if live is not None:
+            lt = live[:, t:t + 1]
+            rn, Mn = torch.where(lt, rn, r), torch.where(lt.unsqueeze(-1), Mn, M)
+        r, M = rn, Mn
+        if return_sequences:
+            out.append(r)
+    return (torch.stack(out, dim=1) if return_sequences else r), M.contiguous()
+
+
+def _ntm_initial_memory(seed):
+    """The initial memory's initialiser: normal with std 0.1 from the seed -- the rows must differ, or the slots never separate."""
+    def init(p):
+        gen = torch.Generator(device="cpu")
+        gen.manual_seed(int(seed))
+        with torch.no_grad():
+            p.copy_((torch.randn(tuple(p.shape), generator=gen, dtype=torch.float32) * 0.1).to(p.device))
+    return init
+
+
+class NTMMemoryLayer(Layer):
+    """A Neural Turing Machine memory over a sequence (extension: the memory of the Multi-channel user Interest Memory Network, the
+    paper's section 4.1; the reference's ReadLayer / WriteLayer / AddressCalLayer / ControlWrapLayer are not restated, their source
+    was not available).
+
+    call(h [B,T,H], mask=None) -> [last read [B,D], final memory [B,m,D]], the reads [B,T,D] first with return_sequences=True;
+    m = memory_slots, D = memory_dim (None: the input width H).  h are the controller's states (in models.MIMN a GRULayer's output):
+    the controller sees the history only, the read is not fed back.  Per live step one Dense(4D + 2) of h_t gives the read key, the
+    write key, the erase and add vectors and the two sharpnesses; both heads address the slots by cosine similarity on the previous
+    memory; the read comes before the erase-then-add write.  mask: a [B,T] bool or uint8 tensor, non-zero = live; a masked step
+    carries the memory and the read (zeros before the first live step).  Weights: read_write_kernel [H,4D+2] glorot_uniform(seed),
+    read_write_bias [4D+2] zeros, initial_memory [m,D] normal(std 0.1) from the seed, shared by all samples.  The whole recurrence
+    runs in ONE HIP kernel per direction (Fn.ntm_memory, include/fil.h fil_ntm_*).  Outside the kernel menu (fits_kernel_menu) or for
+    a non-fp32 input the layer takes the composed path -- ntm_memory_graph on the GPU, computed in fp32 -- instead of raising."""
+
+    def __init__(self, memory_slots=4, memory_dim=None, return_sequences=False, seed=2020):
+        super().__init__()
+        if int(memory_slots) < 1:
+            raise ValueError("NTMMemoryLayer: memory_slots must be positive, got %r" % (memory_slots,))
+        if memory_dim is not None and int(memory_dim) < 1:
+            raise ValueError("NTMMemoryLayer: memory_dim must be positive or None, got %r" % (memory_dim,))
+        self.memory_slots = int(memory_slots)
+        self.memory_dim = None if memory_dim is None else int(memory_dim)
+        self.return_sequences = bool(return_sequences)
+        self.seed = seed
+
+    def build(self, input_shape):
+        h = int(input_shape[-1])
+        d = self.memory_dim or h
+        self.read_write_kernel = self.add_weight("read_write_kernel", [h, 4 * d + 2], "glorot_uniform", seed=self.seed)
+        self.read_write_bias = self.add_weight("read_write_bias", [4 * d + 2], "zeros")
+        self.initial_memory = self.add_weight("initial_memory", [self.memory_slots, d], _ntm_initial_memory(self.seed))
+        super().build(input_shape)
+
+    def _weights(self):
+        return self.read_write_kernel, self.read_write_bias, self.initial_memory
+
+    def fits_kernel_menu(self, h):
+        """fil_ntm_*'s menu (include/fil.h): H % 4 == 0, D % 4 == 0, H <= 64, D <= 64, m <= 16 -- fil_ntm_plan answers from the
+        launchers' own arithmetic; the answer is cached per shape."""
+        if h.dim() != 3:
+            return False
+        return _menu_fits(Fn.ntm_plan, 1, 1, int(h.shape[2]), self.memory_slots, int(self.initial_memory.shape[1]))      # (the menu does not depend on T)
+
+    def _composed(self, h, mask):
+        """ntm_memory_graph on the GPU in fp32: about thirty launches per step where the fused kernel makes one per direction -- it
+        exists so that a shape outside the kernel menu never raises."""
+        Fn._require_cuda(h, mask)      # (torch ops would run on a CPU tensor: there is no CPU path in this package)
+        return ntm_memory_graph(h.to(torch.float32), mask, *self._weights(), return_sequences=self.return_sequences)
+
+    def call(self, inputs, mask=None, **kwargs):
+        h = inputs[0] if isinstance(inputs, (list, tuple)) and len(inputs) == 1 else inputs
+        if not torch.is_tensor(h) or h.dim() != 3:
+            raise ValueError("NTMMemoryLayer: h must be [B,T,H], got %s" % (tuple(h.shape) if torch.is_tensor(h) else type(h).__name__,))
+        if h.shape[2] != self.read_write_kernel.shape[0]:
+            raise ValueError("NTMMemoryLayer: built for H = %d, got %s" % (self.read_write_kernel.shape[0], tuple(h.shape)))
+        _check_seq_mask("NTMMemoryLayer", mask, h.shape[0], h.shape[1])
+        if h.dtype == torch.float32 and self.fits_kernel_menu(h):
+            out, mem = Fn.ntm_memory(h, mask, *self._weights(), return_sequences=self.return_sequences)
+        else:
+            out, mem = self._composed(h, mask)
+        return [out, mem]
 
 
 def seq_self_attention_graph(x, mask, wq, wk, wv, heads, use_scale=True):

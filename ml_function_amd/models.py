@@ -9,7 +9,8 @@ DIEN (extension): the Deep Interest Evolution Network's GRU + AUGRU over the sam
 BST (extension): the Behaviour Sequence Transformer's block over them (layers.SeqSelfAttentionLayer),
 DSIN (extension): the Deep Session Interest Network's sessions, self-attention and bidirectional LSTM (layers.BiLSTMLayer),
 SIMInput / SIM (extension): the Search-based Interest Model's top-k retrieval over long histories (functional.seq_search),
-and SeqFM (extension): the Sequence-Aware Factorization Machine's static, dynamic and cross views (layers.SeqViewAttentionLayer).
+SeqFM (extension): the Sequence-Aware Factorization Machine's static, dynamic and cross views (layers.SeqViewAttentionLayer),
+and MIMN (extension): the Multi-channel user Interest Memory Network's Neural Turing Machine memory (layers.NTMMemoryLayer).
 """
 from collections import namedtuple
 
@@ -17,10 +18,10 @@ import torch
 
 from . import functional as Fn
 from .layers import (CIN, AFMLayer, AttentionBaseLayer, BagEmbed, BiLSTMLayer, CrossLayer, DinAttentionLayer, DnnLayer, FmLayer, GRULayer, InnerLayer, IPnnLayer, MergeScoreLayer,
-                     MultHeadAttentionLayer, OPnnLayer, ScoreLayer, SeqSelfAttentionLayer, SeqViewAttentionLayer, SparseEmbed, StackLayer)
+                     MultHeadAttentionLayer, NTMMemoryLayer, OPnnLayer, ScoreLayer, SeqSelfAttentionLayer, SeqViewAttentionLayer, SparseEmbed, StackLayer)
 from .layers.core_layer import Dense
 from .layers.base import Layer, merge_packed_views
-from .layers.behavior_layer import _masked_softmax
+from .layers.behavior_layer import _masked_softmax, ntm_address, ntm_beta
 from .layers.interactive_layer import pack_fields
 from .layers.core_layer import keras_add
 
@@ -792,6 +793,69 @@ class DSIN(_BehaviorModel):
         return _DsinBehavior(self.sess_count, self.att_heads, self.att_hidden_units, self.ffn_units, seed=self.seed + 2 * n)
 
     def _collect(self, out):      # [the attention over the session interests, the attention over the LSTM's states]
+        return out
+
+
+class _MimnBehavior(Layer):
+    """One behaviour of MIMN: the controller over the history, the memory it writes, and the candidate's read of the final memory."""
+
+    def __init__(self, memory_slots, memory_dim, controller_units, seed=2020):
+        super().__init__()
+        self.memory_slots = memory_slots
+        self.memory_dim = memory_dim
+        self.controller_units = controller_units
+        self.seed = seed
+
+    def build(self, input_shape):
+        k = int(input_shape[1][-1])
+        units = self.controller_units or k
+        d = self.memory_dim or units
+        self.controller = GRULayer(units, mode="gru", return_sequences=True, seed=self.seed)
+        self.memory = NTMMemoryLayer(self.memory_slots, d, return_sequences=False, seed=self.seed + 1)
+        if d != k:
+            self.query_kernel = self.add_weight("query_kernel", [k, d], "glorot_uniform", seed=self.seed)      # a Dense without bias
+        self.read_beta = self.add_weight("read_beta", [], "zeros")
+        super().build(input_shape)
+
+    def call(self, inputs, mask=None, **kwargs):
+        query, keys = inputs
+        q = query.reshape(keys.shape[0], keys.shape[2])
+        if hasattr(self, "query_kernel"):
+            q = torch.matmul(q, self.query_kernel)
+        r_last, mem = self.memory(self.controller(keys, mask=mask), mask=mask)      # [B,D], [B,m,D]
+        wq = ntm_address(mem, q.to(mem.dtype), ntm_beta(self.read_beta))
+        r_q = (wq.unsqueeze(-1) * mem).sum(dim=1)
+        return [r_q.unsqueeze(1), r_last.unsqueeze(1)]
+
+
+class MIMN(_BehaviorModel):
+    """Multi-channel user Interest Memory Network (extension; the model of "Practice on Long Sequential User Behavior Modeling for CTR
+    Prediction" on DINInput's features, its section 4.1: the history is compressed into a fixed-size memory -- the counterpart of SIM,
+    which retrieves from it).  Per behaviour: GRULayer(controller_units or K, return_sequences=True) over the history's keys is the
+    controller (it sees the history only: the read is not fed back); NTMMemoryLayer(memory_slots, memory_dim or the controller's
+    width) reads and writes m slots of width D at every live step; the candidate then reads the final memory, wq = softmax_i(beta_q
+    c_i(q')) and r_q = sum_i wq_i M_T[i], with q' the candidate's embedding (through a [K,D] kernel without bias only if D != K),
+    c_i the layer's cosine and beta_q = softplus(read_beta) + 1 for a trainable scalar initialised to 0 (torch ops on [B,m,D]).  The
+    behaviour contributes [r_q, the last read], each [B,1,D].  Then, as DIN: StackLayer over dense + field embeddings + those
+    features -> DnnLayer -> MergeScoreLayer(use_merge=False).  The Memory Utilization Regularization and the Memory Induction Unit
+    are not built."""
+
+    def __init__(self, memory_slots=4, memory_dim=None, controller_units=None, hidden_units=None, seed=2020):
+        if int(memory_slots) < 1:
+            raise ValueError("MIMN: memory_slots must be positive, got %r" % (memory_slots,))
+        for name, v in (("memory_dim", memory_dim), ("controller_units", controller_units)):
+            if v is not None and int(v) < 1:
+                raise ValueError("MIMN: %s must be positive or None, got %r" % (name, v))
+        super().__init__(hidden_units)
+        self.memory_slots = int(memory_slots)
+        self.memory_dim = None if memory_dim is None else int(memory_dim)
+        self.controller_units = None if controller_units is None else int(controller_units)
+        self.seed = seed
+
+    def _behavior(self, n):
+        return _MimnBehavior(self.memory_slots, self.memory_dim, self.controller_units, seed=self.seed + 2 * n)
+
+    def _collect(self, out):      # [the candidate's read of the final memory, the last read of the recurrence]
         return out
 
 
