@@ -680,6 +680,55 @@ int fil_ntm_bwd(const float* h, const unsigned char* mask, const float* Wp, cons
                 int H, int m, int D, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * N5  Time-stream GRU over a behaviour sequence with event gaps (extension: the core of the Deep Time-Stream model -- a GRU whose
+ *     state moves between two events, and from the last event to the prediction time, under a learned ODE dh/dt = tanh(h Wf + bf),
+ *     integrated by S explicit Euler substeps; the reference's layer was not available, this is the project's own statement).  All
+ *     tensors fp32 except mask.  Entry points added only: the ABI version stays.
+ *   x [B,T,K]; dt [B,T] the time from the previous live event to this one, in the caller's units (documented as >= 0; any finite
+ *   value runs, nothing is checked on the device); dt_out [B] the time from the last event to the prediction, or NULL; mask [B,T]
+ *   uint8, non-zero = live, NULL = all live; W [K,3H], U [H,3H], b [2,3H]: fil_gru_*'s in the mode FIL_GRU_GRU; Wf [H,H], bf [H] the
+ *   ODE's; S the substeps.  One live step on the carried state h (zeros at first):
+ *     delta = dt[b,t] / (float)S                                  (one correctly rounded fp32 division)
+ *     S times:  f_j = tanhf(bf_j + sum_k h_k Wf[k,j])             (one fmaf chain, k ascending, started from bf_j)
+ *               h_j = fmaf(delta, f_j, h_j)                       (explicit Euler; every unit reads the OLD h)
+ *     then fil_gru_fwd's step (reset_after, columns z | r | h, h_new = fma(u, c, (1 - u) h)) on the evolved h.
+ *   A masked step carries h bit for bit; its x row and its dt are never read.
+ *   fil_tsgru_fwd: hs [B,T,H] the states after each step; with dt_out, z [B,H] = the last state of EVERY sample (zeros for one
+ *     without a live step) evolved by S more substeps of dt_out[b] / S (dt_out and z are both given or both NULL); and `saved` for
+ *     the backward (fil_tsgru_saved_bytes; opaque to the caller: per live step fil_gru_fwd's four planes and, per substep, the state
+ *     before it and f, [B,T,4+2S,H]; behind them the final evolution's pairs [B,2S,H]; masked steps are left unwritten; NULL: nothing
+ *     is saved, for inference).
+ *   fil_tsgru_bwd: g_hs [B,T,H], g_last [B,H] (the gradient of hs[:,T-1]) and g_z [B,H] (needs dt_out): any non-empty subset, the
+ *     others NULL -> dx, dW, dU, db, dWf, dbf.  dt and dt_out are data: they get no gradient.  Per substep, in reverse:
+ *     q = delta dh (1 - f^2); dh += q Wf^T; dWf += h_s^T q; dbf += q.  No product and no tanhf is taken again: the GRU step's previous
+ *     state is fma(delta, f, h) of the last saved pair.  Each output may be NULL and is then not computed, the others keep the bits
+ *     of the full call (all five parameter gradients NULL: no parameter pass, no workspace; all six NULL: FIL_ERR_ARG).  The
+ *     parameter gradients leave the main launch as one partial per workgroup in `workspace` (fil_tsgru_bwd_workspace_bytes; every
+ *     byte that is read was written by that launch) and a second small launch adds the partials in a fixed order.
+ *   One launch per direction for all T steps and all substeps (plus the partial sum).  No atomics; every sum has a fixed order for a
+ *   given shape: the same inputs give the same bits on every call, and a sample's hs, z and dx depend neither on its place in the
+ *   batch nor on B.  With dt = 0 and dt_out = 0, or with Wf = 0 and bf = 0, hs has fil_gru_fwd's bits and z those of hs[:,T-1].
+ *   Menu: any T >= 1; K % 4 == 0, H % 4 == 0, K <= 64, H <= 64; 1 <= S <= 8; both passes within 163,328 bytes of dynamic LDS: the
+ *   weights, Wf (forward) or its transpose (backward) and the substep images sit beside fil_gru_*'s sections, which leaves out the
+ *   largest shapes (every H <= 52 is in; H = 56: K >= 52 is out, H = 60: K >= 40, H = 64: K >= 36, and at the tiles of 16 samples
+ *   that large batches take H = 60: K >= 36, H = 64: K >= 20; fil_tsgru_plan decides, and S does not enter).  FIL_ERR_UNSUPPORTED
+ *   otherwise (also for S > 8), the limit in the message; S < 1 is FIL_ERR_ARG.
+ *   B == 0 returns FIL_OK before any pointer is looked at.  A workspace smaller than needed: FIL_ERR_ARG, the needed size in the message.
+ *   fil_tsgru_plan: the launchers' own arithmetic (no GPU call): plan[8] = {fwd_ok, bwd_ok, samples per workgroup tile, grid, grid cap,
+ *     parameter-gradient partials (= grid), forward LDS bytes, backward LDS bytes}, as fil_gru_plan's.
+ */
+int fil_tsgru_plan(int B, int T, int K, int H, int S, int* plan /* [8] */);
+size_t fil_tsgru_saved_bytes(int B, int T, int K, int H, int S);
+int fil_tsgru_fwd(const float* x, const float* dt, const float* dt_out, const unsigned char* mask, const float* W, const float* U,
+                  const float* b, const float* Wf, const float* bf, float* hs, float* z, float* saved, int B, int T, int K, int H, int S,
+                  void* stream);
+size_t fil_tsgru_bwd_workspace_bytes(int B, int T, int K, int H, int S);
+int fil_tsgru_bwd(const float* x, const float* dt, const float* dt_out, const unsigned char* mask, const float* W, const float* U,
+                  const float* Wf, const float* saved, const float* g_hs, const float* g_last, const float* g_z, float* dx, float* dW,
+                  float* dU, float* db, float* dWf, float* dbf, void* workspace, size_t workspace_bytes, int B, int T, int K, int H, int S,
+                  void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * N2  The score head and the loss behind the interaction layers (all tensors fp32, n = batch rows).
  *   ScoreLayer(use_add=True).call (kon/model/ctr_model/layer/core_layer/core_layer.py:58-84): keras Add over the [B,1] parts,
  *   then sigmoid.  fil_score_add_sigmoid_fwd: out[i] = sigmoid(((a[i] + b[i]) + c[i]) + d[i]) -- left to right like the

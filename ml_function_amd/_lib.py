@@ -136,6 +136,12 @@ SIGNATURES = {
     "fil_ntm_fwd": (_I, [_P] * 9 + [_I] * 5 + [_P]),
     "fil_ntm_bwd_workspace_bytes": (_Z, [_I, _I, _I, _I, _I]),
     "fil_ntm_bwd": (_I, [_P] * 12 + [_Z] + [_I] * 5 + [_P]),
+    # N5: time-stream GRU over a behaviour sequence with event gaps
+    "fil_tsgru_plan": (_I, [_I, _I, _I, _I, _I, _P]),
+    "fil_tsgru_saved_bytes": (_Z, [_I, _I, _I, _I, _I]),
+    "fil_tsgru_fwd": (_I, [_P] * 12 + [_I] * 5 + [_P]),
+    "fil_tsgru_bwd_workspace_bytes": (_Z, [_I, _I, _I, _I, _I]),
+    "fil_tsgru_bwd": (_I, [_P] * 18 + [_Z] + [_I] * 5 + [_P]),
     "fil_score_add_sigmoid_fwd": (_I, [_P, _P, _P, _P, _P, _I, _P]),
     "fil_score_add_sigmoid_bwd": (_I, [_P, _P, _P, _I, _P]),
     "fil_bce_mean_fwd": (_I, [_P, _P, _F, _P, _P, _I, _P]),

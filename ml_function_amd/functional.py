@@ -439,6 +439,133 @@ def gru_plan(B, T, K, H, mode="gru"):
     return _tiled_plan("fil_gru_plan", int(B), int(T), int(K), int(H), GRU_MODES[mode])
 
 
+class _TsGruFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, dt, dt_out, mask, w, u, b, wf, bf, steps, return_sequences):
+        _require_cuda(x, dt, dt_out, mask, w, u, b, wf, bf)
+        x, dt, dt_out, w, u, b, wf, bf = (_f32c(t) for t in (x, dt, dt_out, w, u, b, wf, bf))
+        if x.dim() != 3 or w.dim() != 2 or u.dim() != 2 or w.shape[0] != x.shape[2] or u.shape[1] != 3 * u.shape[0] or w.shape[1] != u.shape[1]:
+            raise FilError("ts_gru: x must be [B,T,K], W [K,3H] and U [H,3H], got %s, %s and %s" % (tuple(x.shape), tuple(w.shape), tuple(u.shape)))
+        B, T, K = x.shape
+        H = u.shape[0]
+        if tuple(b.shape) != (2, 3 * H):
+            raise FilError("ts_gru: b must be [2,3H] with H = %d (input bias, recurrent bias), got %s" % (H, tuple(b.shape)))
+        if tuple(wf.shape) != (H, H) or tuple(bf.shape) != (H,):
+            raise FilError("ts_gru: Wf and bf must be [H,H] and [H] with H = %d, got %s and %s" % (H, tuple(wf.shape), tuple(bf.shape)))
+        if tuple(dt.shape) != (B, T) or (dt_out is not None and tuple(dt_out.shape) != (B,)):
+            raise FilError("ts_gru: dt must be [B,T] and dt_out [B] or None, got %s and %s"
+                           % (tuple(dt.shape), None if dt_out is None else tuple(dt_out.shape)))
+        mask = _seq_mask("ts_gru", mask, B, T)
+        lib = _lib.load()
+        dev = x.device
+        hs = torch.empty((B, T, H), dtype=torch.float32, device=dev)
+        z = None if dt_out is None else torch.empty((B, H), dtype=torch.float32, device=dev)
+        need = ctx.needs_input_grad
+        saved = None
+        if any(need[i] for i in (0, 4, 5, 6, 7, 8)):
+            saved = _saved_floats(lib.fil_tsgru_saved_bytes(B, T, K, H, steps), dev)
+        check(lib.fil_tsgru_fwd(ptr(x), ptr(dt), ptr(dt_out), ptr(mask), ptr(w), ptr(u), ptr(b), ptr(wf), ptr(bf), ptr(hs), ptr(z), ptr(saved),
+                                B, T, K, H, steps, stream_ptr()), "fil_tsgru_fwd")
+        _save(ctx, x, dt, dt_out, mask, w, u, wf, saved)
+        ctx.steps, ctx.return_sequences = steps, return_sequences
+        ctx.set_materialize_grads(False)
+        out = hs if return_sequences else (hs[:, T - 1].clone() if B > 0 else hs.new_zeros((0, H)))
+        return out if z is None else (out, z)
+
+    @staticmethod
+    def backward(ctx, g, g_z=None):
+        need = ctx.needs_input_grad
+        none = (None,) * 11
+        if not any(need[i] for i in (0, 4, 5, 6, 7, 8)) or (g is None and g_z is None):
+            return none
+        x, dt, dt_out, mask, w, u, wf, saved = _saved(ctx)
+        B, T, K = x.shape
+        H = u.shape[0]
+        dev = x.device
+        dx = _grad(need[0], x.shape, dev)
+        dw = _grad(need[4], w.shape, dev)
+        du = _grad(need[5], u.shape, dev)
+        db = _grad(need[6], (2, 3 * H), dev)
+        dwf = _grad(need[7], (H, H), dev)
+        dbf = _grad(need[8], (H,), dev)
+        if _no_samples(B, dw, du, db, dwf, dbf):
+            return dx, None, None, None, dw, du, db, dwf, dbf, None, None
+        g, g_z = _f32c(g), _f32c(g_z)
+        g_hs, g_last = (g, None) if ctx.return_sequences else (None, g)
+        ws, nws = _partials_scratch("fil_tsgru_bwd_workspace_bytes", "tsgru_bwd", any(need[i] for i in (4, 5, 6, 7, 8)), dev, B, T, K, H,
+                                    ctx.steps)
+        check(_lib.load().fil_tsgru_bwd(ptr(x), ptr(dt), ptr(dt_out), ptr(mask), ptr(w), ptr(u), ptr(wf), ptr(saved), ptr(g_hs), ptr(g_last),
+                                        ptr(g_z), ptr(dx), ptr(dw), ptr(du), ptr(db), ptr(dwf), ptr(dbf), ptr(ws), nws, B, T, K, H, ctx.steps,
+                                        stream_ptr()), "fil_tsgru_bwd")
+        return dx, None, None, None, dw, du, db, dwf, dbf, None, None
+
+
+def _ts_steps(who, steps):
+    if int(steps) != steps or int(steps) < 1:
+        raise ValueError("%s: steps must be a positive integer, got %r" % (who, steps))
+    return int(steps)
+
+
+def ts_gru(x, dt, dt_out, mask, W, U, b, Wf, bf, steps=2, return_sequences=True):
+    """A time-stream GRU over a behaviour sequence with event gaps (extension: the core of the Deep Time-Stream model; include/fil.h
+    fil_tsgru_*): x [B,T,K], dt [B,T] the time from the previous live event to this one (>= 0, the caller's units), dt_out [B] the
+    time from the last event to the prediction or None, mask [B,T] bool / uint8 (non-zero = live; None = all live), W [K,3H], U [H,3H],
+    b [2,3H] (Fn.gru's in the mode "gru"), Wf [H,H], bf [H] -> hs [B,T,H] (hs[:, -1] [B,H] with return_sequences=False), and with
+    dt_out (hs or last, z [B,H]).  Before each live step the state moves under dh/dt = tanh(h Wf + bf) by `steps` explicit Euler
+    substeps of dt / steps, then the GRU step runs on it; z is the last state moved by dt_out in the same way.  A masked step repeats
+    the state.  dt and dt_out are data: they get no gradient, and one that requires it raises.  One launch per direction for all
+    steps and substeps (plus the small fixed-order sum of the parameter-gradient partials); an output that received no gradient enters
+    the backward as NULL and only the gradients that are asked for are computed.  GPU only; shapes outside the kernel menu raise
+    FilError (layers.TimeStreamGRULayer takes its composed path there)."""
+    steps = _ts_steps("ts_gru", steps)
+    for name, t in (("dt", dt), ("dt_out", dt_out)):
+        if t is not None and t.requires_grad:
+            raise ValueError("ts_gru: %s requires grad -- the gaps are data, there is no gradient to them" % name)
+    return _TsGruFn.apply(x, dt, dt_out, mask, W, U, b, Wf, bf, steps, bool(return_sequences))
+
+
+def ts_gru_plan(B, T, K, H, steps=2):
+    """fil_tsgru_plan's answer as a dict (fits, tile, grid, cap, partials, lds_fwd, lds_bwd); fits=False (and nothing else) for a shape
+    outside the kernel menu (more than 8 substeps are outside it too)."""
+    return _tiled_plan("fil_tsgru_plan", int(B), int(T), int(K), int(H), _ts_steps("ts_gru_plan", steps))
+
+
+def ts_gru_graph(x, dt, dt_out, mask, W, U, b, Wf, bf, steps=2, return_sequences=True):
+    """ts_gru's math as torch ops on the tensors given (their dtype and device; autograd for the backward), one substep and one step at
+    a time: the composed path of TimeStreamGRULayer and the comparator of its benchmark -- about 10 + 4 steps launches per step.
+    mask: [B,T] bool or None.  x_t and dt of a masked step are replaced by zero before anything reads them."""
+    steps = _ts_steps("ts_gru_graph", steps)
+    B, T, K = x.shape
+    H = U.shape[0]
+    zero = torch.zeros((), dtype=x.dtype, device=x.device)
+    live = None if mask is None else mask.to(torch.bool)
+    if live is not None:
+        x = torch.where(live.unsqueeze(-1), x, zero)
+        dt = torch.where(live, dt, zero)
+
+    def evolve(h, gap):
+        delta = (gap / steps).unsqueeze(-1)
+        for _ in range(steps):
+            h = h + delta * torch.tanh(torch.matmul(h, Wf) + bf)
+        return h
+
+    h = torch.zeros((B, H), dtype=x.dtype, device=x.device)
+    out = []
+    for t in range(T):
+        he = evolve(h, dt[:, t])
+        xp = torch.matmul(x[:, t], W) + b[0]
+        hp = torch.matmul(he, U) + b[1]
+        z = torch.sigmoid(xp[:, :H] + hp[:, :H])
+        r = torch.sigmoid(xp[:, H:2 * H] + hp[:, H:2 * H])
+        c = torch.tanh(xp[:, 2 * H:] + r * hp[:, 2 * H:])
+        hn = z * he + (1 - z) * c
+        h = hn if live is None else torch.where(live[:, t:t + 1], hn, h)
+        if return_sequences:
+            out.append(h)
+    res = torch.stack(out, dim=1) if return_sequences else h
+    return res if dt_out is None else (res, evolve(h, dt_out))
+
+
 LSTM_DIRECTIONS = {"forward": _lib.FIL_LSTM_FORWARD, "reverse": _lib.FIL_LSTM_REVERSE, "bidirectional": _lib.FIL_LSTM_BIDIR}
 
 

@@ -1,7 +1,7 @@
 from ..capture import capture_step
 from .base import Layer
 from .behavior_layer import (BiLSTMLayer, DinAttentionLayer, GRULayer, LSTMLayer, MultHeadAttentionLayer, NTMMemoryLayer, ProductAttentionLayer,
-                             SeqSelfAttentionLayer, SeqViewAttentionLayer)
+                             SeqSelfAttentionLayer, SeqViewAttentionLayer, TimeStreamGRULayer)
 from .core_layer import (AlignLayer, Dense, DnnLayer, HiddenLayer, IntraViewPoolingLayer, MergeScoreLayer, ResActivateLayer, ScoreLayer,
                          StackLayer)
 from .interactive_layer import (CIN, AFMLayer, AttentionBaseLayer, BagEmbed, CrossLayer, ExtractLayer, FmLayer, InnerLayer, IPnnLayer, LinearLayer,
@@ -11,4 +11,4 @@ __all__ = ["capture_step", "Layer", "InnerLayer", "FmLayer", "CrossLayer", "CIN"
            "MultHeadAttentionLayer", "StackLayer", "ScoreLayer", "MergeScoreLayer", "HiddenLayer", "ResActivateLayer",
            "DnnLayer", "Dense", "IPnnLayer", "OPnnLayer", "LinearLayer", "AttentionBaseLayer", "ExtractLayer",
            "IntraViewPoolingLayer", "AlignLayer", "BagEmbed", "AFMLayer", "DinAttentionLayer", "GRULayer",
-           "SeqSelfAttentionLayer", "LSTMLayer", "BiLSTMLayer", "SeqViewAttentionLayer", "NTMMemoryLayer"]
+           "SeqSelfAttentionLayer", "LSTMLayer", "BiLSTMLayer", "SeqViewAttentionLayer", "NTMMemoryLayer", "TimeStreamGRULayer"]

@@ -4,7 +4,7 @@ sigmoid (:286,308), V is projected with key_w (:360; value_w exists but never re
 epsilon is Keras' default 1e-3, the output is head-major [H,B,F,A].
 Behaviour-sequence layers (extensions), each one fused kernel per direction with a composed torch path outside the kernel menu:
 DinAttentionLayer (the Deep Interest Network's attention pooling), GRULayer (a GRU and the Deep Interest Evolution Network's AUGRU /
-AGRU), LSTMLayer / BiLSTMLayer (Keras' LSTM and Bidirectional(LSTM), the Deep Session Interest Network's session interest
+AGRU), TimeStreamGRULayer (the Deep Time-Stream model's GRU under an ODE over the event gaps), LSTMLayer / BiLSTMLayer (Keras' LSTM and Bidirectional(LSTM), the Deep Session Interest Network's session interest
 interacting layer), SeqSelfAttentionLayer (the Behaviour Sequence Transformer's masked self-attention) and NTMMemoryLayer (the
 Multi-channel user Interest Memory Network's Neural Turing Machine memory)."""
 import torch
@@ -334,6 +334,77 @@ class GRULayer(Layer):
             return Fn.gru(x, scores, mask, self.kernel, self.recurrent_kernel, self.bias, mode=self.mode,
                           return_sequences=self.return_sequences)
         return self._composed(x, scores, mask)
+
+
+class TimeStreamGRULayer(Layer):
+    """A GRU over a behaviour sequence whose state moves through the time between the events (extension: the core of the Deep
+    Time-Stream model; the reference's layer was not available).
+
+    call([x [B,T,K], dt [B,T], dt_out [B] or None], mask=None): dt is the time from the previous live event to this one, dt_out the
+    time from the last event to the prediction.  Before every live step the state follows dh/dt = tanh(h ode_kernel + ode_bias) for
+    dt in `steps` explicit Euler substeps, then GRULayer's step (mode "gru") runs on it -> hs [B,T,units], or the last state
+    [B,units] with return_sequences=False; with dt_out a pair (hs or last, z [B,units]), z = the last state moved on by dt_out.  mask
+    as GRULayer's.  Weights: GRULayer's under its names and initialisers, ode_kernel [units,units] glorot_uniform(seed) and ode_bias
+    [units] zeros.  The gaps are data and get no gradient.  The whole recurrence runs in ONE HIP kernel per direction (Fn.ts_gru,
+    include/fil.h fil_tsgru_*).  Outside the kernel menu (fits_kernel_menu; more than 8 substeps are outside it) or for a non-fp32
+    input the layer takes the composed path -- Fn.ts_gru_graph on the GPU, computed in fp32 -- instead of raising."""
+
+    def __init__(self, units, steps=2, return_sequences=False, seed=2020):
+        super().__init__()
+        if int(units) < 1:
+            raise ValueError("TimeStreamGRULayer: units must be positive, got %r" % (units,))
+        if int(steps) != steps or int(steps) < 1:
+            raise ValueError("TimeStreamGRULayer: steps must be a positive integer, got %r" % (steps,))
+        self.units = int(units)
+        self.steps = int(steps)
+        self.return_sequences = bool(return_sequences)
+        self.seed = seed
+
+    def build(self, input_shape):
+        shape = input_shape[0] if isinstance(input_shape, list) else input_shape
+        k, h = int(shape[-1]), self.units
+        self.kernel = self.add_weight("kernel", [k, 3 * h], "glorot_uniform", seed=self.seed)
+        self.recurrent_kernel = self.add_weight("recurrent_kernel", [h, 3 * h], "orthogonal", seed=self.seed)
+        self.bias = self.add_weight("bias", [2, 3 * h], "zeros")
+        self.ode_kernel = self.add_weight("ode_kernel", [h, h], "glorot_uniform", seed=self.seed)
+        self.ode_bias = self.add_weight("ode_bias", [h], "zeros")
+        super().build(input_shape)
+
+    def fits_kernel_menu(self, x):
+        """fil_tsgru_*'s menu (include/fil.h): K % 4 == 0, H % 4 == 0, K <= 64, H <= 64, at most 8 substeps, and the LDS of both passes
+        -- fil_tsgru_plan answers from the launchers' own arithmetic at the batch given (the tile, and with it the LDS, grows with
+        every 4096 samples up to 64 samples a tile: the batch is rounded up to that step, so the cached answers stay few)."""
+        if x.dim() != 3:
+            return False
+        batch = min(-(-max(int(x.shape[0]), 1) // 4096), 64) * 4096
+        return _menu_fits(Fn.ts_gru_plan, batch, 1, int(x.shape[2]), self.units, self.steps)
+
+    def _weights(self):
+        return self.kernel, self.recurrent_kernel, self.bias, self.ode_kernel, self.ode_bias
+
+    def _composed(self, x, dt, dt_out, mask):
+        """Fn.ts_gru_graph on the GPU in fp32: about 10 + 4 steps launches per step where the fused kernel makes one per direction --
+        it exists so that a shape outside the kernel menu never raises."""
+        Fn._require_cuda(x, dt, dt_out, mask)      # (torch ops would run on a CPU tensor: there is no CPU path in this package)
+        f32 = lambda t: None if t is None else t.to(torch.float32)
+        return Fn.ts_gru_graph(f32(x), f32(dt), f32(dt_out), mask, *self._weights(), steps=self.steps,
+                               return_sequences=self.return_sequences)
+
+    def call(self, inputs, mask=None, **kwargs):
+        if not isinstance(inputs, (list, tuple)) or len(inputs) != 3:
+            raise ValueError("TimeStreamGRULayer: the call takes [x, dt, dt_out or None]")
+        x, dt, dt_out = inputs
+        if x.dim() != 3:
+            raise ValueError("TimeStreamGRULayer: x must be [B,T,K], got %s" % (tuple(x.shape),))
+        if dt is None or tuple(dt.shape) != tuple(x.shape[:2]) or (dt_out is not None and tuple(dt_out.shape) != (x.shape[0],)):
+            raise ValueError("TimeStreamGRULayer: dt must be [B,T] = %s and dt_out [B] or None, got %s and %s"
+                             % (tuple(x.shape[:2]), None if dt is None else tuple(dt.shape), None if dt_out is None else tuple(dt_out.shape)))
+        if dt.requires_grad or (dt_out is not None and dt_out.requires_grad):
+            raise ValueError("TimeStreamGRULayer: dt / dt_out requires grad -- the gaps are data, there is no gradient to them")
+        _check_seq_mask("TimeStreamGRULayer", mask, x.shape[0], x.shape[1])
+        if all(t is None or t.dtype == torch.float32 for t in (x, dt, dt_out)) and self.fits_kernel_menu(x):
+            return Fn.ts_gru(x, dt, dt_out, mask, *self._weights(), steps=self.steps, return_sequences=self.return_sequences)
+        return self._composed(x, dt, dt_out, mask)
 
 
 _LSTM_DIRECTIONS = ("forward", "reverse", "bidirectional")

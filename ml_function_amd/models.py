@@ -10,7 +10,8 @@ BST (extension): the Behaviour Sequence Transformer's block over them (layers.Se
 DSIN (extension): the Deep Session Interest Network's sessions, self-attention and bidirectional LSTM (layers.BiLSTMLayer),
 SIMInput / SIM (extension): the Search-based Interest Model's top-k retrieval over long histories (functional.seq_search),
 SeqFM (extension): the Sequence-Aware Factorization Machine's static, dynamic and cross views (layers.SeqViewAttentionLayer),
-and MIMN (extension): the Multi-channel user Interest Memory Network's Neural Turing Machine memory (layers.NTMMemoryLayer).
+MIMN (extension): the Multi-channel user Interest Memory Network's Neural Turing Machine memory (layers.NTMMemoryLayer),
+and DTSInput / DTS (extension): the Deep Time-Stream model's GRU under an ODE over the event gaps (layers.TimeStreamGRULayer).
 """
 from collections import namedtuple
 
@@ -18,7 +19,7 @@ import torch
 
 from . import functional as Fn
 from .layers import (CIN, AFMLayer, AttentionBaseLayer, BagEmbed, BiLSTMLayer, CrossLayer, DinAttentionLayer, DnnLayer, FmLayer, GRULayer, InnerLayer, IPnnLayer, MergeScoreLayer,
-                     MultHeadAttentionLayer, NTMMemoryLayer, OPnnLayer, ScoreLayer, SeqSelfAttentionLayer, SeqViewAttentionLayer, SparseEmbed, StackLayer)
+                     MultHeadAttentionLayer, NTMMemoryLayer, OPnnLayer, ScoreLayer, SeqSelfAttentionLayer, SeqViewAttentionLayer, SparseEmbed, StackLayer, TimeStreamGRULayer)
 from .layers.core_layer import Dense
 from .layers.base import Layer, merge_packed_views
 from .layers.behavior_layer import _masked_softmax, ntm_address, ntm_beta
@@ -857,6 +858,59 @@ class MIMN(_BehaviorModel):
 
     def _collect(self, out):      # [the candidate's read of the final memory, the last read of the recurrence]
         return out
+
+
+class DTSInput(DINInput):
+    """Feature input of a Deep Time-Stream model (extension): DINInput's fields and histories plus, per behaviour, WHEN the events
+    happened -- hist_dt [B,N,T] float, the time from the previous event of the history to this one (>= 0, any unit; padded slots
+    are never read), and next_dt [B,N] float, the time from the last event to the prediction.
+
+    call((dense, sparse_idx [B,F], (hist_idx [B,N,T], hist_dt, next_dt))), as CTRModel passes it: model(dense, sparse_idx, (hist_idx,
+    hist_dt, next_dt)) -> DINInput's InputFeature with the gaps beside the keys and masks: seq_embed_list = [keys, masks, N x dt
+    [B,T], N x next_dt [B]], fp32.  The gaps are data: nothing here or below gives them a gradient."""
+
+    def call(self, inputs, **kwargs):
+        if len(inputs) != 3 or not isinstance(inputs[2], (tuple, list)) or len(inputs[2]) != 3:
+            raise ValueError("DTSInput: the call takes (dense, sparse_idx, (hist_idx, hist_dt, next_dt))")
+        dense, sparse_idx, (hist_idx, hist_dt, next_dt) = inputs
+        if hist_idx is None or hist_dt is None or next_dt is None:
+            raise ValueError("DTSInput: hist_idx, hist_dt and next_dt are required")
+        if hist_idx.dim() != 3 or tuple(hist_dt.shape) != tuple(hist_idx.shape) or tuple(next_dt.shape) != tuple(hist_idx.shape[:2]) or \
+                not hist_dt.is_floating_point() or not next_dt.is_floating_point():
+            raise ValueError("DTSInput: hist_dt must be a float tensor of hist_idx's shape [B,N,T] and next_dt a float [B,N], got %s, %s and %s"
+                             % (tuple(hist_idx.shape), tuple(hist_dt.shape), tuple(next_dt.shape)))
+        Fn._require_cuda(hist_dt, next_dt)
+        fea = super().call((dense, sparse_idx, hist_idx))
+        N = len(self.behavior)
+        hist_dt, next_dt = hist_dt.detach().to(torch.float32), next_dt.detach().to(torch.float32)
+        fea.seq_embed_list = list(fea.seq_embed_list) + [[hist_dt[:, n].contiguous() for n in range(N)],
+                                                         [next_dt[:, n].contiguous() for n in range(N)]]
+        return fea
+
+
+class DTS(_BehaviorModel):
+    """Deep Time-Stream model (extension; the model's core on DTSInput's features): per behaviour one TimeStreamGRULayer(K, steps,
+    return_sequences=False) over the history's keys and gaps -- a GRU whose state follows a learned ODE through the time between
+    the events -- and its z [B,1,K], the interest state moved on to the prediction time, joins the dense inputs and field embeddings.
+    Then, as DIN: StackLayer -> DnnLayer -> MergeScoreLayer(use_merge=False).  The candidate does not enter the recurrence.  Not
+    built: the paper's guide loss, adaptive or higher-order solvers (fixed-step Euler only), attention gates under the ODE."""
+
+    def __init__(self, steps=2, hidden_units=None, seed=2020):
+        if int(steps) != steps or int(steps) < 1:
+            raise ValueError("DTS: steps must be a positive integer, got %r" % (steps,))
+        super().__init__(hidden_units)
+        self.steps = int(steps)
+        self.seed = seed
+
+    def forward(self, inputFea):
+        if len(inputFea.seq_embed_list) != 4:
+            raise ValueError("DTS: the features carry no gaps (models.DTSInput makes them)")
+        keys, masks, gaps, nexts = inputFea.seq_embed_list
+        while len(self.behaviors) < len(keys):
+            n = len(self.behaviors)
+            self.behaviors.append(TimeStreamGRULayer(int(keys[n].shape[-1]), steps=self.steps, return_sequences=False, seed=self.seed + n))
+        feats = [self.behaviors[n]([keys[n], gaps[n], nexts[n]], mask=masks[n])[1].unsqueeze(1) for n in range(len(keys))]
+        return self.score(self.dnn(self.stack(list(inputFea.dense_inputs) + list(inputFea.sparse_embed) + feats)))
 
 
 class CTRModel(torch.nn.Module):
